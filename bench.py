@@ -2,6 +2,8 @@
 """bench.py -- Gibbs iterations/sec of the BayesFMMM sweep on MI355X (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR                 (+ the chain state after the last timed step, DIR/<name>.npy)
+  python bench.py ... --full                             (+ every side record below)
 
 A "step" is one Gibbs iteration of every chain in flight.  Data: SURVEY.md 8(d) "Config 2" (n_funct = 4096 curves of
 n_i = 100 points, cubic B-splines with 26 internal knots => P = 30, K = 3, M = 6, fp64), synthetic.
@@ -11,6 +13,9 @@ BFMMM_MTT_warm_start (Z, pi, alpha_3, Phi, delta, A, gamma, nu, tau, sigma^2, ch
 started at the generating values, inputs and chain resident in HBM -- with ONE independent chain per GPU: a chain does not shard
 ("replicas only" inside a chain), so N GPUs run N replicas with RNG chain ids 0 .. N - 1 and `value` is the
 whole-node rate, N x steps / (time of the slowest rank).  No collective inside the timed steps.
+
+A plain run does only that: set-up, W warm-up steps, the K timed steps, the dump of --dump-outputs, and the result line, whose
+`roofline` is then the iteration's algorithmic bytes against N x the HBM peak (no run of its own).  With --full:
 
 The same line carries, with the SAME keys at every N, `config5`: BASELINE.json configs[4] / SURVEY 8(d) "Config 5", the 8 chains
 of BFMMM_Nu_Z_multiple_try (n_try = 7; reduced sweep Z, pi, alpha_3, nu, tau, sigma^2, log-likelihood, BFMMM.h:1073-1113) on
@@ -67,6 +72,22 @@ def make_config2(n=4096, n_i=100, K=3, M=6, n_internal=26, seed=1):
                  sigma_sq=np.array([sigma_sq]))
     return dict(y=[Y[i] for i in range(n)], t=[t] * n, B=[B] * n, internal_knots=ik,
                 boundary_knots=np.array([b0, b1]), K=K, M=M, P=P, n=n, n_i=n_i, degree=degree, state=state)
+
+
+DUMP_NAMES = ("nu", "Phi", "chi", "Z", "pi", "alpha_3", "delta", "A", "gamma", "tau", "sigma_sq", "loglik")
+DUMP_MAX_CURVES = 1 << 18       # per-curve arrays (chi, Z) beyond this: a fixed, seeded sample of curves (keeps a dump < 64 MB)
+
+
+def dump_outputs(smp, T, d):
+    """--dump-outputs: the chain state the timed run leaves in its last slot (iteration T - 1), i.e. what a caller of the
+    warm-start sweep receives for that iteration, one fp64 DIR/<name>.npy per parameter (0.3 MB at n_funct = 4096)"""
+    os.makedirs(d, exist_ok=True)
+    for nm in DUMP_NAMES:
+        a = smp.get_chain(nm, T)
+        last = a[T - 1] if nm == "tau" else a[..., T - 1]          # tau is stored (T, K), every other trace slot-last
+        if nm in ("chi", "Z") and last.shape[0] > DUMP_MAX_CURVES:
+            last = last[np.sort(np.random.default_rng(0).choice(last.shape[0], DUMP_MAX_CURVES, replace=False))]
+        np.save(os.path.join(d, nm + ".npy"), np.atleast_1d(np.ascontiguousarray(last, dtype=np.float64)))
 
 
 def algorithmic_bytes_per_iteration(n, P, M, K, n_blocks=5, dense=True, bw=3):
@@ -349,9 +370,13 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--n", type=int, default=4096)
-    ap.add_argument("--profile-steps", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip config5 / chains_sweep / other_configs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel pass (roofline), config5, chains_sweep, other_configs and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the chain state after the last timed step as DIR/<name>.npy (fp64)")
+    ap.add_argument("--profile-steps", type=int, default=200, help="(--full) steps of the per-kernel pass")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip config5 / chains_sweep / other_configs")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -413,12 +438,14 @@ def main():
     dev_ms, _ = smp.timing("total")
     assert np.isfinite(smp.get_chain("loglik", T)).all()
     value = world * args.steps / dt
+    if args.dump_outputs and rank == 0:      # before the per-kernel pass below rewrites the chain slots
+        dump_outputs(smp, T, args.dump_outputs)
 
-    # per-kernel pass (N = 1): the same sweep, eager launches bracketed by HIP events on the sampler's stream (a replayed graph
-    # cannot carry per-launch events; the brackets add about 3 us per launch, so these are upper bounds -- the rocprofv3
+    # per-kernel pass (--full, N = 1): the same sweep, eager launches bracketed by HIP events on the sampler's stream (a replayed
+    # graph cannot carry per-launch events; the brackets add about 3 us per launch, so these are upper bounds -- the rocprofv3
     # averages of the same command are committed under profiles/)
     fams = {}
-    if args.profile_steps > 0 and world == 1:
+    if args.full and args.profile_steps > 0 and world == 1:
         smp.set_state(**w["state"])
         smp.set_profile(True)
         smp.run(bf.SWEEP_WARM, args.profile_steps, first_iter=0, seed=1, chain=0)
@@ -509,7 +536,7 @@ def main():
             note="the iteration is five dependent kernels, each bound by dependent-step latency at this size (the records, 5 MB, "
                  "live in L2 / Infinity Cache): `frac` is small by construction; `traffic` (rocprofv3 FETCH_SIZE x 2 + "
                  "WRITE_SIZE per launch) and iteration.measured_* are what actually moves")
-    if roofline is None:      # N > 1 (the per-kernel figures are on the N = 1 line): the iteration's bytes against N x 8 TB/s
+    if roofline is None:      # plain run, or N > 1 (the per-kernel figures are on the N = 1 --full line): the iteration's bytes against N x 8 TB/s
         roofline = dict(bound="hbm", kernel="iteration (all kernels of a chain-iteration)", unit="GB/s", peak=HBM_PEAK_GBS * world,
                         achieved=b_band * value / 1e9, frac=b_band * value / 1e9 / (HBM_PEAK_GBS * world), traffic=None,
                         bytes="band-packed records this build stores, 8 (5 P + 1) bytes per curve and data-touching block",
@@ -526,11 +553,11 @@ def main():
                        "chains": world, "chains_per_gpu": 1, "device_ms_per_step": dev_ms / args.steps},
             "roofline": roofline,
         }
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         c5 = config5_record(bf, w, torch, dist, backend, rank, world, local_rank, max(args.steps, 100), max(args.warmup, 20), barrier)
         if rank == 0:
             out["config5"] = c5
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         cs = chains_sweep(bf, w, local_rank, torch)
         out["chains_sweep"] = cs
         out["multi_chain"] = dict(next(c for c in cs if c["chains"] == 8),
@@ -552,7 +579,7 @@ def main():
         except Exception:
             pass
         out["other_configs"] = other_configs(bf)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # rank 0's host cores, N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # rank 0's host cores, N = 1 only
         out["cpu_baseline"] = cpu_baseline(w)
     if rank == 0:
         print(json.dumps(out))
