@@ -116,6 +116,11 @@ POST_SYMBOLS = {
     "bfmmm_post_pointwise": (C.c_int, [C.POINTER(PostInput), C.c_int32, c_double_p, c_double_p, c_double_p]),
     "bfmmm_post_pointwise_joint": (C.c_int, [C.POINTER(PostInput), C.c_int32, c_double_p, c_double_p, c_double_p]),
     "bfmmm_post_cpo": (C.c_int, [C.POINTER(PostInput), C.c_int32, c_double_p]),
+    "bfmmm_post_curve_loglik": (C.c_int, [C.POINTER(PostInput), C.c_int32, c_double_p]),
+    "bfmmm_post_psis": (C.c_int, [c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
+                                  c_double_p, c_double_p]),
+    "bfmmm_FLOO": (C.c_int, [C.POINTER(PostArgs), C.POINTER(C.c_void_p)]),
+    "bfmmm_MVLOO": (C.c_int, [C.POINTER(PostArgs), C.POINTER(C.c_void_p)]),
     "bfmmm_ConditionalPredictiveOrdinates": (C.c_int, [C.POINTER(PostArgs), C.c_int32, C.POINTER(C.c_void_p)]),
     "bfmmm_post_last_kernel_ms": (C.c_double, []),
     "bfmmm_FSamplePaths": (C.c_int, [C.POINTER(PostArgs), C.c_double, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -760,6 +765,99 @@ def ConditionalPredictiveOrdinates(dir, n_files, basis_degree, boundary_knots, i
         return _result_to_dict(lib, res, None, 0)["value"]
     finally:
         lib.bfmmm_result_free(res)
+
+
+# ---- PSIS-LOO and WAIC over curves (include/bfmmm_post.h) ------------------------------------------------
+_LOO_SCALARS = ("elpd_loo", "se_elpd_loo", "p_loo", "se_p_loo", "looic", "se_looic", "elpd_waic", "se_elpd_waic", "p_waic",
+                "se_p_waic", "waic", "se_waic", "khat_threshold", "n_khat_above")
+
+
+def _loo_dict(d):
+    out = {k: float(np.asarray(d[k]).reshape(-1)[0]) for k in _LOO_SCALARS}
+    out["n_khat_above"] = int(out["n_khat_above"])
+    for k in ("pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "lppd", "pointwise_elpd_waic", "pointwise_p_waic"):
+        out[k] = np.asarray(d[k]).reshape(-1)
+    return out
+
+
+def _loo_call(fn, args):
+    lib = _lib_entry()
+    res = C.c_void_p()
+    _check(fn(C.byref(args.a), C.byref(res)))
+    try:
+        return _loo_dict(_result_to_dict(lib, res, None, 0))
+    finally:
+        lib.bfmmm_result_free(res)
+
+
+def FLOO(dir, n_files, basis_degree, boundary_knots, internal_knots, time, Y, burnin_prop=0.1, X=None, cov_adj=False):
+    """PSIS-LOO and WAIC over curves (leave one curve out, scores integrated out) on the draws t >= floor(burnin_prop T),
+    the ones ConditionalPredictiveOrdinates uses; relative efficiency 1.  Returns a dict: the totals and their standard
+    errors (floats), the number of curves with Pareto k above the threshold (int), the per-curve arrays."""
+    args = _PostArgs(dir, n_files, basis_degree, boundary_knots, internal_knots, time, Y, burnin_prop, X, cov_adj)
+    return _loo_call(_lib_entry().bfmmm_FLOO, args)
+
+
+def MVLOO(dir, n_files, Y, burnin_prop=0.1, X=None, cov_adj=False):
+    """FLOO for the multivariate model (the arguments of MVDIC); the log-density carries the full (P / 2) log 2 pi."""
+    args = _PostArgsMV(dir, n_files, Y, burnin_prop, X, cov_adj)
+    return _loo_call(_lib_entry().bfmmm_MVLOO, args)
+
+
+def post_curve_loglik(Y, B, nu, Phi, Z, chi, sigma, first_kept=0, X=None, eta=None, xi=None, device=0):
+    """bfmmm_post_curve_loglik on in-memory draws (the shapes of post_pointwise): the marginal log-density of every curve
+    under every draw t >= first_kept, scores integrated out, as an (n, kept) array (row i = curve i; its memory is R's
+    S x N column-major log_lik)."""
+    lib = _lib_entry()
+    inp, keep = _post_input(Y, B, nu, Phi, Z, chi, sigma, X, eta, xi, device)
+    n, T = len(Y), nu.shape[2]
+    out = np.zeros((n, T - int(first_kept)))
+    _check(lib.bfmmm_post_curve_loglik(C.byref(inp), int(first_kept), out.ctypes.data_as(c_double_p)))
+    return out
+
+
+def _total_se(v):
+    """sum in curve order and sqrt(n var_{n-1}) (NaN for one curve)"""
+    s = 0.0
+    for x in v:
+        s += float(x)
+    n = len(v)
+    if n < 2:
+        return s, float("nan")
+    mean = s / n
+    q = 0.0
+    for x in v:
+        q += (float(x) - mean) ** 2
+    return s, float(np.sqrt(n * (q / (n - 1))))
+
+
+def loo_totals(pointwise, S):
+    """the totals of per-curve PSIS / WAIC values (keys as FLOO returns them) for S draws per curve"""
+    e_loo, se_loo = _total_se(pointwise["pointwise_elpd_loo"])
+    p_loo, se_ploo = _total_se(pointwise["pointwise_p_loo"])
+    e_waic, se_ewaic = _total_se(pointwise["pointwise_elpd_waic"])
+    p_waic, se_pwaic = _total_se(pointwise["pointwise_p_waic"])
+    with np.errstate(divide="ignore"):
+        thr = float(min(1.0 - 1.0 / np.log10(float(S)), 0.7))
+    out = dict(elpd_loo=e_loo, se_elpd_loo=se_loo, p_loo=p_loo, se_p_loo=se_ploo, looic=-2 * e_loo, se_looic=2 * se_loo,
+               elpd_waic=e_waic, se_elpd_waic=se_ewaic, p_waic=p_waic, se_p_waic=se_pwaic, waic=-2 * e_waic, se_waic=2 * se_ewaic,
+               khat_threshold=thr, n_khat_above=int(np.sum(np.asarray(pointwise["pareto_k"]) > thr)))
+    out.update(pointwise)
+    return out
+
+
+def psis_loo(ll, device=0):
+    """PSIS-LOO and WAIC (relative efficiency 1) of any n x S pointwise log-likelihood matrix (row = unit left out,
+    column = draw) on the device; the dict FLOO returns."""
+    lib = _lib_entry()
+    m = np.ascontiguousarray(ll, dtype=np.float64)
+    if m.ndim != 2:
+        raise ValueError("'ll' must be an n x S matrix")
+    n, S = m.shape
+    outs = [np.zeros(n) for _ in range(6)]
+    _check(lib.bfmmm_post_psis(m.ctypes.data_as(c_double_p), n, S, device, *[o.ctypes.data_as(c_double_p) for o in outs]))
+    pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs))
+    return loo_totals(pw, S)
 
 
 # ---- credible intervals (src/PostProcessing.cpp:99, :3435, :3505) -------------------------------------------------------

@@ -1,0 +1,353 @@
+// Pareto-smoothed importance-sampling leave-one-out (PSIS-LOO) and WAIC of every row of a pointwise log-likelihood matrix
+// (include/bfmmm_post.h): row i = the log-density of curve i under each of S kept draws, draw fastest.  The procedure is
+// psis() / gpdfit() of the R package loo with relative efficiency 1 (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson,
+// Gelman, Yao & Gabry 2024), in the numbered steps DESIGN.md 7b states; everything in fp64.
+//
+// k_post_psis: one workgroup of 256 threads per row.  Every sum is a fixed-order reduction (thread-strided partials, then an
+// LDS tree), the only atomics are integer ones (histogram counts, gather slots) and the gathered set is sorted by a unique
+// key, so two calls give the same bits.
+//   pass 1  min, max, sum of the row
+//   pass 2  sum exp(l - max) (lppd), sum (l - mean)^2 (p_waic), 256-bin histogram of the first digit of the tail key
+//   pass 3+ radix select of the (L + 1)-th largest composite key (the order-preserving 64-bit image of lw, then the draw
+//           index: the stable sort's tie order), one 8-bit digit per pass over the entries that share the chosen prefix,
+//           until the entries at or above the prefix fit the on-chip table (usually after one or two digits)
+//   gather  those entries -> LDS, bitonic sort by (key, index): the tail is the last L, the cutoff the one before
+//   fit     the generalized Pareto fit of the tail: the m <= 30 + sqrt(L) candidate thetas over lanes (a few lanes per
+//           candidate, fixed segments), the weights and k in one thread / one reduction; the smoothed tail -> LDS
+//   last    elpd_loo = logsumexp(lw + l) - logsumexp(lw): non-tail draws from the row, tail draws from the LDS table
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/bfmmm_post.h"
+
+int bfmmm_io_fail(const std::string& m);      // entry_points.cpp: sets bfmmm_entry_last_error
+void bfmmm_post_set_kernel_ms(float ms);      // kernels_post.hip
+
+namespace {
+
+constexpr int NT = 256;                        // threads per workgroup = histogram bins
+constexpr int CAP_MAX = 8192;                  // largest on-chip table of gathered tail candidates
+constexpr long long S_MAX = 1LL << 22;         // kept draws per row in this build (L <= 6144 < CAP_MAX)
+
+struct PsisOut {
+  double *lppd, *elpd_loo, *p_loo, *khat, *elpd_waic, *p_waic;
+};
+
+typedef unsigned long long u64;
+
+// order-preserving image of a double (ascending doubles -> ascending unsigned keys) and its inverse
+__device__ inline u64 okey(double x) {
+  const u64 u = (u64)__double_as_longlong(x);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
+}
+__device__ inline double key_value(u64 k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ULL) : ~k));
+}
+// digit p (0..11) of the 96-bit composite (key, draw index), most significant first
+__device__ inline unsigned digit(u64 key, unsigned idx, int p) {
+  return p < 8 ? (unsigned)(key >> (56 - 8 * p)) & 255u : (idx >> (24 - 8 * (p - 8))) & 255u;
+}
+
+struct OpSum { __device__ double operator()(double a, double b) const { return a + b; } };
+struct OpMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
+struct OpMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } };
+
+// fixed-order tree over the workgroup's 256 partials; every thread gets the result
+template <class Op>
+__device__ double block_reduce(double v, double* red, Op op) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int s = NT / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] = op(red[tid], red[tid + s]);
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// histogram count with the adds of a wave's lanes that share a bin merged (a concentrated row puts most lanes in one bin)
+__device__ inline void hist_add(unsigned* hist, unsigned d, bool on) {
+  u64 pending = __ballot(on);
+  while (pending) {
+    const int leader = __ffsll((long long)pending) - 1;
+    const unsigned dl = (unsigned)__shfl((int)d, leader);
+    const u64 same = __ballot(on && d == dl) & pending;
+    if ((int)__lane_id() == leader) atomicAdd(&hist[dl], (unsigned)__popcll(same));
+    pending &= ~same;
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld, int S, int L, int cap, PsisOut o) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int tid = threadIdx.x, i = blockIdx.x;
+  double* red = sm;                                    // NT
+  double* sTh = red + NT;                              // 2 x 128: candidate thetas and their profile log-likelihoods
+  unsigned* hist = (unsigned*)(sTh + 256);             // NT
+  unsigned* scan = hist + NT;                          // NT
+  unsigned* sI = scan + NT;                            // 8: selected bin, its count, the count above it, gather slots
+  u64* sKey = (u64*)(sI + 8);                          // cap (after the fit: e_j, then the smoothed tail, as doubles)
+  unsigned* sIdx = (unsigned*)(sKey + cap);            // cap
+  double* sE = (double*)sKey;
+  const double* row = ll + (size_t)i * (size_t)ld;
+
+  // ---- pass 1 ----
+  double mx = -INFINITY, mn = INFINITY, sum = 0.0;
+  for (int t = tid; t < S; t += NT) { const double x = row[t]; mx = fmax(mx, x); mn = fmin(mn, x); sum += x; }
+  mx = block_reduce(mx, red, OpMax());
+  mn = block_reduce(mn, red, OpMin());
+  sum = block_reduce(sum, red, OpSum());
+  const double mean = sum / (double)S;
+  const double rmax = -mn;                             // max_t r_t, r_t = -l_t;  lw_t = r_t - rmax
+  const bool select = L >= 5;
+
+  // ---- pass 2 (+ the first digit's histogram) ----
+  hist[tid] = 0;
+  __syncthreads();
+  double se = 0.0, sq = 0.0;
+  for (int b = 0; b < S; b += NT) {
+    const int t = b + tid;
+    const bool on = t < S;
+    const double x = on ? row[t] : mn;
+    if (on) { se += exp(x - mx); const double d = x - mean; sq += d * d; }
+    if (select) hist_add(hist, digit(okey(-x - rmax), (unsigned)t, 0), on);
+  }
+  se = block_reduce(se, red, OpSum());
+  sq = block_reduce(sq, red, OpSum());
+  const double lppd = mx + log(se) - log((double)S);
+  const double p_waic = S > 1 ? sq / (double)(S - 1) : 0.0;
+
+  double khat = INFINITY;
+  bool smooth = false;
+  int base = 0;                                        // sorted position of the first tail entry
+  u64 kc = 0;                                          // composite of the cutoff
+  unsigned ic = 0;
+  double c = 0.0;
+  if (select) {
+    // ---- radix select: the entries at or above a prefix of the composite key, until they fit the table ----
+    u64 kmask = 0, kval = 0;
+    unsigned imask = 0, ival = 0, above = 0;
+    for (int p = 0; p < 12; ++p) {
+      if (p > 0) {
+        __syncthreads();
+        hist[tid] = 0;
+        __syncthreads();
+        for (int b = 0; b < S; b += NT) {
+          const int t = b + tid;
+          bool on = t < S;
+          u64 key = 0;
+          if (on) { key = okey(-row[t] - rmax); on = (key & kmask) == kval && ((unsigned)t & imask) == ival; }
+          hist_add(hist, digit(key, (unsigned)t, p), on);
+        }
+      }
+      __syncthreads();
+      // inclusive suffix sums of the bins; the bin holding rank need = L + 1 - above from the top
+      scan[tid] = hist[tid];
+      __syncthreads();
+      for (int off = 1; off < NT; off <<= 1) {
+        const unsigned v = (tid + off < NT) ? scan[tid + off] : 0u;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+      }
+      const unsigned need = (unsigned)(L + 1) - above;
+      if (scan[tid] >= need && scan[tid] - hist[tid] < need) { sI[0] = (unsigned)tid; sI[1] = hist[tid]; sI[2] = scan[tid] - hist[tid]; }
+      __syncthreads();
+      const unsigned sel = sI[0], inbin = sI[1];
+      above += sI[2];
+      if (p < 8) { kmask |= 255ULL << (56 - 8 * p); kval |= (u64)sel << (56 - 8 * p); }
+      else { imask |= 255u << (24 - 8 * (p - 8)); ival |= sel << (24 - 8 * (p - 8)); }
+      if (above + inbin <= (unsigned)cap) break;
+    }
+    // ---- gather every entry at or above the prefix, sort by (key, index) ----
+    if (tid == 0) sI[3] = 0;
+    __syncthreads();
+    for (int t = tid; t < S; t += NT) {
+      const u64 key = okey(-row[t] - rmax), km = key & kmask;
+      if (km > kval || (km == kval && ((unsigned)t & imask) >= ival)) {
+        const unsigned s = atomicAdd(&sI[3], 1u);
+        if (s < (unsigned)cap) { sKey[s] = key; sIdx[s] = (unsigned)t; }      // s < cap by the selection; kept in bounds regardless
+      }
+    }
+    __syncthreads();
+    const int G = min((int)sI[3], cap);
+    int npow = 1;
+    while (npow < G) npow <<= 1;
+    for (int e = G + tid; e < npow; e += NT) { sKey[e] = 0; sIdx[e] = 0; }      // below every finite key
+    __syncthreads();
+    for (int k = 2; k <= npow; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int e = tid; e < npow; e += NT) {
+          const int f = e ^ j;
+          if (f > e) {
+            const u64 ka = sKey[e], kb = sKey[f];
+            const unsigned ia = sIdx[e], ib = sIdx[f];
+            const bool gt = ka > kb || (ka == kb && ia > ib);
+            if (gt == ((e & k) == 0)) { sKey[e] = kb; sKey[f] = ka; sIdx[e] = ib; sIdx[f] = ia; }
+          }
+        }
+        __syncthreads();
+      }
+    base = npow - L;
+    kc = sKey[base - 1];
+    ic = sIdx[base - 1];
+    c = key_value(kc);
+    const double x1 = key_value(sKey[base]), xL = key_value(sKey[npow - 1]);
+    __syncthreads();
+    if (!(xL - x1 < DBL_EPSILON / 100)) {
+      // ---- generalized Pareto fit of e_j = exp(x_j) - exp(c), ascending, N = L ----
+      const double ec = exp(c);
+      for (int j = tid; j < L; j += NT) sE[base + j] = exp(key_value(sKey[base + j])) - ec;     // in place, own entries
+      __syncthreads();
+      const double* e = sE + base;
+      const int N = L;
+      const int m = 30 + (int)floor(sqrt((double)N));
+      const double xstar = e[(int)floor(N / 4.0 + 0.5) - 1], eN = e[N - 1];
+      const int nseg = max(1, NT / m);
+      {
+        const int j = tid / nseg, s = tid - j * nseg;
+        double part = 0.0;
+        if (j < m) {
+          const double th = 1.0 / eN + (1.0 - sqrt((double)m / ((j + 1) - 0.5))) / (3.0 * xstar);
+          const int l0 = (int)((long long)N * s / nseg), l1 = (int)((long long)N * (s + 1) / nseg);
+          for (int l = l0; l < l1; ++l) part += log1p(-th * e[l]);
+          if (s == 0) sTh[j] = th;
+        }
+        red[tid] = part;
+      }
+      __syncthreads();
+      if (tid < m) {
+        double kap = 0.0;
+        for (int s = 0; s < nseg; ++s) kap += red[tid * nseg + s];
+        kap /= (double)N;
+        sTh[128 + tid] = (double)N * (log(-sTh[tid] / kap) - kap - 1.0);
+      }
+      __syncthreads();
+      if (tid == 0) {
+        double lmax = -INFINITY;
+        for (int j = 0; j < m; ++j) { const double v = sTh[128 + j]; lmax = (isnan(lmax) || isnan(v)) ? NAN : fmax(lmax, v); }
+        double z = 0.0;
+        for (int j = 0; j < m; ++j) z += exp(sTh[128 + j] - lmax);
+        const double lse = lmax + log(z);
+        double th = 0.0;
+        for (int j = 0; j < m; ++j) th += exp(sTh[128 + j] - lse) * sTh[j];
+        red[NT - 1] = th;      // handed over through the reduction scratch (read before its next use)
+      }
+      __syncthreads();
+      const double that = red[NT - 1];
+      __syncthreads();
+      double kp = 0.0;
+      for (int l = tid; l < N; l += NT) kp += log1p(-that * e[l]);
+      const double kk = block_reduce(kp, red, OpSum()) / (double)N;
+      const double sigma = -kk / that;
+      khat = ((double)N * kk + 5.0) / ((double)N + 10.0);
+      if (isnan(khat)) khat = INFINITY;
+      if (isfinite(khat)) {
+        smooth = true;
+        for (int j = tid; j < L; j += NT) {
+          const double pj = (j + 0.5) / (double)L;
+          sE[base + j] = log(sigma * expm1(-khat * log1p(-pj)) / khat + ec);
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  // ---- last pass: logsumexp(lw + l) - logsumexp(lw), lw <- min(lw, 0) ----
+  double sh1 = mn, sh2 = 0.0;
+  if (smooth) {
+    double a1 = -INFINITY, a2 = -INFINITY;
+    for (int j = tid; j < L; j += NT) {
+      const double w = fmin(sE[base + j], 0.0);
+      a1 = fmax(a1, w + row[sIdx[base + j]]);
+      a2 = fmax(a2, w);
+    }
+    sh1 = fmax(mn, block_reduce(a1, red, OpMax()));
+    sh2 = fmax(c, block_reduce(a2, red, OpMax()));
+  }
+  double s1 = 0.0, s2 = 0.0;
+  for (int t = tid; t < S; t += NT) {
+    const double x = row[t], lw = -x - rmax;
+    if (smooth) {
+      const u64 key = okey(lw);
+      if (key > kc || (key == kc && (unsigned)t > ic)) continue;     // a tail draw: taken from the table below
+    }
+    const double w = fmin(lw, 0.0);
+    s1 += exp(w + x - sh1);
+    s2 += exp(w - sh2);
+  }
+  if (smooth)
+    for (int j = tid; j < L; j += NT) {
+      const double w = fmin(sE[base + j], 0.0);
+      s1 += exp(w + row[sIdx[base + j]] - sh1);
+      s2 += exp(w - sh2);
+    }
+  s1 = block_reduce(s1, red, OpSum());
+  s2 = block_reduce(s2, red, OpSum());
+  if (tid == 0) {
+    const double elpd = (sh1 + log(s1)) - (sh2 + log(s2));
+    o.lppd[i] = lppd;
+    o.elpd_loo[i] = elpd;
+    o.p_loo[i] = lppd - elpd;
+    o.khat[i] = khat;
+    o.elpd_waic[i] = lppd - p_waic;
+    o.p_waic[i] = p_waic;
+  }
+}
+
+}  // namespace
+
+// the PSIS / WAIC pass over n rows of S values on the current device (row i at d_ll + i * ld); out: six host arrays of n
+// (lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic).  Shared by bfmmm_post_psis and the file-based entry points, which
+// keep the matrix on the device.
+int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]) {
+  if (S > S_MAX)
+    return bfmmm_io_fail("bfmmm_post_psis: at most 4194304 (2^22) kept draws per curve in this build, got " + std::to_string(S));
+  const int L = (int)std::ceil(std::min(0.2 * S, 3.0 * std::sqrt((double)S)));
+  int cap = 256;
+  while (cap < 2 * (L + 1) && cap < CAP_MAX) cap <<= 1;
+  double* d_out = nullptr;
+  if (hipMalloc(&d_out, sizeof(double) * 6 * (size_t)n) != hipSuccess) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_psis: device allocation failed"); }
+  PsisOut o{d_out, d_out + n, d_out + 2 * (size_t)n, d_out + 3 * (size_t)n, d_out + 4 * (size_t)n, d_out + 5 * (size_t)n};
+  const size_t lds = (size_t)(NT + 256) * sizeof(double) + (size_t)(3 * NT + 8) * sizeof(unsigned) + (size_t)cap * (sizeof(u64) + sizeof(unsigned));
+  (void)hipFuncSetAttribute((const void*)k_post_psis, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+  (void)hipEventRecord(e0, 0);
+  hipLaunchKernelGGL(k_post_psis, dim3(n), dim3(NT), lds, 0, d_ll, ld, S, L, cap, o);
+  (void)hipEventRecord(e1, 0);
+  const bool ran = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
+  if (ran) { float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1); bfmmm_post_set_kernel_ms(ms); }
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  std::vector<double> h(6 * (size_t)n);
+  const bool copied = ran && hipMemcpy(h.data(), d_out, sizeof(double) * h.size(), hipMemcpyDeviceToHost) == hipSuccess;
+  (void)hipFree(d_out);
+  if (!copied) return bfmmm_io_fail("bfmmm_post_psis: kernel launch or copy back failed");
+  for (int q = 0; q < 6; ++q)
+    if (out[q]) std::copy(h.begin() + (size_t)q * n, h.begin() + (size_t)(q + 1) * n, out[q]);
+  return 0;
+}
+
+extern "C" int bfmmm_post_psis(const double* ll, int32_t n, int32_t S, int32_t device, double* lppd, double* elpd_loo, double* p_loo,
+                               double* pareto_k, double* elpd_waic, double* p_waic) {
+  if (!ll || !lppd || !elpd_loo || !p_loo || !pareto_k || !elpd_waic || !p_waic) return bfmmm_io_fail("bfmmm_post_psis: null argument");
+  if (n < 1 || S < 1) return bfmmm_io_fail("bfmmm_post_psis: bad dimensions");
+  if (S > S_MAX)
+    return bfmmm_io_fail("bfmmm_post_psis: at most 4194304 (2^22) kept draws per curve in this build, got " + std::to_string(S));
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return bfmmm_io_fail("bfmmm_post_psis: no HIP device (the MI355X library has no CPU path)");
+  if (hipSetDevice(device) != hipSuccess) return bfmmm_io_fail("bfmmm_post_psis: cannot select the device");
+  double* d_ll = nullptr;
+  const size_t bytes = sizeof(double) * (size_t)n * (size_t)S;
+  if (hipMalloc(&d_ll, bytes) != hipSuccess) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_psis: device allocation failed"); }
+  if (hipMemcpy(d_ll, ll, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_ll); return bfmmm_io_fail("bfmmm_post_psis: copy failed"); }
+  double* const out[6] = {lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic};
+  const int rc = post_psis_device(d_ll, S, n, S, out);
+  (void)hipFree(d_ll);
+  return rc;
+}

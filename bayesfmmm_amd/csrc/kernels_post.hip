@@ -467,8 +467,15 @@ struct DevBufs {
 
 }  // namespace
 
+int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]);      // kernels_loo.hip
+
+void bfmmm_post_set_kernel_ms(float ms) { g_last_kernel_ms = ms; }
+
+// The CPO pass (cpo, ll_kept or loo set) leaves the marginal log-density of every curve under every kept draw in the device
+// matrix cpo_ll[i][t]; from it: cpo -> k_post_cpo_reduce (log CPO), ll_kept -> the n x kept block copied out (draw fastest),
+// loo -> the PSIS / WAIC pass on the device matrix (kernels_loo.hip; six arrays of n).
 static int post_impl(const bfmmm_post_input* in, int32_t first_kept, double* llik, double* mean_pdf, double* mean_fit, double* mean_joint,
-                     double* cpo = nullptr) {
+                     double* cpo = nullptr, double* ll_kept = nullptr, double* const* loo = nullptr) {
   if (!in || !in->offsets || !in->y || (!in->B && !in->identity_basis) || !in->nu || !in->Phi || !in->Z || !in->chi || !in->sigma)
     return bfmmm_io_fail("bfmmm_post_pointwise: null argument");
   const int n = in->n, K = in->K, P = in->P, M = in->M, D = in->X ? in->D : 0, T = in->T;
@@ -549,7 +556,7 @@ static int post_impl(const bfmmm_post_input* in, int32_t first_kept, double* lli
             db.put(&d_fit, (const double*)nullptr, (size_t)n_obs) && db.put(&d_joint, (const double*)nullptr, (size_t)n);
   if (ok && D > 0) ok = db.put((double**)&a.X, in->X, (size_t)n * D) && db.put((double**)&a.thetaX, thetaX.data(), thetaX.size());
   if (!ok) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_pointwise: device allocation or copy failed"); }
-  if (cpo) {
+  if (cpo || ll_kept || loo) {
     if (M < 1 || M > CPO_MMAX || K > KMAXP) return bfmmm_io_fail("bfmmm_post_cpo: 1 <= M <= 16 and K <= 16 in this build");
     long long ni_max = 1;
     for (int i = 0; i < n; ++i) ni_max = std::max<long long>(ni_max, in->offsets[i + 1] - in->offsets[i]);
@@ -566,13 +573,18 @@ static int post_impl(const bfmmm_post_input* in, int32_t first_kept, double* lli
     (void)hipEventCreate(&c0); (void)hipEventCreate(&c1);
     (void)hipEventRecord(c0, 0);
     hipLaunchKernelGGL(k_post_cpo, dim3(n), dim3(256), lds_c, 0, a, d_cll, Gc, NIPX);
-    hipLaunchKernelGGL(k_post_cpo_reduce, dim3((n + 255) / 256), dim3(256), 0, 0, a, d_cll, d_cpo);
+    if (cpo) hipLaunchKernelGGL(k_post_cpo_reduce, dim3((n + 255) / 256), dim3(256), 0, 0, a, d_cll, d_cpo);
     (void)hipEventRecord(c1, 0);
     const bool ran_c = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
     if (ran_c) (void)hipEventElapsedTime(&g_last_kernel_ms, c0, c1);
     (void)hipEventDestroy(c0); (void)hipEventDestroy(c1);
-    if (!ran_c || hipMemcpy(cpo, d_cpo, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess)
+    if (!ran_c || (cpo && hipMemcpy(cpo, d_cpo, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess))
       return bfmmm_io_fail("bfmmm_post_cpo: kernel launch or copy back failed");
+    const size_t kept = (size_t)(T - first_kept);
+    if (ll_kept && hipMemcpy2D(ll_kept, kept * sizeof(double), d_cll + first_kept, (size_t)T * sizeof(double), kept * sizeof(double), (size_t)n,
+                               hipMemcpyDeviceToHost) != hipSuccess)
+      return bfmmm_io_fail("bfmmm_post_curve_loglik: copy back failed");
+    if (loo) return post_psis_device(d_cll + first_kept, T, n, (int)kept, loo);
     return 0;
   }
   const size_t lds = ((size_t)GMAX * (P | 1) + (size_t)GMAX * WMAX + 2048 + 64 + BL_MAX + 8) * sizeof(double);
@@ -607,6 +619,18 @@ extern "C" int bfmmm_post_pointwise_joint(const bfmmm_post_input* in, int32_t fi
 extern "C" int bfmmm_post_cpo(const bfmmm_post_input* in, int32_t first_kept, double* log_cpo) {
   if (!log_cpo) return bfmmm_io_fail("bfmmm_post_cpo: null argument");
   return post_impl(in, first_kept, nullptr, nullptr, nullptr, nullptr, log_cpo);
+}
+
+extern "C" int bfmmm_post_curve_loglik(const bfmmm_post_input* in, int32_t first_kept, double* ll) {
+  if (!ll) return bfmmm_io_fail("bfmmm_post_curve_loglik: null argument");
+  return post_impl(in, first_kept, nullptr, nullptr, nullptr, nullptr, nullptr, ll);
+}
+
+// the CPO pass and the PSIS / WAIC pass on its matrix, which stays on the device (bfmmm_FLOO, bfmmm_MVLOO)
+int post_loo_pointwise(const bfmmm_post_input* in, int32_t first_kept, double* const out[6]) {
+  if (in && in->T - first_kept > (1 << 22))
+    return bfmmm_io_fail("bfmmm_post_psis: at most 4194304 (2^22) kept draws per curve in this build, got " + std::to_string(in->T - first_kept));
+  return post_impl(in, first_kept, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 // device time of the last bfmmm_post_pointwise call's two kernels (HIP events on the launch stream), for measurement

@@ -2,8 +2,10 @@
 // observation under every draw on the device (bfmmm_post_pointwise, kernels_post.hip) and apply the reference's formulas.
 #include "../../include/bfmmm_post.h"
 
+#include <algorithm>
 #include <cmath>
 #include <string>
+#include <utility>
 #include <vector>
 
 int bfmmm_io_fail(const std::string& m);
@@ -346,6 +348,93 @@ extern "C" int bfmmm_MVBIC(const bfmmm_post_args* a, double* out) {
   if (mv_loglik_at_means(a, dr, &ll)) return 1;
   *out = 2 * ll - std::log((double)a->n_funct) * n_params(dr, a->X != nullptr, a->cov_adj != 0);      // :5560 (log(Y.n_rows))
   return 0;
+}
+
+// ---- PSIS-LOO and WAIC over curves (bfmmm_FLOO, bfmmm_MVLOO) ---------------------------------------------------------
+int post_loo_pointwise(const bfmmm_post_input* in, int32_t first_kept, double* const out[6]);      // kernels_post.hip
+
+namespace {
+
+// totals of the per-curve values, summed in curve order: estimate, se = sqrt(n var_{n-1}) (NaN for one curve)
+void total_se(const std::vector<double>& v, double* est, double* se) {
+  const size_t n = v.size();
+  double s = 0.0;
+  for (double x : v) s += x;
+  double q = 0.0;
+  const double mean = s / (double)n;
+  for (double x : v) q += (x - mean) * (x - mean);
+  *est = s;
+  *se = n > 1 ? std::sqrt((double)n * (q / (double)(n - 1))) : std::nan("");
+}
+
+int loo_result(const bfmmm_post_input& in, int first, bfmmm_result** out) {
+  const size_t n = (size_t)in.n;
+  std::vector<double> lppd(n), elpd(n), ploo(n), khat(n), ewaic(n), pwaic(n);
+  double* const pw[6] = {lppd.data(), elpd.data(), ploo.data(), khat.data(), ewaic.data(), pwaic.data()};
+  if (post_loo_pointwise(&in, first, pw)) return 1;
+  const double S = (double)(in.T - first);
+  double e_loo, se_loo, p_loo, se_ploo, e_waic, se_waic, p_waic, se_pwaic;
+  total_se(elpd, &e_loo, &se_loo);
+  total_se(ploo, &p_loo, &se_ploo);
+  total_se(ewaic, &e_waic, &se_waic);
+  total_se(pwaic, &p_waic, &se_pwaic);
+  const double thr = std::min(1.0 - 1.0 / std::log10(S), 0.7);
+  double above = 0.0;
+  for (double k : khat) above += (k > thr) ? 1.0 : 0.0;
+  bfmmm_result* r = bfmmm_result_create();
+  const int64_t one = 1, nn = (int64_t)n;
+  const std::pair<const char*, double> sc[] = {
+      {"elpd_loo", e_loo}, {"se_elpd_loo", se_loo}, {"p_loo", p_loo}, {"se_p_loo", se_ploo}, {"looic", -2 * e_loo}, {"se_looic", 2 * se_loo},
+      {"elpd_waic", e_waic}, {"se_elpd_waic", se_waic}, {"p_waic", p_waic}, {"se_p_waic", se_pwaic}, {"waic", -2 * e_waic},
+      {"se_waic", 2 * se_waic}, {"khat_threshold", thr}, {"n_khat_above", above}};
+  for (const auto& e : sc) bfmmm_result_set(r, e.first, &e.second, 1, &one, 1);
+  const std::pair<const char*, const std::vector<double>*> pv[] = {
+      {"pointwise_elpd_loo", &elpd}, {"pointwise_p_loo", &ploo}, {"pareto_k", &khat}, {"lppd", &lppd},
+      {"pointwise_elpd_waic", &ewaic}, {"pointwise_p_waic", &pwaic}};
+  for (const auto& e : pv) bfmmm_result_set(r, e.first, e.second->data(), nn, &nn, 1);
+  *out = r;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int bfmmm_FLOO(const bfmmm_post_args* a, bfmmm_result** out) {
+  if (!out) return bfmmm_io_fail("null argument");
+  // the checks of ConditionalPredictiveOrdinates, in its order
+  if (a && a->n_files <= 0) return bfmmm_io_fail("'n_files' must be greater than 0");
+  if (a && (a->burnin_prop < 0 || a->burnin_prop >= 1)) return bfmmm_io_fail("'burnin_prop' must be between 0 and 1");
+  if (check(a, true)) return 1;
+  Draws dr;
+  if (load_draws(a, dr)) return 1;
+  bfmmm_post_input in{};
+  in.n = dr.n; in.K = dr.K; in.P = dr.P; in.M = dr.M; in.D = dr.D;
+  in.offsets = a->offsets; in.y = a->y; in.B = dr.B.data(); in.X = a->X;
+  in.T = dr.T; in.nu = dr.nu.data(); in.Phi = dr.Phi.data(); in.Z = dr.Z.data(); in.chi = dr.chi.data(); in.sigma = dr.sigma.data();
+  in.eta = dr.eta.empty() ? nullptr : dr.eta.data();
+  in.xi = dr.xi.empty() ? nullptr : dr.xi.data();
+  in.device = a->device;
+  return loo_result(in, (int)std::floor(a->burnin_prop * dr.T), out);      // the kept draws of CPO (CalculateLikelihood.h:361)
+}
+
+extern "C" int bfmmm_MVLOO(const bfmmm_post_args* a, bfmmm_result** out) {
+  if (!out) return bfmmm_io_fail("null argument");
+  if (check(a, true, true)) return 1;
+  Draws dr;
+  if (load_draws(a, dr, true)) return 1;
+  const int n = a->n_funct, P = a->P;
+  std::vector<int64_t> off((size_t)n + 1);
+  for (int i = 0; i <= n; ++i) off[(size_t)i] = (int64_t)i * P;
+  std::vector<double> y((size_t)n * P);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < P; ++j) y[(size_t)i * P + j] = a->y[(size_t)i + (size_t)n * j];
+  bfmmm_post_input in{};
+  in.n = n; in.K = dr.K; in.P = P; in.M = dr.M; in.D = dr.D;
+  in.offsets = off.data(); in.y = y.data(); in.B = nullptr; in.identity_basis = 1; in.X = a->X;
+  in.T = dr.T; in.nu = dr.nu.data(); in.Phi = dr.Phi.data(); in.Z = dr.Z.data(); in.chi = dr.chi.data(); in.sigma = dr.sigma.data();
+  in.eta = dr.eta.empty() ? nullptr : dr.eta.data();
+  in.xi = dr.xi.empty() ? nullptr : dr.xi.data();
+  in.device = a->device;
+  return loo_result(in, (int)std::floor(a->burnin_prop * dr.T), out);
 }
 
 // ---- credible intervals: SigmaCI, ZCI, FMeanCI -----------------------------------------------------------------------

@@ -56,7 +56,17 @@ int bfmmm_post_pointwise_joint(const bfmmm_post_input* in, int32_t first_kept, d
  * log-density of y_i under each kept draw (scores integrated out; the rank-M form of the reference's n_i x n_i
  * log_det_sympd / inv_sympd) and the harmonic mean in the reference's stabilised form.  log_cpo has n entries. */
 int bfmmm_post_cpo(const bfmmm_post_input* in, int32_t first_kept, double* log_cpo);
-/* device time (ms, HIP events) of the kernels of the last bfmmm_post_pointwise call of this process: measurement aid */
+/* the matrix behind bfmmm_post_cpo: the marginal log-density of curve i under kept draw t (scores integrated out), n x kept
+ * values with the draw fastest (ll[i * kept + t - first_kept]; R's S x N column-major log_lik layout).  Works with
+ * identity_basis = 1.  Limits of the CPO pass: K <= 16, 1 <= M <= 16, at most 1024 observations per curve. */
+int bfmmm_post_curve_loglik(const bfmmm_post_input* in, int32_t first_kept, double* ll);
+/* Pareto-smoothed importance-sampling leave-one-out and WAIC of every row of an n x S host matrix (draw fastest), relative
+ * efficiency 1: six arrays of n.  pareto_k is +inf where the tail is too short (S < 21) or flat.  At most
+ * 2^22 draws per row in this build. */
+int bfmmm_post_psis(const double* ll, int32_t n, int32_t S, int32_t device, double* lppd, double* elpd_loo, double* p_loo,
+                    double* pareto_k, double* elpd_waic, double* p_waic);
+/* device time (ms, HIP events) of the kernels of the last post-processing pass of this process (the pointwise, CPO or PSIS
+ * pass): measurement aid */
 double bfmmm_post_last_kernel_ms(void);
 
 typedef struct {
@@ -97,6 +107,14 @@ int bfmmm_post_sample_paths(const bfmmm_post_input* in, int32_t first_kept, uint
  * simultaneous band over all columns (src/PostProcessing.cpp:6829-6855) */
 int bfmmm_post_table_bands(const double* V, int32_t T, int32_t ncol, double alpha, int32_t simultaneous, int32_t device,
                            double* upper, double* mid, double* lower);
+/* PSIS-LOO and WAIC over curves (leave one curve out, scores integrated out) from the on-disk batches, over the draws
+ * t >= floor(burnin_prop T) that CPO uses; the matrix stays on the device.  Not reference functions; the arguments and checks
+ * are those of ConditionalPredictiveOrdinates (functional) and MVDIC (multivariate; full (P / 2) log 2 pi).  Result
+ * elements, one entry each: elpd_loo, se_elpd_loo, p_loo, se_p_loo, looic, se_looic, elpd_waic, se_elpd_waic, p_waic,
+ * se_p_waic, waic, se_waic, khat_threshold, n_khat_above; n entries each: pointwise_elpd_loo, pointwise_p_loo, pareto_k,
+ * lppd, pointwise_elpd_waic, pointwise_p_waic. */
+int bfmmm_FLOO(const bfmmm_post_args* a, bfmmm_result** out);
+int bfmmm_MVLOO(const bfmmm_post_args* a, bfmmm_result** out);
 /* multivariate model: MVLLik (src/PostProcessing.cpp:6099), MVDIC (:5789), MVAIC (:5116), MVBIC (:5452) */
 int bfmmm_MVLLik(const bfmmm_post_args* a, bfmmm_result** out);
 int bfmmm_MVDIC(const bfmmm_post_args* a, double* out);
