@@ -12,6 +12,7 @@
 #include <chrono>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 namespace bfmmm {
@@ -26,6 +27,7 @@ int curve_blocks(int n, int P);
 void prepare_curve_kernels();
 void prepare_sweep_kernels();
 void launch_pair_gram(const Ctx& c, int do_pg, int NKS, int KS, hipStream_t st);
+size_t pair_gram_lds_bytes(const Dims& d, int KS);
 void launch_pg_reduce(const Ctx& c, int NKS, hipStream_t st);
 bool pgp_geometry(const Dims& d, int nch, int KS, int NKS, PgPack& g);
 size_t pgp_pack_doubles(const PgPack& g);
@@ -74,8 +76,8 @@ static const char* kFamNames[FAM_COUNT] = {"total", "curve_z", "pair_gram", "fac
 struct bfmmm_handle {
   bfmmm_config cfg;
   int device = 0;
-  hipStream_t st = nullptr, st2 = nullptr;
-  hipEvent_t evA = nullptr, evB = nullptr, evC = nullptr, evD = nullptr;
+  hipStream_t st = nullptr;
+  hipEvent_t evA = nullptr;
   Ctx c;                       // template context (full MD); its per-chain pointers are those of chain 0 of the batch
   int nch = 1;                 // chains in the batch (bfmmm_create_batch), all advanced in lockstep by bfmmm_run
   int sel = 0;                 // the chain the state / chain accessors address (bfmmm_select_chain)
@@ -89,38 +91,24 @@ struct bfmmm_handle {
   uint32_t* status_host = nullptr;     // pinned, host-mapped: the chains' status words after a run
   uint32_t* status_dev = nullptr;      // its device address (written by the run's last kernel)
   size_t pg_part_doubles = 0;
-  // graph cache for the last (mask, md, seed, chain)
-  // Captured graphs of a run, one set per SUB-BATCH (run_impl splits a chain batch over up to MAX_SUB streams):
-  //   gN  GRAPH_UNROLL full iterations (amortises the fixed cost of a graph launch);
-  //   fused runs (chi kernel of iteration i also runs the Z update of i + 1): gFN = GRAPH_UNROLL bodies [pair_gram .. chi + Z],
-  //   gL = the closing iteration without the Z part;
-  //   gR / gFR = the remainder of a run after the unrolled graphs, as ONE graph of rem / remF iterations
-  //   (one per remainder length, kept: a warm-up run of another length between prepare_run and the run does not evict the run's graph)
-  static constexpr int NREM = 10;        // = GRAPH_UNROLL
-  struct GraphSet {
-    hipGraphExec_t gN = nullptr, gFN = nullptr, gL = nullptr;
-    hipGraphExec_t gR[NREM] = {}, gFR[NREM] = {};
-    hipGraphExec_t gW = nullptr;      // a WHOLE short run (first Z, bodies, closing iteration, flush) of gW_n iterations
-    int gW_n = 0;
-    template <typename F> void each(F f) { f(&gN); f(&gFN); f(&gL); f(&gW); for (int r = 0; r < NREM; ++r) { f(&gR[r]); f(&gFR[r]); } }
-  };
   static constexpr int MAX_SUB = 4;
-  // packed partial tiles of k_pair_gram_pack, one buffer per sub-batch stream (+ one for the whole batch on one stream)
   // snapshot of the chains' work state for the dry launch of freshly captured graphs (bfmmm_prepare_run)
   char* dry_snap = nullptr;
   size_t dry_snap_bytes = 0;
+  // packed partial tiles of k_pair_gram_pack, one buffer per sub-batch stream (+ one for the whole batch on one stream)
   double* pg_pack[MAX_SUB + 1] = {};
   size_t pg_pack_doubles[MAX_SUB + 1] = {};
-  GraphSet gs[MAX_SUB];
   hipStream_t sub_st[MAX_SUB] = {nullptr, nullptr, nullptr, nullptr};     // [0] = st
   hipEvent_t sub_ev[MAX_SUB] = {nullptr, nullptr, nullptr, nullptr};
-  int g_nsub = 1;
-  int g_pack_mode = 0;
-  uint32_t g_mask = 0; int g_md = -1; uint64_t g_seed = 0; uint32_t g_chain = 0;
+  // Captured graphs of runs with the key below, oldest first: (sub-batch, kind, repetitions) -> graph (run_impl)
+  struct CachedGraph { int sub, kind, reps; hipGraphExec_t g; };
+  std::vector<CachedGraph> graphs;
+  using GraphKey = std::tuple<uint32_t, int, uint64_t, uint32_t, int, int>;      // (mask, MD, seed, chain, nsub, exact instances)
+  GraphKey g_key;
+  bool g_valid = false;                // the cached graphs were captured for g_key
   int last_md = -1;
   int64_t tab_key = -1;                // (MD, mask) the step tables of k_sweep_chain were built for
   int launch_error = 0;
-  bool g_valid = false;                // the captured graphs match (g_mask, g_md, g_seed, g_chain)
   int slot_base = 0;                   // chain slot of iteration i is i - slot_base (bfmmm_set_slot_base)
   double* tt_save = nullptr;            // state saved across a tempered-transition block
   std::vector<double> B_host;           // bfmmm_create_from_basis: the caller's basis rows (bfmmm_get_basis)
@@ -150,15 +138,15 @@ static int dalloc(bfmmm_handle* h, T** p, size_t count) {
   return 0;
 }
 
+static void drop_graphs(bfmmm_handle* h) {
+  for (const auto& e : h->graphs) (void)hipGraphExecDestroy(e.g);
+  h->graphs.clear();
+  h->g_valid = false;
+}
+
 // Per-chain buffers come out of one arena per chain: the requests are collected first, then ONE allocation of
 // nch * stride bytes is made and the pointers of chain 0 are handed out; chain q's copy of every buffer sits q * stride
 // bytes further (Ctx::chain_bytes, chain_ctx in model.hpp).
-static std::vector<hipGraphExec_t*> graph_slots(bfmmm_handle::GraphSet& g) {
-  std::vector<hipGraphExec_t*> v;
-  g.each([&](hipGraphExec_t* p) { v.push_back(p); });
-  return v;
-}
-
 struct ArenaReq { void* slot; size_t bytes; };
 template <typename T>
 static void areq(std::vector<ArenaReq>& v, T** p, size_t count) { v.push_back({(void*)p, std::max<size_t>(count, 1) * sizeof(T)}); }
@@ -207,7 +195,7 @@ static void set_md(Dims& d, int MD) {
   d.NT = d.RT * d.CTG + d.AT * d.CTS;
 }
 
-static void pg_geometry(const Dims& d, int& NTG, int& NKS, int& KS) {
+static void pg_geometry(const Dims& d, int& NKS, int& KS) {
   // k-slices of the pair-Gram contraction.  LDS doubles per curve: the raw weight row, the record columns and,
   // for the G workgroups, the pair-weight row (k_pair_gram); a workgroup never stages more than 96 KB.
   const int row_g = (d.K + d.MD + 1) + 16 + (d.NZZ + d.NCC + 1);
@@ -220,7 +208,6 @@ static void pg_geometry(const Dims& d, int& NTG, int& NKS, int& KS) {
   KS = (KS + 15) / 16 * 16;                  // MFMA k-slots are taken in trips of 4 steps per slot (two 16-byte LDS reads)
   KS = std::min(KS, ks_cap);
   NKS = (d.n + KS - 1) / KS;
-  NTG = 1;
 }
 
 // a basis supplied by the caller (bfmmm_create_from_basis): rows of B, its band, the penalty of the nu prior
@@ -318,11 +305,10 @@ static int create_impl(const bfmmm_config* cfg, int device, const double* y, con
   h->nch = n_chains;
   HIPCHK(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
   HIPCHK(hipEventCreate(&h->evA));
-  HIPCHK(hipEventCreate(&h->evB));
-  HIPCHK(hipEventCreate(&h->evC));
-  HIPCHK(hipEventCreate(&h->evD));
   HIPCHK(hipEventCreate(&h->ev0));
   HIPCHK(hipEventCreate(&h->ev1));
+  HIPCHK(hipHostMalloc((void**)&h->status_host, sizeof(uint32_t) * (size_t)n_chains, hipHostMallocMapped));
+  if (hipHostGetDevicePointer((void**)&h->status_dev, h->status_host, 0) != hipSuccess) { (void)hipGetLastError(); h->status_dev = nullptr; }
   Ctx& c = h->c;
   memset(&c, 0, sizeof c);
   Dims& d = c.d;
@@ -358,8 +344,8 @@ static int create_impl(const bfmmm_config* cfg, int device, const double* y, con
   areq(ar, &c.dyn, 1);
   areq(ar, &c.Z, (size_t)n * K); areq(ar, &c.chi, (size_t)n * M); areq(ar, &c.theta, (size_t)K * (M + 1) * P);
   areq(ar, &c.delta, (size_t)K * M); areq(ar, &c.Aa, (size_t)K * 2); areq(ar, &c.gamma, (size_t)K * P * M);
-  int NTG, NKS, KS;
-  pg_geometry(d, NTG, NKS, KS);
+  int NKS, KS;
+  pg_geometry(d, NKS, KS);
   h->pg_part_doubles = (size_t)NKS * d.NT * 256;
   areq(ar, &c.logz_part, (size_t)c.nblk_curve * K); areq(ar, &c.rss_part, c.nblk_curve);
   // (+ 2 doubles on H and Cmat: for odd P the last row thread of k_sweep_chain reads a 16-byte pair that starts at the last
@@ -505,10 +491,7 @@ extern "C" int bfmmm_set_covariates(bfmmm_handle* h, const double* X, int D, int
     HIPCHK(copy_sync(h, cq.delta_xi, ones.data(), sizeof(double) * K * M * D, hipMemcpyHostToDevice));
     HIPCHK(copy_sync(h, cq.A_xi, ones.data(), sizeof(double) * K * 2 * D, hipMemcpyHostToDevice));
   }
-  for (auto& g_ : h->gs)
-    for (hipGraphExec_t* g : graph_slots(g_))
-      if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
-  h->g_valid = false;
+  drop_graphs(h);
   return 0;
 }
 
@@ -516,19 +499,13 @@ extern "C" void bfmmm_destroy(bfmmm_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->st) (void)hipStreamSynchronize(h->st);
-  for (auto& g_ : h->gs)
-    for (hipGraphExec_t* gp_ : graph_slots(g_)) if (hipGraphExec_t g = *gp_)
-      if (g) (void)hipGraphExecDestroy(g);
+  drop_graphs(h);
   for (int q = 1; q < bfmmm_handle::MAX_SUB; ++q) { if (h->sub_st[q]) (void)hipStreamDestroy(h->sub_st[q]); if (h->sub_ev[q]) (void)hipEventDestroy(h->sub_ev[q]); }
   for (void* p : h->allocs) (void)hipFree(p);
   if (h->status_host) (void)hipHostFree(h->status_host);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->evA) (void)hipEventDestroy(h->evA);
-  if (h->evB) (void)hipEventDestroy(h->evB);
-  if (h->evC) (void)hipEventDestroy(h->evC);
-  if (h->evD) (void)hipEventDestroy(h->evD);
-  if (h->st2) (void)hipStreamDestroy(h->st2);
   if (h->st) (void)hipStreamDestroy(h->st);
   delete h;
 }
@@ -797,6 +774,48 @@ static Plan make_plan(uint32_t mask, int MD) {
   return p;
 }
 
+// How a (sub-)batch runs its pair-Gram contraction: k_pair_gram_pack with its geometry and buffer, or k_pair_gram +
+// k_pg_reduce; KS / NKS are the k-slices of either.
+struct PgRoute {
+  int KS, NKS;
+  bool packed = false;
+  PgPack pk;
+  double* pack = nullptr;
+};
+
+// cnt chains (a sub-batch of the handle's batch) whose packed tiles go to pg_pack[slot].
+// Packed: the batch has four or more chains -- warm-start and Nu_Z sweeps alike (measured, chain-iterations/s plain / packed:
+// 4 warm chains 35.3 k / 40.4 k, 6: 44.9 / 46.9; 4 Nu_Z chains 65.0 / 68.3, 6: 84.4 / 92.6, 8: 105 / 114; two chains: no gain) --
+// or the curve set is long (beyond the cache-resident sizes: k_pair_gram's k-slices are capped by its LDS staging, so at
+// n = 262144 it writes 1366 slabs of partial tiles -- as many bytes as the records themselves; k_pair_gram_pack walks a slice
+// of ANY length in 16-curve chunks with persistent accumulators: about 128 slices whatever n, chosen from n alone so that a
+// chain of a batch and the same chain alone sum in the same order).  Both kernels sum in the same order.
+static int pg_route(bfmmm_handle* h, const Dims& d, bool pg, int cnt, int slot, PgRoute& r) {
+  r = PgRoute();
+  pg_geometry(d, r.NKS, r.KS);
+  const int KSl = ((d.n + 127) / 128 + 15) / 16 * 16, NKSl = (d.n + KSl - 1) / KSl;
+  const bool long_set = d.n > 16384 && pgp_geometry(d, 1, KSl, NKSl, r.pk);
+  if (long_set) { r.KS = KSl; r.NKS = NKSl; }
+  if (pg && (long_set || h->nch >= 4) && pgp_geometry(d, cnt, r.KS, r.NKS, r.pk)) {
+    const size_t need = pgp_pack_doubles(r.pk);
+    if (h->pg_pack_doubles[slot] < need) {
+      double* nb = nullptr;
+      if (hipMalloc((void**)&nb, need * sizeof(double)) == hipSuccess) {
+        h->allocs.push_back(nb);      // (an outgrown buffer stays until the handle is destroyed: graphs captured earlier may still hold it)
+        h->pg_pack[slot] = nb; h->pg_pack_doubles[slot] = need;
+      } else {
+        (void)hipGetLastError();      // (no room: the plain kernel needs no extra buffer)
+      }
+    }
+    if (h->pg_pack_doubles[slot] >= need) { r.packed = true; r.pack = h->pg_pack[slot]; return 0; }
+  }
+  // k_pair_gram keeps the long-set slices where it can stage them (a chain then sums as it does alone), its own otherwise
+  if (long_set && (pair_gram_lds_bytes(d, r.KS) > 160 * 1024 || (size_t)r.NKS * d.NT * 256 > h->pg_part_doubles))
+    pg_geometry(d, r.NKS, r.KS);
+  if ((size_t)r.NKS * d.NT * 256 > h->pg_part_doubles) return fail("bfmmm_run: internal workspace too small");
+  return 0;
+}
+
 // One Gibbs iteration on the sampler's stream:
 //   k_curve_z -> k_pair_gram (+1 workgroup: pi/alpha_3) -> k_pg_reduce -> k_factor -> k_sweep
 //   -> k_curve_chi (+1 workgroup: delta/A/gamma/tau) -> k_loglik
@@ -806,26 +825,23 @@ static Plan make_plan(uint32_t mask, int MD) {
 // trail_z: the iteration ends with the stand-alone Z update of the NEXT iteration, in its lean form (the proposals were prepared
 // by this iteration's k_factor): sweeps without a chi pass cannot fuse the Z update into k_curve_chi, but they can still run
 // it in the order "first Z of the run, then bodies [pair_gram .. chi, next Z]".
-// pk / pack: the (sub-)batch runs its pair-Gram contraction through k_pair_gram_pack (chain batches, long curve sets)
-static void launch_iteration(bfmmm_handle* h, const Ctx& c, const Plan& p, int NKS, int KS, hipStream_t st,
-                             std::vector<hipEvent_t>* evs, bool skip_z = false, bool fuse_z = false, bool trail_z = false,
-                             const PgPack* pk = nullptr, double* pack = nullptr, int side = -1) {
+static void launch_iteration(bfmmm_handle* h, const Ctx& c, const Plan& p, const PgRoute& r, hipStream_t st,
+                             std::vector<hipEvent_t>* evs, bool skip_z, bool fuse_z, bool trail_z) {
   auto mark = [&]() {
     if (evs) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, st); evs->push_back(e); }
   };
   mark();
   if (p.z && !skip_z) launch_curve(c, 0, p.z_update, st);
   mark();
-  const bool packed = p.pg && pk;
   Ctx cf = c;
-  cf.pi_in_factor = packed ? 1 : 0;      // (the pi / alpha_3 job: an extra workgroup of k_pair_gram, or -- packed path -- of k_factor)
-  if (packed) {
-    launch_pair_gram_pack(c, *pk, pack, st);      // (contraction + reduction)
+  cf.pi_in_factor = r.packed ? 1 : 0;      // (the pi / alpha_3 job: an extra workgroup of k_pair_gram, or -- packed path -- of k_factor)
+  if (r.packed) {
+    launch_pair_gram_pack(c, r.pk, r.pack, st);      // (contraction + reduction)
     mark();
   } else {
-    launch_pair_gram(c, p.pg ? 1 : 0, NKS, KS, st);
+    launch_pair_gram(c, p.pg ? 1 : 0, r.NKS, r.KS, st);
     mark();
-    if (p.pg) launch_pg_reduce(c, NKS, st);
+    if (p.pg) launch_pg_reduce(c, r.NKS, st);
   }
   mark();
   if (p.factor) launch_factor(cf, st);
@@ -842,293 +858,150 @@ static void launch_iteration(bfmmm_handle* h, const Ctx& c, const Plan& p, int N
   mark();
 }
 
-static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters, uint64_t seed, uint32_t chain,
-                    int phi_chi_zero, double beta, uint32_t tt_step, bool prepare_only = false) {
-  if (!h) return fail("bfmmm_run: null handle");
-  // BFMMM_TRACE_RUN=1: host-side time stamps of the phases of a call (diagnostic: where the fixed cost of a short run goes)
-  static const bool trace_run = getenv("BFMMM_TRACE_RUN") && atoi(getenv("BFMMM_TRACE_RUN")) != 0;
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto tmark = [&](const char* what) {
-    if (trace_run && !prepare_only)
-      fprintf(stderr, "[bfmmm_run] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count());
-  };
-  if (n_iters < 0 || first_iter < h->slot_base || first_iter - h->slot_base + n_iters > h->T)
-    return fail("bfmmm_run: iterations exceed the allocated chain");
-  HIPCHK(hipSetDevice(h->device));
-  Ctx c = h->c;
-  const int MD = phi_chi_zero ? 1 : (c.d.M + 1);
-  set_md(c.d, MD);
-  c.seed = seed; c.chain = chain; c.mask = mask;
-  int NTG, NKS, KS;
-  pg_geometry(c.d, NTG, NKS, KS);
-  if ((size_t)NKS * c.d.NT * 256 > h->pg_part_doubles) return fail("bfmmm_run: internal workspace too small");
-  // Long curve sets (beyond the cache-resident sizes): k_pair_gram's k-slices are capped by its LDS staging (192 curves), so at
-  // n = 262144 it writes 1366 slabs of partial tiles -- as many bytes as the records themselves.  k_pair_gram_pack walks a slice of
-  // ANY length in 16-curve chunks with persistent accumulators: about 128 slices whatever n, chosen from n alone so that a chain
-  // of a batch and the same chain alone sum in the same order.
-  bool long_set = false;
-  {
-    const char* e = getenv("BFMMM_PG_PACK");
-    PgPack gt;
-    const int KSb = ((c.d.n + 127) / 128 + 15) / 16 * 16, NKSb = (c.d.n + KSb - 1) / KSb;
-    if (c.d.n > 16384 && !(e && atoi(e) == 0) && pgp_geometry(c.d, 1, KSb, NKSb, gt)) { long_set = true; KS = KSb; NKS = NKSb; }
+// the step tables of k_sweep_chain for (MD, the mask's nu / Phi bits), rebuilt when they change
+static void ensure_sweep_tables(bfmmm_handle* h, const Ctx& c, uint32_t mask) {
+  const int64_t tkey = ((int64_t)c.d.MD << 32) | (mask & (U_PHI | U_NU));
+  if (h->tab_key != tkey) { launch_sweep_tables(c, h->st); h->tab_key = tkey; }
+}
+
+// A chain batch runs as SUB-BATCHES on separate streams: the kernels are the same (a sub-batch is a Ctx whose per-chain
+// pointers start at its first chain), but while one sub-batch is in its narrow kernels -- k_sweep_fast is one workgroup per
+// chain, k_pg_reduce and the factorisations a few dozen -- the others' wide per-curve kernels have the CUs.
+struct Sub { Ctx c; hipStream_t st; PgRoute r; };
+
+// Graph kinds: full iterations; bodies of a fused run (no Z in front, k_curve_chi also runs the next iteration's Z update);
+// the closing iteration of a fused or deferred run (no Z in front, plain chi); bodies of a deferred run (no Z in front, the next
+// iteration's lean Z update at the end); a whole run on one stream (first Z, bodies, closing iteration, closing kernel).
+enum { GK_FULL, GK_FUSED, GK_CLOSING, GK_DEFERRED, GK_WHOLE };
+static constexpr int WHOLE_MAX = 64;      // the longest run captured as one graph
+static constexpr int WHOLE_KEEP = 4;      // whole-run graphs kept (of different lengths; the oldest is evicted)
+
+struct FreshGraph { hipGraphExec_t g; hipStream_t st; };
+
+// queues the kernels of a graph of `kind` (reps iterations) on the sub-batch's stream
+static void queue_graph(bfmmm_handle* h, const Ctx& c, const Sub& sb, const Plan& plan, int kind, int reps, int body_kind) {
+  if (kind == GK_WHOLE) {
+    launch_curve(sb.c, 0, plan.z_update, sb.st);              // Z of the first iteration
+    queue_graph(h, c, sb, plan, body_kind, reps - 1, body_kind);
+    queue_graph(h, c, sb, plan, GK_CLOSING, 1, body_kind);
+    launch_loglik_flush(c, sb.st, h->status_dev);
+    return;
   }
-  Plan plan = make_plan(mask, MD);
-  if (c.d.D > 0) { plan.z = true; plan.chi = true; plan.use_rss_part = 1; }
-  // pair-Gram through k_pair_gram_pack: batches of four or more chains -- warm-start and Nu_Z sweeps alike (measured, chain-iterations/s
-  // plain / packed: 4 warm chains 35.3 k / 40.4 k, 6: 44.9 / 46.9; 4 Nu_Z chains 65.0 / 68.3, 6: 84.4 / 92.6, 8: 105 / 114; two chains:
-  // no gain) -- and long curve sets (BFMMM_PG_PACK=0 / 1 switches it off / forces it wherever its limits allow: both kernels sum
-  // in the same order, the results are bit-identical)
-  auto want_pack = [&](int cnt) {
-    const char* e = getenv("BFMMM_PG_PACK");
-    if (long_set) return true;
-    if (e) return atoi(e) != 0;
-    (void)cnt;
-    return h->nch >= 4;
-  };
-  auto pack_for = [&](int slot, int cnt, PgPack& g, double** buf) -> int {      // 0: packed path ready, 1: not applicable, -1: error
-    *buf = nullptr;
-    if (!plan.pg || !want_pack(cnt) || !pgp_geometry(c.d, cnt, KS, NKS, g)) return 1;
-    const size_t need = pgp_pack_doubles(g);
-    if (h->pg_pack_doubles[slot] < need) {
-      double* nb = nullptr;
-      if (hipMalloc((void**)&nb, need * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return 1; }      // (no room: the plain kernel needs no extra buffer)
-      h->allocs.push_back(nb);      // (an outgrown buffer stays until the handle is destroyed: graphs captured earlier may still hold it)
-      h->pg_pack[slot] = nb; h->pg_pack_doubles[slot] = need;
-    }
-    *buf = h->pg_pack[slot];
-    return 0;
-  };
-  // without covariates the iteration ends with k_curve_chi: its scalar-job workgroup advances the counters and the
-  // log-likelihood is reduced by the next iteration's k_pair_gram job (one kernel boundary less per iteration)
-  c.defer_loglik = (c.d.D == 0) ? 1 : 0;
-  // single chain: the scalar job of k_curve_chi rides the next iteration's k_pair_gram instead (its grid has NKS - 1 idle extra
-  // workgroups); the run's flush kernel runs the last one.  BFMMM_DEFER_HYPER=0 / 1 overrides (diagnostic).
-  {
-    static const int env = getenv("BFMMM_DEFER_HYPER") ? atoi(getenv("BFMMM_DEFER_HYPER")) : -1;
-    const bool can = c.defer_loglik && plan.pg && plan.chi && h->nch == 1 && NKS >= 2 && !want_pack(1);
-    c.defer_hyper = (can && (env < 0 || env != 0)) ? 1 : 0;
+  for (int r = 0; r < reps; ++r)
+    launch_iteration(h, sb.c, plan, sb.r, sb.st, nullptr, kind != GK_FULL, kind == GK_FUSED, kind == GK_DEFERRED);
+}
+
+// The graph (sub, kind, reps) of the cache; captured from what `body` queues on `st`, instantiated, uploaded and listed in
+// `fresh` when the cache does not hold it.
+template <typename F>
+static int cached_graph(bfmmm_handle* h, int sub, int kind, int reps, hipStream_t st, std::vector<FreshGraph>& fresh, F body,
+                        hipGraphExec_t* out) {
+  int n_whole = 0;
+  for (const auto& e : h->graphs) {
+    if (e.sub == sub && e.kind == kind && e.reps == reps) { *out = e.g; return 0; }
+    n_whole += e.kind == GK_WHOLE;
   }
-  c.ll_use_part = plan.use_rss_part;
-  h->last_md = MD;
-  if (!prepare_only) {
-    const int64_t tkey = ((int64_t)MD << 32) | (mask & (U_PHI | U_NU));
-    if (h->tab_key != tkey) { launch_sweep_tables(c, h->st); h->tab_key = tkey; }
-    // every chain of the batch starts the run at the same iteration
-    hipLaunchKernelGGL(k_run_begin, dim3(h->nch), dim3(64), 0, h->st, h->c, (uint32_t)first_iter, (uint32_t)h->slot_base, tt_step, beta,
-                       h->state_dirty ? 1 : 0);
-    h->state_dirty = false;
-    for (int f = 0; f < FAM_COUNT; ++f) { h->fam_ms[f] = 0; h->fam_launches[f] = 0; }
-    HIPCHK(hipEventRecord(h->ev0, h->st));
-    tmark("run_begin queued");
+  if (kind == GK_WHOLE && n_whole >= WHOLE_KEEP) {      // evict the oldest whole-run graph
+    auto it = std::find_if(h->graphs.begin(), h->graphs.end(), [](const bfmmm_handle::CachedGraph& e) { return e.kind == GK_WHOLE; });
+    (void)hipGraphExecDestroy(it->g);
+    h->graphs.erase(it);
   }
-  if (h->profile && prepare_only) return 0;
-  bool whole_launched = false;      // the run went out as ONE graph that ends with the closing kernel (short runs, below)
-  if (h->profile) {
-    // the same kernels as the graph path (including the fused chi + next-Z launches), bracketed by events
-    const bool pfuse = plan.z && plan.z_update && plan.chi && c.d.D == 0 && n_iters >= 2 && tt_step == 0;
-    for (int it = 0; it < n_iters; ++it) {
-      std::vector<hipEvent_t> evs;
-      const bool skip_z = pfuse && it > 0, fuse_z = pfuse && it + 1 < n_iters;
-      PgPack pkp; double* packp = nullptr;
-      const bool use_p = pack_for(bfmmm_handle::MAX_SUB, h->nch, pkp, &packp) == 0;
-      launch_iteration(h, c, plan, NKS, KS, h->st, &evs, skip_z, fuse_z, false, use_p ? &pkp : nullptr, packp, bfmmm_handle::MAX_SUB);
+  std::lock_guard<std::mutex> lock(g_capture_mutex);
+  hipGraph_t graph = nullptr;
+  HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+  body();
+  const hipError_t ec = hipStreamEndCapture(st, &graph);      // always leaves capture mode, also after a failed launch
+  if (ec != hipSuccess) { if (graph) (void)hipGraphDestroy(graph); HIPCHK(ec); }
+  hipGraphExec_t g = nullptr;
+  const hipError_t ei = hipGraphInstantiate(&g, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  HIPCHK(ei);
+  (void)hipGraphUpload(g, st);      // (set-up: the first launch of a graph otherwise pays for its upload)
+  h->graphs.push_back({sub, kind, reps, g});
+  fresh.push_back({g, st});
+  *out = g;
+  return 0;
+}
+
+// DRY LAUNCH (set-up): the first launch of an instantiated graph costs the device 13 - 20 us more than every later one, upload
+// or not (measured: three fresh graphs = +40 us on a 20-iteration run, tools/gpu/trace_run.py).  So every graph a prepare call
+// instantiated is launched here, on the real state, between a snapshot and a restore of the chains' work state (everything of
+// the per-chain arenas but the chain storage; the slots a dry launch writes are those of the coming run, which rewrites them).
+// For about 10 ms: the device's clocks keep rising over the first ~5 ms of activity after an idle period -- a capture is one --,
+// measured as 1240 -> 1219 -> 1212 -> 1205 us of device time for four consecutive 20-iteration runs; us per step of the 20-step
+// form 64.6 / 63.7 / 63.1 with one launch / 4 ms / 12 ms.
+static int dry_launch(bfmmm_handle* h, const Ctx& c, uint32_t mask, const Sub* subs, int nsub, const std::vector<FreshGraph>& fresh,
+                      int first_iter, uint32_t tt_step, double beta) {
+  if (fresh.empty()) return 0;
+  const size_t wb1 = (size_t)((char*)h->c.c_nu - (char*)h->c.dyn);
+  const size_t wb2 = (c.d.D > 0 && h->arena_cov) ? (size_t)((char*)h->c.c_eta - (char*)h->c.thetaX) : 0;
+  const size_t need = (size_t)h->nch * (wb1 + wb2);
+  if (h->dry_snap_bytes < need) {
+    char* nb = nullptr;
+    if (hipMalloc((void**)&nb, need) != hipSuccess) { (void)hipGetLastError(); return 0; }      // (no room: the run's first launch pays)
+    h->allocs.push_back(nb);
+    h->dry_snap = nb; h->dry_snap_bytes = need;
+  }
+  const size_t cb1 = h->nch > 1 ? h->c.chain_bytes : wb1, cb2 = h->nch > 1 ? h->c.chain_bytes_cov : wb2;
+  char* snap2 = h->dry_snap + (size_t)h->nch * wb1;
+  for (int q = 0; q < nsub; ++q) HIPCHK(hipStreamSynchronize(subs[q].st));
+  HIPCHK(hipMemcpy2DAsync(h->dry_snap, wb1, h->c.dyn, cb1, wb1, (size_t)h->nch, hipMemcpyDeviceToDevice, h->st));
+  if (wb2) HIPCHK(hipMemcpy2DAsync(snap2, wb2, h->c.thetaX, cb2, wb2, (size_t)h->nch, hipMemcpyDeviceToDevice, h->st));
+  ensure_sweep_tables(h, c, mask);
+  const auto t_dry = std::chrono::steady_clock::now();
+  for (int round = 0; round < 64; ++round) {
+    for (const FreshGraph& fg : fresh) {
+      hipLaunchKernelGGL(k_run_begin, dim3(h->nch), dim3(64), 0, h->st, h->c, (uint32_t)first_iter, (uint32_t)h->slot_base, tt_step, beta, 0);
       HIPCHK(hipStreamSynchronize(h->st));
-      const int fams[7] = {FAM_Z, FAM_PG, FAM_REDUCE, FAM_FACTOR, FAM_SWEEP, FAM_CHI, FAM_LOGLIK};
-      const bool ran[7] = {plan.z && !skip_z, true, plan.pg, plan.factor, true, true, c.defer_loglik == 0};
-      for (int q = 0; q < 7; ++q) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, evs[q], evs[q + 1]);
-        if (ran[q]) { h->fam_ms[fams[q]] += ms; h->fam_launches[fams[q]] += 1; }
-      }
-      for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+      HIPCHK(hipGraphLaunch(fg.g, fg.st));
+      HIPCHK(hipStreamSynchronize(fg.st));
     }
-  } else if (n_iters > 0) {
-    // A chain batch runs as SUB-BATCHES on separate streams: the kernels are the same (a sub-batch is a Ctx whose per-chain
-    // pointers start at its first chain), but while one sub-batch is in its narrow kernels -- k_sweep_fast is one workgroup per
-    // chain, k_pg_reduce and the factorisations a few dozen -- the others' wide per-curve kernels have the CUs.
-    const char* env_split = getenv("BFMMM_BATCH_SPLIT");
-    int nsub = (h->nch >= 4) ? 2 : 1;
-    if (env_split) nsub = std::max(1, std::min({atoi(env_split), (int)bfmmm_handle::MAX_SUB, h->nch / 2}));
-    // (the captured graphs bake in the kernel instances the launchers chose: the cache key carries the switches that choose them)
-    const int pack_mode = (getenv("BFMMM_PG_PACK") ? 1 + (atoi(getenv("BFMMM_PG_PACK")) != 0) : 0) + 4 * (bfmmm::g_exact_instances ? 1 : 0);
-    const bool reuse = h->g_valid && h->g_mask == mask && h->g_md == MD && h->g_seed == seed && h->g_chain == chain && h->g_nsub == nsub && h->g_pack_mode == pack_mode;
-    if (!reuse) {
-      for (auto& g_ : h->gs)
-        for (hipGraphExec_t* g : graph_slots(g_))
-          if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
-      h->g_mask = mask; h->g_md = MD; h->g_seed = seed; h->g_chain = chain; h->g_nsub = nsub; h->g_pack_mode = pack_mode; h->g_valid = true;
-    }
-    struct Sub { Ctx c; hipStream_t st; hipGraphExec_t *gN, *gFN, *gL, *gR, *gFR; PgPack pk; double* pack; bool use_pack; int slot; };
-    Sub subs[bfmmm_handle::MAX_SUB];
-    h->sub_st[0] = h->st;
-    for (int q = 0, q0 = 0; q < nsub; ++q) {
-      const int cnt = h->nch / nsub + (q < h->nch % nsub ? 1 : 0);
-      if (!h->sub_st[q]) HIPCHK(hipStreamCreateWithFlags(&h->sub_st[q], hipStreamNonBlocking));
-      if (!h->sub_ev[q]) HIPCHK(hipEventCreateWithFlags(&h->sub_ev[q], hipEventDisableTiming));
-      bfmmm_handle::GraphSet& g_ = h->gs[q];
-      subs[q] = Sub{chain_ctx(c, (unsigned)q0), h->sub_st[q], &g_.gN, &g_.gFN, &g_.gL, g_.gR, g_.gFR};
-      subs[q].c.nch = cnt;
-      subs[q].use_pack = pack_for(q, cnt, subs[q].pk, &subs[q].pack) == 0;
-      subs[q].slot = q;
-      q0 += cnt;
-    }
-    // graphs are captured on demand: kind 0 = full iterations, 1 = fused bodies (no Z in front, chi + next Z at the end),
-    // 2 = the closing iteration of a fused run (no Z in front, plain chi)
-    std::vector<std::pair<hipGraphExec_t, hipStream_t>> fresh;      // graphs instantiated by this call
-    auto ensure = [&](const Sub& sb, hipGraphExec_t* g, int kind, int reps) -> int {
-      if (*g) return 0;
-      std::lock_guard<std::mutex> lock(g_capture_mutex);
-      hipGraph_t graph = nullptr;
-      HIPCHK(hipStreamBeginCapture(sb.st, hipStreamCaptureModeRelaxed));
-      for (int r = 0; r < reps; ++r) launch_iteration(h, sb.c, plan, NKS, KS, sb.st, nullptr, kind != 0, kind == 1, kind == 3, sb.use_pack ? &sb.pk : nullptr, sb.pack, sb.slot);
-      const hipError_t ec = hipStreamEndCapture(sb.st, &graph);      // always leaves capture mode, also after a failed launch
-      if (ec != hipSuccess) { if (graph) (void)hipGraphDestroy(graph); HIPCHK(ec); }
-      const hipError_t ei = hipGraphInstantiate(g, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      HIPCHK(ei);
-      (void)hipGraphUpload(*g, sb.st);      // (set-up: the first launch of a graph otherwise pays for its upload)
-      fresh.push_back({*g, sb.st});
-      return 0;
-    };
-    // a run of nrep repetitions = nrep / GRAPH_UNROLL replays of the unrolled graph + ONE graph holding the remainder
-    // (re-captured only when the remainder changes), so that a short run costs two or three graph launches, not one per iteration
-    auto ensure_rem = [&](const Sub& sb, hipGraphExec_t* garr, int kind, int rem) -> int {
-      if (rem <= 0) return 0;
-      return ensure(sb, &garr[rem], kind, rem);
-    };
-    if (!h->status_host) {
-      HIPCHK(hipHostMalloc((void**)&h->status_host, sizeof(uint32_t) * (size_t)h->nch, hipHostMallocMapped));
-      if (hipHostGetDevicePointer((void**)&h->status_dev, h->status_host, 0) != hipSuccess) { (void)hipGetLastError(); h->status_dev = nullptr; }
-    }
-    const bool fuse = plan.z && plan.z_update && plan.chi && c.d.D == 0 && n_iters >= 2 && tt_step == 0;
-    // sweeps whose Z update cannot ride in k_curve_chi (no chi pass: the Nu_Z stage) still run it at the END of the previous
-    // iteration's body, as the lean stand-alone kernel (kind 3 bodies)
-    const bool defer = !fuse && plan.z && plan.z_update && plan.factor && (mask & U_Z) && c.d.D == 0 && c.d.K <= 4 && c.d.BW <= 5 &&
-                       n_iters >= 2 && tt_step == 0;
-    const int body_kind = fuse ? 1 : 3;
-    const bool bodies = fuse || defer;
-    const int nrep = bodies ? n_iters - 1 : n_iters;                // fused / deferred run: n_iters - 1 bodies + the closing iteration
-    const int nfull = nrep / GRAPH_UNROLL, rem = nrep % GRAPH_UNROLL;
-    // A SHORT run on one stream is ONE graph: the first Z update, the bodies, the closing iteration and the closing kernel --
-    // one graph launch instead of three and two kernel launches (a 20-iteration call: ~30 us of host time, 1.5 us per step).
-    // Keyed by the number of iterations (re-captured when it changes); BFMMM_WHOLE_GRAPH=0 switches it off.
-    static const int env_whole = getenv("BFMMM_WHOLE_GRAPH") ? atoi(getenv("BFMMM_WHOLE_GRAPH")) : 1;
-    constexpr int WHOLE_MAX = 64;
-    const bool whole = env_whole && bodies && nsub == 1 && n_iters <= WHOLE_MAX && c.defer_loglik && h->status_dev != nullptr;
-    if (whole) {
-      const Sub& sb = subs[0];
-      bfmmm_handle::GraphSet& g_ = h->gs[0];
-      if (g_.gW && g_.gW_n != n_iters) { (void)hipGraphExecDestroy(g_.gW); g_.gW = nullptr; }
-      if (!g_.gW) {
-        std::lock_guard<std::mutex> lock(g_capture_mutex);
-        hipGraph_t graph = nullptr;
-        HIPCHK(hipStreamBeginCapture(sb.st, hipStreamCaptureModeRelaxed));
-        launch_curve(sb.c, 0, plan.z_update, sb.st);              // Z of the first iteration
-        for (int r = 0; r < nrep; ++r) launch_iteration(h, sb.c, plan, NKS, KS, sb.st, nullptr, true, body_kind == 1, body_kind == 3, sb.use_pack ? &sb.pk : nullptr, sb.pack, sb.slot);
-        launch_iteration(h, sb.c, plan, NKS, KS, sb.st, nullptr, true, false, false, sb.use_pack ? &sb.pk : nullptr, sb.pack, sb.slot);
-        launch_loglik_flush(c, sb.st, h->status_dev);
-        const hipError_t ec = hipStreamEndCapture(sb.st, &graph);
-        if (ec != hipSuccess) { if (graph) (void)hipGraphDestroy(graph); HIPCHK(ec); }
-        const hipError_t ei = hipGraphInstantiate(&g_.gW, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        HIPCHK(ei);
-        (void)hipGraphUpload(g_.gW, sb.st);
-        g_.gW_n = n_iters;
-        fresh.push_back({g_.gW, sb.st});
-      }
-    }
-    for (int s = 0; s < nsub && !whole; ++s) {
-      const Sub& sb = subs[s];
-      if (!bodies) {
-        if ((nfull > 0 && ensure(sb, sb.gN, 0, GRAPH_UNROLL)) || ensure_rem(sb, sb.gR, 0, rem)) return 1;
-      } else {
-        if ((nfull > 0 && ensure(sb, sb.gFN, body_kind, GRAPH_UNROLL)) || ensure_rem(sb, sb.gFR, body_kind, rem) || ensure(sb, sb.gL, 2, 1)) return 1;
-      }
-    }
-    if (prepare_only) {
-      // DRY LAUNCH (set-up): the first launch of an instantiated graph costs the device 13 - 20 us more than every later one,
-      // upload or not (measured: three fresh graphs = +40 us on a 20-iteration run, tools/gpu/trace_run.py).  So every graph this
-      // call instantiated is launched once here, on the real state, between a snapshot and a restore of the chains' work state
-      // (everything of the per-chain arenas but the chain storage; the slots a dry launch writes are the first slots of the
-      // coming run, which rewrites them).  BFMMM_DRY_LAUNCH=0 switches it off.
-      const char* ed = getenv("BFMMM_DRY_LAUNCH");
-      if (!fresh.empty() && !(ed && atoi(ed) == 0)) {
-        const size_t wb1 = (size_t)((char*)h->c.c_nu - (char*)h->c.dyn);
-        const size_t wb2 = (c.d.D > 0 && h->arena_cov) ? (size_t)((char*)h->c.c_eta - (char*)h->c.thetaX) : 0;
-        const size_t need = (size_t)h->nch * (wb1 + wb2);
-        if (h->dry_snap_bytes < need) {
-          char* nb = nullptr;
-          if (hipMalloc((void**)&nb, need) != hipSuccess) { (void)hipGetLastError(); return 0; }      // (no room: the run's first launch pays)
-          h->allocs.push_back(nb);
-          h->dry_snap = nb; h->dry_snap_bytes = need;
-        }
-        const size_t cb1 = h->nch > 1 ? h->c.chain_bytes : wb1, cb2 = h->nch > 1 ? h->c.chain_bytes_cov : wb2;
-        char* snap2 = h->dry_snap + (size_t)h->nch * wb1;
-        for (int q = 0; q < nsub; ++q) HIPCHK(hipStreamSynchronize(subs[q].st));
-        HIPCHK(hipMemcpy2DAsync(h->dry_snap, wb1, h->c.dyn, cb1, wb1, (size_t)h->nch, hipMemcpyDeviceToDevice, h->st));
-        if (wb2) HIPCHK(hipMemcpy2DAsync(snap2, wb2, h->c.thetaX, cb2, wb2, (size_t)h->nch, hipMemcpyDeviceToDevice, h->st));
-        const int64_t tkey = ((int64_t)MD << 32) | (mask & (U_PHI | U_NU));
-        if (h->tab_key != tkey) { launch_sweep_tables(c, h->st); h->tab_key = tkey; }
-        // (a few milliseconds of it: the device's clocks keep rising over the first ~5 ms of activity after an idle period -- a
-        //  capture is one --, measured as 1240 -> 1219 -> 1212 -> 1205 us of device time for four consecutive 20-iteration runs;
-        //  BFMMM_DRY_LAUNCH_MS sets the duration, default 10: us per step of the 20-step form 64.6 / 63.7 / 63.1 with one launch / 4 ms / 12 ms)
-        const char* ems = getenv("BFMMM_DRY_LAUNCH_MS");
-        const double want_ms = ems ? atof(ems) : 10.0;
-        const auto t_dry = std::chrono::steady_clock::now();
-        for (int round = 0; round < 64; ++round) {
-          for (auto& fg : fresh) {
-            hipLaunchKernelGGL(k_run_begin, dim3(h->nch), dim3(64), 0, h->st, h->c, (uint32_t)first_iter, (uint32_t)h->slot_base, tt_step, beta, 0);
-            HIPCHK(hipStreamSynchronize(h->st));
-            HIPCHK(hipGraphLaunch(fg.first, fg.second));
-            HIPCHK(hipStreamSynchronize(fg.second));
-          }
-          if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dry).count() >= want_ms) break;
-        }
-        HIPCHK(hipMemcpy2DAsync(h->c.dyn, cb1, h->dry_snap, wb1, wb1, (size_t)h->nch, hipMemcpyDeviceToDevice, h->st));
-        if (wb2) HIPCHK(hipMemcpy2DAsync(h->c.thetaX, cb2, snap2, wb2, wb2, (size_t)h->nch, hipMemcpyDeviceToDevice, h->st));
-        HIPCHK(hipStreamSynchronize(h->st));
-        HIPCHK(hipGetLastError());
-      }
-      return 0;
-    }
-    HIPCHK(hipEventRecord(h->ev0, h->st));
-    for (int q = 1; q < nsub; ++q) { HIPCHK(hipEventRecord(h->evA, h->st)); HIPCHK(hipStreamWaitEvent(subs[q].st, h->evA, 0)); }      // k_run_begin first
-    if (whole) { HIPCHK(hipGraphLaunch(h->gs[0].gW, subs[0].st)); tmark("graph (whole run) queued"); whole_launched = true; }
-    for (int s = 0; s < nsub && !whole; ++s) {
-      const Sub& sb = subs[s];
-      if (!bodies) {
-        for (int q = 0; q < nfull; ++q) HIPCHK(hipGraphLaunch(*sb.gN, sb.st));
-        if (rem > 0) HIPCHK(hipGraphLaunch(sb.gR[rem], sb.st));
-      } else {
-        launch_curve(sb.c, 0, plan.z_update, sb.st);              // Z of the first iteration
-        tmark("first Z queued");
-        for (int q = 0; q < nfull; ++q) { HIPCHK(hipGraphLaunch(*sb.gFN, sb.st)); tmark("graph (full) queued"); }
-        if (rem > 0) HIPCHK(hipGraphLaunch(sb.gFR[rem], sb.st));
-        HIPCHK(hipGraphLaunch(*sb.gL, sb.st));
-      }
-    }
-    for (int q = 1; q < nsub; ++q) { HIPCHK(hipEventRecord(h->sub_ev[q], subs[q].st)); HIPCHK(hipStreamWaitEvent(h->st, h->sub_ev[q], 0)); }
+    if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dry).count() >= 10.0) break;
   }
-  if (prepare_only) return 0;
-  if (!h->status_host) {
-    HIPCHK(hipHostMalloc((void**)&h->status_host, sizeof(uint32_t) * (size_t)h->nch, hipHostMallocMapped));
-    if (hipHostGetDevicePointer((void**)&h->status_dev, h->status_host, 0) != hipSuccess) { (void)hipGetLastError(); h->status_dev = nullptr; }
+  HIPCHK(hipMemcpy2DAsync(h->c.dyn, cb1, h->dry_snap, wb1, wb1, (size_t)h->nch, hipMemcpyDeviceToDevice, h->st));
+  if (wb2) HIPCHK(hipMemcpy2DAsync(h->c.thetaX, cb2, snap2, wb2, wb2, (size_t)h->nch, hipMemcpyDeviceToDevice, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the profile form of a run: the same kernels as the graph path (including the fused chi + next-Z launches) on the sampler's
+// stream, each bracketed by events
+static int run_profiled(bfmmm_handle* h, const Ctx& c, const Plan& plan, const PgRoute& r, int n_iters, uint32_t tt_step) {
+  const bool fuse = plan.z && plan.z_update && plan.chi && c.d.D == 0 && n_iters >= 2 && tt_step == 0;
+  for (int it = 0; it < n_iters; ++it) {
+    std::vector<hipEvent_t> evs;
+    const bool skip_z = fuse && it > 0, fuse_z = fuse && it + 1 < n_iters;
+    launch_iteration(h, c, plan, r, h->st, &evs, skip_z, fuse_z, false);
+    HIPCHK(hipStreamSynchronize(h->st));
+    const int fams[7] = {FAM_Z, FAM_PG, FAM_REDUCE, FAM_FACTOR, FAM_SWEEP, FAM_CHI, FAM_LOGLIK};
+    const bool ran[7] = {plan.z && !skip_z, true, plan.pg, plan.factor, true, true, c.defer_loglik == 0};
+    for (int q = 0; q < 7; ++q) {
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, evs[q], evs[q + 1]);
+      if (ran[q]) { h->fam_ms[fams[q]] += ms; h->fam_launches[fams[q]] += 1; }
+    }
+    for (hipEvent_t e : evs) (void)hipEventDestroy(e);
   }
+  return 0;
+}
+
+// closing step of a run: the deferred log-likelihood's flush (unless the run's graph ended with it), the chain slots of the
+// blocks the sweep does not touch, the chains' status words
+static int finish_run(bfmmm_handle* h, const Ctx& c, const Plan& plan, uint32_t mask, int first_iter, int n_iters, bool whole) {
   // the status words reach the host from the run's last kernel when there is one that can carry them (the deferred
   // log-likelihood's flush; the fill kernels behind it never touch a status word), by a queued copy otherwise
   const bool status_by_kernel = c.defer_loglik && n_iters > 0 && h->status_dev != nullptr;
-  if (c.defer_loglik && n_iters > 0 && !whole_launched) launch_loglik_flush(c, h->st, status_by_kernel ? h->status_dev : nullptr);      // (a whole-run graph ends with it)
+  if (c.defer_loglik && n_iters > 0 && !whole) launch_loglik_flush(c, h->st, status_by_kernel ? h->status_dev : nullptr);
   // chain slots of blocks this sweep does not touch hold the (constant) current value
-  if (!(mask & U_Z)) launch_fill_slots(c, c.c_Z, c.Z, (size_t)c.d.n * c.d.K, first_iter - h->slot_base, first_iter - h->slot_base + n_iters, h->st);
-  if (!plan.chi_update) launch_fill_slots(c, c.c_chi, c.chi, (size_t)c.d.n * c.d.M, first_iter - h->slot_base, first_iter - h->slot_base + n_iters, h->st);
+  const int s0 = first_iter - h->slot_base, s1 = s0 + n_iters;
+  if (!(mask & U_Z)) launch_fill_slots(c, c.c_Z, c.Z, (size_t)c.d.n * c.d.K, s0, s1, h->st);
+  if (!plan.chi_update) launch_fill_slots(c, c.c_chi, c.chi, (size_t)c.d.n * c.d.M, s0, s1, h->st);
   HIPCHK(hipEventRecord(h->ev1, h->st));
   if (!status_by_kernel)      // the chains' status words: one strided copy queued behind the run
     HIPCHK(hipMemcpy2DAsync(h->status_host, sizeof(uint32_t), &h->c.dyn->status, h->nch > 1 ? h->c.chain_bytes : sizeof(uint32_t), sizeof(uint32_t),
                             (size_t)h->nch, hipMemcpyDeviceToHost, h->st));
-  tmark("all queued");
   HIPCHK(hipStreamSynchronize(h->st));
-  tmark("synchronised");
   if (h->launch_error) { h->launch_error = 0; return fail("bfmmm_run: problem size exceeds the sweep kernel's LDS (5 A P doubles + A^2 ints must fit 160 KB)"); }
   HIPCHK(hipGetLastError());
   float ms = 0;
@@ -1144,6 +1017,106 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
       return fail("bfmmm_run: a conditional precision matrix was not positive definite");
   }
   return 0;
+}
+
+static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters, uint64_t seed, uint32_t chain,
+                    int phi_chi_zero, double beta, uint32_t tt_step, bool prepare_only = false) {
+  if (!h) return fail("bfmmm_run: null handle");
+  if (n_iters < 0 || first_iter < h->slot_base || first_iter - h->slot_base + n_iters > h->T)
+    return fail("bfmmm_run: iterations exceed the allocated chain");
+  HIPCHK(hipSetDevice(h->device));
+  // ---- plan: the updates, the sub-batches and their pair-Gram routes ----
+  Ctx c = h->c;
+  const int MD = phi_chi_zero ? 1 : (c.d.M + 1);
+  set_md(c.d, MD);
+  c.seed = seed; c.chain = chain; c.mask = mask;
+  Plan plan = make_plan(mask, MD);
+  if (c.d.D > 0) { plan.z = true; plan.chi = true; plan.use_rss_part = 1; }
+  // without covariates the iteration ends with k_curve_chi: its scalar-job workgroup advances the counters and the
+  // log-likelihood is reduced by the next iteration's k_pair_gram job (one kernel boundary less per iteration)
+  c.defer_loglik = (c.d.D == 0) ? 1 : 0;
+  c.ll_use_part = plan.use_rss_part;
+  h->last_md = MD;
+  int nsub = 1;
+  if (!h->profile && h->nch >= 4) nsub = 2;
+  if (const char* env_split = h->profile ? nullptr : getenv("BFMMM_BATCH_SPLIT"))
+    nsub = std::max(1, std::min({atoi(env_split), (int)bfmmm_handle::MAX_SUB, h->nch / 2}));
+  Sub subs[bfmmm_handle::MAX_SUB];
+  h->sub_st[0] = h->st;
+  for (int q = 0, q0 = 0; q < nsub; ++q) {
+    const int cnt = h->nch / nsub + (q < h->nch % nsub ? 1 : 0);
+    // (the profile form runs the whole batch on the sampler's stream, its packed tiles in the extra buffer)
+    if (pg_route(h, c.d, plan.pg, cnt, h->profile ? bfmmm_handle::MAX_SUB : q, subs[q].r)) return 1;
+    if (!h->sub_st[q]) HIPCHK(hipStreamCreateWithFlags(&h->sub_st[q], hipStreamNonBlocking));
+    if (!h->sub_ev[q]) HIPCHK(hipEventCreateWithFlags(&h->sub_ev[q], hipEventDisableTiming));
+    subs[q].c = chain_ctx(c, (unsigned)q0);
+    subs[q].c.nch = cnt;
+    subs[q].st = h->sub_st[q];
+    q0 += cnt;
+  }
+  // single chain: the scalar job of k_curve_chi rides the next iteration's k_pair_gram instead (its grid has NKS - 1 idle extra
+  // workgroups); the run's flush kernel runs the last one
+  c.defer_hyper = (c.defer_loglik && plan.pg && plan.chi && h->nch == 1 && !subs[0].r.packed && subs[0].r.NKS >= 2) ? 1 : 0;
+  subs[0].c.defer_hyper = c.defer_hyper;      // (one chain: one sub-batch)
+  if (!prepare_only) {
+    ensure_sweep_tables(h, c, mask);
+    // every chain of the batch starts the run at the same iteration
+    hipLaunchKernelGGL(k_run_begin, dim3(h->nch), dim3(64), 0, h->st, h->c, (uint32_t)first_iter, (uint32_t)h->slot_base, tt_step, beta,
+                       h->state_dirty ? 1 : 0);
+    h->state_dirty = false;
+    for (int f = 0; f < FAM_COUNT; ++f) { h->fam_ms[f] = 0; h->fam_launches[f] = 0; }
+  }
+  if (h->profile) {
+    if (prepare_only) return 0;
+    HIPCHK(hipEventRecord(h->ev0, h->st));
+    if (run_profiled(h, c, plan, subs[0].r, n_iters, tt_step)) return 1;
+    return finish_run(h, c, plan, mask, first_iter, n_iters, false);
+  }
+  // ---- the graphs of the run: one launch sequence per sub-batch ----
+  const bool fuse = plan.z && plan.z_update && plan.chi && c.d.D == 0 && n_iters >= 2 && tt_step == 0;
+  // sweeps whose Z update cannot ride in k_curve_chi (no chi pass: the Nu_Z stage) still run it at the END of the previous
+  // iteration's body, as the lean stand-alone kernel (deferred bodies)
+  const bool defer = !fuse && plan.z && plan.z_update && plan.factor && (mask & U_Z) && c.d.D == 0 && c.d.K <= 4 && c.d.BW <= 5 &&
+                     n_iters >= 2 && tt_step == 0;
+  const bool bodies = fuse || defer;
+  const int body_kind = fuse ? GK_FUSED : GK_DEFERRED;
+  const int nrep = bodies ? n_iters - 1 : n_iters;                // fused / deferred run: n_iters - 1 bodies + the closing iteration
+  // A run of nrep repetitions = nrep / GRAPH_UNROLL replays of the unrolled graph + ONE graph holding the remainder, so that a
+  // long run costs a few graph launches, not one per iteration.  A SHORT run on one stream is ONE graph: the first Z update, the
+  // bodies, the closing iteration and the closing kernel (a 20-iteration call: ~30 us of host time, 1.5 us per step).
+  const bool whole = bodies && nsub == 1 && n_iters <= WHOLE_MAX && c.defer_loglik && h->status_dev != nullptr;
+  std::vector<std::pair<int, int>> segs;      // (kind, repetitions) of the run's graphs in launch order
+  const int kind = bodies ? body_kind : GK_FULL;
+  if (whole) {
+    segs.push_back({GK_WHOLE, n_iters});
+  } else {
+    for (int q = 0; q < nrep / GRAPH_UNROLL; ++q) segs.push_back({kind, GRAPH_UNROLL});
+    if (nrep % GRAPH_UNROLL) segs.push_back({kind, nrep % GRAPH_UNROLL});
+    if (bodies) segs.push_back({GK_CLOSING, 1});
+  }
+  // (the captured graphs bake in the kernel instances the launchers chose: the key carries the switch that chooses them)
+  const bfmmm_handle::GraphKey key{mask, MD, seed, chain, nsub, bfmmm::g_exact_instances ? 1 : 0};
+  if (n_iters > 0 && !(h->g_valid && h->g_key == key)) { drop_graphs(h); h->g_key = key; h->g_valid = true; }
+  std::vector<FreshGraph> fresh;      // graphs instantiated by this call
+  std::vector<hipGraphExec_t> seq[bfmmm_handle::MAX_SUB];
+  for (int s = 0; s < nsub; ++s)
+    for (const auto& sg : segs) {
+      hipGraphExec_t g = nullptr;
+      if (cached_graph(h, s, sg.first, sg.second, subs[s].st, fresh, [&]() { queue_graph(h, c, subs[s], plan, sg.first, sg.second, body_kind); }, &g))
+        return 1;
+      seq[s].push_back(g);
+    }
+  if (prepare_only) return dry_launch(h, c, mask, subs, nsub, fresh, first_iter, tt_step, beta);
+  // ---- launch ----
+  HIPCHK(hipEventRecord(h->ev0, h->st));
+  if (nsub > 1) HIPCHK(hipEventRecord(h->evA, h->st));      // k_run_begin first
+  for (int q = 1; q < nsub; ++q) HIPCHK(hipStreamWaitEvent(subs[q].st, h->evA, 0));
+  for (int s = 0; s < nsub && n_iters > 0; ++s) {
+    if (bodies && !whole) launch_curve(subs[s].c, 0, plan.z_update, subs[s].st);      // Z of the first iteration
+    for (hipGraphExec_t g : seq[s]) HIPCHK(hipGraphLaunch(g, subs[s].st));
+  }
+  for (int q = 1; q < nsub; ++q) { HIPCHK(hipEventRecord(h->sub_ev[q], subs[q].st)); HIPCHK(hipStreamWaitEvent(h->st, h->sub_ev[q], 0)); }
+  return finish_run(h, c, plan, mask, first_iter, n_iters, whole);
 }
 
 extern "C" int bfmmm_set_slot_base(bfmmm_handle* h, int base) {

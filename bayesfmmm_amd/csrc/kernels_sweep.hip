@@ -479,10 +479,11 @@ __global__ __launch_bounds__(256) void k_pg_reduce(Ctx c0, int NKS) {
 constexpr int PGP_CH = 16;                     // chunk: 16 curves = 4 k-steps
 constexpr int PGP_RB = 66;                     // row stride of the staged chunk (doubles): 64 record columns + 2 (16-byte aligned rows)
 constexpr int PGP_NWV = 3;                     // most weight values (Z_ik, chi_im) a thread stages per chunk
+constexpr int PGP_WPG = 4;                     // waves (= packed row tiles) per workgroup
 
-template <int PGP_WAVES>
-__global__ __launch_bounds__(64 * PGP_WAVES, 4) void k_pair_gram_pack(Ctx c0, PgPack g, double* __restrict__ pack) {
-  constexpr int PGP_THREADS = 64 * PGP_WAVES;
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES, 4) void k_pair_gram_pack(Ctx c0, PgPack g, double* __restrict__ pack) {
+  constexpr int PGP_THREADS = 64 * WAVES;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const Dims& d = c0.d;
   const int n = d.n, K = d.K, MD = d.MD, nch = c0.nch;
@@ -490,7 +491,7 @@ __global__ __launch_bounds__(64 * PGP_WAVES, 4) void k_pair_gram_pack(Ctx c0, Pg
   const int ks = blockIdx.y, wg = blockIdx.x;
   const int nwg_g = g.NRG * g.NCG;
   if (ks >= g.NKS || wg >= nwg_g + g.NWG_S) return;
-  // A workgroup is (row group, column group): PGP_WAVES packed row tiles (one per wave) x 64 record columns (two 32-column pairs,
+  // A workgroup is (row group, column group): WAVES packed row tiles (one per wave) x 64 record columns (two 32-column pairs,
   // four accumulators per wave).  The s part -- single-weight rows against the P columns of s_i -- runs through the SAME code: its
   // rows multiply Z_j chit_m by 1 x 1 (exact), its 32 columns fill the first pair and the second pair's accumulators are dropped.
   const bool single = wg >= nwg_g;
@@ -499,10 +500,10 @@ __global__ __launch_bounds__(64 * PGP_WAVES, 4) void k_pair_gram_pack(Ctx c0, Pg
   const int nchunk = (min(g.KS, n - i0) + PGP_CH - 1) / PGP_CH;
   const int SL = g.SLS;                     // raw weight row of a (chain, curve): Z_1 .. Z_K | 1, chi_1 .. chi_M | 0 (| pad)
   const int RW = single ? d.A : d.R;        // rows per chain
-  const int tile0 = rg * PGP_WAVES;
+  const int tile0 = rg * WAVES;
   const int ntile = single ? g.TS : g.TG;
   const int q0 = min((tile0 * 16) / RW, nch - 1);       // the chains this workgroup's rows belong to
-  const int q1 = min(((min(tile0 + PGP_WAVES, ntile)) * 16 - 1) / RW, nch - 1);
+  const int q1 = min(((min(tile0 + WAVES, ntile)) * 16 - 1) / RW, nch - 1);
   const int nq = q1 - q0 + 1;
   constexpr int nbuf_b = 16 * PGP_RB;
   double* sBb = smem;                                   // 2 x 16 x RB     record chunk, [curve][column]
@@ -2022,18 +2023,25 @@ __global__ void k_fill_slots(double* chain, const double* cur, size_t len, int s
 }
 
 // ---- host launchers -------------------------------------------------------------------------
+// LDS of k_pair_gram for groups of G chains: record columns + G chains' tables (G workgroups: 16 + G (RS + RP) rows; s workgroup:
+// 16 CTS + G RS) + pair table, and at least the scalar jobs' scratch
+static size_t pair_gram_lds_bytes(const Dims& d, int KS, int G) {
+  const int RS = d.K + d.MD + 1, RP = d.NZZ + d.NCC + 1;
+  const size_t tables = (size_t)(KS + 2) * std::max(16 + G * (RS + RP), d.CTS * 16 + G * RS) + 128;
+  return std::max(tables, (size_t)std::max(PI_ALPHA_LDS_DOUBLES, HYPER_LDS_DOUBLES)) * sizeof(double);
+}
+// the request of a launch with KS-curve slices (chains are only grouped where the group fits)
+size_t pair_gram_lds_bytes(const Dims& d, int KS) { return pair_gram_lds_bytes(d, KS, 1); }
+
 void launch_pair_gram(const Ctx& c, int do_pg, int NKS, int KS, hipStream_t st) {
   const Dims& d = c.d;
-  const int RS = d.K + d.MD + 1, RP = d.NZZ + d.NCC + 1, ncw = d.K + d.MD - 1;
-  auto lds_doubles = [&](int G) {            // record columns + G chains' tables (G workgroups: 16 + G (RS + RP) rows; s workgroup: 16 CTS + G RS) + pair table
-    return (size_t)(KS + 2) * std::max(16 + G * (RS + RP), d.CTS * 16 + G * RS) + 128;
-  };
+  const int ncw = d.K + d.MD - 1;
   // chains staged together (k_pair_gram): as many as 144 KB of LDS and 12 staged doubles per thread allow; covariate-adjusted
   // models stage s~_i per chain and keep one chain per group
   int G = 1;
   if (c.nch > 1 && d.D == 0 && d.RT < 8)      // (with eight or more row tiles per chain the waves are busy chain by chain)
-    while (G < c.nch && lds_doubles(G + 1) * sizeof(double) <= 144 * 1024 && (size_t)(G + 1) * ncw * KS <= 12 * 512) ++G;
-  const size_t lds = std::max(lds_doubles(G), (size_t)std::max(PI_ALPHA_LDS_DOUBLES, HYPER_LDS_DOUBLES)) * sizeof(double);
+    while (G < c.nch && pair_gram_lds_bytes(d, KS, G + 1) <= 144 * 1024 && (size_t)(G + 1) * ncw * KS <= 12 * 512) ++G;
+  const size_t lds = pair_gram_lds_bytes(d, KS, G);
   if (c.nch > 1 && G > 1) hipLaunchKernelGGL((k_pair_gram<true, true>), dim3(d.CTG + 2, do_pg ? std::max(NKS, c.nch) : c.nch, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, G);
   else if (c.nch > 1) hipLaunchKernelGGL((k_pair_gram<true, false>), dim3(d.CTG + 2, do_pg ? std::max(NKS, c.nch) : c.nch, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, 1);
   else hipLaunchKernelGGL((k_pair_gram<false, false>), dim3(d.CTG + 2, do_pg ? NKS : 1, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, 1);
@@ -2049,26 +2057,20 @@ bool pgp_geometry(const Dims& d, int nch, int KS, int NKS, PgPack& g) {
   g.KS = KS; g.NKS = NKS;
   g.NP2 = (d.LG + 31) / 32;
   g.TG = (nch * d.R + 15) / 16; g.TS = (nch * d.A + 15) / 16;
-  const char* ew = getenv("BFMMM_PGP_WAVES");
-  g.WPG = (ew && atoi(ew) == 8) ? 8 : (ew && atoi(ew) == 2) ? 2 : 4;
-  const int PGP_WAVES = g.WPG, PGP_THREADS = 64 * g.WPG;
-  g.NRG = (g.TG + PGP_WAVES - 1) / PGP_WAVES; g.NCG = (g.NP2 + 1) / 2; g.NWG_S = (g.TS + PGP_WAVES - 1) / PGP_WAVES;
+  g.WPG = PGP_WPG;
+  g.NRG = (g.TG + PGP_WPG - 1) / PGP_WPG; g.NCG = (g.NP2 + 1) / 2; g.NWG_S = (g.TS + PGP_WPG - 1) / PGP_WPG;
   g.SLG = (d.NZZ + d.NCC + 1 + 1) & ~1; g.SLS = (d.K + d.MD + 1 + 1) & ~1;
-  g.NQG = std::min(nch, (PGP_WAVES * 16 + d.R - 2) / d.R + 1); g.NQS = std::min(nch, (PGP_WAVES * 16 + d.A - 2) / d.A + 1);
+  g.NQG = std::min(nch, (PGP_WPG * 16 + d.R - 2) / d.R + 1); g.NQS = std::min(nch, (PGP_WPG * 16 + d.A - 2) / d.A + 1);
   g.NTP = g.TG * 2 * g.NP2 + g.TS * 2;
   const int NV = d.K + d.MD - 1;
-  if (std::max(g.NQG, g.NQS) * NV * 16 > PGP_NWV * PGP_THREADS) return false;      // weight values a thread stages per chunk
+  if (std::max(g.NQG, g.NQS) * NV * 16 > PGP_NWV * 64 * PGP_WPG) return false;      // weight values a thread stages per chunk
   return pgp_lds_bytes(g) <= 64 * 1024;
 }
 size_t pgp_pack_doubles(const PgPack& g) { return (size_t)g.NKS * g.NTP * 256; }
 
 void launch_pair_gram_pack(const Ctx& c, const PgPack& g, double* pack, hipStream_t st) {
   const dim3 grid(g.NRG * g.NCG + g.NWG_S, g.NKS, 1);
-  switch (g.WPG) {
-    case 8: hipLaunchKernelGGL(k_pair_gram_pack<8>, grid, dim3(512), pgp_lds_bytes(g), st, c, g, pack); break;
-    case 2: hipLaunchKernelGGL(k_pair_gram_pack<2>, grid, dim3(128), pgp_lds_bytes(g), st, c, g, pack); break;
-    default: hipLaunchKernelGGL(k_pair_gram_pack<4>, grid, dim3(256), pgp_lds_bytes(g), st, c, g, pack); break;
-  }
+  hipLaunchKernelGGL(k_pair_gram_pack<PGP_WPG>, grid, dim3(64 * PGP_WPG), pgp_lds_bytes(g), st, c, g, pack);
   const int nblk_red = (g.NTP * 256 * 4 + 255) / 256;
   hipLaunchKernelGGL(k_pg_reduce_pack, dim3(nblk_red), dim3(256), 0, st, c, g, pack);      // (the pi / alpha_3 job: a workgroup of k_factor, Ctx::pi_in_factor)
 }

@@ -226,7 +226,7 @@ struct PgPack {
                          // = 64 record columns each); s workgroups per slice (WPG single tiles each)
   int SLG, SLS;          // doubles per (chain, curve) of the pair-weight table (NZZ + NCC + 1, even) / the raw table (K + MD + 1, even)
   int NQG, NQS;          // most chains a G / an s workgroup stages
-  int WPG;               // waves (= packed row tiles) per workgroup
+  int WPG;               // waves (= packed row tiles) per workgroup: PGP_WPG = 4, the one instance of the kernel
   int NTP;               // output tiles per slice: TG 2 NP2 + TS 2
   int NP2;               // 32-column pairs of the G part
 };

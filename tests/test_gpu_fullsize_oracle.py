@@ -296,3 +296,31 @@ def test_long_curve_set_through_the_chunked_contraction():
         err = rel_err(batch.get_chain(nm), getattr(chains[3], ORC_FIELD.get(nm, nm)))
         assert err < 1e-6, (3, nm, err)
     batch.close()
+
+
+def test_long_nu_z_batch_through_the_plain_contraction():
+    """n_funct = 73728, a Nu_Z batch of 34 chains: two streams of 17, more weight values per chunk than k_pair_gram_pack stages,
+    so each sub-batch runs k_pair_gram.  The long-set k-slices (576 curves) would ask it for 172 KB of LDS: it takes its own
+    slices instead.  2 sweeps; the last chain against the sufficient-statistics form of the oracle (BFMMM.h:1073-1113)"""
+    import bayesfmmm_amd as bf
+    from bench import make_config2
+    T, NCH = 2, 34
+    w = make_config2(n=73728, n_i=12, seed=4)
+    sim = dict(n=w["n"], K=w["K"], M=w["M"], P=w["P"], nu=w["state"]["nu"], Phi=w["state"]["Phi"], chi=w["state"]["chi"])
+    model = O.Model(w["y"], w["B"], w["K"], w["M"])
+    cfg = bf.default_config(model=bf.MODEL_FUNCTIONAL, K=w["K"], n_eigen=w["M"], basis_degree=3, tot_mcmc_iters=T)
+    ch = O.Chain(model, T)
+    generic_state(ch, sim, np.random.default_rng(73))
+    ch.chi[:] = 0.0
+    ch.Phi[:] = 0.0
+    batch = make_sampler(bf, cfg, w, n_chains=NCH)
+    for q in range(NCH):          # the same state everywhere: the chains differ by their RNG ids
+        batch.select_chain(q)
+        push_state(batch, ch)
+    batch.run(bf.sampler.SWEEP_NU_Z, T, seed=8, chain=0, phi_chi_zero=True)
+    O.run_warm_gram(model, O.make_hyper(3), ch, n_iter=T, seed=8, chain_id=NCH - 1, sweep=O.SWEEP_NU_Z)
+    batch.select_chain(NCH - 1)
+    for nm in ["nu", "Z", "pi", "alpha_3", "tau", "sigma_sq", "loglik"]:
+        err = rel_err(batch.get_chain(nm), getattr(ch, ORC_FIELD.get(nm, nm)))
+        assert err < 1e-6, (nm, err)
+    batch.close()
