@@ -120,6 +120,8 @@ POST_SYMBOLS = {
     "bfmmm_post_psis": (C.c_int, [c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                   c_double_p, c_double_p]),
     "bfmmm_FLOO": (C.c_int, [C.POINTER(PostArgs), C.POINTER(C.c_void_p)]),
+    "bfmmm_post_diagnostics": (C.c_int, [c_double_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p,
+                                         c_double_p, c_double_p, c_double_p, c_double_p]),
     "bfmmm_MVLOO": (C.c_int, [C.POINTER(PostArgs), C.POINTER(C.c_void_p)]),
     "bfmmm_ConditionalPredictiveOrdinates": (C.c_int, [C.POINTER(PostArgs), C.c_int32, C.POINTER(C.c_void_p)]),
     "bfmmm_post_last_kernel_ms": (C.c_double, []),
@@ -858,6 +860,28 @@ def psis_loo(ll, device=0):
     _check(lib.bfmmm_post_psis(m.ctypes.data_as(c_double_p), n, S, device, *[o.ctypes.data_as(c_double_p) for o in outs]))
     pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs))
     return loo_totals(pw, S)
+
+
+# ---- convergence diagnostics (include/bfmmm_post.h) -----------------------------------------------------
+DIAG_STATS = ("rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd")
+
+
+def diagnostics(draws, device=0):
+    """Split R-hat (rank-normalised, bulk and folded), bulk / tail ESS, ESS and MCSE of the mean, mean and sd of draws of
+    shape (S, C) or (S, C, *shape) -- S draws of C chains -- on the device.  Returns a dict of the seven statistics, each of
+    shape `shape`."""
+    lib = _lib_entry()
+    d = np.asarray(draws, dtype=np.float64)
+    if d.ndim < 2:
+        raise ValueError("'draws' must be (S, C) or (S, C, *shape)")
+    S, C = d.shape[:2]
+    shape = d.shape[2:]
+    n_param = int(np.prod(shape, dtype=np.int64))
+    rows = np.ascontiguousarray(d.reshape(S, C, n_param).transpose(2, 1, 0))      # x[s + S (c + C p)]
+    outs = [np.zeros(n_param) for _ in DIAG_STATS]
+    _check(lib.bfmmm_post_diagnostics(rows.ctypes.data_as(c_double_p), n_param, C, S, device,
+                                      *[o.ctypes.data_as(c_double_p) for o in outs]))
+    return {k: o.reshape(shape) for k, o in zip(DIAG_STATS, outs)}
 
 
 # ---- credible intervals (src/PostProcessing.cpp:99, :3435, :3505) -------------------------------------------------------

@@ -1263,6 +1263,81 @@ extern "C" int bfmmm_get_chain(bfmmm_handle* h, const char* name, int n_slots, d
   return fail("bfmmm_get_chain: unknown name '" + s + "'");
 }
 
+// ---- convergence diagnostics over the chain slots (kernels_diag.hip) --------------------------------------
+long long diag_row_max();
+size_t diag_row_ws_doubles(int C, int S);
+std::string diag_launch(const double* d_x, long long rows, int C, int S, double* d_out, long long ld_out, double* ws, long long ws_rows,
+                        hipStream_t st);
+std::string diag_gather(const double* base, size_t chain_bytes, long long ss, long long ps, int first, int S, int C, int p0, int P,
+                        double* ws, hipStream_t st);
+
+// Every chain of the batch, slots [first_slot, first_slot + n_slots) of `name`: elements are gathered in chunks of
+// consecutive elements into a row-major workspace (draw fastest, then chain) and reduced there; nothing goes to the host
+// but the seven statistics.
+extern "C" int bfmmm_chain_diagnostics(bfmmm_handle* h, const char* name, int first_slot, int n_slots, int64_t max_workspace_bytes,
+                                       double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
+                                       double* mean, double* sd, int64_t capacity) {
+  const char* pn[] = {"h", "name", "rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd"};
+  const void* pv[] = {h, name, rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
+  for (int i = 0; i < 9; ++i)
+    if (!pv[i]) return fail(std::string("bfmmm_chain_diagnostics: '") + pn[i] + "' is null");
+  if (first_slot < 0 || first_slot >= h->T) return fail("bfmmm_chain_diagnostics: 'first_slot' out of range");
+  if (n_slots < 1 || n_slots > h->T - first_slot) return fail("bfmmm_chain_diagnostics: 'n_slots' out of range (first_slot + n_slots > T)");
+  if (max_workspace_bytes < 0) return fail("bfmmm_chain_diagnostics: 'max_workspace_bytes' must not be negative");
+  const Ctx& c = h->c;          // chain 0's pointers; chain q's are q * chain_bytes (covariate blocks: chain_bytes_cov) further
+  const Dims& d = c.d;
+  const int64_t n = d.n, K = d.K, P = d.P, M = d.M;
+  const std::string s(name);
+  struct Arr { const char* nm; const double* p; int64_t len; bool cov; };
+  const Arr arrs[] = {{"nu", c.c_nu, K * P, false}, {"chi", c.c_chi, n * M, false}, {"Z", c.c_Z, n * K, false}, {"pi", c.c_pi, K, false},
+                      {"alpha_3", c.c_alpha3, 1, false}, {"delta", c.c_delta, K * M, false}, {"A", c.c_A, K * 2, false},
+                      {"sigma_sq", c.c_sigma, 1, false}, {"gamma", c.c_gamma, K * P * M, false}, {"Phi", c.c_Phi, K * P * M, false},
+                      {"loglik", c.c_loglik, 1, false},
+                      {"eta", c.c_eta, P * d.D * K, true}, {"xi", c.c_xi, K * P * d.D * M, true}, {"tau_eta", c.c_tau_eta, K * d.D, true},
+                      {"gamma_xi", c.c_gamma_xi, K * P * d.D * M, true}, {"delta_xi", c.c_delta_xi, K * M * d.D, true},
+                      {"A_xi", c.c_A_xi, K * 2 * d.D, true},
+                      {"tau", c.c_tau, K, false}};      // tau: T_alloc x K column-major (slot fastest)
+  const Arr* a = nullptr;
+  for (const Arr& e : arrs)
+    if (s == e.nm && e.p) a = &e;
+  if (!a) return fail("bfmmm_chain_diagnostics: unknown name '" + s + "'");
+  const int64_t len = a->len;
+  if (capacity < len) return fail("bfmmm_chain_diagnostics(" + s + "): 'capacity' below " + std::to_string(len) + " entries");
+  const int C = h->nch, S = n_slots;
+  if ((long long)C * S > diag_row_max())
+    return fail("bfmmm_chain_diagnostics: at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " +
+                std::to_string((long long)C * S));
+  const long long ss = s == "tau" ? 1 : len, ps = s == "tau" ? h->T : 1;
+  const size_t cb = a->cov ? c.chain_bytes_cov : c.chain_bytes;
+  const size_t budget = max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20;
+  const size_t per_row = sizeof(double) * ((size_t)C * S + diag_row_ws_doubles(C, S)) + 7 * sizeof(double);
+  if (budget < per_row)
+    return fail("bfmmm_chain_diagnostics: 'max_workspace_bytes' below the " + std::to_string(per_row) + " bytes of one row");
+  const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
+  HIPCHK(hipSetDevice(h->device));
+  double* d_ws = nullptr;
+  HIPCHK(hipMalloc(&d_ws, per_row * (size_t)chunk));
+  double* d_x = d_ws;
+  double* d_out = d_x + (size_t)chunk * C * S;
+  double* d_tier = d_out + 7 * (size_t)chunk;
+  std::vector<double> hb(7 * (size_t)chunk);
+  double* const outs[7] = {rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
+  std::string err;
+  for (int64_t p0 = 0; p0 < len && err.empty(); p0 += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, len - p0);
+    err = diag_gather(a->p, cb, ss, ps, first_slot, S, C, (int)p0, rows, d_x, h->st);
+    if (err.empty()) err = diag_launch(d_x, rows, C, S, d_out, rows, d_tier, rows, h->st);
+    if (err.empty() && copy_sync(h, hb.data(), d_out, sizeof(double) * 7 * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess)
+      err = "kernel or copy back failed";
+    if (err.empty())
+      for (int q = 0; q < 7; ++q) std::copy(hb.begin() + (size_t)q * rows, hb.begin() + (size_t)(q + 1) * rows, outs[q] + p0);
+  }
+  (void)hipStreamSynchronize(h->st);
+  (void)hipFree(d_ws);
+  if (!err.empty()) { (void)hipGetLastError(); return fail("bfmmm_chain_diagnostics(" + s + "): " + err); }
+  return 0;
+}
+
 extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capacity, int64_t* count) {
   if (!h || !name || !out || !count) return fail("bfmmm_debug_get: null argument");
   HIPCHK(hipSetDevice(h->device));

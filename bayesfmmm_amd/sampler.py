@@ -166,6 +166,23 @@ class Sampler:
         _lib.check(self.lib.bfmmm_get_chain(self.h, name.encode(), T, _dp(out), out.size))
         return out
 
+    def diagnostics(self, name, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """Split R-hat, bulk / tail ESS, ESS and MCSE of the mean, mean and sd of chain slots [first_slot, first_slot + n_slots)
+        of `name` (a get_chain name) over every chain of the batch, computed on the device (bfmmm_chain_diagnostics).
+        Returns a dict of the seven statistics, each shaped like one draw of `name` (Z: (n, K); tau: (K,))."""
+        T = self.T - int(first_slot) if n_slots is None else int(n_slots)
+        shp = {"nu": (self.K, self.P), "chi": (self.n, self.M), "Z": (self.n, self.K), "pi": (self.K,), "alpha_3": (), "delta": (self.K, self.M),
+               "A": (self.K, 2), "sigma_sq": (), "tau": (self.K,), "gamma": (self.K, self.P, self.M), "Phi": (self.K, self.P, self.M),
+               "loglik": (), "eta": (self.P, self.D, self.K), "xi": (self.P, self.D, self.M, self.K),
+               "gamma_xi": (self.P, self.D, self.M, self.K), "tau_eta": (self.K, self.D), "delta_xi": (self.K, self.M, self.D),
+               "A_xi": (self.K, 2, self.D)}.get(name, (1,))
+        cnt = int(np.prod(shp, dtype=np.int64))
+        outs = [np.zeros(cnt) for _ in range(7)]
+        _lib.check(self.lib.bfmmm_chain_diagnostics(self.h, name.encode(), int(first_slot), T, int(max_workspace_bytes),
+                                                    *[_dp(o) for o in outs], cnt))
+        names = ("rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd")
+        return {k: o.reshape(shp, order="F") for k, o in zip(names, outs)}
+
     def get_basis(self):
         n_obs = int(self.offsets[-1])
         out = np.zeros((n_obs, self.P))

@@ -178,6 +178,16 @@ int bfmmm_tempered_transition(bfmmm_handle* h, uint32_t mask, int iter, int N_t,
  * "delta" K x M x T, "sigma_sq" T, "tau" T x K, "gamma"/"Phi" T arrays of K x P x M, "loglik" T. */
 int bfmmm_get_chain(bfmmm_handle* h, const char* name, int n_slots, double* out, int64_t capacity);
 
+/* Convergence diagnostics of chain slots [first_slot, first_slot + n_slots) of `name` (the names of bfmmm_get_chain) over
+ * EVERY chain of the batch (bfmmm_select_chain is ignored), on the device: split R-hat, bulk / tail ESS, ESS and MCSE of the
+ * mean, mean and sd.  One entry per element of one draw, in bfmmm_get_chain's per-draw order ("tau": K
+ * entries); capacity >= that count.  The slots are gathered on the sampler's stream into a workspace of at most
+ * max_workspace_bytes (0: 256 MiB), in several chunks where a block does not fit.  At most 2^22 draws per row
+ * (n_chains x n_slots).  Only the statistics are copied to the host. */
+int bfmmm_chain_diagnostics(bfmmm_handle* h, const char* name, int first_slot, int n_slots, int64_t max_workspace_bytes,
+                            double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
+                            double* mean, double* sd, int64_t capacity);
+
 /* Diagnostics for the parity tests: "rec" (n x LREC per-curve statistics), "H", "tvec", "Cmat", "Lmat",
  * "dims" (as doubles).  Returns the number of doubles written through *count. */
 int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capacity, int64_t* count);

@@ -65,8 +65,15 @@ int bfmmm_post_curve_loglik(const bfmmm_post_input* in, int32_t first_kept, doub
  * 2^22 draws per row in this build. */
 int bfmmm_post_psis(const double* ll, int32_t n, int32_t S, int32_t device, double* lppd, double* elpd_loo, double* p_loo,
                     double* pareto_k, double* elpd_waic, double* p_waic);
-/* device time (ms, HIP events) of the kernels of the last post-processing pass of this process (the pointwise, CPO or PSIS
- * pass): measurement aid */
+/* Convergence diagnostics of every row of a host draws array: x[s + n_draws (c + n_chains p)] (draw fastest, then chain,
+ * then parameter: R's draws_array order), p < n_param.  Split R-hat (rank-normalised, the max of bulk and folded), bulk and
+ * tail ESS, ESS and MCSE of the mean, mean and sd over all draws (Vehtari et al. 2021): seven arrays of
+ * n_param.  NaN where a statistic is undefined (constant or non-finite rows, too few draws).  At most 2^22 draws per row
+ * (n_chains x n_draws) in this build. */
+int bfmmm_post_diagnostics(const double* draws, int64_t n_param, int32_t n_chains, int32_t n_draws, int32_t device, double* rhat,
+                           double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean, double* mean, double* sd);
+/* device time (ms, HIP events) of the kernels of the last post-processing pass of this process (the pointwise, CPO, PSIS
+ * or diagnostics pass): measurement aid */
 double bfmmm_post_last_kernel_ms(void);
 
 typedef struct {
