@@ -103,7 +103,7 @@ struct bfmmm_handle {
   // Captured graphs of runs with the key below, oldest first: (sub-batch, kind, repetitions) -> graph (run_impl)
   struct CachedGraph { int sub, kind, reps; hipGraphExec_t g; };
   std::vector<CachedGraph> graphs;
-  using GraphKey = std::tuple<uint32_t, int, uint64_t, uint32_t, int, int>;      // (mask, MD, seed, chain, nsub, exact instances)
+  using GraphKey = std::tuple<uint32_t, int, uint64_t, uint32_t, int, int>;      // (mask, MD, seed, chain, nsub, instance switches)
   GraphKey g_key;
   bool g_valid = false;                // the cached graphs were captured for g_key
   int last_md = -1;
@@ -1095,7 +1095,7 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
     if (bodies) segs.push_back({GK_CLOSING, 1});
   }
   // (the captured graphs bake in the kernel instances the launchers chose: the key carries the switch that chooses them)
-  const bfmmm_handle::GraphKey key{mask, MD, seed, chain, nsub, bfmmm::g_exact_instances ? 1 : 0};
+  const bfmmm_handle::GraphKey key{mask, MD, seed, chain, nsub, (bfmmm::g_exact_instances ? 1 : 0) | (bfmmm::g_solo_pair_gram ? 2 : 0)};
   if (n_iters > 0 && !(h->g_valid && h->g_key == key)) { drop_graphs(h); h->g_key = key; h->g_valid = true; }
   std::vector<FreshGraph> fresh;      // graphs instantiated by this call
   std::vector<hipGraphExec_t> seq[bfmmm_handle::MAX_SUB];
@@ -1369,8 +1369,9 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
   return fail("bfmmm_debug_get: unknown name '" + s + "'");
 }
 
-namespace bfmmm { int g_exact_instances = 1; }
+namespace bfmmm { int g_exact_instances = 1; int g_solo_pair_gram = 1; }
 extern "C" void bfmmm_set_exact_instances(int enable) { bfmmm::g_exact_instances = enable ? 1 : 0; }
+extern "C" void bfmmm_set_solo_pair_gram(int enable) { bfmmm::g_solo_pair_gram = enable ? 1 : 0; }
 
 extern "C" int bfmmm_set_profile(bfmmm_handle* h, int enable) {
   if (!h) return fail("bfmmm_set_profile: null handle");

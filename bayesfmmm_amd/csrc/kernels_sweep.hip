@@ -69,6 +69,160 @@ constexpr int PG_THREADS = 512;   // 8 waves, two per SIMD: a wave's LDS reads a
 // number of lines per instruction, not by bytes).
 __host__ __device__ inline int h2_index(int P, int p, int k) { return (((k >> 1) * P + p) << 1) + (k & 1); }
 
+// Single-chain body of the G workgroups of k_pair_gram (k_pair_gram<false, false> launched with do_pg == PG_SOLO).  Same
+// output and the same canonical summation order as the general body below (and as k_pair_gram_pack), three differences:
+//  * the pair rows are formed at staging, from the registers that load a curve's Z and chi (thread il owns curve il of the
+//    slice), and stored with them: no LDS re-read of the raw rows and no second barrier (the general body spends 1.7 us there);
+//  * a wave runs exactly its row tiles wave, wave + 8, .. (1 .. PGS_TMAX, scalar count): the general body issues TPW = 2
+//    MFMA chains per wave whether or not the second tile exists, so every SIMD ran four 44-step chains at config 2 where
+//    three suffice (row tiles of SIMD s: s, s + 4, s + 8, ..: 3/3/3/2 for 11 tiles);
+//  * the B operand (one record column per lane, the same for every tile of the workgroup) is read once per step pair for all
+//    tiles of the wave, and the k-loop stops at the last live 16-curve chunk of a partial slice.
+// Limits (otherwise the general body): functional model, no covariates, K <= 4, M <= 8, P <= 32, LG <= 128, KS <= 256.
+constexpr int PG_SOLO = 2;                 // do_pg value that selects it
+constexpr int PGS_TMAX = 4;                // row tiles per wave: RT <= 32
+constexpr int PGS_KS = 256;                // curves per k-slice: one weight-loading thread per curve, 8 record loads per thread
+
+inline bool pg_solo_fits(const Dims& d, int KS) {
+  return !d.mv && d.D == 0 && d.K <= 4 && d.MD - 1 <= 8 && d.P <= 32 && d.LG <= 128 && KS <= PGS_KS &&
+         d.RT <= PGS_TMAX * (PG_THREADS / 64);
+}
+
+template <int NTL>
+__device__ inline void pg_solo_tiles(const double* sP, const double* sB, int KSP, int KQ, int nchunk, const int (&o1)[PGS_TMAX],
+                                     const int (&o2)[PGS_TMAX], int lr, int kq, double4_t (&acc)[PGS_TMAX]) {
+  const v2d* pa[NTL]; const v2d* pb[NTL];
+#pragma unroll
+  for (int q = 0; q < NTL; ++q) {
+    pa[q] = (const v2d*)(sP + o1[q] * KSP + kq * KQ);
+    pb[q] = (const v2d*)(sP + o2[q] * KSP + kq * KQ);
+  }
+  const v2d* pc = (const v2d*)(sB + lr * KSP + kq * KQ);
+  // chunk t = steps 4 t .. 4 t + 3 = v2d entries 2 t, 2 t + 1 of every row; the operands of chunk t + 1 are read into the other
+  // set before the MFMAs of chunk t issue (as in the general body)
+  struct Ops { v2d a[2][NTL], b[2][NTL], c[2]; };
+  auto load = [&](Ops& o, int t) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      o.c[u] = pc[2 * t + u];
+#pragma unroll
+      for (int q = 0; q < NTL; ++q) { o.a[u][q] = pa[q][2 * t + u]; o.b[u][q] = pb[q][2 * t + u]; }
+    }
+  };
+  auto mfma = [&](const Ops& o) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int q = 0; q < NTL; ++q) {
+        acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[u][q].x * o.b[u][q].x, o.c[u].x, acc[q], 0, 0, 0);
+        acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[u][q].y * o.b[u][q].y, o.c[u].y, acc[q], 0, 0, 0);
+      }
+  };
+  Ops s0, s1;
+  load(s0, 0);
+  for (int t = 0; t < nchunk; t += 2) {
+    if (t + 1 < nchunk) load(s1, t + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma(s0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (t + 2 < nchunk) load(s0, t + 2);
+    __builtin_amdgcn_sched_barrier(0);
+    if (t + 1 < nchunk) mfma(s1);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+__device__ inline void pg_solo_g(const Ctx& c0, int KS, int ks, int ct, double* smem) {
+  const Dims& d = c0.d;
+  const int n = d.n, K = d.K, MD = d.MD, tid = threadIdx.x;
+#ifdef BFMMM_TIMELINE
+  struct { Dyn* dyn; } c = {c0.dyn};
+#endif
+  TSTAMP0(c, 40);
+  const int i0 = ks * KS;
+  const int nlive = min(KS, n - i0);
+  const int nchunk = (nlive + 15) >> 4;
+  const int nst = nchunk * 16;               // curves staged: the live ones and the zero tail of the last chunk
+  const int KSP = KS + 2, KQ = KS >> 2;      // the general body's layout: curve il at position (il & 3) KS/4 + (il >> 2)
+  const int NZZ = d.NZZ, NP = NZZ + d.NCC;
+  double* sB = smem;                         // 16 x KSP  record columns
+  double* sP = sB + 16 * KSP;                // (NP + 1) x KSP  pair rows, row NP = 0 (padding rows of the last tile)
+  // ---- every global load of the slice first: Z / chi of curve tid, the record entries of (curve tid / 16 + 32 u, column tid % 16)
+  const bool wl = tid < nlive;
+  const int iw = i0 + tid;
+  double z[4], x[8];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) z[a] = (wl && a < K) ? c0.Z[iw + (size_t)n * a] : 0.0;
+#pragma unroll
+  for (int m = 0; m < 8; ++m) x[m] = (wl && m < MD - 1) ? c0.chi[iw + (size_t)n * m] : 0.0;
+  const int ccg = tid & 15, ilg = tid >> 4;
+  const bool colok = ct * 16 + ccg < d.LG;
+  const double* srcg = c0.rec + (size_t)i0 * d.LREC + min(ct * 16 + ccg, d.LREC - 1);
+  double vb[PGS_KS / 32];
+#pragma unroll
+  for (int u = 0; u < PGS_KS / 32; ++u) {
+    const int il = ilg + 32 * u;
+    vb[u] = (il < nlive && colok) ? srcg[(size_t)il * d.LREC] : 0.0;
+  }
+  TSTAMP0(c, 47);
+  // ---- pair rows of curve tid from registers: Z_a Z_b (a <= b), then chit_a chit_b (a <= b; chit_0 = 1), the order of the
+  //      general body's pair table; each entry is the same product of two raw weights
+  if (tid < nst) {
+    double* dst = sP + (tid & 3) * KQ + (tid >> 2);
+    int e = 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = a; b < 4; ++b)
+        if (b < K) { dst[e * KSP] = z[a] * z[b]; ++e; }
+    const double xt[9] = {1.0, x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7]};
+#pragma unroll
+    for (int a = 0; a < 9; ++a)
+#pragma unroll
+      for (int b = a; b < 9; ++b)
+        if (b < MD) { dst[e * KSP] = xt[a] * xt[b]; ++e; }
+    dst[NP * KSP] = 0.0;
+  }
+#pragma unroll
+  for (int u = 0; u < PGS_KS / 32; ++u) {
+    const int il = ilg + 32 * u;
+    if (il < nst) sB[ccg * KSP + (il & 3) * KQ + (il >> 2)] = vb[u];
+  }
+  TSTAMP0(c, 41);
+  lds_barrier();
+  TSTAMP0(c, 42);
+  // ---- MFMA phase: wave w owns row tiles w, w + 8, ..
+  constexpr int NW = PG_THREADS / 64;
+  const int wave = tid >> 6, lane = tid & 63, lr = lane & 15, kq = lane >> 4;
+  const int ntl = __builtin_amdgcn_readfirstlane(max(0, min(PGS_TMAX, (d.RT - wave + NW - 1) / NW)));
+  int o1[PGS_TMAX], o2[PGS_TMAX];
+#pragma unroll
+  for (int q = 0; q < PGS_TMAX; ++q) {
+    const int row = (wave + NW * q) * 16 + lr;
+    o1[q] = o2[q] = NP;
+    if (q < ntl && row < d.R) { const int zz = row / d.NCC; o1[q] = zz; o2[q] = NZZ + (row - zz * d.NCC); }
+  }
+  double4_t acc[PGS_TMAX];
+#pragma unroll
+  for (int q = 0; q < PGS_TMAX; ++q) acc[q] = double4_t{0.0, 0.0, 0.0, 0.0};
+  switch (ntl) {
+    case 1: pg_solo_tiles<1>(sP, sB, KSP, KQ, nchunk, o1, o2, lr, kq, acc); break;
+    case 2: pg_solo_tiles<2>(sP, sB, KSP, KQ, nchunk, o1, o2, lr, kq, acc); break;
+    case 3: pg_solo_tiles<3>(sP, sB, KSP, KQ, nchunk, o1, o2, lr, kq, acc); break;
+    case 4: pg_solo_tiles<4>(sP, sB, KSP, KQ, nchunk, o1, o2, lr, kq, acc); break;
+    default: break;
+  }
+  // partial tiles: the general body's layout and streaming stores
+#pragma unroll
+  for (int q = 0; q < PGS_TMAX; ++q)
+    if (q < ntl) {
+      double* out = c0.pg_part + ((size_t)ks * d.NT + (size_t)(wave + NW * q) * d.CTG + ct) * 256 + lane;
+      __builtin_nontemporal_store(acc[q][0], out); __builtin_nontemporal_store(acc[q][1], out + 64);
+      __builtin_nontemporal_store(acc[q][2], out + 128); __builtin_nontemporal_store(acc[q][3], out + 192);
+    }
+  TSTAMP0(c, 44);
+}
+
 template <bool BATCH, bool GROUPS>
 __global__ __launch_bounds__(PG_THREADS) void k_pair_gram(Ctx c0, int KS, int nks, int do_pg, int G) {
   // Chain batches (BATCH): the workgroup stages its record columns ONCE and walks the chains of the batch in groups of G
@@ -114,6 +268,9 @@ __global__ __launch_bounds__(PG_THREADS) void k_pair_gram(Ctx c0, int KS, int nk
   if (ks >= nks) return;            // (the grid's y extent is max(k-slices, chains))
   if (!do_pg) return;
   const bool single = ct == d.CTG;
+  if constexpr (!BATCH) {
+    if (do_pg == PG_SOLO && !single) { pg_solo_g(c0, KS, ks, ct, smem); return; }
+  }
   const int ncol = single ? d.CTS * 16 : 16;
   const int col0 = single ? d.LG : ct * 16;
   const int colend = single ? d.LG + d.P : d.LG;
@@ -2044,7 +2201,11 @@ void launch_pair_gram(const Ctx& c, int do_pg, int NKS, int KS, hipStream_t st) 
   const size_t lds = pair_gram_lds_bytes(d, KS, G);
   if (c.nch > 1 && G > 1) hipLaunchKernelGGL((k_pair_gram<true, true>), dim3(d.CTG + 2, do_pg ? std::max(NKS, c.nch) : c.nch, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, G);
   else if (c.nch > 1) hipLaunchKernelGGL((k_pair_gram<true, false>), dim3(d.CTG + 2, do_pg ? std::max(NKS, c.nch) : c.nch, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, 1);
-  else hipLaunchKernelGGL((k_pair_gram<false, false>), dim3(d.CTG + 2, do_pg ? NKS : 1, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, 1);
+  else {
+    // (the single-chain body of the G workgroups where the shape allows: pg_solo_g; bfmmm_set_solo_pair_gram(0) keeps the general one)
+    const int pg = (do_pg && g_solo_pair_gram && pg_solo_fits(d, KS)) ? PG_SOLO : do_pg;
+    hipLaunchKernelGGL((k_pair_gram<false, false>), dim3(d.CTG + 2, do_pg ? NKS : 1, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, pg, 1);
+  }
 }
 
 // geometry of k_pair_gram_pack for this (sub-)batch; returns false when the shape is outside its limits (the caller keeps k_pair_gram)

@@ -204,6 +204,11 @@ int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* lau
  * general instances instead -- the parity tests run both and compare.  Process-wide; default 1. */
 void bfmmm_set_exact_instances(int enable);
 
+/* Single chains run the G workgroups of the pair-Gram contraction through a body of their own where the shape allows (DESIGN.md
+ * section 5); 0 makes later runs use the general body instead -- the parity tests run both and compare bit for bit.
+ * Process-wide; default 1. */
+void bfmmm_set_solo_pair_gram(int enable);
+
 const char* bfmmm_last_error(void);
 
 #ifdef __cplusplus
