@@ -27,6 +27,7 @@ int curve_blocks(int n, int P);
 void prepare_curve_kernels();
 void prepare_sweep_kernels();
 void launch_pair_gram(const Ctx& c, int do_pg, int NKS, int KS, hipStream_t st);
+int pair_gram_body(const Ctx& c, int KS, int& G);
 size_t pair_gram_lds_bytes(const Dims& d, int KS);
 void launch_pg_reduce(const Ctx& c, int NKS, hipStream_t st);
 bool pgp_geometry(const Dims& d, int nch, int KS, int NKS, PgPack& g);
@@ -107,6 +108,7 @@ struct bfmmm_handle {
   GraphKey g_key;
   bool g_valid = false;                // the cached graphs were captured for g_key
   int last_md = -1;
+  double last_route[5] = {0, 0, 0, -1, 0};     // bfmmm_debug_get("pg_route"): {packed, KS, NKS, body, G} of sub-batch 0 of the last run
   int64_t tab_key = -1;                // (MD, mask) the step tables of k_sweep_chain were built for
   int launch_error = 0;
   int slot_base = 0;                   // chain slot of iteration i is i - slot_base (bfmmm_set_slot_base)
@@ -1054,6 +1056,14 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
     subs[q].st = h->sub_st[q];
     q0 += cnt;
   }
+  {
+    // what sub-batch 0 runs, for bfmmm_debug_get("pg_route"): body / G as launch_pair_gram picks them (packed: -1 / 0)
+    const PgRoute& r0 = subs[0].r;
+    int G = 0;
+    const int body = r0.packed ? -1 : pair_gram_body(subs[0].c, r0.KS, G);
+    const double v[5] = {r0.packed ? 1.0 : 0.0, (double)r0.KS, (double)r0.NKS, (double)body, (double)G};
+    memcpy(h->last_route, v, sizeof v);
+  }
   // single chain: the scalar job of k_curve_chi rides the next iteration's k_pair_gram instead (its grid has NKS - 1 idle extra
   // workgroups); the run's flush kernel runs the last one
   c.defer_hyper = (c.defer_loglik && plan.pg && plan.chi && h->nch == 1 && !subs[0].r.packed && subs[0].r.NKS >= 2) ? 1 : 0;
@@ -1355,8 +1365,16 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
     *count = cnt;
     return 0;
   }
+  if (s == "pg_route") {      // host-side record of the last bfmmm_run (run_impl)
+    const int64_t cnt = sizeof h->last_route / sizeof h->last_route[0];
+    if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
+    memcpy(out, h->last_route, sizeof h->last_route);
+    *count = cnt;
+    return 0;
+  }
   struct Arr { const char* nm; const double* p; int64_t len; };
   const Arr arrs[] = {{"rec", c.rec, (int64_t)d.n * d.LREC}, {"H", c.H, (int64_t)d.R * d.LG}, {"tvec", c.tvec, (int64_t)d.A * d.P},
+                      {"H2", c.H2, (int64_t)d.R * d.P * (2 * d.BW + 2)},
                       {"Cmat", c.Cmat, (int64_t)d.A * d.P * d.P},
                       {"theta", c.theta, (int64_t)d.K * (d.M + 1) * d.P}};
   for (const Arr& a : arrs)

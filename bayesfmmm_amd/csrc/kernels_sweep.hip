@@ -2190,20 +2190,31 @@ static size_t pair_gram_lds_bytes(const Dims& d, int KS, int G) {
 // the request of a launch with KS-curve slices (chains are only grouped where the group fits)
 size_t pair_gram_lds_bytes(const Dims& d, int KS) { return pair_gram_lds_bytes(d, KS, 1); }
 
-void launch_pair_gram(const Ctx& c, int do_pg, int NKS, int KS, hipStream_t st) {
+// The body of k_pair_gram a (sub-)batch runs with KS-curve slices: 0 the general body (one chain), 1 the single-chain body of
+// the G workgroups (pg_solo_g), 2 the chain loop, 3 the chain loop with G chains staged together.  launch_pair_gram launches
+// what this says; bfmmm_debug_get("pg_route") reports it.
+int pair_gram_body(const Ctx& c, int KS, int& G) {
   const Dims& d = c.d;
   const int ncw = d.K + d.MD - 1;
   // chains staged together (k_pair_gram): as many as 144 KB of LDS and 12 staged doubles per thread allow; covariate-adjusted
   // models stage s~_i per chain and keep one chain per group
-  int G = 1;
+  G = 1;
   if (c.nch > 1 && d.D == 0 && d.RT < 8)      // (with eight or more row tiles per chain the waves are busy chain by chain)
     while (G < c.nch && pair_gram_lds_bytes(d, KS, G + 1) <= 144 * 1024 && (size_t)(G + 1) * ncw * KS <= 12 * 512) ++G;
+  if (c.nch > 1) return G > 1 ? 3 : 2;
+  // (the single-chain body of the G workgroups where the shape allows: pg_solo_g; bfmmm_set_solo_pair_gram(0) keeps the general one)
+  return (g_solo_pair_gram && pg_solo_fits(d, KS)) ? 1 : 0;
+}
+
+void launch_pair_gram(const Ctx& c, int do_pg, int NKS, int KS, hipStream_t st) {
+  const Dims& d = c.d;
+  int G = 1;
+  const int body = pair_gram_body(c, KS, G);
   const size_t lds = pair_gram_lds_bytes(d, KS, G);
-  if (c.nch > 1 && G > 1) hipLaunchKernelGGL((k_pair_gram<true, true>), dim3(d.CTG + 2, do_pg ? std::max(NKS, c.nch) : c.nch, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, G);
-  else if (c.nch > 1) hipLaunchKernelGGL((k_pair_gram<true, false>), dim3(d.CTG + 2, do_pg ? std::max(NKS, c.nch) : c.nch, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, 1);
+  if (body == 3) hipLaunchKernelGGL((k_pair_gram<true, true>), dim3(d.CTG + 2, do_pg ? std::max(NKS, c.nch) : c.nch, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, G);
+  else if (body == 2) hipLaunchKernelGGL((k_pair_gram<true, false>), dim3(d.CTG + 2, do_pg ? std::max(NKS, c.nch) : c.nch, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, 1);
   else {
-    // (the single-chain body of the G workgroups where the shape allows: pg_solo_g; bfmmm_set_solo_pair_gram(0) keeps the general one)
-    const int pg = (do_pg && g_solo_pair_gram && pg_solo_fits(d, KS)) ? PG_SOLO : do_pg;
+    const int pg = (do_pg && body == 1) ? PG_SOLO : do_pg;
     hipLaunchKernelGGL((k_pair_gram<false, false>), dim3(d.CTG + 2, do_pg ? NKS : 1, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, pg, 1);
   }
 }

@@ -188,8 +188,12 @@ int bfmmm_chain_diagnostics(bfmmm_handle* h, const char* name, int first_slot, i
                             double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
                             double* mean, double* sd, int64_t capacity);
 
-/* Diagnostics for the parity tests: "rec" (n x LREC per-curve statistics), "H", "tvec", "Cmat", "Lmat",
- * "dims" (as doubles).  Returns the number of doubles written through *count. */
+/* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
+ * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
+ * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P), "theta" (K (M + 1) x P), "dims" (as doubles) and
+ * "pg_route": how sub-batch 0 of the last bfmmm_run ran its pair-Gram contraction, {packed (0 / 1), KS, NKS,
+ * body (0 general, 1 single-chain, 2 chain loop, 3 chain loop with staged groups; -1 packed), G (chains per group; 0 packed)}
+ * as doubles, recorded on the host.  Returns the number of doubles written through *count. */
 int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capacity, int64_t* count);
 
 /* Timing of the last bfmmm_run: milliseconds between HIP events recorded on the sampler's stream
