@@ -28,6 +28,7 @@ void prepare_curve_kernels();
 void prepare_sweep_kernels();
 void launch_pair_gram(const Ctx& c, int do_pg, int NKS, int KS, hipStream_t st);
 int pair_gram_body(const Ctx& c, int KS, int& G);
+int pair_gram_tail(const Ctx& c, int KS, int NKS, int body);
 size_t pair_gram_lds_bytes(const Dims& d, int KS);
 void launch_pg_reduce(const Ctx& c, int NKS, hipStream_t st);
 bool pgp_geometry(const Dims& d, int nch, int KS, int NKS, PgPack& g);
@@ -108,7 +109,7 @@ struct bfmmm_handle {
   GraphKey g_key;
   bool g_valid = false;                // the cached graphs were captured for g_key
   int last_md = -1;
-  double last_route[5] = {0, 0, 0, -1, 0};     // bfmmm_debug_get("pg_route"): {packed, KS, NKS, body, G} of sub-batch 0 of the last run
+  double last_route[6] = {0, 0, 0, -1, 0, 0};  // bfmmm_debug_get("pg_route"): {packed, KS, NKS, body, G, tail} of sub-batch 0 of the last run
   int64_t tab_key = -1;                // (MD, mask) the step tables of k_sweep_chain were built for
   int launch_error = 0;
   int slot_base = 0;                   // chain slot of iteration i is i - slot_base (bfmmm_set_slot_base)
@@ -1061,7 +1062,8 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
     const PgRoute& r0 = subs[0].r;
     int G = 0;
     const int body = r0.packed ? -1 : pair_gram_body(subs[0].c, r0.KS, G);
-    const double v[5] = {r0.packed ? 1.0 : 0.0, (double)r0.KS, (double)r0.NKS, (double)body, (double)G};
+    const int tail = (r0.packed || !plan.pg) ? 0 : pair_gram_tail(subs[0].c, r0.KS, r0.NKS, body);
+    const double v[6] = {r0.packed ? 1.0 : 0.0, (double)r0.KS, (double)r0.NKS, (double)body, (double)G, (double)tail};
     memcpy(h->last_route, v, sizeof v);
   }
   // single chain: the scalar job of k_curve_chi rides the next iteration's k_pair_gram instead (its grid has NKS - 1 idle extra
@@ -1105,7 +1107,8 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
     if (bodies) segs.push_back({GK_CLOSING, 1});
   }
   // (the captured graphs bake in the kernel instances the launchers chose: the key carries the switch that chooses them)
-  const bfmmm_handle::GraphKey key{mask, MD, seed, chain, nsub, (bfmmm::g_exact_instances ? 1 : 0) | (bfmmm::g_solo_pair_gram ? 2 : 0)};
+  const bfmmm_handle::GraphKey key{mask, MD, seed, chain, nsub, (bfmmm::g_exact_instances ? 1 : 0) | (bfmmm::g_solo_pair_gram ? 2 : 0) |
+                                                                        (bfmmm::g_solo_pair_gram_tail ? 4 : 0)};
   if (n_iters > 0 && !(h->g_valid && h->g_key == key)) { drop_graphs(h); h->g_key = key; h->g_valid = true; }
   std::vector<FreshGraph> fresh;      // graphs instantiated by this call
   std::vector<hipGraphExec_t> seq[bfmmm_handle::MAX_SUB];
@@ -1387,9 +1390,10 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
   return fail("bfmmm_debug_get: unknown name '" + s + "'");
 }
 
-namespace bfmmm { int g_exact_instances = 1; int g_solo_pair_gram = 1; }
+namespace bfmmm { int g_exact_instances = 1; int g_solo_pair_gram = 1; int g_solo_pair_gram_tail = 1; }
 extern "C" void bfmmm_set_exact_instances(int enable) { bfmmm::g_exact_instances = enable ? 1 : 0; }
 extern "C" void bfmmm_set_solo_pair_gram(int enable) { bfmmm::g_solo_pair_gram = enable ? 1 : 0; }
+extern "C" void bfmmm_set_solo_pair_gram_tail(int enable) { bfmmm::g_solo_pair_gram_tail = enable ? 1 : 0; }
 
 extern "C" int bfmmm_set_profile(bfmmm_handle* h, int enable) {
   if (!h) return fail("bfmmm_set_profile: null handle");

@@ -79,7 +79,7 @@ __host__ __device__ inline int h2_index(int P, int p, int k) { return (((k >> 1)
 //  * the B operand (one record column per lane, the same for every tile of the workgroup) is read once per step pair for all
 //    tiles of the wave, and the k-loop stops at the last live 16-curve chunk of a partial slice.
 // Limits (otherwise the general body): functional model, no covariates, K <= 4, M <= 8, P <= 32, LG <= 128, KS <= 256.
-constexpr int PG_SOLO = 2;                 // do_pg value that selects it
+constexpr int PG_SOLO = 2;                 // do_pg flag that selects it
 constexpr int PGS_TMAX = 4;                // row tiles per wave: RT <= 32
 constexpr int PGS_KS = 256;                // curves per k-slice: one weight-loading thread per curve, 8 record loads per thread
 
@@ -223,6 +223,102 @@ __device__ inline void pg_solo_g(const Ctx& c0, int KS, int ks, int ct, double* 
   TSTAMP0(c, 44);
 }
 
+// Single-chain body of the s-part workgroup (ct == CTG) of the same launch, beside pg_solo_g (do_pg carries PG_SOLO_S;
+// bfmmm_set_solo_pair_gram_tail(0) keeps the general body).  Same output slots and the same canonical summation order:
+//  * one round of global loads per thread, all issued before the first LDS store: Z and chi of curve tid, and the CTS 16
+//    columns of s_i (record offset LG) of the slice's live curves, element (il, cc) = (tid / ncol + (512 / ncol) u, tid % ncol)
+//    with ncol = 16 or 32 (shifts and constant offsets; the general body divides per element and runs two serial rounds);
+//  * the single-weight rows Z_j chit_m are formed from the loading registers and stored once -- the same product of the same
+//    two raw weights the general body forms at MFMA time, so the A operand is bit-identical; one barrier;
+//  * each of the AT CTS tiles gets one wave and one MFMA chain (the general body issues TPW = 2 chains per wave although
+//    there are at most 6 tiles for 8 waves) that stops at the last live 16-curve chunk; waves without a tile leave.
+// Limits: pg_solo_fits, hence CTS <= 2 and A <= 36 (AT CTS <= 6 tiles).
+constexpr int PG_SOLO_S = 4;               // do_pg flag (with PG_SOLO): the s-part workgroup runs pg_solo_s
+constexpr int PG_SOLO_LL = 8;              // do_pg flag (with PG_SOLO): the deferred log-likelihood has an extra workgroup of its own
+constexpr int PGS_SU = PGS_KS / (PG_THREADS / 32);      // s_i entries per thread (32 columns; 16 columns use the first half)
+
+__device__ inline void pg_solo_s(const Ctx& c0, int KS, int ks, double* smem) {
+  const Dims& d = c0.d;
+  const int n = d.n, K = d.K, MD = d.MD, tid = threadIdx.x;
+  const int i0 = ks * KS;
+  const int nlive = min(KS, n - i0);
+  const int nchunk = (nlive + 15) >> 4;
+  const int nst = nchunk * 16;               // curves staged: the live ones and the zero tail of the last chunk
+  const int KSP = KS + 2, KQ = KS >> 2;      // the general body's layout: curve il at position (il & 3) KS/4 + (il >> 2)
+  const int ncol = d.CTS * 16;               // 16 or 32
+  double* sB = smem;                         // ncol x KSP  columns of s_i
+  double* sS = sB + ncol * KSP;              // (A + 1) x KSP  single-weight rows, row A = 0 (padding rows of the last row tile)
+  // ---- every global load of the slice first
+  const bool wl = tid < nlive;
+  const int iw = i0 + tid;
+  double z[4], x[8];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) z[a] = (wl && a < K) ? c0.Z[iw + (size_t)n * a] : 0.0;
+#pragma unroll
+  for (int m = 0; m < 8; ++m) x[m] = (wl && m < MD - 1) ? c0.chi[iw + (size_t)n * m] : 0.0;
+  const int sh = (d.CTS == 1) ? 4 : 5;
+  const int cc = tid & (ncol - 1), ilg = tid >> sh, ilstep = PG_THREADS >> sh;
+  const bool colok = cc < d.P;
+  const double* src = c0.rec + (size_t)i0 * d.LREC + min(d.LG + cc, d.LREC - 1);
+  double vb[PGS_SU];
+#pragma unroll
+  for (int u = 0; u < PGS_SU; ++u) {
+    const int il = ilg + ilstep * u;
+    vb[u] = (il < nlive && colok) ? src[(size_t)il * d.LREC] : 0.0;
+  }
+  // ---- single-weight rows of curve tid from registers: row j MD + m = Z_j chit_m (chit_0 = 1), the general body's product
+  if (tid < nst) {
+    double* dst = sS + (tid & 3) * KQ + (tid >> 2);
+    const double xt[9] = {1.0, x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7]};
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int m = 0; m < 9; ++m)
+        if (a < K && m < MD) dst[(a * MD + m) * KSP] = z[a] * xt[m];
+    dst[d.A * KSP] = 0.0;
+  }
+#pragma unroll
+  for (int u = 0; u < PGS_SU; ++u) {
+    const int il = ilg + ilstep * u;
+    if (il < nst) sB[cc * KSP + (il & 3) * KQ + (il >> 2)] = vb[u];
+  }
+  lds_barrier();
+  // ---- MFMA phase: wave w owns tile w = (row tile w / CTS, column tile w % CTS)
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, lr = lane & 15, kq = lane >> 4;
+  if (wave >= d.AT * d.CTS) return;
+  const int at = wave / d.CTS, cs = wave - at * d.CTS;
+  const int row = at * 16 + lr;
+  const v2d* pa = (const v2d*)(sS + (row < d.A ? row : d.A) * KSP + kq * KQ);
+  const v2d* pc = (const v2d*)(sB + (cs * 16 + lr) * KSP + kq * KQ);
+  // chunk t = steps 4 t .. 4 t + 3 = v2d entries 2 t, 2 t + 1 of the two rows, double-buffered as in pg_solo_tiles
+  struct Ops { v2d a[2], c[2]; };
+  auto load = [&](Ops& o, int t) { o.a[0] = pa[2 * t]; o.c[0] = pc[2 * t]; o.a[1] = pa[2 * t + 1]; o.c[1] = pc[2 * t + 1]; };
+  double4_t acc = double4_t{0.0, 0.0, 0.0, 0.0};
+  auto mfma = [&](const Ops& o) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[u].x, o.c[u].x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[u].y, o.c[u].y, acc, 0, 0, 0);
+    }
+  };
+  Ops s0, s1;
+  load(s0, 0);
+  for (int t = 0; t < nchunk; t += 2) {
+    if (t + 1 < nchunk) load(s1, t + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma(s0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (t + 2 < nchunk) load(s0, t + 2);
+    __builtin_amdgcn_sched_barrier(0);
+    if (t + 1 < nchunk) mfma(s1);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // partial tile: the general body's slot (tix = RT CTG + tile) and streaming stores
+  double* out = c0.pg_part + ((size_t)ks * d.NT + (size_t)d.RT * d.CTG + wave) * 256 + lane;
+  __builtin_nontemporal_store(acc[0], out); __builtin_nontemporal_store(acc[1], out + 64);
+  __builtin_nontemporal_store(acc[2], out + 128); __builtin_nontemporal_store(acc[3], out + 192);
+}
+
 template <bool BATCH, bool GROUPS>
 __global__ __launch_bounds__(PG_THREADS) void k_pair_gram(Ctx c0, int KS, int nks, int do_pg, int G) {
   // Chain batches (BATCH): the workgroup stages its record columns ONCE and walks the chains of the batch in groups of G
@@ -251,7 +347,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pair_gram(Ctx c0, int KS, int nk
   if (ct == d.CTG + 1) {            // extra workgroups: pi / alpha_3 of chain ks, hidden under the contraction
     if (ks < nch && threadIdx.x < 256) {      // the scalar jobs are written for 256 threads (waves 4-7 leave)
       const Ctx c = chain_ctx(c0, (unsigned)ks);
-      job_pi_alpha(c);
+      job_pi_alpha(c, BATCH || !(do_pg & PG_SOLO_LL));      // (PG_SOLO_LL: the deferred log-likelihood runs in workgroup 2 nch below)
       TSTAMP(c, 46);
     } else if (ks >= nch && ks < 2 * nch && threadIdx.x < 256) {
       // the previous iteration's scalar job (delta, A, gamma, tau), left pending by k_curve_chi (Ctx::defer_hyper): its results are
@@ -262,6 +358,10 @@ __global__ __launch_bounds__(PG_THREADS) void k_pair_gram(Ctx c0, int KS, int nk
         __syncthreads();
         if (threadIdx.x == 0) c.dyn->hyper_pending = 0u;
       }
+    } else if (!BATCH && (do_pg & PG_SOLO_LL) && ks == 2 * nch && threadIdx.x < 256) {
+      // the previous iteration's log-likelihood, in a workgroup of its own: it shares nothing with pi / alpha_3 (reads rss,
+      // rss_part, sigma2, ll_slot; writes rss, loglik, ll_pending and its chain slot), so it need not run in front of them
+      if (c0.dyn->ll_pending) deferred_loglik(c0, smem);
     }
     return;
   }
@@ -269,7 +369,8 @@ __global__ __launch_bounds__(PG_THREADS) void k_pair_gram(Ctx c0, int KS, int nk
   if (!do_pg) return;
   const bool single = ct == d.CTG;
   if constexpr (!BATCH) {
-    if (do_pg == PG_SOLO && !single) { pg_solo_g(c0, KS, ks, ct, smem); return; }
+    if ((do_pg & PG_SOLO) && !single) { pg_solo_g(c0, KS, ks, ct, smem); return; }
+    if ((do_pg & PG_SOLO_S) && single) { pg_solo_s(c0, KS, ks, smem); return; }
   }
   const int ncol = single ? d.CTS * 16 : 16;
   const int col0 = single ? d.LG : ct * 16;
@@ -2206,6 +2307,18 @@ int pair_gram_body(const Ctx& c, int KS, int& G) {
   return (g_solo_pair_gram && pg_solo_fits(d, KS)) ? 1 : 0;
 }
 
+// What else a single-chain launch (body 1) does in bodies of its own, as do_pg flags: PG_SOLO_S the s-part workgroup
+// (pg_solo_s), PG_SOLO_LL the deferred log-likelihood in the third extra workgroup (the grid's y extent is NKS: three
+// k-slices or more).  0 where a condition fails or after bfmmm_set_solo_pair_gram_tail(0): the launch is then the one
+// pair_gram_body describes.  bfmmm_debug_get("pg_route") reports it as its sixth entry.
+int pair_gram_tail(const Ctx& c, int KS, int NKS, int body) {
+  if (body != 1 || !g_solo_pair_gram_tail) return 0;
+  int f = 0;
+  if (c.d.AT * c.d.CTS <= PG_THREADS / 64 && c.d.CTS <= 2) f |= PG_SOLO_S;
+  if (c.defer_loglik && NKS >= 3) f |= PG_SOLO_LL;
+  return f;
+}
+
 void launch_pair_gram(const Ctx& c, int do_pg, int NKS, int KS, hipStream_t st) {
   const Dims& d = c.d;
   int G = 1;
@@ -2214,8 +2327,10 @@ void launch_pair_gram(const Ctx& c, int do_pg, int NKS, int KS, hipStream_t st) 
   if (body == 3) hipLaunchKernelGGL((k_pair_gram<true, true>), dim3(d.CTG + 2, do_pg ? std::max(NKS, c.nch) : c.nch, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, G);
   else if (body == 2) hipLaunchKernelGGL((k_pair_gram<true, false>), dim3(d.CTG + 2, do_pg ? std::max(NKS, c.nch) : c.nch, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, do_pg, 1);
   else {
-    const int pg = (do_pg && body == 1) ? PG_SOLO : do_pg;
-    hipLaunchKernelGGL((k_pair_gram<false, false>), dim3(d.CTG + 2, do_pg ? NKS : 1, 1), dim3(PG_THREADS), lds, st, c, KS, NKS, pg, 1);
+    const int pg = (do_pg && body == 1) ? (PG_SOLO | pair_gram_tail(c, KS, NKS, body)) : do_pg;
+    // (pg_solo_s stages A + 1 single-weight rows where the general body stages RS raw ones; KS <= 256: at most 142 KB)
+    const size_t lds1 = (pg & PG_SOLO_S) ? std::max(lds, (size_t)(KS + 2) * (d.CTS * 16 + d.A + 1) * sizeof(double)) : lds;
+    hipLaunchKernelGGL((k_pair_gram<false, false>), dim3(d.CTG + 2, do_pg ? NKS : 1, 1), dim3(PG_THREADS), lds1, st, c, KS, NKS, pg, 1);
   }
 }
 

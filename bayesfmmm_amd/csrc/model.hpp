@@ -266,6 +266,7 @@ __device__ inline Ctx chain_view(const Ctx& c0) { return chain_ctx(c0, blockIdx.
 
 extern int g_exact_instances;      // bfmmm_set_exact_instances (bfmmm_capi.hip): 0 = the launchers use only the general instances
 extern int g_solo_pair_gram;       // bfmmm_set_solo_pair_gram (bfmmm_capi.hip): 0 = single chains keep k_pair_gram's general body
+extern int g_solo_pair_gram_tail;  // bfmmm_set_solo_pair_gram_tail: 0 = the s-part workgroup keeps the general body, the log-likelihood rides with pi / alpha_3
 
 __host__ __device__ inline int tri_index(int n, int a, int b) {  // a <= b < n  -> index in packed upper triangle
   return a * n - (a * (a - 1)) / 2 + (b - a);

@@ -139,7 +139,8 @@ __device__ inline void job_pi_prepare(const Ctx& c) {
   if (threadIdx.x == 0) { dyn->piprep_iter = dyn->iter + 1u; dyn->zprep_chain = c.chain; dyn->zprep_seed = c.seed; dyn->piprep_valid = 1u; }
 }
 
-__device__ inline void job_pi_alpha(const Ctx& c) {
+// loglik = false: the caller runs the deferred log-likelihood elsewhere in the same launch (k_pair_gram, PG_SOLO_LL)
+__device__ inline void job_pi_alpha(const Ctx& c, bool loglik = true) {
   // scratch carved from k_pair_gram's dynamic LDS (the launcher guarantees PI_ALPHA_LDS_DOUBLES)
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double (*red)[256] = (double (*)[256])smem;       // KMAX x 256
@@ -150,7 +151,7 @@ __device__ inline void job_pi_alpha(const Ctx& c) {
   const int K = d.K, n = d.n, tid = threadIdx.x;
   Dyn* dyn = c.dyn;
   const uint32_t mask = c.mask;
-  if (dyn->ll_pending) deferred_loglik(c, smem);
+  if (loglik && dyn->ll_pending) deferred_loglik(c, smem);
   if (!(mask & (U_PI | U_ALPHA3))) {
     if (tid == 0) {
       c.c_alpha3[dyn->slot] = dyn->alpha3;

@@ -192,8 +192,9 @@ int bfmmm_chain_diagnostics(bfmmm_handle* h, const char* name, int first_slot, i
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
  * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P), "theta" (K (M + 1) x P), "dims" (as doubles) and
  * "pg_route": how sub-batch 0 of the last bfmmm_run ran its pair-Gram contraction, {packed (0 / 1), KS, NKS,
- * body (0 general, 1 single-chain, 2 chain loop, 3 chain loop with staged groups; -1 packed), G (chains per group; 0 packed)}
- * as doubles, recorded on the host.  Returns the number of doubles written through *count. */
+ * body (0 general, 1 single-chain, 2 chain loop, 3 chain loop with staged groups; -1 packed), G (chains per group; 0 packed),
+ * tail (single-chain body only, a sum of flags: 4 the s-part workgroup runs its single-chain body, 8 the deferred
+ * log-likelihood has a workgroup of its own; 0 otherwise)} as doubles, recorded on the host.  Returns the number of doubles written through *count. */
 int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capacity, int64_t* count);
 
 /* Timing of the last bfmmm_run: milliseconds between HIP events recorded on the sampler's stream
@@ -212,6 +213,12 @@ void bfmmm_set_exact_instances(int enable);
  * section 5); 0 makes later runs use the general body instead -- the parity tests run both and compare bit for bit.
  * Process-wide; default 1. */
 void bfmmm_set_solo_pair_gram(int enable);
+
+/* On the same route the s-part workgroup of the contraction has a single-chain body too, and the deferred log-likelihood
+ * of the previous iteration runs in an extra workgroup of its own instead of in front of pi / alpha_3;
+ * 0 makes later runs keep the general s-part body and the shared workgroup -- tests/test_gpu_pair_gram_solo_s.py compares
+ * the two bit for bit.  What a run took is the last entry of "pg_route".  Process-wide; default 1. */
+void bfmmm_set_solo_pair_gram_tail(int enable);
 
 const char* bfmmm_last_error(void);
 
