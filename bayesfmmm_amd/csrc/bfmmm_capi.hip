@@ -3,6 +3,7 @@
 #include "../../include/bfmmm.h"
 #include "model.hpp"
 #include "rng.hpp"
+#include "launchers.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -15,44 +16,6 @@
 #include <tuple>
 #include <vector>
 
-namespace bfmmm {
-int launch_stats_functional(int degree, int n, int P, int LREC, const int64_t* off, const double* t, const double* y,
-                            const double* knots, int n_knots, double* rec, int* ni, double* B_dense, int* err,
-                            hipStream_t st);
-void launch_stats_multivariate(int n, int P, int LREC, const double* Y, double* rec, int* ni, hipStream_t st);
-void launch_stats_totals(int n, int LREC, int yy_off, const double* rec, const int* ni, double* out_yy,
-                         long long* out_counts, hipStream_t st);
-int launch_curve(const Ctx& c, int which, int do_update, hipStream_t st);
-int curve_blocks(int n, int P);
-void prepare_curve_kernels();
-void prepare_sweep_kernels();
-void launch_pair_gram(const Ctx& c, int do_pg, int NKS, int KS, hipStream_t st);
-int pair_gram_body(const Ctx& c, int KS, int& G);
-int pair_gram_tail(const Ctx& c, int KS, int NKS, int body);
-size_t pair_gram_lds_bytes(const Dims& d, int KS);
-void launch_pg_reduce(const Ctx& c, int NKS, hipStream_t st);
-bool pgp_geometry(const Dims& d, int nch, int KS, int NKS, PgPack& g);
-size_t pgp_pack_doubles(const PgPack& g);
-void launch_pair_gram_pack(const Ctx& c, const PgPack& g, double* pack, hipStream_t st);
-void launch_factor(const Ctx& c, hipStream_t st);
-int launch_sweep(const Ctx& c, hipStream_t st);
-void launch_sweep_tables(const Ctx& c, hipStream_t st);
-size_t sweep_tab_ints(int A);
-void launch_loglik(const Ctx& c, int use_rss_part, int r_stored, hipStream_t st);
-void launch_loglik_flush(const Ctx& c, hipStream_t st, uint32_t* status_out);
-void launch_fill_slots(const Ctx& c, double* chain, const double* cur, size_t len, int s0, int s1, hipStream_t st);
-void launch_cov_block(const Ctx& c, hipStream_t st);
-int cov_step_blocks(int nblk_curve);
-int cov_w2_chunks(int n);
-void prepare_cov_kernels();
-bool cov_block_fits(const Ctx& c);
-#ifdef BFMMM_TIMELINE
-void fetch_wgtrace(unsigned long long* out);
-void fetch_ztrace(unsigned long long* out);
-void fetch_zphase(unsigned long long* out);
-void fetch_fct(unsigned long long* out);
-#endif
-}  // namespace bfmmm
 
 using namespace bfmmm;
 
@@ -198,21 +161,6 @@ static void set_md(Dims& d, int MD) {
   d.NT = d.RT * d.CTG + d.AT * d.CTS;
 }
 
-static void pg_geometry(const Dims& d, int& NKS, int& KS) {
-  // k-slices of the pair-Gram contraction.  LDS doubles per curve: the raw weight row, the record columns and,
-  // for the G workgroups, the pair-weight row (k_pair_gram); a workgroup never stages more than 96 KB.
-  const int row_g = (d.K + d.MD + 1) + 16 + (d.NZZ + d.NCC + 1);
-  const int row_s = (d.K + d.MD + 1) + d.CTS * 16;
-  const int ks_cap = std::max(16, (int)((96 * 1024) / (sizeof(double) * (size_t)std::max(row_g, row_s)) - 2) / 16 * 16);
-  // one workgroup per CU: (CTG + 2) column groups x NKS k-slices <= 256 whenever the LDS cap allows, so that
-  // every workgroup is resident at once (a 257th would wait a whole workgroup lifetime for a free CU)
-  NKS = std::max(1, std::min(256 / (d.CTG + 2), d.n / 16));
-  KS = (d.n + NKS - 1) / NKS;
-  KS = (KS + 15) / 16 * 16;                  // MFMA k-slots are taken in trips of 4 steps per slot (two 16-byte LDS reads)
-  KS = std::min(KS, ks_cap);
-  NKS = (d.n + KS - 1) / KS;
-}
-
 // a basis supplied by the caller (bfmmm_create_from_basis): rows of B, its band, the penalty of the nu prior
 struct BasisSpec {
   int P, band, pen_band;
@@ -297,6 +245,8 @@ static int create_impl(const bfmmm_config* cfg, int device, const double* y, con
 
   HIPCHK(hipSetDevice(device));
   prepare_curve_kernels();
+  prepare_pair_gram_kernels();
+  prepare_factor_kernels();
   prepare_sweep_kernels();
   prepare_cov_kernels();
   { hipError_t e0 = hipGetLastError(); if (e0 != hipSuccess) fprintf(stderr, "[bfmmm] note: kernel attribute setup reported %s\n", hipGetErrorString(e0)); }
@@ -777,29 +727,12 @@ static Plan make_plan(uint32_t mask, int MD) {
   return p;
 }
 
-// How a (sub-)batch runs its pair-Gram contraction: k_pair_gram_pack with its geometry and buffer, or k_pair_gram +
-// k_pg_reduce; KS / NKS are the k-slices of either.
-struct PgRoute {
-  int KS, NKS;
-  bool packed = false;
-  PgPack pk;
-  double* pack = nullptr;
-};
-
-// cnt chains (a sub-batch of the handle's batch) whose packed tiles go to pg_pack[slot].
-// Packed: the batch has four or more chains -- warm-start and Nu_Z sweeps alike (measured, chain-iterations/s plain / packed:
-// 4 warm chains 35.3 k / 40.4 k, 6: 44.9 / 46.9; 4 Nu_Z chains 65.0 / 68.3, 6: 84.4 / 92.6, 8: 105 / 114; two chains: no gain) --
-// or the curve set is long (beyond the cache-resident sizes: k_pair_gram's k-slices are capped by its LDS staging, so at
-// n = 262144 it writes 1366 slabs of partial tiles -- as many bytes as the records themselves; k_pair_gram_pack walks a slice
-// of ANY length in 16-curve chunks with persistent accumulators: about 128 slices whatever n, chosen from n alone so that a
-// chain of a batch and the same chain alone sum in the same order).  Both kernels sum in the same order.
-static int pg_route(bfmmm_handle* h, const Dims& d, bool pg, int cnt, int slot, PgRoute& r) {
-  r = PgRoute();
-  pg_geometry(d, r.NKS, r.KS);
-  const int KSl = ((d.n + 127) / 128 + 15) / 16 * 16, NKSl = (d.n + KSl - 1) / KSl;
-  const bool long_set = d.n > 16384 && pgp_geometry(d, 1, KSl, NKSl, r.pk);
-  if (long_set) { r.KS = KSl; r.NKS = NKSl; }
-  if (pg && (long_set || h->nch >= 4) && pgp_geometry(d, cnt, r.KS, r.NKS, r.pk)) {
+// The pair-Gram route of cnt chains (a sub-batch of the handle's batch), as pg_route_decide decides it; this function owns the
+// buffers: a packed route's tiles go to pg_pack[slot], grown here, and without room for it the route is decided again unpacked.
+static int pg_route(bfmmm_handle* h, const Ctx& c, bool pg, int cnt, int slot, PgRoute& r) {
+  const Dims& d = c.d;
+  r = pg_route_decide(d, h->nch, cnt, pg, c.defer_loglik != 0, h->pg_part_doubles, true);
+  if (r.packed) {
     const size_t need = pgp_pack_doubles(r.pk);
     if (h->pg_pack_doubles[slot] < need) {
       double* nb = nullptr;
@@ -810,11 +743,9 @@ static int pg_route(bfmmm_handle* h, const Dims& d, bool pg, int cnt, int slot, 
         (void)hipGetLastError();      // (no room: the plain kernel needs no extra buffer)
       }
     }
-    if (h->pg_pack_doubles[slot] >= need) { r.packed = true; r.pack = h->pg_pack[slot]; return 0; }
+    if (h->pg_pack_doubles[slot] >= need) { r.pack = h->pg_pack[slot]; return 0; }
+    r = pg_route_decide(d, h->nch, cnt, pg, c.defer_loglik != 0, h->pg_part_doubles, false);
   }
-  // k_pair_gram keeps the long-set slices where it can stage them (a chain then sums as it does alone), its own otherwise
-  if (long_set && (pair_gram_lds_bytes(d, r.KS) > 160 * 1024 || (size_t)r.NKS * d.NT * 256 > h->pg_part_doubles))
-    pg_geometry(d, r.NKS, r.KS);
   if ((size_t)r.NKS * d.NT * 256 > h->pg_part_doubles) return fail("bfmmm_run: internal workspace too small");
   return 0;
 }
@@ -839,10 +770,10 @@ static void launch_iteration(bfmmm_handle* h, const Ctx& c, const Plan& p, const
   Ctx cf = c;
   cf.pi_in_factor = r.packed ? 1 : 0;      // (the pi / alpha_3 job: an extra workgroup of k_pair_gram, or -- packed path -- of k_factor)
   if (r.packed) {
-    launch_pair_gram_pack(c, r.pk, r.pack, st);      // (contraction + reduction)
+    launch_pair_gram_pack(c, r, st);      // (contraction + reduction)
     mark();
   } else {
-    launch_pair_gram(c, p.pg ? 1 : 0, r.NKS, r.KS, st);
+    launch_pair_gram(c, r, st);
     mark();
     if (p.pg) launch_pg_reduce(c, r.NKS, st);
   }
@@ -1049,7 +980,7 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
   for (int q = 0, q0 = 0; q < nsub; ++q) {
     const int cnt = h->nch / nsub + (q < h->nch % nsub ? 1 : 0);
     // (the profile form runs the whole batch on the sampler's stream, its packed tiles in the extra buffer)
-    if (pg_route(h, c.d, plan.pg, cnt, h->profile ? bfmmm_handle::MAX_SUB : q, subs[q].r)) return 1;
+    if (pg_route(h, c, plan.pg, cnt, h->profile ? bfmmm_handle::MAX_SUB : q, subs[q].r)) return 1;
     if (!h->sub_st[q]) HIPCHK(hipStreamCreateWithFlags(&h->sub_st[q], hipStreamNonBlocking));
     if (!h->sub_ev[q]) HIPCHK(hipEventCreateWithFlags(&h->sub_ev[q], hipEventDisableTiming));
     subs[q].c = chain_ctx(c, (unsigned)q0);
@@ -1058,12 +989,9 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
     q0 += cnt;
   }
   {
-    // what sub-batch 0 runs, for bfmmm_debug_get("pg_route"): body / G as launch_pair_gram picks them (packed: -1 / 0)
+    // what sub-batch 0 runs, for bfmmm_debug_get("pg_route"): the route its launches read (packed: body -1, G 0)
     const PgRoute& r0 = subs[0].r;
-    int G = 0;
-    const int body = r0.packed ? -1 : pair_gram_body(subs[0].c, r0.KS, G);
-    const int tail = (r0.packed || !plan.pg) ? 0 : pair_gram_tail(subs[0].c, r0.KS, r0.NKS, body);
-    const double v[6] = {r0.packed ? 1.0 : 0.0, (double)r0.KS, (double)r0.NKS, (double)body, (double)G, (double)tail};
+    const double v[6] = {r0.packed ? 1.0 : 0.0, (double)r0.KS, (double)r0.NKS, (double)r0.body, (double)r0.G, (double)r0.tail};
     memcpy(h->last_route, v, sizeof v);
   }
   // single chain: the scalar job of k_curve_chi rides the next iteration's k_pair_gram instead (its grid has NKS - 1 idle extra

@@ -25,9 +25,6 @@ static __device__ unsigned long long g_fct[8];
 #define FCT(i) do { } while (0)
 #endif
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-typedef double v2d __attribute__((ext_vector_type(2)));
-
 __device__ inline double readlane_f64(double v, int lane) {     // lane is wave-uniform
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);

@@ -19,6 +19,7 @@
 #include "rng.hpp"
 #include "scalar_jobs.hpp"
 #include "factor_core.hpp"
+#include "launchers.hpp"
 
 namespace bfmmm {
 

@@ -20,6 +20,7 @@
 #include "scalar_jobs.hpp"
 #include "z_proposal.hpp"
 #include "lds_dot.hpp"
+#include "launchers.hpp"
 
 #include <algorithm>
 

@@ -9,6 +9,7 @@
 // LDS; phase 2 gives every band element of G_i (and every s_p) to one lane, which accumulates
 // over the chunk in observation order -- a fixed summation order, so results are reproducible.
 #include "model.hpp"
+#include "launchers.hpp"
 
 namespace bfmmm {
 

@@ -1,0 +1,71 @@
+// Host interface of the kernel files to the driver (bfmmm_capi.hip): every launcher, geometry and prepare_* function the
+// driver calls.  Included by the driver and by every file that defines one of them, so that a declaration and its
+// definition cannot drift apart.
+#pragma once
+#include "model.hpp"
+
+namespace bfmmm {
+
+// ---- kernels_stats.hip ----
+int launch_stats_functional(int degree, int n, int P, int LREC, const int64_t* off, const double* t, const double* y,
+                            const double* knots, int n_knots, double* rec, int* ni, double* B_dense, int* err,
+                            hipStream_t st);
+void launch_stats_multivariate(int n, int P, int LREC, const double* Y, double* rec, int* ni, hipStream_t st);
+void launch_stats_totals(int n, int LREC, int yy_off, const double* rec, const int* ni, double* out_yy,
+                         long long* out_counts, hipStream_t st);
+
+// ---- kernels_curve.hip ----
+int launch_curve(const Ctx& c, int which, int do_update, hipStream_t st);
+int curve_blocks(int n, int P);
+void prepare_curve_kernels();
+
+// ---- kernels_pair_gram.hip ----
+// How a (sub-)batch runs its pair-Gram contraction: everything pg_route_decide decides, and all the two launchers read.
+struct PgRoute {
+  bool packed = false;      // k_pair_gram_pack + k_pg_reduce_pack (geometry pk, tiles in pack); otherwise k_pair_gram + k_pg_reduce
+  int KS = 0, NKS = 0;      // curves per k-slice and k-slices of either
+  int body = -1;            // k_pair_gram: 0 the general body (one chain), 1 the single-chain body of the G workgroups (pg_solo_g),
+                            // 2 the chain loop, 3 the chain loop with G chains staged together; packed: -1
+  int G = 0;                // chains k_pair_gram stages together (packed: 0)
+  int tail = 0;             // what else a body-1 launch runs in bodies of its own: PG_SOLO_S | PG_SOLO_LL (do_pg flag bits)
+  int do_pg = 0;            // k_pair_gram's flag word: 0 = only the extra workgroups' scalar jobs run
+  size_t lds = 0;           // dynamic LDS bytes of the contraction's launch
+  PgPack pk;
+  double* pack = nullptr;   // packed partial tiles, pgp_pack_doubles(pk) doubles: owned and filled in by the driver
+};
+void pg_geometry(const Dims& d, int& NKS, int& KS);
+PgRoute pg_route_decide(const Dims& d, int nch_handle, int nch, bool pg, bool defer_loglik, size_t pg_part_doubles, bool may_pack);
+size_t pgp_pack_doubles(const PgPack& g);
+void launch_pair_gram(const Ctx& c, const PgRoute& r, hipStream_t st);
+void launch_pg_reduce(const Ctx& c, int NKS, hipStream_t st);
+void launch_pair_gram_pack(const Ctx& c, const PgRoute& r, hipStream_t st);
+void prepare_pair_gram_kernels();
+
+// ---- kernels_factor.hip ----
+void launch_factor(const Ctx& c, hipStream_t st);
+void prepare_factor_kernels();
+
+// ---- kernels_sweep.hip ----
+int launch_sweep(const Ctx& c, hipStream_t st);
+void launch_sweep_tables(const Ctx& c, hipStream_t st);
+size_t sweep_tab_ints(int A);
+void launch_loglik(const Ctx& c, int use_rss_part, int r_stored, hipStream_t st);
+void launch_loglik_flush(const Ctx& c, hipStream_t st, uint32_t* status_out);
+void launch_fill_slots(const Ctx& c, double* chain, const double* cur, size_t len, int s0, int s1, hipStream_t st);
+void prepare_sweep_kernels();
+
+// ---- kernels_cov.hip ----
+void launch_cov_block(const Ctx& c, hipStream_t st);
+int cov_step_blocks(int nblk_curve);
+int cov_w2_chunks(int n);
+void prepare_cov_kernels();
+bool cov_block_fits(const Ctx& c);
+
+#ifdef BFMMM_TIMELINE
+void fetch_wgtrace(unsigned long long* out);      // kernels_pair_gram.hip
+void fetch_ztrace(unsigned long long* out);       // kernels_curve.hip
+void fetch_zphase(unsigned long long* out);       // kernels_curve.hip
+void fetch_fct(unsigned long long* out);          // kernels_factor.hip
+#endif
+
+}  // namespace bfmmm

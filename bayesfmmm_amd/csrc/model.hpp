@@ -161,7 +161,7 @@ struct Ctx {
   double* rss_part;             // nblk_curve       partial residual sums of squares
   double* pg_part;              // NWG x NT x 256   pair-Gram partial tiles
   double* H;                    // R x LG           pair-weighted Gram blocks (band-packed)
-  double* H2;                   // R x P x (2BW+2)  the same blocks by row p: [G(p,p-BW) .. G(p,p+BW), 0], piece-major (h2_index, kernels_sweep.hip)
+  double* H2;                   // R x P x (2BW+2)  the same blocks by row p: [G(p,p-BW) .. G(p,p+BW), 0], piece-major (h2_index, sweep_helpers.hpp)
   double* tvec;                 // A x P            sum_i w_ai s_i
   double* rvec;                 // A x P            r_a = t_a - sum_b H_ab theta_b at the start of the sweep
   double* hq;                   // A x P            H_aa theta_a
@@ -218,7 +218,7 @@ struct Ctx {
   int nblk_curve;
 };
 
-// geometry of k_pair_gram_pack (kernels_sweep.hip), the pair-Gram kernel of chain batches and long curve sets
+// geometry of k_pair_gram_pack (kernels_pair_gram.hip), the pair-Gram kernel of chain batches and long curve sets
 struct PgPack {
   int KS, NKS;           // curves per k-slice (a multiple of 16), slices
   int TG, TS;            // packed row tiles: pair rows (nch R), single-weight rows (nch A)
@@ -291,6 +291,9 @@ struct Timeline {
 #define TSTAMP(c, i) do { } while (0)
 #define TSTAMP0(c, i) do { } while (0)
 #endif
+
+typedef double double4_t __attribute__((ext_vector_type(4)));      // accumulator of v_mfma_f64_16x16x4_f64
+typedef double v2d __attribute__((ext_vector_type(2)));            // one 16-byte load
 
 template <int CTRL>
 __device__ inline double dpp_add(double v) {   // v + dpp_permute<CTRL>(v) within a row of 16 lanes

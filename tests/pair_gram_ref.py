@@ -1,6 +1,6 @@
 """High-precision restatement of the pair-Gram contraction and its entry-by-entry tolerance.  (Test infrastructure.)
 
-What the device computes (kernels_sweep.hip: k_pair_gram + k_pg_reduce, k_pair_gram_pack + k_pg_reduce_pack):
+What the device computes (kernels_pair_gram.hip: k_pair_gram + k_pg_reduce, k_pair_gram_pack + k_pg_reduce_pack):
 
     H[row, d P + p] = sum_i (Z_ij Z_ij') (chit_im chit_im') G_i[p, p + d]      row = tri(K, j, j') NCC + tri(MD, m, m')
     t[j MD + m, p]  = sum_i  Z_ij chit_im  s_i[p]                              chit_i0 = 1, chit_i,m+1 = chi_im

@@ -1,5 +1,5 @@
 """The pair-Gram contraction, entry by entry, on every route the run driver can take (pg_route in bfmmm_capi.hip,
-launch_pair_gram in kernels_sweep.hip):
+pg_route_decide and launch_pair_gram in kernels_pair_gram.hip):
 
   1 general     k_pair_gram<false,false>, general body + k_pg_reduce      one chain, outside pg_solo_fits or solo switched off
   2 solo        the same kernel, pg_solo_g in the G workgroups            one chain inside pg_solo_fits
@@ -160,7 +160,7 @@ def make_sampler(c, nch):
 
 
 def expected_h2(H, P, bw, mv):
-    """the piece-major band copy (h2_index, kernels_sweep.hip) that belongs to H: entry k of row p is G(p, p + k - BW)"""
+    """the piece-major band copy (h2_index, sweep_helpers.hpp) that belongs to H: entry k of row p is G(p, p + k - BW)"""
     Rr = H.shape[0]
     W = 2 * bw + 2
     idx = lambda p, k: (((k >> 1) * P + p) << 1) + (k & 1)
