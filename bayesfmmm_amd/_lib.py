@@ -54,6 +54,11 @@ SYMBOLS = {
     "bfmmm_get_chain": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, c_double_p, C.c_int64]),
     "bfmmm_chain_diagnostics": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int64, c_double_p, c_double_p, c_double_p,
                                           c_double_p, c_double_p, c_double_p, c_double_p, C.c_int64]),
+    "bfmmm_chain_curve_loglik": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, C.c_int64]),
+    "bfmmm_chain_curve_diagnostics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                                c_double_p, c_double_p, c_double_p, c_double_p, C.c_int64]),
+    "bfmmm_chain_loo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
+                                  c_double_p, c_double_p, C.c_int64]),
     "bfmmm_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, c_double_p, C.c_int64, c_int64_p]),
     "bfmmm_set_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "bfmmm_get_timing": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), c_int64_p]),

@@ -83,6 +83,7 @@ struct bfmmm_handle {
   double fam_ms[FAM_COUNT] = {0};
   int64_t fam_launches[FAM_COUNT] = {0};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  double curve_ll_ms = 0;              // bfmmm_debug_get("curve_ll_ms"): device time of k_chain_curve_ll in the last call that ran it
 };
 
 // Synchronous copy on the sampler's own stream: the legacy (NULL) stream must not be touched while
@@ -1279,6 +1280,147 @@ extern "C" int bfmmm_chain_diagnostics(bfmmm_handle* h, const char* name, int fi
   return 0;
 }
 
+// ---- per-curve marginal log-density of the chain slots (kernels_curve_ll.hip) ------------------------------
+int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]);      // kernels_loo.hip
+extern "C" const char* bfmmm_entry_last_error(void);                                              // (its failure text)
+
+// one launch of k_chain_curve_ll between the handle's two events; curve_ll_collect adds its device time once the stream has
+// been synchronised
+static std::string curve_ll_timed(bfmmm_handle* h, int first_slot, int S, int i0, int rows, double* d_x) {
+  (void)hipEventRecord(h->ev0, h->st);
+  const std::string err = launch_chain_curve_ll(h->c, first_slot, S, i0, rows, d_x, h->st);
+  (void)hipEventRecord(h->ev1, h->st);
+  return err;
+}
+static void curve_ll_collect(bfmmm_handle* h) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->curve_ll_ms += ms;
+  else (void)hipGetLastError();
+}
+
+static int curve_ll_range(const std::string& fn, const bfmmm_handle* h, int first_slot, int n_slots) {
+  if (first_slot < 0 || first_slot >= h->T) return fail(fn + ": 'first_slot' out of range");
+  if (n_slots < 1 || n_slots > h->T - first_slot) return fail(fn + ": 'n_slots' out of range (first_slot + n_slots > T)");
+  return 0;
+}
+
+// The n x C x n_slots matrix (draw fastest, then chain, then curve) on the host, computed in chunks of consecutive curves
+// on the sampler's stream.
+extern "C" int bfmmm_chain_curve_loglik(bfmmm_handle* h, int first_slot, int n_slots, double* out, int64_t capacity) {
+  const std::string fn = "bfmmm_chain_curve_loglik";
+  if (!h) return fail(fn + ": 'h' is null");
+  if (!out) return fail(fn + ": 'out' is null");
+  if (curve_ll_range(fn, h, first_slot, n_slots)) return 1;
+  const int n = h->c.d.n, C = h->nch, S = n_slots;
+  const int64_t per_row = (int64_t)C * S;
+  if (capacity < (int64_t)n * per_row) return fail(fn + ": 'capacity' below " + std::to_string((int64_t)n * per_row) + " entries");
+  HIPCHK(hipSetDevice(h->device));
+  h->curve_ll_ms = 0;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(((size_t)256 << 20) / (sizeof(double) * (size_t)per_row))));
+  double* d_x = nullptr;
+  HIPCHK(hipMalloc(&d_x, sizeof(double) * (size_t)chunk * (size_t)per_row));
+  std::string err;
+  for (int64_t i0 = 0; i0 < n && err.empty(); i0 += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, n - i0);
+    err = curve_ll_timed(h, first_slot, S, (int)i0, rows, d_x);
+    if (err.empty() && copy_sync(h, out + (size_t)i0 * per_row, d_x, sizeof(double) * (size_t)rows * per_row, hipMemcpyDeviceToHost) != hipSuccess)
+      err = "kernel or copy back failed";
+    if (err.empty()) curve_ll_collect(h);
+  }
+  (void)hipStreamSynchronize(h->st);
+  (void)hipFree(d_x);
+  if (!err.empty()) { (void)hipGetLastError(); return fail(fn + ": " + err); }
+  return 0;
+}
+
+// The seven statistics of bfmmm_chain_diagnostics for the n rows of that matrix: chunks of consecutive curves are computed
+// into the workspace and reduced there by the same diag_launch; the matrix never leaves the device.
+extern "C" int bfmmm_chain_curve_diagnostics(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes,
+                                             double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
+                                             double* mean, double* sd, int64_t capacity) {
+  const std::string fn = "bfmmm_chain_curve_diagnostics";
+  const char* pn[] = {"h", "rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd"};
+  const void* pv[] = {h, rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
+  for (int i = 0; i < 8; ++i)
+    if (!pv[i]) return fail(fn + ": '" + pn[i] + "' is null");
+  if (curve_ll_range(fn, h, first_slot, n_slots)) return 1;
+  if (max_workspace_bytes < 0) return fail(fn + ": 'max_workspace_bytes' must not be negative");
+  const int64_t len = h->c.d.n;
+  if (capacity < len) return fail(fn + ": 'capacity' below " + std::to_string(len) + " entries");
+  const int C = h->nch, S = n_slots;
+  if ((long long)C * S > diag_row_max())
+    return fail(fn + ": at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " + std::to_string((long long)C * S));
+  const size_t budget = max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20;
+  const size_t per_row = sizeof(double) * ((size_t)C * S + diag_row_ws_doubles(C, S)) + 7 * sizeof(double);
+  if (budget < per_row) return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(per_row) + " bytes of one row");
+  const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
+  HIPCHK(hipSetDevice(h->device));
+  h->curve_ll_ms = 0;
+  double* d_ws = nullptr;
+  HIPCHK(hipMalloc(&d_ws, per_row * (size_t)chunk));
+  double* d_x = d_ws;
+  double* d_out = d_x + (size_t)chunk * C * S;
+  double* d_tier = d_out + 7 * (size_t)chunk;
+  std::vector<double> hb(7 * (size_t)chunk);
+  double* const outs[7] = {rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
+  std::string err;
+  for (int64_t p0 = 0; p0 < len && err.empty(); p0 += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, len - p0);
+    err = curve_ll_timed(h, first_slot, S, (int)p0, rows, d_x);
+    if (err.empty()) err = diag_launch(d_x, rows, C, S, d_out, rows, d_tier, rows, h->st);
+    if (err.empty() && copy_sync(h, hb.data(), d_out, sizeof(double) * 7 * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess)
+      err = "kernel or copy back failed";
+    if (err.empty()) {
+      curve_ll_collect(h);
+      for (int q = 0; q < 7; ++q) std::copy(hb.begin() + (size_t)q * rows, hb.begin() + (size_t)(q + 1) * rows, outs[q] + p0);
+    }
+  }
+  (void)hipStreamSynchronize(h->st);
+  (void)hipFree(d_ws);
+  if (!err.empty()) { (void)hipGetLastError(); return fail(fn + ": " + err); }
+  return 0;
+}
+
+// PSIS-LOO and WAIC over curves with the chains pooled: a row is the C n_slots draws of a curve, chain-major, relative
+// efficiency 1.  Chunks of consecutive curves go through the same post_psis_device on the device.
+extern "C" int bfmmm_chain_loo(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes, double* lppd,
+                               double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, int64_t capacity) {
+  const std::string fn = "bfmmm_chain_loo";
+  const char* pn[] = {"h", "lppd", "elpd_loo", "p_loo", "pareto_k", "elpd_waic", "p_waic"};
+  const void* pv[] = {h, lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic};
+  for (int i = 0; i < 7; ++i)
+    if (!pv[i]) return fail(fn + ": '" + pn[i] + "' is null");
+  if (curve_ll_range(fn, h, first_slot, n_slots)) return 1;
+  if (max_workspace_bytes < 0) return fail(fn + ": 'max_workspace_bytes' must not be negative");
+  const int64_t len = h->c.d.n;
+  if (capacity < len) return fail(fn + ": 'capacity' below " + std::to_string(len) + " entries");
+  const int C = h->nch, S = n_slots;
+  if ((long long)C * S > diag_row_max())
+    return fail(fn + ": at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " + std::to_string((long long)C * S));
+  const size_t budget = max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20;
+  const size_t per_row = sizeof(double) * (size_t)C * S;
+  if (budget < per_row) return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(per_row) + " bytes of one row");
+  const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
+  HIPCHK(hipSetDevice(h->device));
+  h->curve_ll_ms = 0;
+  double* d_x = nullptr;
+  HIPCHK(hipMalloc(&d_x, per_row * (size_t)chunk));
+  std::string err;
+  for (int64_t p0 = 0; p0 < len && err.empty(); p0 += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, len - p0);
+    err = curve_ll_timed(h, first_slot, S, (int)p0, rows, d_x);
+    // post_psis_device runs on the device's default stream: the matrix must be complete before it starts
+    if (err.empty() && (hipStreamSynchronize(h->st) != hipSuccess || hipGetLastError() != hipSuccess)) err = "kernel failed";
+    if (err.empty()) curve_ll_collect(h);
+    double* const outs[6] = {lppd + p0, elpd_loo + p0, p_loo + p0, pareto_k + p0, elpd_waic + p0, p_waic + p0};
+    if (err.empty() && post_psis_device(d_x, (long long)C * S, rows, C * S, outs)) err = bfmmm_entry_last_error();
+  }
+  (void)hipStreamSynchronize(h->st);
+  (void)hipFree(d_x);
+  if (!err.empty()) { (void)hipGetLastError(); return fail(fn + ": " + err); }
+  return 0;
+}
+
 extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capacity, int64_t* count) {
   if (!h || !name || !out || !count) return fail("bfmmm_debug_get: null argument");
   HIPCHK(hipSetDevice(h->device));
@@ -1301,6 +1443,12 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
     if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
     memcpy(out, h->last_route, sizeof h->last_route);
     *count = cnt;
+    return 0;
+  }
+  if (s == "curve_ll_ms") {   // device time of k_chain_curve_ll in the last bfmmm_chain_curve_loglik / _diagnostics / bfmmm_chain_loo
+    if (capacity < 1) return fail("bfmmm_debug_get: buffer too small");
+    out[0] = h->curve_ll_ms;
+    *count = 1;
     return 0;
   }
   struct Arr { const char* nm; const double* p; int64_t len; };

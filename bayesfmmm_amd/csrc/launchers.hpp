@@ -3,6 +3,7 @@
 // definition cannot drift apart.
 #pragma once
 #include "model.hpp"
+#include <string>
 
 namespace bfmmm {
 
@@ -60,6 +61,11 @@ int cov_step_blocks(int nblk_curve);
 int cov_w2_chunks(int n);
 void prepare_cov_kernels();
 bool cov_block_fits(const Ctx& c);
+
+// ---- kernels_curve_ll.hip ----
+// per-curve marginal log-density of curves [i0, i0 + rows), every chain, slots [first_slot, first_slot + n_slots) into
+// out[(i - i0) C S + q S + (t - first_slot)] (device); "" or what the kernel cannot take
+std::string launch_chain_curve_ll(const Ctx& c, int first_slot, int n_slots, int i0, int rows, double* out, hipStream_t st);
 
 #ifdef BFMMM_TIMELINE
 void fetch_wgtrace(unsigned long long* out);      // kernels_pair_gram.hip

@@ -183,6 +183,36 @@ class Sampler:
         names = ("rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd")
         return {k: o.reshape(shp, order="F") for k, o in zip(names, outs)}
 
+    def curve_loglik(self, first_slot=0, n_slots=None):
+        """The marginal log-density (scores integrated out) of every curve under chain slots [first_slot, first_slot + n_slots)
+        of every chain of the batch, computed on the device from the resident per-curve statistics (bfmmm_chain_curve_loglik;
+        DESIGN.md 7d).  Label- and sign-invariant.  Returns an (n, C, S) array."""
+        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
+        out = np.zeros((self.n, self.n_chains, max(S, 0)))
+        _lib.check(self.lib.bfmmm_chain_curve_loglik(self.h, int(first_slot), S, _dp(out), out.size))
+        return out
+
+    def curve_diagnostics(self, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """The seven statistics of `diagnostics` for each curve's log-density (`curve_loglik`), which never leaves the device
+        (bfmmm_chain_curve_diagnostics).  Where the R-hat of nu, Phi or Z reports a label switch between chains, this one
+        reports mixing, curve by curve.  Returns a dict of arrays of shape (n,)."""
+        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
+        outs = [np.zeros(self.n) for _ in range(7)]
+        _lib.check(self.lib.bfmmm_chain_curve_diagnostics(self.h, int(first_slot), S, int(max_workspace_bytes),
+                                                          *[_dp(o) for o in outs], self.n))
+        names = ("rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd")
+        return dict(zip(names, outs))
+
+    def loo(self, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """PSIS-LOO and WAIC over curves from the chain slots of every chain, pooled (bfmmm_chain_loo): the dict api.psis_loo
+        returns for the (n, C * S) matrix `curve_loglik` holds, without that matrix leaving the device."""
+        from . import api
+        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
+        outs = [np.zeros(self.n) for _ in range(6)]
+        _lib.check(self.lib.bfmmm_chain_loo(self.h, int(first_slot), S, int(max_workspace_bytes), *[_dp(o) for o in outs], self.n))
+        pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs))
+        return api.loo_totals(pw, self.n_chains * S)
+
     def get_basis(self):
         n_obs = int(self.offsets[-1])
         out = np.zeros((n_obs, self.P))

@@ -188,9 +188,28 @@ int bfmmm_chain_diagnostics(bfmmm_handle* h, const char* name, int first_slot, i
                             double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
                             double* mean, double* sd, int64_t capacity);
 
+/* The marginal log-density of every curve under the draws of chain slots [first_slot, first_slot + n_slots) of EVERY chain
+ * of the batch, scores integrated out: y_i ~ N(B_i c, sigma^2 I + U U'), c = sum_k Z_ik (nu_k + eta_k x_i),
+ * U = B_i [V_1 .. V_M], V_m = sum_k Z_ik (phi_km + xi_km x_i).  It does not depend on the components' labels or on the signs
+ * of the eigenfunctions, and is computed on the device from the resident per-curve statistics and the chain slots alone.
+ *   bfmmm_chain_curve_loglik       copies the matrix to the host: out[i C S + q S + (t - first_slot)] (curve i, chain q, S =
+ *                                  n_slots; draw fastest, then chain, then curve), capacity >= n C S.
+ *   bfmmm_chain_curve_diagnostics  the seven statistics of bfmmm_chain_diagnostics of each curve's log-density, n entries each.
+ *   bfmmm_chain_loo                PSIS-LOO and WAIC over curves with the chains pooled (a curve's row is its C S draws,
+ *                                  chain-major; relative efficiency 1), n entries each.
+ * The last two keep the matrix on the device and work in chunks of consecutive curves under max_workspace_bytes (0: 256 MiB);
+ * at most 2^22 draws per row (n_chains x n_slots).  capacity >= n. */
+int bfmmm_chain_curve_loglik(bfmmm_handle* h, int first_slot, int n_slots, double* out, int64_t capacity);
+int bfmmm_chain_curve_diagnostics(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes,
+                                  double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
+                                  double* mean, double* sd, int64_t capacity);
+int bfmmm_chain_loo(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes, double* lppd, double* elpd_loo,
+                    double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, int64_t capacity);
+
 /* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
- * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P), "theta" (K (M + 1) x P), "dims" (as doubles) and
+ * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P), "theta" (K (M + 1) x P), "dims" (as doubles), "curve_ll_ms" (device
+ * milliseconds of k_chain_curve_ll in the last bfmmm_chain_curve_loglik / bfmmm_chain_curve_diagnostics / bfmmm_chain_loo) and
  * "pg_route": how sub-batch 0 of the last bfmmm_run ran its pair-Gram contraction, {packed (0 / 1), KS, NKS,
  * body (0 general, 1 single-chain, 2 chain loop, 3 chain loop with staged groups; -1 packed), G (chains per group; 0 packed),
  * tail (single-chain body only, a sum of flags: 4 the s-part workgroup runs its single-chain body, 8 the deferred
