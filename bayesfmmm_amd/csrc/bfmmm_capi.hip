@@ -84,6 +84,8 @@ struct bfmmm_handle {
   int64_t fam_launches[FAM_COUNT] = {0};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double curve_ll_ms = 0;              // bfmmm_debug_get("curve_ll_ms"): device time of k_chain_curve_ll in the last call that ran it
+  double fit_ms[4] = {0};              // bfmmm_get_timing("curve_fit_project" / "_rows" / "_values" / "_reduce"; "curve_fit": their sum):
+  int64_t fit_launches[4] = {0};       // device time of the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands
 };
 
 // Synchronous copy on the sampler's own stream: the legacy (NULL) stream must not be touched while
@@ -1421,6 +1423,195 @@ extern "C" int bfmmm_chain_loo(bfmmm_handle* h, int first_slot, int n_slots, int
   return 0;
 }
 
+// ---- pooled per-curve fitted functions of the chain slots and their bands (kernels_curve_fit.hip) ----------
+namespace bfmmm { int g_curve_fit_route = 0; }
+extern "C" void bfmmm_set_curve_fit_route(int route) { bfmmm::g_curve_fit_route = route == 1 ? 1 : 0; }
+
+enum { FIT_T_PROJECT = 0, FIT_T_ROWS, FIT_T_VALUES, FIT_T_REDUCE, FIT_T_COUNT };
+static const char* kFitNames[FIT_T_COUNT] = {"curve_fit_project", "curve_fit_rows", "curve_fit_values", "curve_fit_reduce"};
+
+// what a call allocates: freed when the call returns, whichever way
+struct FitBufs {
+  std::vector<void*> p;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // project start / end, chunk start / middle / end
+  ~FitBufs() {
+    for (void* q : p) (void)hipFree(q);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  template <typename T>
+  hipError_t get(T** out, size_t count) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
+    return e;
+  }
+};
+static void fit_collect(bfmmm_handle* h, const FitBufs& b, int from, int to, int what) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, b.ev[from], b.ev[to]) == hipSuccess) { h->fit_ms[what] += ms; h->fit_launches[what] += 1; }
+  else (void)hipGetLastError();
+}
+
+struct FitSetup {
+  FitCall f;
+  int m = 0, C = 0, S = 0;
+  long long CS = 0, NJ = 0;
+};
+
+// The checks both calls share, then E, the curve list and the projection table on the device (owned by b) and the table
+// filled.  shared_bytes: what these take of the budget.
+static int fit_check_args(const std::string& fn, bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves,
+                          int first_slot, int n_slots, FitSetup& s) {
+  if (!E) return fail(fn + ": 'E' is null");
+  if (which != 0 && which != 1) return fail(fn + ": 'which' must be 0 (mean) or 1 (fit), got " + std::to_string(which));
+  if (G < 1) return fail(fn + ": 'G' must be at least 1");
+  const int n = h->c.d.n;
+  if (curves) {
+    if (n_curves < 1) return fail(fn + ": 'n_curves' must be at least 1 where 'curves' is given");
+    for (int j = 0; j < n_curves; ++j)
+      if (curves[j] < 0 || curves[j] >= n)
+        return fail(fn + ": 'curves'[" + std::to_string(j) + "] = " + std::to_string(curves[j]) + " outside 0 .. " + std::to_string(n - 1));
+  }
+  if (curve_ll_range(fn, h, first_slot, n_slots)) return 1;
+  s.m = curves ? n_curves : n;
+  s.C = h->nch; s.S = n_slots; s.CS = (long long)s.C * s.S;
+  if (s.CS > diag_row_max())
+    return fail(fn + ": at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " + std::to_string(s.CS));
+  s.f.which = which; s.f.G = G; s.f.first_slot = first_slot; s.f.n_slots = n_slots;
+  const std::string err = fit_check(h->c, s.f);
+  if (!err.empty()) return fail(fn + ": " + err);
+  s.NJ = fit_directions(h->c.d, which);
+  return 0;
+}
+static size_t fit_shared_bytes(const bfmmm_handle* h, const FitSetup& s) {
+  return sizeof(double) * ((size_t)s.CS * s.f.G * (size_t)s.NJ + (size_t)s.f.G * h->c.d.P + 16) + sizeof(int32_t) * (((size_t)s.m + 1) & ~(size_t)1);
+}
+static int fit_prepare(const std::string& fn, bfmmm_handle* h, const double* E, const int32_t* curves, FitSetup& s, FitBufs& b) {
+  double *d_E = nullptr, *d_tab = nullptr;
+  int* d_curves = nullptr;
+  for (hipEvent_t& e : b.ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(b.get(&d_E, (size_t)s.f.G * h->c.d.P));
+  HIPCHK(b.get(&d_tab, (size_t)s.CS * s.f.G * (size_t)s.NJ));
+  HIPCHK(copy_sync(h, d_E, E, sizeof(double) * (size_t)s.f.G * h->c.d.P, hipMemcpyHostToDevice));
+  if (curves) {
+    HIPCHK(b.get(&d_curves, (size_t)s.m));
+    HIPCHK(copy_sync(h, d_curves, curves, sizeof(int32_t) * (size_t)s.m, hipMemcpyHostToDevice));
+  }
+  s.f.E = d_E; s.f.curves = d_curves; s.f.tab = d_tab;
+  for (int q = 0; q < FIT_T_COUNT; ++q) { h->fit_ms[q] = 0; h->fit_launches[q] = 0; }
+  (void)hipEventRecord(b.ev[0], h->st);
+  const std::string err = launch_fit_project(h->c, s.f, h->st);
+  (void)hipEventRecord(b.ev[1], h->st);
+  if (!err.empty()) { (void)hipStreamSynchronize(h->st); return fail(fn + ": " + err); }
+  HIPCHK(hipStreamSynchronize(h->st));
+  fit_collect(h, b, 0, 1, FIT_T_PROJECT);
+  return 0;
+}
+
+// The values themselves on the host, in chunks of consecutive result rows.
+extern "C" int bfmmm_chain_curve_fit(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves,
+                                     int first_slot, int n_slots, double* out, int64_t capacity) {
+  const std::string fn = "bfmmm_chain_curve_fit";
+  if (!h) return fail(fn + ": 'h' is null");
+  if (!out) return fail(fn + ": 'out' is null");
+  FitSetup s;
+  if (fit_check_args(fn, h, which, E, G, curves, n_curves, first_slot, n_slots, s)) return 1;
+  const int64_t per_curve = (int64_t)G * s.CS;
+  if (capacity < (int64_t)s.m * per_curve) return fail(fn + ": 'capacity' below " + std::to_string((int64_t)s.m * per_curve) + " entries");
+  HIPCHK(hipSetDevice(h->device));
+  FitBufs b;
+  if (fit_prepare(fn, h, E, curves, s, b)) return 1;
+  int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (sizeof(double) * (size_t)per_curve)));
+  chunk = std::min<int64_t>(std::min<int64_t>(chunk, s.m), std::max<int64_t>(1, (1LL << 30) / G));
+  double* d_v = nullptr;
+  HIPCHK(b.get(&d_v, (size_t)chunk * per_curve));
+  std::string err;
+  for (int64_t r0 = 0; r0 < s.m && err.empty(); r0 += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, s.m - r0);
+    (void)hipEventRecord(b.ev[2], h->st);
+    err = launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st);
+    (void)hipEventRecord(b.ev[3], h->st);
+    if (err.empty() && copy_sync(h, out + (size_t)r0 * per_curve, d_v, sizeof(double) * (size_t)rows * per_curve, hipMemcpyDeviceToHost) != hipSuccess)
+      err = "kernel or copy back failed";
+    if (err.empty()) fit_collect(h, b, 2, 3, FIT_T_VALUES);
+  }
+  (void)hipStreamSynchronize(h->st);
+  if (!err.empty()) { (void)hipGetLastError(); return fail(fn + ": " + err); }
+  return 0;
+}
+
+// Mean, sd and quantiles of every row; the values stay on the device (rows of up to 8192 draws: in LDS).
+extern "C" int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves,
+                                       int first_slot, int n_slots, const double* probs, int nq, int64_t max_workspace_bytes,
+                                       double* mean, double* sd, double* quantiles, int64_t capacity) {
+  const std::string fn = "bfmmm_chain_curve_bands";
+  const char* pn[] = {"h", "probs", "mean", "sd", "quantiles"};
+  const void* pv[] = {h, probs, mean, sd, quantiles};
+  for (int i = 0; i < 5; ++i)
+    if (!pv[i]) return fail(fn + ": '" + pn[i] + "' is null");
+  FitSetup s;
+  if (fit_check_args(fn, h, which, E, G, curves, n_curves, first_slot, n_slots, s)) return 1;
+  if (nq < 1 || nq > 16) return fail(fn + ": 'nq' outside 1 .. 16");
+  for (int q = 0; q < nq; ++q)
+    if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail(fn + ": 'probs'[" + std::to_string(q) + "] outside [0, 1]");
+  if (max_workspace_bytes < 0) return fail(fn + ": 'max_workspace_bytes' must not be negative");
+  if (capacity < (int64_t)s.m * G) return fail(fn + ": 'capacity' below " + std::to_string((int64_t)s.m * G) + " rows");
+  const bool lds_rows = s.CS <= fit_lds_rows() && !g_curve_fit_route;
+  const bool sort_ws = s.CS > fit_lds_rows();               // k_bands_quantiles_big sorts in a workspace
+  const int NP = sort_ws ? bands_sort_pad((int)s.CS) : 0;
+  const size_t budget = max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20;
+  const size_t shared = fit_shared_bytes(h, s);
+  const size_t per_curve = sizeof(double) * (size_t)G * ((size_t)(2 + nq) + (lds_rows ? 0 : (size_t)s.CS + (size_t)NP));
+  if (budget < shared + per_curve)
+    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
+                std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
+  int64_t chunk = std::min<int64_t>(s.m, (int64_t)((budget - shared) / per_curve));
+  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (1LL << 30) / G));
+  HIPCHK(hipSetDevice(h->device));
+  FitBufs b;
+  double *d_probs = nullptr, *d_out = nullptr, *d_v = nullptr, *d_w = nullptr;
+  HIPCHK(b.get(&d_probs, 16));
+  HIPCHK(b.get(&d_out, (size_t)chunk * G * (2 + nq)));
+  if (!lds_rows) HIPCHK(b.get(&d_v, (size_t)chunk * G * (size_t)s.CS));
+  if (sort_ws) HIPCHK(b.get(&d_w, (size_t)chunk * G * (size_t)NP));
+  HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
+  if (fit_prepare(fn, h, E, curves, s, b)) return 1;
+  double* d_mean = d_out;
+  double* d_sd = d_out + (size_t)chunk * G;
+  double* d_q = d_out + 2 * (size_t)chunk * G;
+  std::string err;
+  for (int64_t r0 = 0; r0 < s.m && err.empty(); r0 += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, s.m - r0);
+    const long long ncol = (long long)rows * G;
+    (void)hipEventRecord(b.ev[2], h->st);
+    if (lds_rows) {
+      err = launch_fit_rows(h->c, s.f, (int)r0, rows, d_probs, nq, d_mean, d_sd, d_q, h->st);
+      (void)hipEventRecord(b.ev[3], h->st);
+    } else {
+      err = launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st);
+      (void)hipEventRecord(b.ev[3], h->st);
+      if (err.empty()) err = launch_bands_quantiles(d_v, (int)s.CS, ncol, d_w, d_probs, nq, d_q, h->st);
+      // the sorted rows are in the workspace: the rule again, rounded as k_fit_rows rounds it
+      if (err.empty() && sort_ws) err = launch_fit_quantiles(d_w, NP, (int)s.CS, ncol, d_probs, nq, d_q, h->st);
+      if (err.empty()) err = launch_bands_moments(d_v, (int)s.CS, ncol, d_mean, d_sd, h->st);
+    }
+    (void)hipEventRecord(b.ev[4], h->st);
+    if (err.empty() &&
+        (hipMemcpyAsync(mean + (size_t)r0 * G, d_mean, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+         hipMemcpyAsync(sd + (size_t)r0 * G, d_sd, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+         copy_sync(h, quantiles + (size_t)r0 * G * nq, d_q, sizeof(double) * (size_t)ncol * nq, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (err.empty()) {
+      fit_collect(h, b, 2, 3, lds_rows ? FIT_T_ROWS : FIT_T_VALUES);
+      if (!lds_rows) fit_collect(h, b, 3, 4, FIT_T_REDUCE);
+    }
+  }
+  (void)hipStreamSynchronize(h->st);
+  if (!err.empty()) { (void)hipGetLastError(); return fail(fn + ": " + err); }
+  return 0;
+}
+
 extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capacity, int64_t* count) {
   if (!h || !name || !out || !count) return fail("bfmmm_debug_get: null argument");
   HIPCHK(hipSetDevice(h->device));
@@ -1481,6 +1672,14 @@ extern "C" int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, i
   if (!h || !name || !ms || !launches) return fail("bfmmm_get_timing: null argument");
   for (int f = 0; f < FAM_COUNT; ++f)
     if (!strcmp(name, kFamNames[f])) { *ms = h->fam_ms[f]; *launches = h->fam_launches[f]; return 0; }
+  // the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands: each kernel family of kernels_curve_fit.hip, and their sum
+  for (int f = 0; f < FIT_T_COUNT; ++f)
+    if (!strcmp(name, kFitNames[f])) { *ms = h->fit_ms[f]; *launches = h->fit_launches[f]; return 0; }
+  if (!strcmp(name, "curve_fit")) {
+    *ms = 0; *launches = 0;
+    for (int f = 0; f < FIT_T_COUNT; ++f) { *ms += h->fit_ms[f]; *launches += h->fit_launches[f]; }
+    return 0;
+  }
   return fail("bfmmm_get_timing: unknown name");
 }
 

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/bfmmm_post.h"
+#include "launchers.hpp"
 
 int bfmmm_io_fail(const std::string& m);
 
@@ -206,6 +207,38 @@ static int launch_quantiles(Bufs& b, const double* dV, int T, int ncol, const do
 }
 
 }  // namespace
+
+// The same kernels for callers that hold a device table and a stream (launchers.hpp; the chain-slot bands of DESIGN.md 7e).
+namespace bfmmm {
+
+int bands_sort_pad(int T) {
+  int NP = 2 * TMAX;
+  while (NP < T) NP <<= 1;
+  return NP;
+}
+
+std::string launch_bands_quantiles(const double* V, int T, long long ncol, double* W, const double* probs, int nq, double* out, hipStream_t st) {
+  if (!V || !probs || !out || T < 1 || T > TBIG || ncol < 1 || ncol > 0x7fffffffLL || nq < 1 || nq > QT) return "bands quantiles: bad arguments";
+  if (T <= TMAX) {
+    (void)hipFuncSetAttribute((const void*)k_bands_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds_bytes(TMAX));
+    hipLaunchKernelGGL(k_bands_quantiles, dim3((unsigned)ncol), dim3(QT), sort_lds_bytes(T), st, V, T, probs, nq, out);
+  } else {
+    if (!W) return "bands quantiles: no workspace";
+    (void)hipFuncSetAttribute((const void*)k_bands_quantiles_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LCH * sizeof(double)));
+    hipLaunchKernelGGL(k_bands_quantiles_big, dim3((unsigned)ncol), dim3(BT), LCH * sizeof(double), st, V, T, bands_sort_pad(T), W, probs, nq, out);
+  }
+  if (hipGetLastError() != hipSuccess) return "bands quantiles: launch failed";
+  return "";
+}
+
+std::string launch_bands_moments(const double* V, int T, long long ncol, double* mean, double* sd, hipStream_t st) {
+  if (!V || !mean || !sd || T < 1 || ncol < 1 || ncol > 0x7fffffffLL) return "bands moments: bad arguments";
+  hipLaunchKernelGGL(k_bands_moments, dim3((unsigned)ncol), dim3(QT), 0, st, V, T, mean, sd);
+  if (hipGetLastError() != hipSuccess) return "bands moments: launch failed";
+  return "";
+}
+
+}  // namespace bfmmm
 
 extern "C" int bfmmm_post_col_quantiles(const double* V, int32_t T, int32_t ncol, const double* probs, int32_t nq, int32_t device, double* out) {
   if (!V || !probs || !out || T < 1 || ncol < 1 || nq < 1 || nq > QT) return bfmmm_io_fail("bfmmm_post_col_quantiles: bad arguments");

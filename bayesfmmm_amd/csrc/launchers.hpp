@@ -67,6 +67,35 @@ bool cov_block_fits(const Ctx& c);
 // out[(i - i0) C S + q S + (t - first_slot)] (device); "" or what the kernel cannot take
 std::string launch_chain_curve_ll(const Ctx& c, int first_slot, int n_slots, int i0, int rows, double* out, hipStream_t st);
 
+// ---- kernels_curve_fit.hip ----
+// One call of bfmmm_chain_curve_fit / _bands: which (0 mean, 1 fit), the G x P evaluation basis E, the curve of every result
+// row (null: curve r), the slot range and the call's projection table of G fit_directions() C n_slots doubles (all device).
+struct FitCall {
+  int which = 0, G = 0, first_slot = 0, n_slots = 0;
+  const double* E = nullptr;
+  const int* curves = nullptr;
+  double* tab = nullptr;
+};
+long long fit_directions(const Dims& d, int which);
+int fit_lds_rows();                 // C S of the last row k_fit_rows sorts in LDS
+std::string fit_check(const Ctx& c, const FitCall& f);
+std::string launch_fit_project(const Ctx& c, const FitCall& f, hipStream_t st);
+// result rows [r0, r0 + rows): mean / sd [r G + g] and quant [(r G + g) nq + q] of the chunk (r from 0), rows of <= fit_lds_rows() draws
+std::string launch_fit_rows(const Ctx& c, const FitCall& f, int r0, int rows, const double* probs, int nq, double* mean, double* sd,
+                            double* quant, hipStream_t st);
+// the values out[((r G + g) C + q) S + s] of the chunk
+std::string launch_fit_values(const Ctx& c, const FitCall& f, int r0, int rows, double* out, hipStream_t st);
+// the quantile rule read off ncol sorted rows W[col NP + .] of T values: quant[col nq + q]
+std::string launch_fit_quantiles(const double* W, int NP, int T, long long ncol, const double* probs, int nq, double* quant, hipStream_t st);
+
+// ---- kernels_bands.hip ----
+// The column reductions of the credible-band entry points on device tables V[t + T col], on stream st.  quantiles: LDS sort
+// for T <= 8192 (W unused), else k_bands_quantiles_big over the workspace W of NP ncol doubles, NP = bands_sort_pad(T), which
+// it leaves holding the sorted columns; out[q + nq col].  moments: mean and sd (N - 1) per column.
+int bands_sort_pad(int T);
+std::string launch_bands_quantiles(const double* V, int T, long long ncol, double* W, const double* probs, int nq, double* out, hipStream_t st);
+std::string launch_bands_moments(const double* V, int T, long long ncol, double* mean, double* sd, hipStream_t st);
+
 #ifdef BFMMM_TIMELINE
 void fetch_wgtrace(unsigned long long* out);      // kernels_pair_gram.hip
 void fetch_ztrace(unsigned long long* out);       // kernels_curve.hip

@@ -213,6 +213,45 @@ class Sampler:
         pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs))
         return api.loo_totals(pw, self.n_chains * S)
 
+    def _fit_args(self, E, which, curves, first_slot, n_slots):
+        w = {"mean": 0, "fit": 1}.get(which, which)
+        if isinstance(w, str):
+            raise ValueError("which must be 'mean' or 'fit'")
+        w = int(w)
+        Em = np.ascontiguousarray(E, dtype=np.float64)
+        if Em.ndim != 2 or Em.shape[1] != self.P:
+            raise ValueError(f"E must be a G x {self.P} matrix in the sampler's basis")
+        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
+        if curves is None:
+            idx, pc, m = None, None, self.n
+        else:
+            idx = np.ascontiguousarray(curves, dtype=np.int32).reshape(-1)
+            pc, m = idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size
+        return w, Em, S, idx, pc, m
+
+    def curve_fit(self, E, which="fit", curves=None, first_slot=0, n_slots=None):
+        """Every curve's fitted function on the rows of E (G x P, in the sampler's basis: api.TensorBSpline rows on a time grid,
+        a curve's own get_basis() rows, the identity for the multivariate model) under chain slots [first_slot, first_slot +
+        n_slots) of every chain of the batch (bfmmm_chain_curve_fit).  which="mean": E c_i, the curve's mean
+        function; "fit": E (c_i + sum_m chi_im V_im).  Label- and sign-invariant.  curves: indices, in any order (default: all).
+        Returns an (m, G, C, S) array; meant for a handful of curves."""
+        w, Em, S, idx, pc, m = self._fit_args(E, which, curves, first_slot, n_slots)
+        out = np.zeros((m, Em.shape[0], self.n_chains, max(S, 0)))
+        _lib.check(self.lib.bfmmm_chain_curve_fit(self.h, w, _dp(Em), Em.shape[0], pc, m, int(first_slot), S, _dp(out), out.size))
+        return out
+
+    def curve_bands(self, E, which="fit", probs=(0.025, 0.5, 0.975), curves=None, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """Pointwise posterior mean, sd and quantiles of `curve_fit`'s values with the chains pooled, computed on the device
+        without the values leaving it (bfmmm_chain_curve_bands).  Quantiles follow arma::quantile's rule, as the single-chain
+        credible bands do.  Returns {"mean": (m, G), "sd": (m, G), "quantiles": (m, G, nq), "probs": (nq,)}."""
+        w, Em, S, idx, pc, m = self._fit_args(E, which, curves, first_slot, n_slots)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        G = Em.shape[0]
+        mean, sd, qs = np.zeros((m, G)), np.zeros((m, G)), np.zeros((m, G, pr.size))
+        _lib.check(self.lib.bfmmm_chain_curve_bands(self.h, w, _dp(Em), G, pc, m, int(first_slot), S, _dp(pr), pr.size,
+                                                    int(max_workspace_bytes), _dp(mean), _dp(sd), _dp(qs), m * G))
+        return {"mean": mean, "sd": sd, "quantiles": qs, "probs": pr}
+
     def get_basis(self):
         n_obs = int(self.offsets[-1])
         out = np.zeros((n_obs, self.P))

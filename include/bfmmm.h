@@ -206,6 +206,28 @@ int bfmmm_chain_curve_diagnostics(bfmmm_handle* h, int first_slot, int n_slots, 
 int bfmmm_chain_loo(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes, double* lppd, double* elpd_loo,
                     double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, int64_t capacity);
 
+/* Pooled per-curve fitted functions of chain slots [first_slot, first_slot + n_slots) of EVERY chain of the batch, on the rows
+ * E_g of an evaluation basis E (G x P, row-major, in the sampler's basis), and their credible bands:
+ *   which = 0   mean_i(g) = E_g . c_i,                        c_i  = sum_k Z_ik (nu_k + sum_d x_id eta_kd)
+ *   which = 1   fit_i(g)  = E_g . (c_i + sum_m chi_im V_im),  V_im = sum_k Z_ik (phi_km + sum_d x_id xi_kmd)  (xi: covariance-adjusted)
+ * Neither depends on the components' labels or on the signs of the eigenfunctions, so the chains pool as they are.
+ * curves: NULL for all n curves, or n_curves indices in [0, n) in any order; result row r is curve curves[r] (m rows).
+ *   bfmmm_chain_curve_fit    copies the values to the host: out[((r G + g) C + q) S + s] (chain q, s = t - first_slot, S =
+ *                            n_slots), capacity >= m G C S.  For a handful of curves.
+ *   bfmmm_chain_curve_bands  mean[r G + g], sd[r G + g] (N - 1; NaN for one draw) and quantiles[(r G + g) nq + q] of each row's
+ *                            C S values at probs[0 .. nq) in [0, 1], nq <= 16, by arma::quantile's rule (Hyndman and Fan
+ *                            definition 5); capacity >= m G rows.  The values stay on the device; chunks of consecutive result
+ *                            rows keep everything the call allocates within max_workspace_bytes (0: 256 MiB).
+ * At most 2^22 draws per row (n_chains x n_slots).  Both run on the sampler's stream and leave its state and slots untouched.
+ * bfmmm_set_curve_fit_route(1) sends rows of up to 8192 draws through the workspace route of the longer ones as well
+ * (a measurement switch; 0, the default: they are formed, sorted and reduced in LDS). */
+int bfmmm_chain_curve_fit(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves, int first_slot,
+                          int n_slots, double* out, int64_t capacity);
+int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves, int first_slot,
+                            int n_slots, const double* probs, int nq, int64_t max_workspace_bytes, double* mean, double* sd,
+                            double* quantiles, int64_t capacity);
+void bfmmm_set_curve_fit_route(int route);
+
 /* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
  * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P), "theta" (K (M + 1) x P), "dims" (as doubles), "curve_ll_ms" (device
@@ -219,7 +241,9 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
 /* Timing of the last bfmmm_run: milliseconds between HIP events recorded on the sampler's stream
  * around the whole run and, per kernel family, accumulated over iterations when `profile` was
  * enabled with bfmmm_set_profile (which disables graph replay).
- * names: "total", "curve_z", "pair_gram", "factor", "sweep", "curve_chi", "loglik". */
+ * names: "total", "curve_z", "pair_gram", "factor", "sweep", "curve_chi", "loglik".
+ * Of the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands (always measured): "curve_fit" (the sum of the following),
+ * "curve_fit_project", "curve_fit_rows", "curve_fit_values", "curve_fit_reduce" (quantiles and moments of the workspace route). */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
