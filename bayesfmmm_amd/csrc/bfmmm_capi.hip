@@ -1,96 +1,30 @@
 // C ABI of the sampler (include/bfmmm.h): handle management, state marshalling between the
 // reference's column-major layouts and the device layout, iteration driver with HIP-graph replay.
-#include "../../include/bfmmm.h"
-#include "model.hpp"
+#include "handle.hpp"
 #include "rng.hpp"
 #include "launchers.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <map>
 #include <chrono>
 #include <mutex>
-#include <string>
-#include <tuple>
-#include <vector>
-
 
 using namespace bfmmm;
 
 static thread_local std::string g_err;
 static constexpr int GRAPH_UNROLL = 10;
 static std::mutex g_capture_mutex;   // one stream capture at a time (samplers may run on several host threads)
-static int fail(const std::string& msg) { g_err = msg; return 1; }
+int bfmmm::fail(const std::string& msg) { g_err = msg; return 1; }
 
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) {                                                                         \
-      (void)hipGetLastError(); /* (not sticky: a caller that retries with a smaller batch starts clean) */ \
-      char buf_[512];                                                                               \
-      snprintf(buf_, sizeof buf_, "HIP error %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__, __LINE__, #x); \
-      return fail(buf_);                                                                            \
-    }                                                                                               \
-  } while (0)
-
-enum { FAM_TOTAL = 0, FAM_Z, FAM_PG, FAM_FACTOR, FAM_SWEEP, FAM_CHI, FAM_LOGLIK, FAM_REDUCE, FAM_COUNT };
 static const char* kFamNames[FAM_COUNT] = {"total", "curve_z", "pair_gram", "factor", "sweep", "curve_chi", "loglik", "pg_reduce"};
-
-struct bfmmm_handle {
-  bfmmm_config cfg;
-  int device = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t evA = nullptr;
-  Ctx c;                       // template context (full MD); its per-chain pointers are those of chain 0 of the batch
-  int nch = 1;                 // chains in the batch (bfmmm_create_batch), all advanced in lockstep by bfmmm_run
-  int sel = 0;                 // the chain the state / chain accessors address (bfmmm_select_chain)
-  int T = 0;
-  int64_t n_obs = 0;
-  // raw inputs kept on the device for bfmmm_get_basis
-  double* d_t = nullptr; double* d_y = nullptr; int64_t* d_off = nullptr; double* d_knots = nullptr; int n_knots = 0;
-  std::vector<void*> allocs;
-  char* arena = nullptr;               // base of the per-chain arena (chain q at arena + q * c.chain_bytes)
-  char* arena_cov = nullptr;           // the same for the covariate buffers (c.chain_bytes_cov)
-  uint32_t* status_host = nullptr;     // pinned, host-mapped: the chains' status words after a run
-  uint32_t* status_dev = nullptr;      // its device address (written by the run's last kernel)
-  size_t pg_part_doubles = 0;
-  static constexpr int MAX_SUB = 4;
-  // snapshot of the chains' work state for the dry launch of freshly captured graphs (bfmmm_prepare_run)
-  char* dry_snap = nullptr;
-  size_t dry_snap_bytes = 0;
-  // packed partial tiles of k_pair_gram_pack, one buffer per sub-batch stream (+ one for the whole batch on one stream)
-  double* pg_pack[MAX_SUB + 1] = {};
-  size_t pg_pack_doubles[MAX_SUB + 1] = {};
-  hipStream_t sub_st[MAX_SUB] = {nullptr, nullptr, nullptr, nullptr};     // [0] = st
-  hipEvent_t sub_ev[MAX_SUB] = {nullptr, nullptr, nullptr, nullptr};
-  // Captured graphs of runs with the key below, oldest first: (sub-batch, kind, repetitions) -> graph (run_impl)
-  struct CachedGraph { int sub, kind, reps; hipGraphExec_t g; };
-  std::vector<CachedGraph> graphs;
-  using GraphKey = std::tuple<uint32_t, int, uint64_t, uint32_t, int, int>;      // (mask, MD, seed, chain, nsub, instance switches)
-  GraphKey g_key;
-  bool g_valid = false;                // the cached graphs were captured for g_key
-  int last_md = -1;
-  double last_route[6] = {0, 0, 0, -1, 0, 0};  // bfmmm_debug_get("pg_route"): {packed, KS, NKS, body, G, tail} of sub-batch 0 of the last run
-  int64_t tab_key = -1;                // (MD, mask) the step tables of k_sweep_chain were built for
-  int launch_error = 0;
-  int slot_base = 0;                   // chain slot of iteration i is i - slot_base (bfmmm_set_slot_base)
-  double* tt_save = nullptr;            // state saved across a tempered-transition block
-  std::vector<double> B_host;           // bfmmm_create_from_basis: the caller's basis rows (bfmmm_get_basis)
-  bool state_dirty = true;             // the state was changed from the host: proposals prepared on the device are stale
-  int profile = 0;
-  double fam_ms[FAM_COUNT] = {0};
-  int64_t fam_launches[FAM_COUNT] = {0};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double curve_ll_ms = 0;              // bfmmm_debug_get("curve_ll_ms"): device time of k_chain_curve_ll in the last call that ran it
-  double fit_ms[4] = {0};              // bfmmm_get_timing("curve_fit_project" / "_rows" / "_values" / "_reduce"; "curve_fit": their sum):
-  int64_t fit_launches[4] = {0};       // device time of the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands
-};
+static const char* kFitNames[4] = {"curve_fit_project", "curve_fit_rows", "curve_fit_values", "curve_fit_reduce"};     // h->fit_ms[], in capi_chain.hip's order
+static constexpr int FIT_T_COUNT = sizeof kFitNames / sizeof kFitNames[0];
 
 // Synchronous copy on the sampler's own stream: the legacy (NULL) stream must not be touched while
 // another host thread is capturing a graph.
-static hipError_t copy_sync(bfmmm_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+hipError_t bfmmm::copy_sync(bfmmm_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
   hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, h->st);
   if (e != hipSuccess) return e;
   return hipStreamSynchronize(h->st);
@@ -133,7 +67,7 @@ static int arena_commit(bfmmm_handle* h, const std::vector<ArenaReq>& v, int nch
   return 0;
 }
 // the context of the selected chain (host view)
-static Ctx selc(const bfmmm_handle* h) { return chain_ctx(h->c, (unsigned)h->sel); }
+Ctx bfmmm::selc(const bfmmm_handle* h) { return chain_ctx(h->c, (unsigned)h->sel); }
 
 extern "C" void bfmmm_config_defaults(bfmmm_config* cfg) {
   // defaults of BFMMM_Nu_Z_multiple_try / BFMMM_Theta_est / BFMMM_warm_start
@@ -1169,446 +1103,6 @@ extern "C" int bfmmm_tempered_transition(bfmmm_handle* h, uint32_t mask, int ite
   if (dyn_put(h, dn)) return 1;
   if (logA_out) *logA_out = logA;
   if (accepted_out) *accepted_out = accepted;
-  return 0;
-}
-
-extern "C" int bfmmm_get_chain(bfmmm_handle* h, const char* name, int n_slots, double* out, int64_t capacity) {
-  if (!h || !name || !out) return fail("bfmmm_get_chain: null argument");
-  if (n_slots < 0 || n_slots > h->T) return fail("bfmmm_get_chain: n_slots out of range");
-  HIPCHK(hipSetDevice(h->device));
-  const Ctx c = selc(h);        // the selected chain of the batch
-  const Dims& d = c.d;
-  const int64_t n = d.n, K = d.K, P = d.P, M = d.M;
-  const std::string s(name);
-  struct Arr { const char* nm; const double* p; int64_t len; };
-  const Arr arrs[] = {{"nu", c.c_nu, K * P}, {"chi", c.c_chi, n * M}, {"Z", c.c_Z, n * K}, {"pi", c.c_pi, K},
-                      {"alpha_3", c.c_alpha3, 1}, {"delta", c.c_delta, K * M}, {"A", c.c_A, K * 2},
-                      {"sigma_sq", c.c_sigma, 1}, {"gamma", c.c_gamma, K * P * M}, {"Phi", c.c_Phi, K * P * M},
-                      {"loglik", c.c_loglik, 1},
-                      {"eta", c.c_eta, P * d.D * K}, {"xi", c.c_xi, K * P * d.D * M}, {"tau_eta", c.c_tau_eta, K * d.D},
-                      {"gamma_xi", c.c_gamma_xi, K * P * d.D * M}, {"delta_xi", c.c_delta_xi, K * M * d.D},
-                      {"A_xi", c.c_A_xi, K * 2 * d.D}};
-  HIPCHK(hipStreamSynchronize(h->st));
-  for (const Arr& a : arrs)
-    if (s == a.nm && a.p) {
-      const int64_t want = a.len * n_slots;
-      if (capacity < want) return fail("bfmmm_get_chain(" + s + "): buffer too small");
-      HIPCHK(copy_sync(h, out, a.p, sizeof(double) * (size_t)want, hipMemcpyDeviceToHost));
-      return 0;
-    }
-  if (s == "tau") {   // stored T_alloc x K column-major on the device; returned n_slots x K column-major
-    const int64_t want = (int64_t)n_slots * K;
-    if (capacity < want) return fail("bfmmm_get_chain(tau): buffer too small");
-    for (int k = 0; k < K; ++k)
-      HIPCHK(copy_sync(h, out + (size_t)n_slots * k, c.c_tau + (size_t)h->T * k, sizeof(double) * (size_t)n_slots,
-                       hipMemcpyDeviceToHost));
-    return 0;
-  }
-  return fail("bfmmm_get_chain: unknown name '" + s + "'");
-}
-
-// ---- convergence diagnostics over the chain slots (kernels_diag.hip) --------------------------------------
-long long diag_row_max();
-size_t diag_row_ws_doubles(int C, int S);
-std::string diag_launch(const double* d_x, long long rows, int C, int S, double* d_out, long long ld_out, double* ws, long long ws_rows,
-                        hipStream_t st);
-std::string diag_gather(const double* base, size_t chain_bytes, long long ss, long long ps, int first, int S, int C, int p0, int P,
-                        double* ws, hipStream_t st);
-
-// Every chain of the batch, slots [first_slot, first_slot + n_slots) of `name`: elements are gathered in chunks of
-// consecutive elements into a row-major workspace (draw fastest, then chain) and reduced there; nothing goes to the host
-// but the seven statistics.
-extern "C" int bfmmm_chain_diagnostics(bfmmm_handle* h, const char* name, int first_slot, int n_slots, int64_t max_workspace_bytes,
-                                       double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
-                                       double* mean, double* sd, int64_t capacity) {
-  const char* pn[] = {"h", "name", "rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd"};
-  const void* pv[] = {h, name, rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
-  for (int i = 0; i < 9; ++i)
-    if (!pv[i]) return fail(std::string("bfmmm_chain_diagnostics: '") + pn[i] + "' is null");
-  if (first_slot < 0 || first_slot >= h->T) return fail("bfmmm_chain_diagnostics: 'first_slot' out of range");
-  if (n_slots < 1 || n_slots > h->T - first_slot) return fail("bfmmm_chain_diagnostics: 'n_slots' out of range (first_slot + n_slots > T)");
-  if (max_workspace_bytes < 0) return fail("bfmmm_chain_diagnostics: 'max_workspace_bytes' must not be negative");
-  const Ctx& c = h->c;          // chain 0's pointers; chain q's are q * chain_bytes (covariate blocks: chain_bytes_cov) further
-  const Dims& d = c.d;
-  const int64_t n = d.n, K = d.K, P = d.P, M = d.M;
-  const std::string s(name);
-  struct Arr { const char* nm; const double* p; int64_t len; bool cov; };
-  const Arr arrs[] = {{"nu", c.c_nu, K * P, false}, {"chi", c.c_chi, n * M, false}, {"Z", c.c_Z, n * K, false}, {"pi", c.c_pi, K, false},
-                      {"alpha_3", c.c_alpha3, 1, false}, {"delta", c.c_delta, K * M, false}, {"A", c.c_A, K * 2, false},
-                      {"sigma_sq", c.c_sigma, 1, false}, {"gamma", c.c_gamma, K * P * M, false}, {"Phi", c.c_Phi, K * P * M, false},
-                      {"loglik", c.c_loglik, 1, false},
-                      {"eta", c.c_eta, P * d.D * K, true}, {"xi", c.c_xi, K * P * d.D * M, true}, {"tau_eta", c.c_tau_eta, K * d.D, true},
-                      {"gamma_xi", c.c_gamma_xi, K * P * d.D * M, true}, {"delta_xi", c.c_delta_xi, K * M * d.D, true},
-                      {"A_xi", c.c_A_xi, K * 2 * d.D, true},
-                      {"tau", c.c_tau, K, false}};      // tau: T_alloc x K column-major (slot fastest)
-  const Arr* a = nullptr;
-  for (const Arr& e : arrs)
-    if (s == e.nm && e.p) a = &e;
-  if (!a) return fail("bfmmm_chain_diagnostics: unknown name '" + s + "'");
-  const int64_t len = a->len;
-  if (capacity < len) return fail("bfmmm_chain_diagnostics(" + s + "): 'capacity' below " + std::to_string(len) + " entries");
-  const int C = h->nch, S = n_slots;
-  if ((long long)C * S > diag_row_max())
-    return fail("bfmmm_chain_diagnostics: at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " +
-                std::to_string((long long)C * S));
-  const long long ss = s == "tau" ? 1 : len, ps = s == "tau" ? h->T : 1;
-  const size_t cb = a->cov ? c.chain_bytes_cov : c.chain_bytes;
-  const size_t budget = max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20;
-  const size_t per_row = sizeof(double) * ((size_t)C * S + diag_row_ws_doubles(C, S)) + 7 * sizeof(double);
-  if (budget < per_row)
-    return fail("bfmmm_chain_diagnostics: 'max_workspace_bytes' below the " + std::to_string(per_row) + " bytes of one row");
-  const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
-  HIPCHK(hipSetDevice(h->device));
-  double* d_ws = nullptr;
-  HIPCHK(hipMalloc(&d_ws, per_row * (size_t)chunk));
-  double* d_x = d_ws;
-  double* d_out = d_x + (size_t)chunk * C * S;
-  double* d_tier = d_out + 7 * (size_t)chunk;
-  std::vector<double> hb(7 * (size_t)chunk);
-  double* const outs[7] = {rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
-  std::string err;
-  for (int64_t p0 = 0; p0 < len && err.empty(); p0 += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, len - p0);
-    err = diag_gather(a->p, cb, ss, ps, first_slot, S, C, (int)p0, rows, d_x, h->st);
-    if (err.empty()) err = diag_launch(d_x, rows, C, S, d_out, rows, d_tier, rows, h->st);
-    if (err.empty() && copy_sync(h, hb.data(), d_out, sizeof(double) * 7 * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess)
-      err = "kernel or copy back failed";
-    if (err.empty())
-      for (int q = 0; q < 7; ++q) std::copy(hb.begin() + (size_t)q * rows, hb.begin() + (size_t)(q + 1) * rows, outs[q] + p0);
-  }
-  (void)hipStreamSynchronize(h->st);
-  (void)hipFree(d_ws);
-  if (!err.empty()) { (void)hipGetLastError(); return fail("bfmmm_chain_diagnostics(" + s + "): " + err); }
-  return 0;
-}
-
-// ---- per-curve marginal log-density of the chain slots (kernels_curve_ll.hip) ------------------------------
-int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]);      // kernels_loo.hip
-extern "C" const char* bfmmm_entry_last_error(void);                                              // (its failure text)
-
-// one launch of k_chain_curve_ll between the handle's two events; curve_ll_collect adds its device time once the stream has
-// been synchronised
-static std::string curve_ll_timed(bfmmm_handle* h, int first_slot, int S, int i0, int rows, double* d_x) {
-  (void)hipEventRecord(h->ev0, h->st);
-  const std::string err = launch_chain_curve_ll(h->c, first_slot, S, i0, rows, d_x, h->st);
-  (void)hipEventRecord(h->ev1, h->st);
-  return err;
-}
-static void curve_ll_collect(bfmmm_handle* h) {
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->curve_ll_ms += ms;
-  else (void)hipGetLastError();
-}
-
-static int curve_ll_range(const std::string& fn, const bfmmm_handle* h, int first_slot, int n_slots) {
-  if (first_slot < 0 || first_slot >= h->T) return fail(fn + ": 'first_slot' out of range");
-  if (n_slots < 1 || n_slots > h->T - first_slot) return fail(fn + ": 'n_slots' out of range (first_slot + n_slots > T)");
-  return 0;
-}
-
-// The n x C x n_slots matrix (draw fastest, then chain, then curve) on the host, computed in chunks of consecutive curves
-// on the sampler's stream.
-extern "C" int bfmmm_chain_curve_loglik(bfmmm_handle* h, int first_slot, int n_slots, double* out, int64_t capacity) {
-  const std::string fn = "bfmmm_chain_curve_loglik";
-  if (!h) return fail(fn + ": 'h' is null");
-  if (!out) return fail(fn + ": 'out' is null");
-  if (curve_ll_range(fn, h, first_slot, n_slots)) return 1;
-  const int n = h->c.d.n, C = h->nch, S = n_slots;
-  const int64_t per_row = (int64_t)C * S;
-  if (capacity < (int64_t)n * per_row) return fail(fn + ": 'capacity' below " + std::to_string((int64_t)n * per_row) + " entries");
-  HIPCHK(hipSetDevice(h->device));
-  h->curve_ll_ms = 0;
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(((size_t)256 << 20) / (sizeof(double) * (size_t)per_row))));
-  double* d_x = nullptr;
-  HIPCHK(hipMalloc(&d_x, sizeof(double) * (size_t)chunk * (size_t)per_row));
-  std::string err;
-  for (int64_t i0 = 0; i0 < n && err.empty(); i0 += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, n - i0);
-    err = curve_ll_timed(h, first_slot, S, (int)i0, rows, d_x);
-    if (err.empty() && copy_sync(h, out + (size_t)i0 * per_row, d_x, sizeof(double) * (size_t)rows * per_row, hipMemcpyDeviceToHost) != hipSuccess)
-      err = "kernel or copy back failed";
-    if (err.empty()) curve_ll_collect(h);
-  }
-  (void)hipStreamSynchronize(h->st);
-  (void)hipFree(d_x);
-  if (!err.empty()) { (void)hipGetLastError(); return fail(fn + ": " + err); }
-  return 0;
-}
-
-// The seven statistics of bfmmm_chain_diagnostics for the n rows of that matrix: chunks of consecutive curves are computed
-// into the workspace and reduced there by the same diag_launch; the matrix never leaves the device.
-extern "C" int bfmmm_chain_curve_diagnostics(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes,
-                                             double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
-                                             double* mean, double* sd, int64_t capacity) {
-  const std::string fn = "bfmmm_chain_curve_diagnostics";
-  const char* pn[] = {"h", "rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd"};
-  const void* pv[] = {h, rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
-  for (int i = 0; i < 8; ++i)
-    if (!pv[i]) return fail(fn + ": '" + pn[i] + "' is null");
-  if (curve_ll_range(fn, h, first_slot, n_slots)) return 1;
-  if (max_workspace_bytes < 0) return fail(fn + ": 'max_workspace_bytes' must not be negative");
-  const int64_t len = h->c.d.n;
-  if (capacity < len) return fail(fn + ": 'capacity' below " + std::to_string(len) + " entries");
-  const int C = h->nch, S = n_slots;
-  if ((long long)C * S > diag_row_max())
-    return fail(fn + ": at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " + std::to_string((long long)C * S));
-  const size_t budget = max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20;
-  const size_t per_row = sizeof(double) * ((size_t)C * S + diag_row_ws_doubles(C, S)) + 7 * sizeof(double);
-  if (budget < per_row) return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(per_row) + " bytes of one row");
-  const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
-  HIPCHK(hipSetDevice(h->device));
-  h->curve_ll_ms = 0;
-  double* d_ws = nullptr;
-  HIPCHK(hipMalloc(&d_ws, per_row * (size_t)chunk));
-  double* d_x = d_ws;
-  double* d_out = d_x + (size_t)chunk * C * S;
-  double* d_tier = d_out + 7 * (size_t)chunk;
-  std::vector<double> hb(7 * (size_t)chunk);
-  double* const outs[7] = {rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
-  std::string err;
-  for (int64_t p0 = 0; p0 < len && err.empty(); p0 += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, len - p0);
-    err = curve_ll_timed(h, first_slot, S, (int)p0, rows, d_x);
-    if (err.empty()) err = diag_launch(d_x, rows, C, S, d_out, rows, d_tier, rows, h->st);
-    if (err.empty() && copy_sync(h, hb.data(), d_out, sizeof(double) * 7 * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess)
-      err = "kernel or copy back failed";
-    if (err.empty()) {
-      curve_ll_collect(h);
-      for (int q = 0; q < 7; ++q) std::copy(hb.begin() + (size_t)q * rows, hb.begin() + (size_t)(q + 1) * rows, outs[q] + p0);
-    }
-  }
-  (void)hipStreamSynchronize(h->st);
-  (void)hipFree(d_ws);
-  if (!err.empty()) { (void)hipGetLastError(); return fail(fn + ": " + err); }
-  return 0;
-}
-
-// PSIS-LOO and WAIC over curves with the chains pooled: a row is the C n_slots draws of a curve, chain-major, relative
-// efficiency 1.  Chunks of consecutive curves go through the same post_psis_device on the device.
-extern "C" int bfmmm_chain_loo(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes, double* lppd,
-                               double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, int64_t capacity) {
-  const std::string fn = "bfmmm_chain_loo";
-  const char* pn[] = {"h", "lppd", "elpd_loo", "p_loo", "pareto_k", "elpd_waic", "p_waic"};
-  const void* pv[] = {h, lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic};
-  for (int i = 0; i < 7; ++i)
-    if (!pv[i]) return fail(fn + ": '" + pn[i] + "' is null");
-  if (curve_ll_range(fn, h, first_slot, n_slots)) return 1;
-  if (max_workspace_bytes < 0) return fail(fn + ": 'max_workspace_bytes' must not be negative");
-  const int64_t len = h->c.d.n;
-  if (capacity < len) return fail(fn + ": 'capacity' below " + std::to_string(len) + " entries");
-  const int C = h->nch, S = n_slots;
-  if ((long long)C * S > diag_row_max())
-    return fail(fn + ": at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " + std::to_string((long long)C * S));
-  const size_t budget = max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20;
-  const size_t per_row = sizeof(double) * (size_t)C * S;
-  if (budget < per_row) return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(per_row) + " bytes of one row");
-  const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
-  HIPCHK(hipSetDevice(h->device));
-  h->curve_ll_ms = 0;
-  double* d_x = nullptr;
-  HIPCHK(hipMalloc(&d_x, per_row * (size_t)chunk));
-  std::string err;
-  for (int64_t p0 = 0; p0 < len && err.empty(); p0 += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, len - p0);
-    err = curve_ll_timed(h, first_slot, S, (int)p0, rows, d_x);
-    // post_psis_device runs on the device's default stream: the matrix must be complete before it starts
-    if (err.empty() && (hipStreamSynchronize(h->st) != hipSuccess || hipGetLastError() != hipSuccess)) err = "kernel failed";
-    if (err.empty()) curve_ll_collect(h);
-    double* const outs[6] = {lppd + p0, elpd_loo + p0, p_loo + p0, pareto_k + p0, elpd_waic + p0, p_waic + p0};
-    if (err.empty() && post_psis_device(d_x, (long long)C * S, rows, C * S, outs)) err = bfmmm_entry_last_error();
-  }
-  (void)hipStreamSynchronize(h->st);
-  (void)hipFree(d_x);
-  if (!err.empty()) { (void)hipGetLastError(); return fail(fn + ": " + err); }
-  return 0;
-}
-
-// ---- pooled per-curve fitted functions of the chain slots and their bands (kernels_curve_fit.hip) ----------
-namespace bfmmm { int g_curve_fit_route = 0; }
-extern "C" void bfmmm_set_curve_fit_route(int route) { bfmmm::g_curve_fit_route = route == 1 ? 1 : 0; }
-
-enum { FIT_T_PROJECT = 0, FIT_T_ROWS, FIT_T_VALUES, FIT_T_REDUCE, FIT_T_COUNT };
-static const char* kFitNames[FIT_T_COUNT] = {"curve_fit_project", "curve_fit_rows", "curve_fit_values", "curve_fit_reduce"};
-
-// what a call allocates: freed when the call returns, whichever way
-struct FitBufs {
-  std::vector<void*> p;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // project start / end, chunk start / middle / end
-  ~FitBufs() {
-    for (void* q : p) (void)hipFree(q);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  template <typename T>
-  hipError_t get(T** out, size_t count) {
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
-    return e;
-  }
-};
-static void fit_collect(bfmmm_handle* h, const FitBufs& b, int from, int to, int what) {
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, b.ev[from], b.ev[to]) == hipSuccess) { h->fit_ms[what] += ms; h->fit_launches[what] += 1; }
-  else (void)hipGetLastError();
-}
-
-struct FitSetup {
-  FitCall f;
-  int m = 0, C = 0, S = 0;
-  long long CS = 0, NJ = 0;
-};
-
-// The checks both calls share, then E, the curve list and the projection table on the device (owned by b) and the table
-// filled.  shared_bytes: what these take of the budget.
-static int fit_check_args(const std::string& fn, bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves,
-                          int first_slot, int n_slots, FitSetup& s) {
-  if (!E) return fail(fn + ": 'E' is null");
-  if (which != 0 && which != 1) return fail(fn + ": 'which' must be 0 (mean) or 1 (fit), got " + std::to_string(which));
-  if (G < 1) return fail(fn + ": 'G' must be at least 1");
-  const int n = h->c.d.n;
-  if (curves) {
-    if (n_curves < 1) return fail(fn + ": 'n_curves' must be at least 1 where 'curves' is given");
-    for (int j = 0; j < n_curves; ++j)
-      if (curves[j] < 0 || curves[j] >= n)
-        return fail(fn + ": 'curves'[" + std::to_string(j) + "] = " + std::to_string(curves[j]) + " outside 0 .. " + std::to_string(n - 1));
-  }
-  if (curve_ll_range(fn, h, first_slot, n_slots)) return 1;
-  s.m = curves ? n_curves : n;
-  s.C = h->nch; s.S = n_slots; s.CS = (long long)s.C * s.S;
-  if (s.CS > diag_row_max())
-    return fail(fn + ": at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " + std::to_string(s.CS));
-  s.f.which = which; s.f.G = G; s.f.first_slot = first_slot; s.f.n_slots = n_slots;
-  const std::string err = fit_check(h->c, s.f);
-  if (!err.empty()) return fail(fn + ": " + err);
-  s.NJ = fit_directions(h->c.d, which);
-  return 0;
-}
-static size_t fit_shared_bytes(const bfmmm_handle* h, const FitSetup& s) {
-  return sizeof(double) * ((size_t)s.CS * s.f.G * (size_t)s.NJ + (size_t)s.f.G * h->c.d.P + 16) + sizeof(int32_t) * (((size_t)s.m + 1) & ~(size_t)1);
-}
-static int fit_prepare(const std::string& fn, bfmmm_handle* h, const double* E, const int32_t* curves, FitSetup& s, FitBufs& b) {
-  double *d_E = nullptr, *d_tab = nullptr;
-  int* d_curves = nullptr;
-  for (hipEvent_t& e : b.ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(b.get(&d_E, (size_t)s.f.G * h->c.d.P));
-  HIPCHK(b.get(&d_tab, (size_t)s.CS * s.f.G * (size_t)s.NJ));
-  HIPCHK(copy_sync(h, d_E, E, sizeof(double) * (size_t)s.f.G * h->c.d.P, hipMemcpyHostToDevice));
-  if (curves) {
-    HIPCHK(b.get(&d_curves, (size_t)s.m));
-    HIPCHK(copy_sync(h, d_curves, curves, sizeof(int32_t) * (size_t)s.m, hipMemcpyHostToDevice));
-  }
-  s.f.E = d_E; s.f.curves = d_curves; s.f.tab = d_tab;
-  for (int q = 0; q < FIT_T_COUNT; ++q) { h->fit_ms[q] = 0; h->fit_launches[q] = 0; }
-  (void)hipEventRecord(b.ev[0], h->st);
-  const std::string err = launch_fit_project(h->c, s.f, h->st);
-  (void)hipEventRecord(b.ev[1], h->st);
-  if (!err.empty()) { (void)hipStreamSynchronize(h->st); return fail(fn + ": " + err); }
-  HIPCHK(hipStreamSynchronize(h->st));
-  fit_collect(h, b, 0, 1, FIT_T_PROJECT);
-  return 0;
-}
-
-// The values themselves on the host, in chunks of consecutive result rows.
-extern "C" int bfmmm_chain_curve_fit(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves,
-                                     int first_slot, int n_slots, double* out, int64_t capacity) {
-  const std::string fn = "bfmmm_chain_curve_fit";
-  if (!h) return fail(fn + ": 'h' is null");
-  if (!out) return fail(fn + ": 'out' is null");
-  FitSetup s;
-  if (fit_check_args(fn, h, which, E, G, curves, n_curves, first_slot, n_slots, s)) return 1;
-  const int64_t per_curve = (int64_t)G * s.CS;
-  if (capacity < (int64_t)s.m * per_curve) return fail(fn + ": 'capacity' below " + std::to_string((int64_t)s.m * per_curve) + " entries");
-  HIPCHK(hipSetDevice(h->device));
-  FitBufs b;
-  if (fit_prepare(fn, h, E, curves, s, b)) return 1;
-  int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (sizeof(double) * (size_t)per_curve)));
-  chunk = std::min<int64_t>(std::min<int64_t>(chunk, s.m), std::max<int64_t>(1, (1LL << 30) / G));
-  double* d_v = nullptr;
-  HIPCHK(b.get(&d_v, (size_t)chunk * per_curve));
-  std::string err;
-  for (int64_t r0 = 0; r0 < s.m && err.empty(); r0 += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, s.m - r0);
-    (void)hipEventRecord(b.ev[2], h->st);
-    err = launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st);
-    (void)hipEventRecord(b.ev[3], h->st);
-    if (err.empty() && copy_sync(h, out + (size_t)r0 * per_curve, d_v, sizeof(double) * (size_t)rows * per_curve, hipMemcpyDeviceToHost) != hipSuccess)
-      err = "kernel or copy back failed";
-    if (err.empty()) fit_collect(h, b, 2, 3, FIT_T_VALUES);
-  }
-  (void)hipStreamSynchronize(h->st);
-  if (!err.empty()) { (void)hipGetLastError(); return fail(fn + ": " + err); }
-  return 0;
-}
-
-// Mean, sd and quantiles of every row; the values stay on the device (rows of up to 8192 draws: in LDS).
-extern "C" int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves,
-                                       int first_slot, int n_slots, const double* probs, int nq, int64_t max_workspace_bytes,
-                                       double* mean, double* sd, double* quantiles, int64_t capacity) {
-  const std::string fn = "bfmmm_chain_curve_bands";
-  const char* pn[] = {"h", "probs", "mean", "sd", "quantiles"};
-  const void* pv[] = {h, probs, mean, sd, quantiles};
-  for (int i = 0; i < 5; ++i)
-    if (!pv[i]) return fail(fn + ": '" + pn[i] + "' is null");
-  FitSetup s;
-  if (fit_check_args(fn, h, which, E, G, curves, n_curves, first_slot, n_slots, s)) return 1;
-  if (nq < 1 || nq > 16) return fail(fn + ": 'nq' outside 1 .. 16");
-  for (int q = 0; q < nq; ++q)
-    if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail(fn + ": 'probs'[" + std::to_string(q) + "] outside [0, 1]");
-  if (max_workspace_bytes < 0) return fail(fn + ": 'max_workspace_bytes' must not be negative");
-  if (capacity < (int64_t)s.m * G) return fail(fn + ": 'capacity' below " + std::to_string((int64_t)s.m * G) + " rows");
-  const bool lds_rows = s.CS <= fit_lds_rows() && !g_curve_fit_route;
-  const bool sort_ws = s.CS > fit_lds_rows();               // k_bands_quantiles_big sorts in a workspace
-  const int NP = sort_ws ? bands_sort_pad((int)s.CS) : 0;
-  const size_t budget = max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20;
-  const size_t shared = fit_shared_bytes(h, s);
-  const size_t per_curve = sizeof(double) * (size_t)G * ((size_t)(2 + nq) + (lds_rows ? 0 : (size_t)s.CS + (size_t)NP));
-  if (budget < shared + per_curve)
-    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
-                std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
-  int64_t chunk = std::min<int64_t>(s.m, (int64_t)((budget - shared) / per_curve));
-  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (1LL << 30) / G));
-  HIPCHK(hipSetDevice(h->device));
-  FitBufs b;
-  double *d_probs = nullptr, *d_out = nullptr, *d_v = nullptr, *d_w = nullptr;
-  HIPCHK(b.get(&d_probs, 16));
-  HIPCHK(b.get(&d_out, (size_t)chunk * G * (2 + nq)));
-  if (!lds_rows) HIPCHK(b.get(&d_v, (size_t)chunk * G * (size_t)s.CS));
-  if (sort_ws) HIPCHK(b.get(&d_w, (size_t)chunk * G * (size_t)NP));
-  HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
-  if (fit_prepare(fn, h, E, curves, s, b)) return 1;
-  double* d_mean = d_out;
-  double* d_sd = d_out + (size_t)chunk * G;
-  double* d_q = d_out + 2 * (size_t)chunk * G;
-  std::string err;
-  for (int64_t r0 = 0; r0 < s.m && err.empty(); r0 += chunk) {
-    const int rows = (int)std::min<int64_t>(chunk, s.m - r0);
-    const long long ncol = (long long)rows * G;
-    (void)hipEventRecord(b.ev[2], h->st);
-    if (lds_rows) {
-      err = launch_fit_rows(h->c, s.f, (int)r0, rows, d_probs, nq, d_mean, d_sd, d_q, h->st);
-      (void)hipEventRecord(b.ev[3], h->st);
-    } else {
-      err = launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st);
-      (void)hipEventRecord(b.ev[3], h->st);
-      if (err.empty()) err = launch_bands_quantiles(d_v, (int)s.CS, ncol, d_w, d_probs, nq, d_q, h->st);
-      // the sorted rows are in the workspace: the rule again, rounded as k_fit_rows rounds it
-      if (err.empty() && sort_ws) err = launch_fit_quantiles(d_w, NP, (int)s.CS, ncol, d_probs, nq, d_q, h->st);
-      if (err.empty()) err = launch_bands_moments(d_v, (int)s.CS, ncol, d_mean, d_sd, h->st);
-    }
-    (void)hipEventRecord(b.ev[4], h->st);
-    if (err.empty() &&
-        (hipMemcpyAsync(mean + (size_t)r0 * G, d_mean, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-         hipMemcpyAsync(sd + (size_t)r0 * G, d_sd, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-         copy_sync(h, quantiles + (size_t)r0 * G * nq, d_q, sizeof(double) * (size_t)ncol * nq, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
-    if (err.empty()) {
-      fit_collect(h, b, 2, 3, lds_rows ? FIT_T_ROWS : FIT_T_VALUES);
-      if (!lds_rows) fit_collect(h, b, 3, 4, FIT_T_REDUCE);
-    }
-  }
-  (void)hipStreamSynchronize(h->st);
-  if (!err.empty()) { (void)hipGetLastError(); return fail(fn + ": " + err); }
   return 0;
 }
 

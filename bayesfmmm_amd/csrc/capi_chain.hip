@@ -1,0 +1,411 @@
+// C ABI of the sampler (include/bfmmm.h), what is read off the chain slots after a run: the chain arrays, their convergence
+// diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands.
+// An entry point is its argument checks (SlotCheck), the sizing of its workspace (CallBufs owns it) and one for_chunks.
+#include "handle.hpp"
+#include "launchers.hpp"
+#include "../../include/bfmmm_entry.h"
+
+#include <algorithm>
+#include <initializer_list>
+#include <utility>
+
+using namespace bfmmm;
+
+namespace {
+
+// ---- the chain arrays ---------------------------------------------------------------------------------------------------
+// Element e of slot t of array `name` is p[t ss + e ps] in the chain of context c, and q * c.chain_bytes (cov: chain_bytes_cov)
+// bytes further in the q-th chain after it.  p null: no array of that name (covariate arrays exist once covariates were set).
+struct ChainArr { const char* nm; const double* p; int64_t len; bool cov; int64_t ss, ps; };
+ChainArr chain_array(const Ctx& c, int T, const std::string& name) {
+  const Dims& d = c.d;
+  const int64_t n = d.n, K = d.K, P = d.P, M = d.M, D = d.D;
+  const ChainArr arrs[] = {{"nu", c.c_nu, K * P}, {"chi", c.c_chi, n * M}, {"Z", c.c_Z, n * K}, {"pi", c.c_pi, K},
+                           {"alpha_3", c.c_alpha3, 1}, {"delta", c.c_delta, K * M}, {"A", c.c_A, K * 2},
+                           {"sigma_sq", c.c_sigma, 1}, {"gamma", c.c_gamma, K * P * M}, {"Phi", c.c_Phi, K * P * M},
+                           {"loglik", c.c_loglik, 1},
+                           {"eta", c.c_eta, P * D * K, true}, {"xi", c.c_xi, K * P * D * M, true}, {"tau_eta", c.c_tau_eta, K * D, true},
+                           {"gamma_xi", c.c_gamma_xi, K * P * D * M, true}, {"delta_xi", c.c_delta_xi, K * M * D, true},
+                           {"A_xi", c.c_A_xi, K * 2 * D, true},
+                           {"tau", c.c_tau, K, false, 1, T}};      // tau: T_alloc x K column-major (slot fastest)
+  for (ChainArr a : arrs)
+    if (name == a.nm && a.p) {
+      if (!a.ps) { a.ss = a.len; a.ps = 1; }      // the others: slot by slot
+      return a;
+    }
+  return {};
+}
+
+// ---- argument checks ----------------------------------------------------------------------------------------------------
+// The checks of a call over slots [first_slot, first_slot + n_slots) of every chain, each answering 0 or fail() with the entry
+// point's name in front; an entry point chains them with || in the order of its messages.  ptrs() first: the others read h.
+struct SlotCheck {
+  std::string fn;
+  bfmmm_handle* h;
+  int first_slot, n_slots;
+  std::string tag = "";      // bfmmm_chain_diagnostics: "(name)", shown by capacity() and the chunk loop's failure
+
+  long long CS() const { return (long long)h->nch * n_slots; }      // draws per row
+  int ptrs(std::initializer_list<std::pair<const char*, const void*>> l) const {
+    for (const auto& e : l)
+      if (!e.second) return fail(fn + ": '" + e.first + "' is null");
+    return 0;
+  }
+  int range() const {
+    if (first_slot < 0 || first_slot >= h->T) return fail(fn + ": 'first_slot' out of range");
+    if (n_slots < 1 || n_slots > h->T - first_slot) return fail(fn + ": 'n_slots' out of range (first_slot + n_slots > T)");
+    return 0;
+  }
+  int row_limit() const {
+    if (CS() <= diag_row_max()) return 0;
+    return fail(fn + ": at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " + std::to_string(CS()));
+  }
+  int budget_sign(int64_t bytes) const { return bytes < 0 ? fail(fn + ": 'max_workspace_bytes' must not be negative") : 0; }
+  int budget_row(size_t budget, size_t row) const { return budget < row ? fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(row) + " bytes of one row") : 0; }
+  int capacity(int64_t have, int64_t want, const char* unit = "entries") const { return have < want ? fail(fn + tag + ": 'capacity' below " + std::to_string(want) + " " + unit) : 0; }
+};
+size_t budget_of(int64_t max_workspace_bytes) { return max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20; }
+
+// ---- what a call owns, its chunk loop and its timing ----------------------------------------------------------------------
+// The device buffers and events of one call: released when the call returns, whichever way.
+struct CallBufs {
+  std::vector<void*> p;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // curve fit: project start / end, chunk start / middle / end
+  ~CallBufs() {
+    for (void* q : p) (void)hipFree(q);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  template <typename T>
+  hipError_t get(T** out, size_t count) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
+    return e;
+  }
+};
+
+// Rows [0, len) in chunks of `chunk`: body(p0, rows) launches, copies back and collects the times of one chunk and answers
+// "" or what failed, which ends the loop.  Then the stream is drained and a failure reported under the call's name.
+template <typename Body>
+int for_chunks(const SlotCheck& ck, int64_t len, int64_t chunk, Body body) {
+  std::string err;
+  for (int64_t p0 = 0; p0 < len && err.empty(); p0 += chunk) err = body(p0, (int)std::min<int64_t>(chunk, len - p0));
+  (void)hipStreamSynchronize(ck.h->st);
+  if (!err.empty()) { (void)hipGetLastError(); return fail(ck.fn + ck.tag + ": " + err); }
+  return 0;
+}
+
+// device time between two events of a stream that has been synchronised since: added to *ms and counted
+void add_elapsed(hipEvent_t from, hipEvent_t to, double* ms, int64_t* launches = nullptr) {
+  float t = 0.f;
+  if (hipEventElapsedTime(&t, from, to) != hipSuccess) { (void)hipGetLastError(); return; }
+  *ms += t;
+  if (launches) *launches += 1;
+}
+
+// one launch of k_chain_curve_ll between the handle's two events; curve_ll_collect adds its device time after a synchronise
+std::string curve_ll_timed(const SlotCheck& ck, int i0, int rows, double* d_x) {
+  bfmmm_handle* h = ck.h;
+  (void)hipEventRecord(h->ev0, h->st);
+  const std::string err = launch_chain_curve_ll(h->c, ck.first_slot, ck.n_slots, i0, rows, d_x, h->st);
+  (void)hipEventRecord(h->ev1, h->st);
+  return err;
+}
+void curve_ll_collect(bfmmm_handle* h) { add_elapsed(h->ev0, h->ev1, &h->curve_ll_ms); }
+
+// ---- split R-hat, ESS, MCSE, mean and sd of rows of C S draws (kernels_diag.hip) --------------------------------
+// fill(p0, rows, d_x) puts rows [p0, p0 + rows) of the len rows into the workspace (row-major: draw fastest, then chain),
+// where diag_launch reduces them; nothing goes to the host but the seven statistics.  ll_timed: fill is curve_ll_timed.
+template <typename Fill>
+int seven_stats(const SlotCheck& ck, int64_t len, int64_t max_workspace_bytes, double* const (&outs)[7], bool ll_timed, Fill fill) {
+  bfmmm_handle* h = ck.h;
+  const int C = h->nch, S = ck.n_slots;
+  const size_t budget = budget_of(max_workspace_bytes);
+  const size_t per_row = sizeof(double) * ((size_t)C * S + diag_row_ws_doubles(C, S)) + 7 * sizeof(double);
+  if (ck.budget_row(budget, per_row)) return 1;
+  const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
+  HIPCHK(hipSetDevice(h->device));
+  if (ll_timed) h->curve_ll_ms = 0;
+  CallBufs b;
+  double* d_x = nullptr;
+  HIPCHK(b.get(&d_x, per_row / sizeof(double) * (size_t)chunk));
+  double* d_out = d_x + (size_t)chunk * C * S;
+  double* d_tier = d_out + 7 * (size_t)chunk;
+  std::vector<double> hb(7 * (size_t)chunk);
+  return for_chunks(ck, len, chunk, [&](int64_t p0, int rows) {
+    std::string err = fill((int)p0, rows, d_x);
+    if (err.empty()) err = diag_launch(d_x, rows, C, S, d_out, rows, d_tier, rows, h->st);
+    if (err.empty() && copy_sync(h, hb.data(), d_out, sizeof(double) * 7 * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess)
+      err = "kernel or copy back failed";
+    if (!err.empty()) return err;
+    if (ll_timed) curve_ll_collect(h);
+    for (int q = 0; q < 7; ++q) std::copy(hb.begin() + (size_t)q * rows, hb.begin() + (size_t)(q + 1) * rows, outs[q] + p0);
+    return err;
+  });
+}
+
+// ---- the pooled per-curve fitted functions (kernels_curve_fit.hip) -----------------------------------------
+// h->fit_ms[] / fit_launches[] (bfmmm_get_timing names them in this order)
+enum { FIT_T_PROJECT = 0, FIT_T_ROWS, FIT_T_VALUES, FIT_T_REDUCE, FIT_T_COUNT };
+static_assert(FIT_T_COUNT == sizeof(bfmmm_handle::fit_ms) / sizeof(double), "one slot of the handle per kernel family");
+void fit_collect(bfmmm_handle* h, const CallBufs& b, int from, int to, int what) { add_elapsed(b.ev[from], b.ev[to], &h->fit_ms[what], &h->fit_launches[what]); }
+
+struct FitSetup {
+  FitCall f;
+  long long m = 0, CS = 0, NJ = 0;       // curves of the result, draws per row, projection directions
+};
+
+// The checks both calls share, then E, the curve list and the projection table on the device (owned by b) and the table
+// filled.  shared_bytes: what these take of the budget.
+int fit_check_args(const SlotCheck& ck, int which, const double* E, int G, const int32_t* curves, int n_curves, FitSetup& s) {
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"E", E}})) return 1;
+  if (which != 0 && which != 1) return fail(fn + ": 'which' must be 0 (mean) or 1 (fit), got " + std::to_string(which));
+  if (G < 1) return fail(fn + ": 'G' must be at least 1");
+  const bfmmm_handle* h = ck.h;
+  const int n = h->c.d.n;
+  if (curves) {
+    if (n_curves < 1) return fail(fn + ": 'n_curves' must be at least 1 where 'curves' is given");
+    for (int j = 0; j < n_curves; ++j)
+      if (curves[j] < 0 || curves[j] >= n)
+        return fail(fn + ": 'curves'[" + std::to_string(j) + "] = " + std::to_string(curves[j]) + " outside 0 .. " + std::to_string(n - 1));
+  }
+  if (ck.range() || ck.row_limit()) return 1;
+  s.m = curves ? n_curves : n;
+  s.CS = ck.CS();
+  s.f.which = which; s.f.G = G; s.f.first_slot = ck.first_slot; s.f.n_slots = ck.n_slots;
+  const std::string err = fit_check(h->c, s.f);
+  if (!err.empty()) return fail(fn + ": " + err);
+  s.NJ = fit_directions(h->c.d, which);
+  return 0;
+}
+size_t fit_shared_bytes(const bfmmm_handle* h, const FitSetup& s) {
+  return sizeof(double) * ((size_t)s.CS * s.f.G * (size_t)s.NJ + (size_t)s.f.G * h->c.d.P + 16) + sizeof(int32_t) * (((size_t)s.m + 1) & ~(size_t)1);
+}
+int fit_prepare(const SlotCheck& ck, const double* E, const int32_t* curves, FitSetup& s, CallBufs& b) {
+  bfmmm_handle* h = ck.h;
+  double *d_E = nullptr, *d_tab = nullptr;
+  int* d_curves = nullptr;
+  for (hipEvent_t& e : b.ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(b.get(&d_E, (size_t)s.f.G * h->c.d.P));
+  HIPCHK(b.get(&d_tab, (size_t)s.CS * s.f.G * (size_t)s.NJ));
+  HIPCHK(copy_sync(h, d_E, E, sizeof(double) * (size_t)s.f.G * h->c.d.P, hipMemcpyHostToDevice));
+  if (curves) {
+    HIPCHK(b.get(&d_curves, (size_t)s.m));
+    HIPCHK(copy_sync(h, d_curves, curves, sizeof(int32_t) * (size_t)s.m, hipMemcpyHostToDevice));
+  }
+  s.f.E = d_E; s.f.curves = d_curves; s.f.tab = d_tab;
+  for (int q = 0; q < FIT_T_COUNT; ++q) { h->fit_ms[q] = 0; h->fit_launches[q] = 0; }
+  (void)hipEventRecord(b.ev[0], h->st);
+  const std::string err = launch_fit_project(h->c, s.f, h->st);
+  (void)hipEventRecord(b.ev[1], h->st);
+  if (!err.empty()) { (void)hipStreamSynchronize(h->st); return fail(ck.fn + ": " + err); }
+  HIPCHK(hipStreamSynchronize(h->st));
+  fit_collect(h, b, 0, 1, FIT_T_PROJECT);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int bfmmm_get_chain(bfmmm_handle* h, const char* name, int n_slots, double* out, int64_t capacity) {
+  if (!h || !name || !out) return fail("bfmmm_get_chain: null argument");
+  if (n_slots < 0 || n_slots > h->T) return fail("bfmmm_get_chain: n_slots out of range");
+  HIPCHK(hipSetDevice(h->device));
+  const std::string s(name);
+  const ChainArr a = chain_array(selc(h), h->T, s);        // of the selected chain of the batch
+  HIPCHK(hipStreamSynchronize(h->st));
+  if (!a.p) return fail("bfmmm_get_chain: unknown name '" + s + "'");
+  if (capacity < a.len * n_slots) return fail("bfmmm_get_chain(" + s + "): buffer too small");
+  if (a.ps == 1) HIPCHK(copy_sync(h, out, a.p, sizeof(double) * (size_t)(a.len * n_slots), hipMemcpyDeviceToHost));
+  else      // slot fastest on the device (tau): returned n_slots x len column-major
+    for (int64_t k = 0; k < a.len; ++k)
+      HIPCHK(copy_sync(h, out + (size_t)n_slots * k, a.p + (size_t)a.ps * k, sizeof(double) * (size_t)n_slots, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Every chain of the batch, slots [first_slot, first_slot + n_slots) of `name`: elements are gathered in chunks of
+// consecutive elements into the workspace of seven_stats.
+extern "C" int bfmmm_chain_diagnostics(bfmmm_handle* h, const char* name, int first_slot, int n_slots, int64_t max_workspace_bytes,
+                                       double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
+                                       double* mean, double* sd, int64_t capacity) {
+  SlotCheck ck{"bfmmm_chain_diagnostics", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"name", name}, {"rhat", rhat}, {"ess_bulk", ess_bulk}, {"ess_tail", ess_tail}, {"ess_mean", ess_mean},
+               {"mcse_mean", mcse_mean}, {"mean", mean}, {"sd", sd}}) ||
+      ck.range() || ck.budget_sign(max_workspace_bytes))
+    return 1;
+  const Ctx& c = h->c;          // chain 0 of the batch
+  const ChainArr a = chain_array(c, h->T, name);
+  if (!a.p) return fail(ck.fn + ": unknown name '" + name + "'");
+  ck.tag = std::string("(") + name + ")";
+  if (ck.capacity(capacity, a.len) || ck.row_limit()) return 1;
+  double* const outs[7] = {rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
+  return seven_stats(ck, a.len, max_workspace_bytes, outs, false, [&](int p0, int rows, double* d_x) {
+    return diag_gather(a.p, a.cov ? c.chain_bytes_cov : c.chain_bytes, a.ss, a.ps, first_slot, n_slots, h->nch, p0, rows, d_x, h->st);
+  });
+}
+
+// ---- per-curve marginal log-density of the chain slots (kernels_curve_ll.hip) ------------------------------
+// The n x C x n_slots matrix (draw fastest, then chain, then curve) on the host, computed in chunks of consecutive curves
+// on the sampler's stream.
+extern "C" int bfmmm_chain_curve_loglik(bfmmm_handle* h, int first_slot, int n_slots, double* out, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_curve_loglik", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"out", out}}) || ck.range()) return 1;
+  const int n = h->c.d.n;
+  const int64_t per_row = ck.CS();
+  if (ck.capacity(capacity, (int64_t)n * per_row)) return 1;
+  HIPCHK(hipSetDevice(h->device));
+  h->curve_ll_ms = 0;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(((size_t)256 << 20) / (sizeof(double) * (size_t)per_row))));
+  CallBufs b;
+  double* d_x = nullptr;
+  HIPCHK(b.get(&d_x, (size_t)chunk * (size_t)per_row));
+  return for_chunks(ck, n, chunk, [&](int64_t i0, int rows) {
+    std::string err = curve_ll_timed(ck, (int)i0, rows, d_x);
+    if (err.empty() && copy_sync(h, out + (size_t)i0 * per_row, d_x, sizeof(double) * (size_t)rows * per_row, hipMemcpyDeviceToHost) != hipSuccess)
+      err = "kernel or copy back failed";
+    if (err.empty()) curve_ll_collect(h);
+    return err;
+  });
+}
+
+// The seven statistics of bfmmm_chain_diagnostics for the n rows of that matrix: chunks of consecutive curves are computed
+// into the workspace of seven_stats; the matrix never leaves the device.
+extern "C" int bfmmm_chain_curve_diagnostics(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes,
+                                             double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean,
+                                             double* mean, double* sd, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_curve_diagnostics", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"rhat", rhat}, {"ess_bulk", ess_bulk}, {"ess_tail", ess_tail}, {"ess_mean", ess_mean}, {"mcse_mean", mcse_mean},
+               {"mean", mean}, {"sd", sd}}) ||
+      ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, h->c.d.n) || ck.row_limit())
+    return 1;
+  double* const outs[7] = {rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
+  return seven_stats(ck, h->c.d.n, max_workspace_bytes, outs, true, [&](int p0, int rows, double* d_x) { return curve_ll_timed(ck, p0, rows, d_x); });
+}
+
+// PSIS-LOO and WAIC over curves with the chains pooled: a row is the C n_slots draws of a curve, chain-major, relative
+// efficiency 1.  Chunks of consecutive curves go through the same post_psis_device on the device.
+extern "C" int bfmmm_chain_loo(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes, double* lppd,
+                               double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_loo", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"lppd", lppd}, {"elpd_loo", elpd_loo}, {"p_loo", p_loo}, {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic},
+               {"p_waic", p_waic}}) ||
+      ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, h->c.d.n) || ck.row_limit())
+    return 1;
+  const int64_t len = h->c.d.n;
+  const long long CS = ck.CS();
+  const size_t budget = budget_of(max_workspace_bytes);
+  const size_t per_row = sizeof(double) * (size_t)CS;
+  if (ck.budget_row(budget, per_row)) return 1;
+  const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
+  HIPCHK(hipSetDevice(h->device));
+  h->curve_ll_ms = 0;
+  CallBufs b;
+  double* d_x = nullptr;
+  HIPCHK(b.get(&d_x, (size_t)CS * (size_t)chunk));
+  return for_chunks(ck, len, chunk, [&](int64_t p0, int rows) {
+    std::string err = curve_ll_timed(ck, (int)p0, rows, d_x);
+    // post_psis_device runs on the device's default stream: the matrix must be complete before it starts
+    if (err.empty() && (hipStreamSynchronize(h->st) != hipSuccess || hipGetLastError() != hipSuccess)) err = "kernel failed";
+    if (!err.empty()) return err;
+    curve_ll_collect(h);
+    double* const outs[6] = {lppd + p0, elpd_loo + p0, p_loo + p0, pareto_k + p0, elpd_waic + p0, p_waic + p0};
+    if (post_psis_device(d_x, CS, rows, (int)CS, outs)) err = bfmmm_entry_last_error();
+    return err;
+  });
+}
+
+// ---- pooled per-curve fitted functions of the chain slots and their bands (kernels_curve_fit.hip) ----------
+namespace bfmmm { int g_curve_fit_route = 0; }
+extern "C" void bfmmm_set_curve_fit_route(int route) { bfmmm::g_curve_fit_route = route == 1 ? 1 : 0; }
+
+// The values themselves on the host, in chunks of consecutive result rows.
+extern "C" int bfmmm_chain_curve_fit(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves,
+                                     int first_slot, int n_slots, double* out, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_curve_fit", h, first_slot, n_slots};
+  FitSetup s;
+  if (ck.ptrs({{"h", h}, {"out", out}}) || fit_check_args(ck, which, E, G, curves, n_curves, s)) return 1;
+  const int64_t per_curve = (int64_t)G * s.CS;
+  if (ck.capacity(capacity, (int64_t)s.m * per_curve)) return 1;
+  HIPCHK(hipSetDevice(h->device));
+  CallBufs b;
+  if (fit_prepare(ck, E, curves, s, b)) return 1;
+  int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (sizeof(double) * (size_t)per_curve)));
+  chunk = std::min<int64_t>(std::min<int64_t>(chunk, s.m), std::max<int64_t>(1, (1LL << 30) / G));
+  double* d_v = nullptr;
+  HIPCHK(b.get(&d_v, (size_t)chunk * per_curve));
+  return for_chunks(ck, s.m, chunk, [&](int64_t r0, int rows) {
+    (void)hipEventRecord(b.ev[2], h->st);
+    std::string err = launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st);
+    (void)hipEventRecord(b.ev[3], h->st);
+    if (err.empty() && copy_sync(h, out + (size_t)r0 * per_curve, d_v, sizeof(double) * (size_t)rows * per_curve, hipMemcpyDeviceToHost) != hipSuccess)
+      err = "kernel or copy back failed";
+    if (err.empty()) fit_collect(h, b, 2, 3, FIT_T_VALUES);
+    return err;
+  });
+}
+
+// Mean, sd and quantiles of every row; the values stay on the device (rows of up to 8192 draws: in LDS).
+extern "C" int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves,
+                                       int first_slot, int n_slots, const double* probs, int nq, int64_t max_workspace_bytes,
+                                       double* mean, double* sd, double* quantiles, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_curve_bands", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  FitSetup s;
+  if (ck.ptrs({{"h", h}, {"probs", probs}, {"mean", mean}, {"sd", sd}, {"quantiles", quantiles}}) ||
+      fit_check_args(ck, which, E, G, curves, n_curves, s))
+    return 1;
+  if (nq < 1 || nq > 16) return fail(fn + ": 'nq' outside 1 .. 16");
+  for (int q = 0; q < nq; ++q)
+    if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail(fn + ": 'probs'[" + std::to_string(q) + "] outside [0, 1]");
+  if (ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, (int64_t)s.m * G, "rows")) return 1;
+  const bool lds_rows = s.CS <= fit_lds_rows() && !g_curve_fit_route;
+  const bool sort_ws = s.CS > fit_lds_rows();               // k_bands_quantiles_big sorts in a workspace
+  const int NP = sort_ws ? bands_sort_pad((int)s.CS) : 0;
+  const size_t budget = budget_of(max_workspace_bytes);
+  const size_t shared = fit_shared_bytes(h, s);
+  const size_t per_curve = sizeof(double) * (size_t)G * ((size_t)(2 + nq) + (lds_rows ? 0 : (size_t)s.CS + (size_t)NP));
+  if (budget < shared + per_curve)
+    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
+                std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
+  int64_t chunk = std::min<int64_t>(s.m, (int64_t)((budget - shared) / per_curve));
+  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (1LL << 30) / G));
+  HIPCHK(hipSetDevice(h->device));
+  CallBufs b;
+  double *d_probs = nullptr, *d_out = nullptr, *d_v = nullptr, *d_w = nullptr;
+  HIPCHK(b.get(&d_probs, 16));
+  HIPCHK(b.get(&d_out, (size_t)chunk * G * (2 + nq)));
+  if (!lds_rows) HIPCHK(b.get(&d_v, (size_t)chunk * G * (size_t)s.CS));
+  if (sort_ws) HIPCHK(b.get(&d_w, (size_t)chunk * G * (size_t)NP));
+  HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
+  if (fit_prepare(ck, E, curves, s, b)) return 1;
+  double* d_mean = d_out;
+  double* d_sd = d_out + (size_t)chunk * G;
+  double* d_q = d_out + 2 * (size_t)chunk * G;
+  return for_chunks(ck, s.m, chunk, [&](int64_t r0, int rows) {
+    const long long ncol = (long long)rows * G;
+    std::string err;
+    (void)hipEventRecord(b.ev[2], h->st);
+    if (lds_rows) {
+      err = launch_fit_rows(h->c, s.f, (int)r0, rows, d_probs, nq, d_mean, d_sd, d_q, h->st);
+      (void)hipEventRecord(b.ev[3], h->st);
+    } else {
+      err = launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st);
+      (void)hipEventRecord(b.ev[3], h->st);
+      if (err.empty()) err = launch_bands_quantiles(d_v, (int)s.CS, ncol, d_w, d_probs, nq, d_q, h->st);
+      // the sorted rows are in the workspace: the rule again, rounded as k_fit_rows rounds it
+      if (err.empty() && sort_ws) err = launch_fit_quantiles(d_w, NP, (int)s.CS, ncol, d_probs, nq, d_q, h->st);
+      if (err.empty()) err = launch_bands_moments(d_v, (int)s.CS, ncol, d_mean, d_sd, h->st);
+    }
+    (void)hipEventRecord(b.ev[4], h->st);
+    if (err.empty() &&
+        (hipMemcpyAsync(mean + (size_t)r0 * G, d_mean, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+         hipMemcpyAsync(sd + (size_t)r0 * G, d_sd, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+         copy_sync(h, quantiles + (size_t)r0 * G * nq, d_q, sizeof(double) * (size_t)ncol * nq, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (!err.empty()) return err;
+    fit_collect(h, b, 2, 3, lds_rows ? FIT_T_ROWS : FIT_T_VALUES);
+    if (!lds_rows) fit_collect(h, b, 3, 4, FIT_T_REDUCE);
+    return err;
+  });
+}

@@ -1,0 +1,81 @@
+// What the host files share (bfmmm_capi.hip, the driver, and capi_chain.hip, the chain-slot post-processing): the handle,
+// the kernel-family ids of its timing tables, the HIP error check and three helpers the driver defines.
+#pragma once
+#include "../../include/bfmmm.h"
+#include "model.hpp"
+
+#include <cstdio>
+#include <string>
+#include <tuple>
+#include <vector>
+
+#define HIPCHK(x)                                                                                   \
+  do {                                                                                              \
+    hipError_t e_ = (x);                                                                            \
+    if (e_ != hipSuccess) {                                                                         \
+      (void)hipGetLastError(); /* (not sticky: a caller that retries with a smaller batch starts clean) */ \
+      char buf_[512];                                                                               \
+      snprintf(buf_, sizeof buf_, "HIP error %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__, __LINE__, #x); \
+      return bfmmm::fail(buf_);                                                                     \
+    }                                                                                               \
+  } while (0)
+
+enum { FAM_TOTAL = 0, FAM_Z, FAM_PG, FAM_FACTOR, FAM_SWEEP, FAM_CHI, FAM_LOGLIK, FAM_REDUCE, FAM_COUNT };
+
+struct bfmmm_handle {
+  bfmmm_config cfg;
+  int device = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t evA = nullptr;
+  bfmmm::Ctx c;                // template context (full MD); its per-chain pointers are those of chain 0 of the batch
+  int nch = 1;                 // chains in the batch (bfmmm_create_batch), all advanced in lockstep by bfmmm_run
+  int sel = 0;                 // the chain the state / chain accessors address (bfmmm_select_chain)
+  int T = 0;
+  int64_t n_obs = 0;
+  // raw inputs kept on the device for bfmmm_get_basis
+  double* d_t = nullptr; double* d_y = nullptr; int64_t* d_off = nullptr; double* d_knots = nullptr; int n_knots = 0;
+  std::vector<void*> allocs;
+  char* arena = nullptr;               // base of the per-chain arena (chain q at arena + q * c.chain_bytes)
+  char* arena_cov = nullptr;           // the same for the covariate buffers (c.chain_bytes_cov)
+  uint32_t* status_host = nullptr;     // pinned, host-mapped: the chains' status words after a run
+  uint32_t* status_dev = nullptr;      // its device address (written by the run's last kernel)
+  size_t pg_part_doubles = 0;
+  static constexpr int MAX_SUB = 4;
+  // snapshot of the chains' work state for the dry launch of freshly captured graphs (bfmmm_prepare_run)
+  char* dry_snap = nullptr;
+  size_t dry_snap_bytes = 0;
+  // packed partial tiles of k_pair_gram_pack, one buffer per sub-batch stream (+ one for the whole batch on one stream)
+  double* pg_pack[MAX_SUB + 1] = {};
+  size_t pg_pack_doubles[MAX_SUB + 1] = {};
+  hipStream_t sub_st[MAX_SUB] = {nullptr, nullptr, nullptr, nullptr};     // [0] = st
+  hipEvent_t sub_ev[MAX_SUB] = {nullptr, nullptr, nullptr, nullptr};
+  // Captured graphs of runs with the key below, oldest first: (sub-batch, kind, repetitions) -> graph (run_impl)
+  struct CachedGraph { int sub, kind, reps; hipGraphExec_t g; };
+  std::vector<CachedGraph> graphs;
+  using GraphKey = std::tuple<uint32_t, int, uint64_t, uint32_t, int, int>;      // (mask, MD, seed, chain, nsub, instance switches)
+  GraphKey g_key;
+  bool g_valid = false;                // the cached graphs were captured for g_key
+  int last_md = -1;
+  double last_route[6] = {0, 0, 0, -1, 0, 0};  // bfmmm_debug_get("pg_route"): {packed, KS, NKS, body, G, tail} of sub-batch 0 of the last run
+  int64_t tab_key = -1;                // (MD, mask) the step tables of k_sweep_chain were built for
+  int launch_error = 0;
+  int slot_base = 0;                   // chain slot of iteration i is i - slot_base (bfmmm_set_slot_base)
+  double* tt_save = nullptr;            // state saved across a tempered-transition block
+  std::vector<double> B_host;           // bfmmm_create_from_basis: the caller's basis rows (bfmmm_get_basis)
+  bool state_dirty = true;             // the state was changed from the host: proposals prepared on the device are stale
+  int profile = 0;
+  double fam_ms[FAM_COUNT] = {0};
+  int64_t fam_launches[FAM_COUNT] = {0};
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  double curve_ll_ms = 0;              // bfmmm_debug_get("curve_ll_ms"): device time of k_chain_curve_ll in the last call that ran it
+  double fit_ms[4] = {0};              // bfmmm_get_timing("curve_fit_project" / "_rows" / "_values" / "_reduce"; "curve_fit": their sum):
+  int64_t fit_launches[4] = {0};       // device time of the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands
+};
+
+namespace bfmmm {
+int fail(const std::string& msg);      // sets the calling thread's bfmmm_last_error text; returns 1
+// synchronous copy on the sampler's own stream
+hipError_t copy_sync(bfmmm_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+// the context of the selected chain (host view)
+Ctx selc(const bfmmm_handle* h);
+}

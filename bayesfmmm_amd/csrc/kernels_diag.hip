@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/bfmmm_post.h"
+#include "launchers.hpp"
 
 // The quantiles and the folded values decide ranks and indicators exactly; they must round as the restatement does.
 #pragma clang fp contract(off)

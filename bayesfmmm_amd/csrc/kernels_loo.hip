@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/bfmmm_post.h"
+#include "launchers.hpp"
 
 int bfmmm_io_fail(const std::string& m);      // entry_points.cpp: sets bfmmm_entry_last_error
 void bfmmm_post_set_kernel_ms(float ms);      // kernels_post.hip

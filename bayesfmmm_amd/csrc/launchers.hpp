@@ -1,9 +1,20 @@
-// Host interface of the kernel files to the driver (bfmmm_capi.hip): every launcher, geometry and prepare_* function the
-// driver calls.  Included by the driver and by every file that defines one of them, so that a declaration and its
-// definition cannot drift apart.
+// Host interface of the kernel files to the two host files (bfmmm_capi.hip, the driver, and capi_chain.hip): every launcher,
+// geometry and prepare_* function they call.  Included by both and by every file that defines one of them, so that a
+// declaration and its definition cannot drift apart.
 #pragma once
 #include "model.hpp"
 #include <string>
+
+// ---- kernels_diag.hip ----
+long long diag_row_max();                      // C S of the longest row
+size_t diag_row_ws_doubles(int C, int S);      // workspace doubles a row of the global tier needs (0 in the LDS tier)
+std::string diag_launch(const double* d_x, long long rows, int C, int S, double* d_out, long long ld_out, double* ws, long long ws_rows,
+                        hipStream_t st);
+std::string diag_gather(const double* base, size_t chain_bytes, long long ss, long long ps, int first, int S, int C, int p0, int P,
+                        double* ws, hipStream_t st);
+
+// ---- kernels_loo.hip ----
+int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]);
 
 namespace bfmmm {
 
