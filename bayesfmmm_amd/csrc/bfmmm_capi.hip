@@ -1174,6 +1174,7 @@ extern "C" int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, i
     for (int f = 0; f < FIT_T_COUNT; ++f) { *ms += h->fit_ms[f]; *launches += h->fit_launches[f]; }
     return 0;
   }
+  if (!strcmp(name, "similarity")) { *ms = h->sim_ms; *launches = h->sim_launches; return 0; }      // the last bfmmm_chain_similarity
   return fail("bfmmm_get_timing: unknown name");
 }
 

@@ -1,5 +1,6 @@
 // C ABI of the sampler (include/bfmmm.h), what is read off the chain slots after a run: the chain arrays, their convergence
-// diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands.
+// diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
+// the pooled co-membership matrix of the curves.
 // An entry point is its argument checks (SlotCheck), the sizing of its workspace (CallBufs owns it) and one for_chunks.
 #include "handle.hpp"
 #include "launchers.hpp"
@@ -406,6 +407,58 @@ extern "C" int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double*
     if (!err.empty()) return err;
     fit_collect(h, b, 2, 3, lds_rows ? FIT_T_ROWS : FIT_T_VALUES);
     if (!lds_rows) fit_collect(h, b, 3, 4, FIT_T_REDUCE);
+    return err;
+  });
+}
+
+// ---- pooled co-membership of curves from the chain slots (kernels_similarity.hip) -----------------------------
+extern "C" void bfmmm_set_similarity_block(int block) { bfmmm::g_similarity_block = block == 1 || block == 2 ? block : 0; }
+
+// Mean, sd and per-chain means of d_ij = sum_k Z_ik Z_jk over the draws, in chunks of consecutive result rows; only they
+// reach the host.
+extern "C" int bfmmm_chain_similarity(bfmmm_handle* h, const int32_t* curves, int n_curves, int first_slot, int n_slots,
+                                      int64_t max_workspace_bytes, double* mean, double* sd, double* chain_mean, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_similarity", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"h", h}, {"mean", mean}})) return 1;
+  const int n = h->c.d.n, C = h->nch;
+  if (n_curves < 0) return fail(fn + ": 'n_curves' must not be negative");
+  if (curves)
+    for (int j = 0; j < n_curves; ++j)
+      if (curves[j] < 0 || curves[j] >= n)
+        return fail(fn + ": 'curves'[" + std::to_string(j) + "] = " + std::to_string(curves[j]) + " outside 0 .. " + std::to_string(n - 1));
+  const int64_t m = curves ? n_curves : n;
+  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, m * n) || ck.row_limit()) return 1;
+  // a result row: its n entries of mean, of sd and of every chain's mean, and its curve index
+  const size_t per_row = sizeof(double) * (size_t)n * (1 + (sd ? 1 : 0) + (chain_mean ? (size_t)C : 0)) + (curves ? sizeof(int32_t) : 0);
+  if (ck.budget_row(budget_of(max_workspace_bytes), per_row)) return 1;
+  h->sim_ms = 0;
+  h->sim_launches = 0;
+  if (m == 0) return 0;
+  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(m, (int64_t)(budget_of(max_workspace_bytes) / per_row)), 1 << 30);
+  HIPCHK(hipSetDevice(h->device));
+  CallBufs b;
+  double *d_mean = nullptr, *d_sd = nullptr, *d_cm = nullptr;
+  int* d_curves = nullptr;
+  HIPCHK(hipEventCreate(&b.ev[0]));
+  HIPCHK(hipEventCreate(&b.ev[1]));
+  HIPCHK(b.get(&d_mean, (size_t)chunk * n));
+  if (sd) HIPCHK(b.get(&d_sd, (size_t)chunk * n));
+  if (chain_mean) HIPCHK(b.get(&d_cm, (size_t)chunk * C * n));
+  if (curves) HIPCHK(b.get(&d_curves, (size_t)chunk));
+  return for_chunks(ck, m, chunk, [&](int64_t r0, int rows) {
+    if (curves && copy_sync(h, d_curves, curves + r0, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess)
+      return std::string("copy of the curve list failed");
+    (void)hipEventRecord(b.ev[0], h->st);
+    std::string err = launch_similarity(h->c, first_slot, n_slots, d_curves, (int)r0, rows, d_mean, d_sd, d_cm, h->st);
+    (void)hipEventRecord(b.ev[1], h->st);
+    const size_t cnt = sizeof(double) * (size_t)rows * n;
+    if (err.empty() &&
+        ((sd && hipMemcpyAsync(sd + (size_t)r0 * n, d_sd, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         (chain_mean && hipMemcpyAsync(chain_mean + (size_t)r0 * C * n, d_cm, cnt * C, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         copy_sync(h, mean + (size_t)r0 * n, d_mean, cnt, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (err.empty()) add_elapsed(b.ev[0], b.ev[1], &h->sim_ms, &h->sim_launches);
     return err;
   });
 }

@@ -99,6 +99,14 @@ std::string launch_fit_values(const Ctx& c, const FitCall& f, int r0, int rows, 
 // the quantile rule read off ncol sorted rows W[col NP + .] of T values: quant[col nq + q]
 std::string launch_fit_quantiles(const double* W, int NP, int T, long long ncol, const double* probs, int nq, double* quant, hipStream_t st);
 
+// ---- kernels_similarity.hip ----
+// Pooled co-membership d_ij = sum_k Z_ik Z_jk of result rows [r0, r0 + rows) against all n curves over every chain and slots
+// [first_slot, first_slot + n_slots): mean[r n + j], sd[r n + j] (null: no second pass) and chain_mean[(r C + q) n + j] (null:
+// not written) of the chunk (r from 0, device).  curves: the chunk's curve list on the device, or null: row r is curve r0 + r.
+std::string launch_similarity(const Ctx& c, int first_slot, int n_slots, const int* curves, int r0, int rows, double* mean, double* sd,
+                              double* chain_mean, hipStream_t st);
+extern int g_similarity_block;      // bfmmm_set_similarity_block: 0 the launcher decides, 1 blocks of 64 x 64, 2 of 16 x 64
+
 // ---- kernels_bands.hip ----
 // The column reductions of the credible-band entry points on device tables V[t + T col], on stream st.  quantiles: LDS sort
 // for T <= 8192 (W unused), else k_bands_quantiles_big over the workspace W of NP ncol doubles, NP = bands_sort_pad(T), which

@@ -252,6 +252,29 @@ class Sampler:
                                                     int(max_workspace_bytes), _dp(mean), _dp(sd), _dp(qs), m * G))
         return {"mean": mean, "sd": sd, "quantiles": qs, "probs": pr}
 
+    def similarity(self, curves=None, sd=True, per_chain=False, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """The pooled co-membership matrix of the curves: mean (and sd) over chain slots [first_slot, first_slot + n_slots) of
+        every chain of the batch of d_ij = sum_k Z_ik Z_jk, the posterior similarity of curves i and j, computed on the device
+        (bfmmm_chain_similarity).  Label-invariant, so chains pool as they are.  curves: the rows wanted, indices
+        in any order (default: all n); columns are all curves.  per_chain: also each chain's own mean, which shows whether the
+        chains agree on the clustering where their labels differ.
+        Returns {"mean": (m, n), "sd": (m, n) if sd, "chain_mean": (m, C, n) if per_chain}."""
+        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
+        if curves is None:
+            idx, pc, m = None, None, self.n
+        else:
+            idx = np.ascontiguousarray(curves, dtype=np.int32).reshape(-1)
+            pc, m = idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size
+        out = {"mean": np.zeros((m, self.n))}
+        if sd:
+            out["sd"] = np.zeros((m, self.n))
+        if per_chain:
+            out["chain_mean"] = np.zeros((m, self.n_chains, self.n))
+        _lib.check(self.lib.bfmmm_chain_similarity(self.h, pc, m if curves is not None else 0, int(first_slot), S, int(max_workspace_bytes),
+                                                   _dp(out["mean"]), _dp(out["sd"]) if sd else None,
+                                                   _dp(out["chain_mean"]) if per_chain else None, m * self.n))
+        return out
+
     def get_basis(self):
         n_obs = int(self.offsets[-1])
         out = np.zeros((n_obs, self.P))

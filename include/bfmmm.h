@@ -228,6 +228,26 @@ int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double* E, int G, 
                             double* quantiles, int64_t capacity);
 void bfmmm_set_curve_fit_route(int route);
 
+/* Pooled co-membership of curves under chain slots [first_slot, first_slot + n_slots) of EVERY chain of the batch:
+ *   d_ij(q, t) = sum_k Z_ik(q, t) Z_jk(q, t)      (0 <= d <= 1; d_ii = sum_k Z_ik^2)
+ * the posterior similarity of two curves under a draw.  A sum over k: it does not depend on the components' labels, so the chains
+ * pool as they are.  curves: NULL for all n curves, or n_curves >= 0 indices in [0, n) in any order, repeats allowed; result row r
+ * is curve curves[r] (m rows), column j curve j (all n).  With N = C n_slots draws:
+ *   mean[r n + j]               the mean of d over the N draws; capacity >= m n entries.
+ *   sd[r n + j]                 the sample sd (N - 1; NaN for one draw), by a second pass over the draws.  NULL: not computed.
+ *   chain_mean[(r C + q) n + j] the mean over the slots of chain q alone.  NULL: not computed.
+ * Every sum has a fixed order (slots in order within a chain, then chains in order), so the result does not depend on the chunk
+ * or on repeated calls, and the full matrix is symmetric bit for bit.  Chunks of consecutive result rows keep everything the call
+ * allocates (the chunk's rows of the three results and its curve indices) within max_workspace_bytes (0: 256 MiB); a budget
+ * below one row is refused with the bytes needed.  At most 2^22 draws (n_chains x n_slots).  Runs on the sampler's stream and
+ * leaves its state and slots untouched.
+ * bfmmm_set_similarity_block: the kernel's workgroups own blocks of 64 x 64 entries where that makes enough of them and of
+ * 16 x 64 otherwise (0, the default); 1 / 2 make later calls use the first / second always (a measurement and test switch:
+ * the results are the same bits).  Process-wide. */
+int bfmmm_chain_similarity(bfmmm_handle* h, const int32_t* curves, int n_curves, int first_slot, int n_slots,
+                           int64_t max_workspace_bytes, double* mean, double* sd, double* chain_mean, int64_t capacity);
+void bfmmm_set_similarity_block(int block);
+
 /* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
  * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P), "theta" (K (M + 1) x P), "dims" (as doubles), "curve_ll_ms" (device
@@ -243,7 +263,8 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * enabled with bfmmm_set_profile (which disables graph replay).
  * names: "total", "curve_z", "pair_gram", "factor", "sweep", "curve_chi", "loglik".
  * Of the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands (always measured): "curve_fit" (the sum of the following),
- * "curve_fit_project", "curve_fit_rows", "curve_fit_values", "curve_fit_reduce" (quantiles and moments of the workspace route). */
+ * "curve_fit_project", "curve_fit_rows", "curve_fit_values", "curve_fit_reduce" (quantiles and moments of the workspace route).
+ * Of the last bfmmm_chain_similarity (always measured): "similarity", the device time and launches of its kernel. */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
