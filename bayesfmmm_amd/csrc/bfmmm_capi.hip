@@ -1116,7 +1116,8 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
   HIPCHK(hipStreamSynchronize(h->st));
   if (s == "dims") {
     const double v[] = {(double)d.n, (double)d.K, (double)d.P, (double)d.M, (double)d.BW, (double)d.LG, (double)d.LREC,
-                        (double)d.MD, (double)d.A, (double)d.R, (double)d.NT, (double)d.n_obs_total, (double)d.half_sum, c.YY};
+                        (double)d.MD, (double)d.A, (double)d.R, (double)d.NT, (double)d.n_obs_total, (double)d.half_sum, c.YY,
+                        (double)d.BWP};
     const int64_t cnt = sizeof v / sizeof v[0];
     if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
     memcpy(out, v, sizeof v);
@@ -1139,7 +1140,8 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
   struct Arr { const char* nm; const double* p; int64_t len; };
   const Arr arrs[] = {{"rec", c.rec, (int64_t)d.n * d.LREC}, {"H", c.H, (int64_t)d.R * d.LG}, {"tvec", c.tvec, (int64_t)d.A * d.P},
                       {"H2", c.H2, (int64_t)d.R * d.P * (2 * d.BW + 2)},
-                      {"Cmat", c.Cmat, (int64_t)d.A * d.P * d.P},
+                      {"Cmat", c.Cmat, (int64_t)d.A * d.P * d.P}, {"Lz", c.Lz, (int64_t)d.A * d.P},
+                      {"rvec", c.rvec, (int64_t)d.A * d.P}, {"hq", c.hq, (int64_t)d.A * d.P},      // (k_factor's; the sweep keeps its own copies)
                       {"theta", c.theta, (int64_t)d.K * (d.M + 1) * d.P}};
   for (const Arr& a : arrs)
     if (s == a.nm) {

@@ -292,6 +292,7 @@ class Sampler:
         names = ["n", "K", "P", "M", "BW", "LG", "LREC", "MD", "A", "R", "NT", "n_obs_total", "half_sum"]
         d = {k: int(x) for k, x in zip(names, v)}
         d["YY"] = float(v[13])
+        d["BWP"] = int(v[14])
         return d
 
     def set_profile(self, enable):

@@ -250,7 +250,10 @@ void bfmmm_set_similarity_block(int block);
 
 /* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
- * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P), "theta" (K (M + 1) x P), "dims" (as doubles), "curve_ll_ms" (device
+ * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P: C_a = Prec_a^-1 as k_factor left it), "Lz" (A x P: L_a z_a of the sampled directions),
+ * "rvec" and "hq" (A x P each: r_a = t_a - sum_b H_ab theta_b and H_aa theta_a at the start of the sweep, as k_factor wrote
+ * them -- the sweep updates copies of its own), "theta" (K (M + 1) x P), "dims" (as doubles; the last entry is BWP, the band
+ * half-width of the conditional precisions), "curve_ll_ms" (device
  * milliseconds of k_chain_curve_ll in the last bfmmm_chain_curve_loglik / bfmmm_chain_curve_diagnostics / bfmmm_chain_loo) and
  * "pg_route": how sub-batch 0 of the last bfmmm_run ran its pair-Gram contraction, {packed (0 / 1), KS, NKS,
  * body (0 general, 1 single-chain, 2 chain loop, 3 chain loop with staged groups; -1 packed), G (chains per group; 0 packed),
