@@ -1177,6 +1177,8 @@ extern "C" int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, i
     return 0;
   }
   if (!strcmp(name, "similarity")) { *ms = h->sim_ms; *launches = h->sim_launches; return 0; }      // the last bfmmm_chain_similarity
+  if (!strcmp(name, "curve_cov_project")) { *ms = h->cov_ms[0]; *launches = h->cov_launches[0]; return 0; }      // the last bfmmm_chain_curve_cov
+  if (!strcmp(name, "curve_cov")) { *ms = h->cov_ms[1]; *launches = h->cov_launches[1]; return 0; }
   return fail("bfmmm_get_timing: unknown name");
 }
 

@@ -1,6 +1,6 @@
 // C ABI of the sampler (include/bfmmm.h), what is read off the chain slots after a run: the chain arrays, their convergence
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
-// the pooled co-membership matrix of the curves.
+// the pooled co-membership matrix of the curves, the pooled per-curve covariance surfaces.
 // An entry point is its argument checks (SlotCheck), the sizing of its workspace (CallBufs owns it) and one for_chunks.
 #include "handle.hpp"
 #include "launchers.hpp"
@@ -459,6 +459,88 @@ extern "C" int bfmmm_chain_similarity(bfmmm_handle* h, const int32_t* curves, in
          copy_sync(h, mean + (size_t)r0 * n, d_mean, cnt, hipMemcpyDeviceToHost) != hipSuccess))
       err = "kernel or copy back failed";
     if (err.empty()) add_elapsed(b.ev[0], b.ev[1], &h->sim_ms, &h->sim_launches);
+    return err;
+  });
+}
+
+// ---- pooled per-curve covariance surfaces from the chain slots (kernels_curve_cov.hip) ------------------------
+// Mean, sd and per-chain means of C_i(g, h) = sum_m (E1_g . V_im)(E2_h . V_im) over the draws, in chunks of consecutive result
+// rows; the projection tables are filled once per call and only the three results reach the host.
+extern "C" int bfmmm_chain_curve_cov(bfmmm_handle* h, const double* E1, int G1, const double* E2, int G2, int diagonal,
+                                     const int32_t* curves, int n_curves, int first_slot, int n_slots, int64_t max_workspace_bytes,
+                                     double* mean, double* sd, double* chain_mean, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_curve_cov", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"h", h}, {"E1", E1}, {"mean", mean}})) return 1;
+  if (G1 < 1) return fail(fn + ": 'G1' must be at least 1");
+  if (E2 && G2 < 1) return fail(fn + ": 'G2' must be at least 1 where 'E2' is given");
+  if (diagonal && E2) return fail(fn + ": 'diagonal' requires 'E2' to be null");
+  const int n = h->c.d.n, C = h->nch, P = h->c.d.P;
+  if (!E2) G2 = G1;
+  if (n_curves < 0) return fail(fn + ": 'n_curves' must not be negative");
+  if (curves)
+    for (int j = 0; j < n_curves; ++j)
+      if (curves[j] < 0 || curves[j] >= n)
+        return fail(fn + ": 'curves'[" + std::to_string(j) + "] = " + std::to_string(curves[j]) + " outside 0 .. " + std::to_string(n - 1));
+  const int64_t m = curves ? n_curves : n;
+  const int64_t cells = diagonal ? (int64_t)G1 : (int64_t)G1 * G2;      // entries of a curve's result
+  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, m * cells) || ck.row_limit()) return 1;
+  CovCall f;
+  f.G1 = G1; f.G2 = G2; f.diagonal = diagonal ? 1 : 0; f.first_slot = first_slot; f.n_slots = n_slots;
+  const std::string bad = cov_check(h->c, f);
+  if (!bad.empty()) return fail(fn + ": " + bad);
+  // shared by all curves: the tables, E1, E2 and the curve list; a curve: its entries of mean, of sd and of every chain's mean
+  const size_t tab1 = cov_table_doubles(h->c, f, 0), tab2 = E2 ? cov_table_doubles(h->c, f, 1) : 0;
+  const size_t shared = sizeof(double) * (tab1 + tab2 + (size_t)G1 * P + (E2 ? (size_t)G2 * P : 0)) +
+                        (curves ? sizeof(int32_t) * (((size_t)m + 1) & ~(size_t)1) : 0);
+  const size_t per_curve = sizeof(double) * (size_t)cells * (1 + (sd ? 1 : 0) + (chain_mean ? (size_t)C : 0));
+  const size_t budget = budget_of(max_workspace_bytes);
+  if (budget < shared + per_curve)
+    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
+                std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
+  for (int q = 0; q < 2; ++q) { h->cov_ms[q] = 0; h->cov_launches[q] = 0; }
+  if (m == 0) return 0;
+  int64_t chunk = std::min<int64_t>(m, (int64_t)((budget - shared) / per_curve));
+  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (1LL << 30) / cells));
+  HIPCHK(hipSetDevice(h->device));
+  CallBufs b;
+  double *d_E1 = nullptr, *d_E2 = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_cm = nullptr;
+  int* d_curves = nullptr;
+  for (int e = 0; e < 4; ++e) HIPCHK(hipEventCreate(&b.ev[e]));
+  HIPCHK(b.get(&d_E1, (size_t)G1 * P));
+  HIPCHK(b.get(&f.tab1, tab1));
+  HIPCHK(copy_sync(h, d_E1, E1, sizeof(double) * (size_t)G1 * P, hipMemcpyHostToDevice));
+  if (E2) {
+    HIPCHK(b.get(&d_E2, (size_t)G2 * P));
+    HIPCHK(b.get(&f.tab2, tab2));
+    HIPCHK(copy_sync(h, d_E2, E2, sizeof(double) * (size_t)G2 * P, hipMemcpyHostToDevice));
+  }
+  if (curves) {
+    HIPCHK(b.get(&d_curves, (size_t)m));
+    HIPCHK(copy_sync(h, d_curves, curves, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice));
+  }
+  HIPCHK(b.get(&d_mean, (size_t)chunk * cells));
+  if (sd) HIPCHK(b.get(&d_sd, (size_t)chunk * cells));
+  if (chain_mean) HIPCHK(b.get(&d_cm, (size_t)chunk * C * cells));
+  f.E1 = d_E1; f.E2 = d_E2; f.curves = d_curves;
+  (void)hipEventRecord(b.ev[0], h->st);
+  const std::string perr = launch_cov_project(h->c, f, h->st);
+  (void)hipEventRecord(b.ev[1], h->st);
+  if (!perr.empty()) { (void)hipStreamSynchronize(h->st); return fail(fn + ": " + perr); }
+  HIPCHK(hipStreamSynchronize(h->st));
+  add_elapsed(b.ev[0], b.ev[1], &h->cov_ms[0]);
+  h->cov_launches[0] = E2 ? 2 : 1;
+  return for_chunks(ck, m, chunk, [&](int64_t r0, int rows) {
+    (void)hipEventRecord(b.ev[2], h->st);
+    std::string err = launch_curve_cov(h->c, f, (int)r0, rows, d_mean, d_sd, d_cm, h->st);
+    (void)hipEventRecord(b.ev[3], h->st);
+    const size_t cnt = sizeof(double) * (size_t)rows * cells;
+    if (err.empty() &&
+        ((sd && hipMemcpyAsync(sd + (size_t)r0 * cells, d_sd, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         (chain_mean && hipMemcpyAsync(chain_mean + (size_t)r0 * C * cells, d_cm, cnt * C, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         copy_sync(h, mean + (size_t)r0 * cells, d_mean, cnt, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (err.empty()) add_elapsed(b.ev[2], b.ev[3], &h->cov_ms[1], &h->cov_launches[1]);
     return err;
   });
 }

@@ -72,6 +72,8 @@ struct bfmmm_handle {
   int64_t fit_launches[4] = {0};       // device time of the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands
   double sim_ms = 0;                   // bfmmm_get_timing("similarity"): device time and launches of k_similarity in the last
   int64_t sim_launches = 0;            // bfmmm_chain_similarity
+  double cov_ms[2] = {0};              // bfmmm_get_timing("curve_cov_project" / "curve_cov"): device time and launches of k_cov_project /
+  int64_t cov_launches[2] = {0};       // k_curve_cov in the last bfmmm_chain_curve_cov
 };
 
 namespace bfmmm {

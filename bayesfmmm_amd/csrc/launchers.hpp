@@ -107,6 +107,23 @@ std::string launch_similarity(const Ctx& c, int first_slot, int n_slots, const i
                               double* chain_mean, hipStream_t st);
 extern int g_similarity_block;      // bfmmm_set_similarity_block: 0 the launcher decides, 1 blocks of 64 x 64, 2 of 16 x 64
 
+// ---- kernels_curve_cov.hip ----
+// One call of bfmmm_chain_curve_cov: the evaluation bases E1 (G1 x P) and E2 (G2 x P; null: E2 = E1, G2 = G1), whether only the
+// diagonal g = h is wanted (E2 null), the curve of every result row of the call (null: curve r), the slot range and the call's
+// projection tables of cov_table_doubles(.., 0 / 1) doubles (tab2 null where E2 is; all device).
+struct CovCall {
+  int G1 = 0, G2 = 0, diagonal = 0, first_slot = 0, n_slots = 0;
+  const double *E1 = nullptr, *E2 = nullptr;
+  const int* curves = nullptr;
+  double *tab1 = nullptr, *tab2 = nullptr;
+};
+std::string cov_check(const Ctx& c, const CovCall& f);
+size_t cov_table_doubles(const Ctx& c, const CovCall& f, int which);
+std::string launch_cov_project(const Ctx& c, const CovCall& f, hipStream_t st);
+// result rows [r0, r0 + rows) of the call: mean / sd [(r G1 + g) G2 + h] and chain_mean [((r C + q) G1 + g) G2 + h] of the chunk
+// (r from 0; diagonal: [r G1 + g], [(r C + q) G1 + g]); sd, chain_mean may be null
+std::string launch_curve_cov(const Ctx& c, const CovCall& f, int r0, int rows, double* mean, double* sd, double* chain_mean, hipStream_t st);
+
 // ---- kernels_bands.hip ----
 // The column reductions of the credible-band entry points on device tables V[t + T col], on stream st.  quantiles: LDS sort
 // for T <= 8192 (W unused), else k_bands_quantiles_big over the workspace W of NP ncol doubles, NP = bands_sort_pad(T), which

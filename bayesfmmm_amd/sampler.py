@@ -275,6 +275,42 @@ class Sampler:
                                                    _dp(out["chain_mean"]) if per_chain else None, m * self.n))
         return out
 
+    def curve_cov(self, E, E2=None, curves=None, sd=True, per_chain=False, diagonal=False, first_slot=0, n_slots=None,
+                  max_workspace_bytes=0):
+        """The pooled covariance surface of every curve: mean (and sd) over chain slots [first_slot, first_slot + n_slots) of
+        every chain of the batch of C_i(g, h) = sum_m (E_g . V_im)(E2_h . V_im), the covariance function of curve i under a draw,
+        computed on the device (bfmmm_chain_curve_cov).  Label- and sign-invariant, so chains pool as they are.
+        E (G1 x P) and E2 (G2 x P; default: E) are rows in the sampler's basis, as in `curve_fit`.  curves: indices in any order
+        (default: all n).  diagonal: only g = h, the curve's variance function (E2 must be None).  per_chain: also each chain's
+        own mean.  Returns {"mean": (m, G1, G2), "sd": (m, G1, G2) if sd, "chain_mean": (m, C, G1, G2) if per_chain}; with
+        diagonal the shapes are (m, G1) and (m, C, G1)."""
+        def basis(B, name):
+            Bm = np.ascontiguousarray(B, dtype=np.float64)
+            if Bm.ndim != 2 or Bm.shape[1] != self.P:
+                raise ValueError(f"{name} must be a G x {self.P} matrix in the sampler's basis")
+            return Bm
+        E1m = basis(E, "E")
+        E2m = None if E2 is None else basis(E2, "E2")
+        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
+        if curves is None:
+            idx, pc, m = None, None, self.n
+        else:
+            idx = np.ascontiguousarray(curves, dtype=np.int32).reshape(-1)
+            pc, m = idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size
+        G1 = E1m.shape[0]
+        G2 = G1 if E2m is None else E2m.shape[0]
+        cell = (G1,) if diagonal else (G1, G2)
+        out = {"mean": np.zeros((m,) + cell)}
+        if sd:
+            out["sd"] = np.zeros((m,) + cell)
+        if per_chain:
+            out["chain_mean"] = np.zeros((m, self.n_chains) + cell)
+        _lib.check(self.lib.bfmmm_chain_curve_cov(self.h, _dp(E1m), G1, None if E2m is None else _dp(E2m), G2, int(bool(diagonal)), pc,
+                                                  m if curves is not None else 0, int(first_slot), S, int(max_workspace_bytes),
+                                                  _dp(out["mean"]), _dp(out["sd"]) if sd else None,
+                                                  _dp(out["chain_mean"]) if per_chain else None, out["mean"].size))
+        return out
+
     def get_basis(self):
         n_obs = int(self.offsets[-1])
         out = np.zeros((n_obs, self.P))

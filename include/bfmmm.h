@@ -248,6 +248,30 @@ int bfmmm_chain_similarity(bfmmm_handle* h, const int32_t* curves, int n_curves,
                            int64_t max_workspace_bytes, double* mean, double* sd, double* chain_mean, int64_t capacity);
 void bfmmm_set_similarity_block(int block);
 
+/* Pooled per-curve covariance surfaces under chain slots [first_slot, first_slot + n_slots) of EVERY chain of the batch, on the
+ * rows of two evaluation bases E1 (G1 x P) and E2 (G2 x P), row-major in the sampler's basis.  With the scores
+ * chi_im ~ N(0, 1), the covariance function of curve i under a draw is
+ *   C_i(g, h) = sum_m (E1_g . V_im)(E2_h . V_im),   V_im = sum_k Z_ik (phi_km + sum_d x_id xi_kmd)   (xi: covariance-adjusted)
+ *             = sum_k sum_k' Z_ik Z_ik' C^(k,k')(g, h)
+ * a sum over k and k' of products of two factors that change sign together: it depends neither on the components' labels nor on
+ * the signs of the eigenfunctions, so the chains pool as they are.  The second moment that goes with which = 0 of
+ * bfmmm_chain_curve_bands.  E2 NULL: E2 = E1 and G2 = G1 (the argument G2 is ignored).  curves: NULL for all n curves, or
+ * n_curves >= 0 indices in [0, n) in any order, repeats allowed; result row r is curve curves[r] (m rows).  With N = C n_slots draws:
+ *   mean[(r G1 + g) G2 + h]                the mean of C_i(g, h) over the N draws; capacity >= m G1 G2 entries.
+ *   sd[(r G1 + g) G2 + h]                  the sample sd (N - 1; NaN for one draw), by a second pass over the draws.  NULL: not computed.
+ *   chain_mean[((r C + q) G1 + g) G2 + h]  the mean over the slots of chain q alone.  NULL: not computed.
+ * diagonal != 0 (E2 must be NULL): only the entries g = h, the curve's variance function, at mean[r G1 + g], sd[r G1 + g] and
+ * chain_mean[(r C + q) G1 + g], capacity >= m G1; they are the diagonal of the surface bit for bit.
+ * Every sum has a fixed order (slots in order within a chain, then chains in order), so the result does not depend on the chunk
+ * or on repeated calls, a selected row is the full result's row, and with E2 NULL the surface is symmetric, all bit for bit.
+ * Chunks of consecutive result rows keep everything the call allocates (the projection tables, E1, E2, the curve list and the
+ * chunk's rows of the three results) within max_workspace_bytes (0: 256 MiB); a budget below what is shared plus one curve is
+ * refused with the bytes needed.  At most 2^22 draws (n_chains x n_slots).  Runs on the sampler's stream and leaves its state and
+ * slots untouched. */
+int bfmmm_chain_curve_cov(bfmmm_handle* h, const double* E1, int G1, const double* E2, int G2, int diagonal, const int32_t* curves,
+                          int n_curves, int first_slot, int n_slots, int64_t max_workspace_bytes, double* mean, double* sd,
+                          double* chain_mean, int64_t capacity);
+
 /* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
  * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P: C_a = Prec_a^-1 as k_factor left it), "Lz" (A x P: L_a z_a of the sampled directions),
@@ -267,7 +291,9 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * names: "total", "curve_z", "pair_gram", "factor", "sweep", "curve_chi", "loglik".
  * Of the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands (always measured): "curve_fit" (the sum of the following),
  * "curve_fit_project", "curve_fit_rows", "curve_fit_values", "curve_fit_reduce" (quantiles and moments of the workspace route).
- * Of the last bfmmm_chain_similarity (always measured): "similarity", the device time and launches of its kernel. */
+ * Of the last bfmmm_chain_similarity (always measured): "similarity", the device time and launches of its kernel.
+ * Of the last bfmmm_chain_curve_cov (always measured): "curve_cov", the device time and launches (one per chunk) of k_curve_cov,
+ * and "curve_cov_project", those of the projection that precedes them. */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
