@@ -63,6 +63,8 @@ SYMBOLS = {
                                         c_double_p, C.c_int64]),
     "bfmmm_chain_curve_bands": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
                                           c_double_p, C.c_int, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int64]),
+    "bfmmm_chain_curve_bands_sim": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
+                                              C.c_double, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int64]),
     "bfmmm_set_curve_fit_route": (None, [C.c_int]),
     "bfmmm_chain_similarity": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int64, c_double_p, c_double_p,
                                          c_double_p, C.c_int64]),

@@ -1176,6 +1176,8 @@ extern "C" int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, i
     for (int f = 0; f < FIT_T_COUNT; ++f) { *ms += h->fit_ms[f]; *launches += h->fit_launches[f]; }
     return 0;
   }
+  if (!strcmp(name, "curve_sim")) { *ms = h->band_sim_ms[0]; *launches = h->band_sim_launches[0]; return 0; }      // the last bfmmm_chain_curve_bands_sim
+  if (!strcmp(name, "curve_sim_reduce")) { *ms = h->band_sim_ms[1]; *launches = h->band_sim_launches[1]; return 0; }
   if (!strcmp(name, "similarity")) { *ms = h->sim_ms; *launches = h->sim_launches; return 0; }      // the last bfmmm_chain_similarity
   if (!strcmp(name, "curve_cov_project")) { *ms = h->cov_ms[0]; *launches = h->cov_launches[0]; return 0; }      // the last bfmmm_chain_curve_cov
   if (!strcmp(name, "curve_cov")) { *ms = h->cov_ms[1]; *launches = h->cov_launches[1]; return 0; }

@@ -1,6 +1,6 @@
 // C ABI of the sampler (include/bfmmm.h), what is read off the chain slots after a run: the chain arrays, their convergence
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
-// the pooled co-membership matrix of the curves, the pooled per-curve covariance surfaces.
+// their simultaneous bands, the pooled co-membership matrix of the curves, the pooled per-curve covariance surfaces.
 // An entry point is its argument checks (SlotCheck), the sizing of its workspace (CallBufs owns it) and one for_chunks.
 #include "handle.hpp"
 #include "launchers.hpp"
@@ -71,7 +71,7 @@ size_t budget_of(int64_t max_workspace_bytes) { return max_workspace_bytes ? (si
 // The device buffers and events of one call: released when the call returns, whichever way.
 struct CallBufs {
   std::vector<void*> p;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // curve fit: project start / end, chunk start / middle / end
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // curve fit: project start / end, chunk start / middle / end (/ after the band ends)
   ~CallBufs() {
     for (void* q : p) (void)hipFree(q);
     for (hipEvent_t e : ev)
@@ -407,6 +407,77 @@ extern "C" int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double*
     if (!err.empty()) return err;
     fit_collect(h, b, 2, 3, lds_rows ? FIT_T_ROWS : FIT_T_VALUES);
     if (!lds_rows) fit_collect(h, b, 3, 4, FIT_T_REDUCE);
+    return err;
+  });
+}
+
+// Simultaneous band of every result row: mean, sd, crit = the (1 - alpha) quantile over the draws of the largest
+// standardised deviation over the grid, lower / upper = mean -/+ crit sd.  No value is stored: k_fit_sim forms them three times.
+extern "C" int bfmmm_chain_curve_bands_sim(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves,
+                                           int first_slot, int n_slots, double alpha, int64_t max_workspace_bytes,
+                                           double* mean, double* sd, double* crit, double* lower, double* upper, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_curve_bands_sim", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  FitSetup s;
+  if (ck.ptrs({{"h", h}, {"crit", crit}, {"lower", lower}, {"upper", upper}}) || fit_check_args(ck, which, E, G, curves, n_curves, s)) return 1;
+  if (!(alpha > 0.0 && alpha < 1.0)) return fail(fn + ": 'alpha' must be inside (0, 1)");
+  if (ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, (int64_t)s.m * G, "rows")) return 1;
+  if (G > fit_sim_gmax())
+    return fail(fn + ": 'G' above " + std::to_string(fit_sim_gmax()) + ": mean and sd of a curve's grid points stay in LDS beside its sort row");
+  const bool sort_ws = s.CS > fit_lds_rows();               // C goes to a workspace row that k_bands_quantiles_big sorts
+  const int NP = sort_ws ? bands_sort_pad((int)s.CS) : 0;
+  const size_t budget = budget_of(max_workspace_bytes);
+  const size_t shared = fit_shared_bytes(h, s);
+  const size_t per_curve = sizeof(double) * (4 * (size_t)G + 1 + (sort_ws ? (size_t)s.CS + (size_t)NP : 0));
+  if (budget < shared + per_curve)
+    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
+                std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
+  int64_t chunk = std::min<int64_t>(s.m, (int64_t)((budget - shared) / per_curve));
+  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (1LL << 30) / G));
+  HIPCHK(hipSetDevice(h->device));
+  CallBufs b;
+  double *d_p = nullptr, *d_out = nullptr, *d_crit = nullptr, *d_c = nullptr, *d_w = nullptr;
+  const double p = 1.0 - alpha;
+  HIPCHK(b.get(&d_p, 16));
+  HIPCHK(b.get(&d_out, 4 * (size_t)chunk * G));
+  HIPCHK(b.get(&d_crit, (size_t)chunk));
+  if (sort_ws) {
+    HIPCHK(b.get(&d_c, (size_t)chunk * (size_t)s.CS));
+    HIPCHK(b.get(&d_w, (size_t)chunk * (size_t)NP));
+  }
+  HIPCHK(copy_sync(h, d_p, &p, sizeof(double), hipMemcpyHostToDevice));
+  for (int q = 0; q < 2; ++q) { h->band_sim_ms[q] = 0; h->band_sim_launches[q] = 0; }
+  if (fit_prepare(ck, E, curves, s, b)) return 1;
+  double* d_mean = d_out;
+  double* d_sd = d_out + (size_t)chunk * G;
+  double* d_lo = d_out + 2 * (size_t)chunk * G;
+  double* d_up = d_out + 3 * (size_t)chunk * G;
+  return for_chunks(ck, s.m, chunk, [&](int64_t r0, int rows) {
+    const size_t cnt = sizeof(double) * (size_t)rows * G;
+    (void)hipEventRecord(b.ev[2], h->st);
+    std::string err = launch_fit_sim(h->c, s.f, (int)r0, rows, p, d_mean, d_sd, d_crit, d_lo, d_up, d_c, h->st);
+    (void)hipEventRecord(b.ev[3], h->st);
+    if (sort_ws) {
+      if (err.empty()) err = launch_bands_quantiles(d_c, (int)s.CS, rows, d_w, d_p, 1, d_crit, h->st);
+      // the sorted rows are in the workspace: the rule again, rounded as k_fit_sim rounds it
+      if (err.empty()) err = launch_fit_quantiles(d_w, NP, (int)s.CS, rows, d_p, 1, d_crit, h->st);
+      (void)hipEventRecord(b.ev[4], h->st);
+      if (err.empty()) err = launch_fit_sim_band(d_mean, d_sd, d_crit, G, rows, d_lo, d_up, h->st);
+      (void)hipEventRecord(b.ev[5], h->st);
+    }
+    if (err.empty() &&
+        ((mean && hipMemcpyAsync(mean + (size_t)r0 * G, d_mean, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         (sd && hipMemcpyAsync(sd + (size_t)r0 * G, d_sd, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         hipMemcpyAsync(lower + (size_t)r0 * G, d_lo, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+         hipMemcpyAsync(upper + (size_t)r0 * G, d_up, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+         copy_sync(h, crit + r0, d_crit, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (!err.empty()) return err;
+    add_elapsed(b.ev[2], b.ev[3], &h->band_sim_ms[0], &h->band_sim_launches[0]);
+    if (sort_ws) {
+      add_elapsed(b.ev[3], b.ev[4], &h->band_sim_ms[1], &h->band_sim_launches[1]);
+      add_elapsed(b.ev[4], b.ev[5], &h->band_sim_ms[0], &h->band_sim_launches[0]);
+    }
     return err;
   });
 }

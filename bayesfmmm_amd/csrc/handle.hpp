@@ -70,6 +70,8 @@ struct bfmmm_handle {
   double curve_ll_ms = 0;              // bfmmm_debug_get("curve_ll_ms"): device time of k_chain_curve_ll in the last call that ran it
   double fit_ms[4] = {0};              // bfmmm_get_timing("curve_fit_project" / "_rows" / "_values" / "_reduce"; "curve_fit": their sum):
   int64_t fit_launches[4] = {0};       // device time of the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands
+  double band_sim_ms[2] = {0};         // bfmmm_get_timing("curve_sim" / "curve_sim_reduce"): device time and launches of k_fit_sim (and
+  int64_t band_sim_launches[2] = {0};  // k_fit_sim_band) / of the long-row sort in the last bfmmm_chain_curve_bands_sim
   double sim_ms = 0;                   // bfmmm_get_timing("similarity"): device time and launches of k_similarity in the last
   int64_t sim_launches = 0;            // bfmmm_chain_similarity
   double cov_ms[2] = {0};              // bfmmm_get_timing("curve_cov_project" / "curve_cov"): device time and launches of k_cov_project /

@@ -18,6 +18,12 @@
 //                   k_bands_moments reduce them) and the host copy of bfmmm_chain_curve_fit.
 //   k_fit_quantiles the rule read off rows that are already sorted (k_bands_quantiles_big leaves them so in its workspace):
 //                   kernels_bands.hip is compiled with contraction on, this file is not, and both tiers must round alike.
+//   k_fit_sim       simultaneous band of a curve: one workgroup owns one result row and never stores a value.
+//                   Three passes form every value again with the same fit_value: per-lane sums of tiles of FIT_SIM_GT grid
+//                   points in registers and k_fit_rows' tree -> mean(g) in LDS; the squares likewise -> sd(g); then per draw
+//                   C(cs) = max_g |(v - mean(g)) / sd(g)| over the grid points with sd != 0.  C S <= 8192: C is sorted in LDS
+//                   and crit, lower, upper leave; longer rows: C goes to a workspace row that k_bands_quantiles_big sorts,
+//                   k_fit_quantiles reads crit off it and k_fit_sim_band writes the band ends.
 // Quantile rule (k_bands_quantiles', Hyndman and Fan definition 5): sorted s[0 .. N-1], p < 0.5 / N -> s[0],
 // p > (N - 0.5) / N -> s[N-1], else k = floor(N p + 0.5), w = (p - (k - 0.5) / N) N, (1 - w) s[k-1] + w s[min(k, N-1)].
 // fp64, every sum in a fixed order that depends on (curve, grid point, chain, slot) only, no atomics, no scratch: the bits
@@ -116,27 +122,33 @@ __device__ __forceinline__ double fit_value(const double* __restrict__ tg, size_
   return v;
 }
 
+// Z_i. and chi_i. of draw cs (chi: fit only), zero beyond K and M
+template <int WHICH>
+__device__ __forceinline__ void fit_draw(const FitArgs& a, int i, int cs, double (&z)[KMAX], double (&ch)[FIT_MMAX]) {
+  const int K = a.K, M = a.M, n = a.n;
+  const int q = cs / a.S;
+  const size_t t = (size_t)(a.first_slot + cs - q * a.S);
+  const double* zq = ptr_shift(a.c_Z, (size_t)q * a.chain_bytes) + t * n * K + i;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) z[k] = k < K ? zq[(size_t)n * k] : 0.0;
+  if (WHICH) {
+    const double* cq = ptr_shift(a.c_chi, (size_t)q * a.chain_bytes) + t * n * M + i;
+#pragma unroll
+    for (int m = 0; m < FIT_MMAX; ++m) ch[m] = m < M ? cq[(size_t)n * m] : 0.0;
+  } else {
+#pragma unroll
+    for (int m = 0; m < FIT_MMAX; ++m) ch[m] = 0.0;
+  }
+}
+
 // every draw's value of grid points [g0, g0 + gn) of curve i, lane cs: Z_i. and chi_i. of a draw are read once
 template <int WHICH, typename Sink>
 __device__ __forceinline__ void fit_form(const FitArgs& a, int i, int g0, int gn, const double* sx, int tid, Sink sink) {
-  const int K = a.K, M = a.M, n = a.n;
   for (int cs = tid; cs < a.CS; cs += FIT_NT) {
-    const int q = cs / a.S;
-    const size_t t = (size_t)(a.first_slot + cs - q * a.S);
-    const double* zq = ptr_shift(a.c_Z, (size_t)q * a.chain_bytes) + t * n * K + i;
     double z[KMAX], ch[FIT_MMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) z[k] = k < K ? zq[(size_t)n * k] : 0.0;
-    if (WHICH) {
-      const double* cq = ptr_shift(a.c_chi, (size_t)q * a.chain_bytes) + t * n * M + i;
-#pragma unroll
-      for (int m = 0; m < FIT_MMAX; ++m) ch[m] = m < M ? cq[(size_t)n * m] : 0.0;
-    } else {
-#pragma unroll
-      for (int m = 0; m < FIT_MMAX; ++m) ch[m] = 0.0;
-    }
+    fit_draw<WHICH>(a, i, cs, z, ch);
     for (int gl = 0; gl < gn; ++gl)
-      sink(gl, cs, fit_value<WHICH>(a.tab + (size_t)(g0 + gl) * a.NJ * a.CS + cs, (size_t)a.CS, z, ch, sx, K, M, a.D, a.cadj));
+      sink(gl, cs, fit_value<WHICH>(a.tab + (size_t)(g0 + gl) * a.NJ * a.CS + cs, (size_t)a.CS, z, ch, sx, a.K, a.M, a.D, a.cadj));
   }
 }
 
@@ -147,6 +159,22 @@ __device__ inline double fit_quantile(const double* s, int T, double p) {
   const int k = (int)floor(N * p + 0.5);
   const double pk = ((double)k - 0.5) / N, w = (p - pk) * N;
   return (1.0 - w) * s[k - 1] + w * s[min(k, T - 1)];
+}
+
+// one bitonic network over `rows` rows of NP (a power of two) in LDS at once: pair pr of a step exchanges e and e | jj inside its row
+__device__ __forceinline__ void fit_sort(double* s, int rows, int NP, int tid) {
+  const int half = rows * NP / 2;
+  for (int k = 2; k <= NP; k <<= 1)
+    for (int jj = k >> 1; jj > 0; jj >>= 1) {
+      __syncthreads();
+      for (int pr = tid; pr < half; pr += FIT_NT) {
+        const int e = ((pr & ~(jj - 1)) << 1) | (pr & (jj - 1)), partner = e | jj;
+        const bool up = ((e & (NP - 1)) & k) == 0;
+        const double x = s[e], y = s[partner];
+        if ((x > y) == up) { s[e] = y; s[partner] = x; }
+      }
+    }
+  __syncthreads();
 }
 
 struct FitRowArgs {
@@ -193,19 +221,7 @@ __global__ __launch_bounds__(FIT_NT) void k_fit_rows(FitArgs a, FitRowArgs w) {
     }
     __syncthreads();
   }
-  // one bitonic network over all the tile's rows: pair pr of a step exchanges e and e | jj inside its row
-  const int half = gn * NP / 2;
-  for (int k = 2; k <= NP; k <<= 1)
-    for (int jj = k >> 1; jj > 0; jj >>= 1) {
-      __syncthreads();
-      for (int pr = tid; pr < half; pr += FIT_NT) {
-        const int e = ((pr & ~(jj - 1)) << 1) | (pr & (jj - 1)), partner = e | jj;
-        const bool up = ((e & (NP - 1)) & k) == 0;
-        const double x = s[e], y = s[partner];
-        if ((x > y) == up) { s[e] = y; s[partner] = x; }
-      }
-    }
-  __syncthreads();
+  fit_sort(s, gn, NP, tid);
   if (tid < gn * w.nq) {
     const int gl = tid / w.nq, qi = tid - gl * w.nq;
     w.quant[((size_t)r * a.G + g0 + gl) * w.nq + qi] = fit_quantile(s + gl * NP, T, w.probs[qi]);
@@ -236,6 +252,119 @@ __global__ __launch_bounds__(FIT_NT) void k_fit_quantiles(const double* W, int N
   quant[e] = fit_quantile(W + (size_t)col * NP, T, probs[(int)(e - col * nq)]);
 }
 
+// ---- simultaneous bands ----
+constexpr int FIT_SIM_GT = 8;                  // grid points whose per-lane sums are kept in registers at once
+constexpr int FIT_SIM_GMAX = 4096;             // 16 G bytes of mean and sd beside the 64 KiB sort row and red[]: 130 of 160 KiB
+
+// The loops over grid points below are long and regular: left alone the compiler carries the address of every direction of a
+// value from one grid point to the next in a register pair of its own (8 x 17 pairs for `fit`) and spills.  Hiding the grid
+// point's base address from it makes the directions' addresses base + uniform offset again, as in k_fit_values.
+#define FIT_SIM_OPAQUE(ptr) asm volatile("" : "+v"(ptr))
+
+struct FitSimArgs {
+  int r0, NP, fused;                           // first result row of the chunk; padded sort row, 0: C goes to cw; squares by fma
+  double p;                                    // 1 - alpha
+  double *mean, *sd, *crit, *lower, *upper;    // of the chunk: [r G + g], crit [r]
+  double* cw;                                  // long rows: [r CS + cs]
+};
+
+template <int WHICH>
+__global__ __launch_bounds__(FIT_NT) void k_fit_sim(FitArgs a, FitSimArgs w) {
+  extern __shared__ __attribute__((aligned(16))) double s[];   // mean[G], sd[G], the sort row of NP
+  __shared__ double red[FIT_NT];
+  __shared__ double sx[8];
+  const int tid = threadIdx.x, r = (int)blockIdx.x;
+  const int i = a.curves ? a.curves[w.r0 + r] : w.r0 + r;
+  const int G = a.G, T = a.CS, NP = w.NP;
+  const size_t CS = (size_t)a.CS, gstride = (size_t)a.NJ * CS;
+  double *s_mean = s, *s_sd = s + G, *row = s + 2 * (size_t)G;
+  if (tid < a.D) sx[tid] = a.X[i + (size_t)a.n * tid];
+  for (int e = T + tid; e < NP; e += FIT_NT) row[e] = INFINITY;
+  __syncthreads();
+  // passes 0 and 1: sum of v, then of (v - mean)^2, per grid point: the lane's draws in order, then k_fit_rows' tree
+  for (int pass = 0; pass < 2; ++pass)
+    for (int g0 = 0; g0 < G; g0 += FIT_SIM_GT) {
+      const int gn = min(FIT_SIM_GT, G - g0);
+      // one copy of fit_value: gl is uniform, so picking its accumulator is a uniform test per register pair, not an index
+      double acc[FIT_SIM_GT];
+#pragma unroll
+      for (int j = 0; j < FIT_SIM_GT; ++j) acc[j] = 0.0;
+      // k_bands_moments, which gives the long rows' sd in bfmmm_chain_curve_bands, is compiled with contraction on
+      const bool fz = pass && w.fused;
+      for (int cs = tid; cs < T; cs += FIT_NT) {
+        double z[KMAX], ch[FIT_MMAX];
+        fit_draw<WHICH>(a, i, cs, z, ch);
+#pragma nounroll
+        for (int gl = 0; gl < gn; ++gl) {
+          const double* tg = a.tab + (size_t)(g0 + gl) * gstride + cs;
+          FIT_SIM_OPAQUE(tg);
+          const double v = fit_value<WHICH>(tg, CS, z, ch, sx, a.K, a.M, a.D, a.cadj);
+          const double dlt = pass ? v - s_mean[g0 + gl] : 0.0;
+          const double term = pass ? dlt * dlt : v;
+#pragma unroll
+          for (int j = 0; j < FIT_SIM_GT; ++j)
+            if (j == gl) acc[j] = fz ? __builtin_fma(dlt, dlt, acc[j]) : acc[j] + term;
+        }
+      }
+#pragma unroll
+      for (int gl = 0; gl < FIT_SIM_GT; ++gl)
+        if (gl < gn) {
+          red[tid] = acc[gl];
+          __syncthreads();
+          for (int h = FIT_NT / 2; h > 0; h >>= 1) { if (tid < h) red[tid] += red[tid + h]; __syncthreads(); }
+          if (tid == 0) {
+            if (!pass) s_mean[g0 + gl] = red[0] / (double)T;
+            else s_sd[g0 + gl] = sqrt(red[0] / (double)(T - 1));
+          }
+          __syncthreads();
+        }
+    }
+  // pass 2: C(cs) = max over the grid points with sd != 0 of |(v - mean) / sd|, from 0; a NaN (one draw: sd is NaN) stays
+  for (int cs = tid; cs < T; cs += FIT_NT) {
+    double z[KMAX], ch[FIT_MMAX];
+    fit_draw<WHICH>(a, i, cs, z, ch);
+    double mx = 0.0;
+#pragma nounroll
+    for (int g = 0; g < G; ++g) {
+      const double* tg = a.tab + (size_t)g * gstride + cs;
+      FIT_SIM_OPAQUE(tg);
+      const double v = fit_value<WHICH>(tg, CS, z, ch, sx, a.K, a.M, a.D, a.cadj);
+      const double sg = s_sd[g];
+      if (sg != 0.0) {
+        const double dv = fabs((v - s_mean[g]) / sg);
+        if (dv > mx || dv != dv) mx = dv;
+      }
+    }
+    if (NP) row[cs] = mx;
+    else w.cw[(size_t)r * CS + cs] = mx;
+  }
+  const size_t o = (size_t)r * G;
+  if (!NP) {                                   // long rows: the sort, crit and the band ends follow in launches of their own
+    for (int g = tid; g < G; g += FIT_NT) { w.mean[o + g] = s_mean[g]; w.sd[o + g] = s_sd[g]; }
+    return;
+  }
+  fit_sort(row, 1, NP, tid);
+  const double crit = fit_quantile(row, T, w.p);
+  if (tid == 0) w.crit[r] = crit;
+  for (int g = tid; g < G; g += FIT_NT) {
+    const double m = s_mean[g], sg = s_sd[g];
+    w.mean[o + g] = m;
+    w.sd[o + g] = sg;
+    w.lower[o + g] = m - crit * sg;
+    w.upper[o + g] = m + crit * sg;
+  }
+}
+
+// the band ends of long rows, once crit[r] has been read off the sorted workspace: e = r G + g
+__global__ __launch_bounds__(FIT_NT) void k_fit_sim_band(const double* mean, const double* sd, const double* crit, int G, long long tot,
+                                                         double* lower, double* upper) {
+  const long long e = (long long)blockIdx.x * FIT_NT + threadIdx.x;
+  if (e >= tot) return;
+  const double c = crit[e / G], m = mean[e], sg = sd[e];
+  lower[e] = m - c * sg;
+  upper[e] = m + c * sg;
+}
+
 FitArgs fit_args(const Ctx& c, const FitCall& f) {
   const Dims& d = c.d;
   FitArgs a;
@@ -256,6 +385,7 @@ int fit_np(int CS) { int NP = 1; while (NP < CS) NP <<= 1; return NP; }
 
 long long fit_directions(const Dims& d, int which) { return (long long)d.K * (which ? d.M + 1 : 1) * (1 + d.D); }
 int fit_lds_rows() { return FIT_LDS_ROWS; }
+int fit_sim_gmax() { return FIT_SIM_GMAX; }
 
 std::string fit_check(const Ctx& c, const FitCall& f) {
   const Dims& d = c.d;
@@ -322,6 +452,41 @@ std::string launch_fit_values(const Ctx& c, const FitCall& f, int r0, int rows, 
   if (f.which) hipLaunchKernelGGL(k_fit_values<1>, grid, dim3(FIT_NT), 0, st, a, r0, GT, tiles, out);
   else hipLaunchKernelGGL(k_fit_values<0>, grid, dim3(FIT_NT), 0, st, a, r0, GT, tiles, out);
   if (hipGetLastError() != hipSuccess) return "k_fit_values: launch failed";
+  return "";
+}
+
+// Simultaneous bands of result rows [r0, r0 + rows): mean, sd [r G + g] of the chunk always; rows of C S <= 8192 draws also crit [r],
+// lower, upper [r G + g] (cw unused); longer rows C [r CS + cs] into cw instead, for the sort that launch_fit_sim_band follows
+std::string launch_fit_sim(const Ctx& c, const FitCall& f, int r0, int rows, double p, double* mean, double* sd, double* crit, double* lower,
+                           double* upper, double* cw, hipStream_t st) {
+  const std::string err = fit_check(c, f);
+  if (!err.empty()) return "k_fit_sim: " + err;
+  const FitArgs a = fit_args(c, f);
+  if (a.G > FIT_SIM_GMAX) return "k_fit_sim: G above 4096";
+  if (rows < 1 || !mean || !sd || !crit || !lower || !upper) return "k_fit_sim: bad arguments";
+  const bool lds_row = a.CS <= FIT_LDS_ROWS;
+  if (!lds_row && !cw) return "k_fit_sim: no workspace";
+  FitSimArgs w;
+  w.r0 = r0; w.NP = lds_row ? fit_np(a.CS) : 0; w.fused = lds_row ? 0 : 1; w.p = p;
+  w.mean = mean; w.sd = sd; w.crit = crit; w.lower = lower; w.upper = upper; w.cw = cw;
+  const size_t lds = sizeof(double) * (2 * (size_t)a.G + (size_t)w.NP);
+  const void* fn = f.which ? (const void*)k_fit_sim<1> : (const void*)k_fit_sim<0>;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * (2 * FIT_SIM_GMAX + FIT_LDS_ROWS))) != hipSuccess) {
+    (void)hipGetLastError();
+    return "k_fit_sim: cannot set the LDS size";
+  }
+  if (f.which) hipLaunchKernelGGL(k_fit_sim<1>, dim3((unsigned)rows), dim3(FIT_NT), lds, st, a, w);
+  else hipLaunchKernelGGL(k_fit_sim<0>, dim3((unsigned)rows), dim3(FIT_NT), lds, st, a, w);
+  if (hipGetLastError() != hipSuccess) return "k_fit_sim: launch failed";
+  return "";
+}
+
+std::string launch_fit_sim_band(const double* mean, const double* sd, const double* crit, int G, int rows, double* lower, double* upper,
+                                hipStream_t st) {
+  const long long tot = (long long)rows * G;
+  if (tot < 1 || (tot + FIT_NT - 1) / FIT_NT > 0x7fffffffLL) return "k_fit_sim_band: bad arguments";
+  hipLaunchKernelGGL(k_fit_sim_band, dim3((unsigned)((tot + FIT_NT - 1) / FIT_NT)), dim3(FIT_NT), 0, st, mean, sd, crit, G, tot, lower, upper);
+  if (hipGetLastError() != hipSuccess) return "k_fit_sim_band: launch failed";
   return "";
 }
 

@@ -98,6 +98,15 @@ std::string launch_fit_rows(const Ctx& c, const FitCall& f, int r0, int rows, co
 std::string launch_fit_values(const Ctx& c, const FitCall& f, int r0, int rows, double* out, hipStream_t st);
 // the quantile rule read off ncol sorted rows W[col NP + .] of T values: quant[col nq + q]
 std::string launch_fit_quantiles(const double* W, int NP, int T, long long ncol, const double* probs, int nq, double* quant, hipStream_t st);
+// Simultaneous bands (bfmmm_chain_curve_bands_sim) of result rows [r0, r0 + rows), p = 1 - alpha, one workgroup per row, G <=
+// fit_sim_gmax(): mean / sd [r G + g] of the chunk; rows of <= fit_lds_rows() draws also crit [r], lower / upper [r G + g].  Longer
+// rows: C [r CS + cs] into cw; once it is sorted and crit read off it (launch_bands_quantiles, launch_fit_quantiles),
+// launch_fit_sim_band writes lower and upper.
+int fit_sim_gmax();
+std::string launch_fit_sim(const Ctx& c, const FitCall& f, int r0, int rows, double p, double* mean, double* sd, double* crit, double* lower,
+                           double* upper, double* cw, hipStream_t st);
+std::string launch_fit_sim_band(const double* mean, const double* sd, const double* crit, int G, int rows, double* lower, double* upper,
+                                hipStream_t st);
 
 // ---- kernels_similarity.hip ----
 // Pooled co-membership d_ij = sum_k Z_ik Z_jk of result rows [r0, r0 + rows) against all n curves over every chain and slots

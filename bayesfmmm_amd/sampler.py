@@ -252,6 +252,20 @@ class Sampler:
                                                     int(max_workspace_bytes), _dp(mean), _dp(sd), _dp(qs), m * G))
         return {"mean": mean, "sd": sd, "quantiles": qs, "probs": pr}
 
+    def curve_bands_simultaneous(self, E, which="fit", alpha=0.05, curves=None, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """Simultaneous (1 - alpha) credible band of every curve's `curve_fit` values with the chains pooled, by the reference's
+        rule (FMeanCI's `simultaneous`), on the device (bfmmm_chain_curve_bands_sim): crit is the (1 - alpha)
+        quantile over the draws of max_g |v(g) - mean(g)| / sd(g), and the band mean -/+ crit sd holds whole posterior curves,
+        which `curve_bands`' pointwise quantiles do not.  mean and sd are `curve_bands`'.
+        Returns {"mean": (m, G), "sd": (m, G), "crit": (m,), "lower": (m, G), "upper": (m, G), "alpha": alpha}."""
+        w, Em, S, idx, pc, m = self._fit_args(E, which, curves, first_slot, n_slots)
+        G = Em.shape[0]
+        mean, sd, lower, upper, crit = np.zeros((m, G)), np.zeros((m, G)), np.zeros((m, G)), np.zeros((m, G)), np.zeros(m)
+        _lib.check(self.lib.bfmmm_chain_curve_bands_sim(self.h, w, _dp(Em), G, pc, m, int(first_slot), S, float(alpha),
+                                                        int(max_workspace_bytes), _dp(mean), _dp(sd), _dp(crit), _dp(lower), _dp(upper),
+                                                        m * G))
+        return {"mean": mean, "sd": sd, "crit": crit, "lower": lower, "upper": upper, "alpha": alpha}
+
     def similarity(self, curves=None, sd=True, per_chain=False, first_slot=0, n_slots=None, max_workspace_bytes=0):
         """The pooled co-membership matrix of the curves: mean (and sd) over chain slots [first_slot, first_slot + n_slots) of
         every chain of the batch of d_ij = sum_k Z_ik Z_jk, the posterior similarity of curves i and j, computed on the device

@@ -218,7 +218,22 @@ int bfmmm_chain_loo(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_wo
  *                            C S values at probs[0 .. nq) in [0, 1], nq <= 16, by arma::quantile's rule (Hyndman and Fan
  *                            definition 5); capacity >= m G rows.  The values stay on the device; chunks of consecutive result
  *                            rows keep everything the call allocates within max_workspace_bytes (0: 256 MiB).
- * At most 2^22 draws per row (n_chains x n_slots).  Both run on the sampler's stream and leave its state and slots untouched.
+ *   bfmmm_chain_curve_bands_sim  the simultaneous band of each result row, the reference's rule (FMeanCI's `simultaneous`) with the
+ *                            chains pooled.  With mean(g), sd(g) as above over the N = C S draws,
+ *                              C(cs) = max over g with sd(g) != 0 of |(v(g, cs) - mean(g)) / sd(g)|, from 0.0,
+ *                              crit  = the (1 - alpha) quantile of the N values C(.) by the same rule,
+ *                              lower(g) = mean(g) - crit sd(g),  upper(g) = mean(g) + crit sd(g):
+ *                            the band holds whole curves of the posterior, not each grid point's values separately.  A grid point
+ *                            whose sd is exactly 0 is left out of the maximum and its band is its mean; crit is 0 where every sd
+ *                            is 0; for one draw sd, crit, lower and upper are NaN.  mean, sd, lower, upper [r G + g], crit [r];
+ *                            capacity >= m G rows; crit, lower and upper are required, mean and sd may be NULL; alpha inside
+ *                            (0, 1); G <= 4096 (mean and sd of a curve's grid points stay in LDS, 16 G bytes, beside the 64 KiB
+ *                            row that sorts C).  No value is stored: one workgroup per curve forms them three times.  Chunks of
+ *                            consecutive result rows keep the call within max_workspace_bytes (0: 256 MiB): shared the table, E
+ *                            and the curve list, per curve 8 (4 G + 1) bytes and, for rows above 8192 draws, the row of C and
+ *                            its sort workspace.  mean and sd are bfmmm_chain_curve_bands' bit for bit; the result does not
+ *                            depend on the chunk or on repeated calls.
+ * At most 2^22 draws per row (n_chains x n_slots).  All run on the sampler's stream and leave its state and slots untouched.
  * bfmmm_set_curve_fit_route(1) sends rows of up to 8192 draws through the workspace route of the longer ones as well
  * (a measurement switch; 0, the default: they are formed, sorted and reduced in LDS). */
 int bfmmm_chain_curve_fit(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves, int first_slot,
@@ -226,6 +241,9 @@ int bfmmm_chain_curve_fit(bfmmm_handle* h, int which, const double* E, int G, co
 int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves, int first_slot,
                             int n_slots, const double* probs, int nq, int64_t max_workspace_bytes, double* mean, double* sd,
                             double* quantiles, int64_t capacity);
+int bfmmm_chain_curve_bands_sim(bfmmm_handle* h, int which, const double* E, int G, const int32_t* curves, int n_curves,
+                                int first_slot, int n_slots, double alpha, int64_t max_workspace_bytes,
+                                double* mean, double* sd, double* crit, double* lower, double* upper, int64_t capacity);
 void bfmmm_set_curve_fit_route(int route);
 
 /* Pooled co-membership of curves under chain slots [first_slot, first_slot + n_slots) of EVERY chain of the batch:
@@ -291,6 +309,8 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * names: "total", "curve_z", "pair_gram", "factor", "sweep", "curve_chi", "loglik".
  * Of the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands (always measured): "curve_fit" (the sum of the following),
  * "curve_fit_project", "curve_fit_rows", "curve_fit_values", "curve_fit_reduce" (quantiles and moments of the workspace route).
+ * Of the last bfmmm_chain_curve_bands_sim (always measured): "curve_sim", the device time and launches of k_fit_sim (and, for rows
+ * above 8192 draws, of the kernel that writes the band ends), and "curve_sim_reduce", those of the long rows' sort.
  * Of the last bfmmm_chain_similarity (always measured): "similarity", the device time and launches of its kernel.
  * Of the last bfmmm_chain_curve_cov (always measured): "curve_cov", the device time and launches (one per chunk) of k_curve_cov,
  * and "curve_cov_project", those of the projection that precedes them. */
