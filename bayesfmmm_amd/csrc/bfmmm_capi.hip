@@ -19,8 +19,6 @@ static std::mutex g_capture_mutex;   // one stream capture at a time (samplers m
 int bfmmm::fail(const std::string& msg) { g_err = msg; return 1; }
 
 static const char* kFamNames[FAM_COUNT] = {"total", "curve_z", "pair_gram", "factor", "sweep", "curve_chi", "loglik", "pg_reduce"};
-static const char* kFitNames[4] = {"curve_fit_project", "curve_fit_rows", "curve_fit_values", "curve_fit_reduce"};     // h->fit_ms[], in capi_chain.hip's order
-static constexpr int FIT_T_COUNT = sizeof kFitNames / sizeof kFitNames[0];
 
 // Synchronous copy on the sampler's own stream: the legacy (NULL) stream must not be touched while
 // another host thread is capturing a graph.
@@ -448,144 +446,88 @@ extern "C" int bfmmm_set_chain_id_stride(bfmmm_handle* h, uint32_t stride) {
   return 0;
 }
 
-extern "C" int bfmmm_set_state(bfmmm_handle* h, const char* name, const double* v, int64_t count) {
-  if (!h || !name || !v) return fail("bfmmm_set_state: null argument");
-  h->state_dirty = true;
+// bfmmm_set_state (put) and bfmmm_get_state: `count` elements at v, in the reference's column-major layouts, to or from the
+// state of the selected chain.  The stream is drained before anything is copied.
+static int state_io(bfmmm_handle* h, const char* name, double* v, int64_t count, bool put) {
+  const std::string fn = put ? "bfmmm_set_state" : "bfmmm_get_state";
+  if (!h || !name || !v) return fail(fn + ": null argument");
+  if (put) h->state_dirty = true;
   HIPCHK(hipSetDevice(h->device));
   const Ctx cs = selc(h);       // the selected chain of the batch
   const Dims& d = cs.d;
-  const int n = d.n, K = d.K, P = d.P, M = d.M;
+  const int64_t n = d.n, K = d.K, P = d.P, M = d.M, D = d.D;
   const std::string s(name);
-  auto need = [&](int64_t want) { return count == want ? 0 : fail("bfmmm_set_state(" + s + "): wrong element count"); };
+  auto need = [&](int64_t want) {
+    if (put ? count == want : count >= want) return 0;
+    return fail(fn + "(" + s + ")" + (put ? ": wrong element count" : ": buffer too small"));
+  };
+  const hipMemcpyKind to_dev = hipMemcpyHostToDevice, to_host = hipMemcpyDeviceToHost;
   HIPCHK(hipStreamSynchronize(h->st));
-  if (s == "nu" || s == "Phi") {
-    std::vector<double> th((size_t)K * (M + 1) * P);
-    HIPCHK(copy_sync(h, th.data(), cs.theta, sizeof(double) * th.size(), hipMemcpyDeviceToHost));
-    if (s == "nu") {
-      if (need((int64_t)K * P)) return 1;
-      for (int j = 0; j < K; ++j)
-        for (int p = 0; p < P; ++p) th[((size_t)j * (M + 1)) * P + p] = v[j + (size_t)K * p];
-    } else {
-      if (need((int64_t)K * P * M)) return 1;
-      for (int j = 0; j < K; ++j)
-        for (int m = 0; m < M; ++m)
-          for (int p = 0; p < P; ++p) th[((size_t)j * (M + 1) + m + 1) * P + p] = v[j + (size_t)K * (p + (size_t)P * m)];
-    }
-    HIPCHK(copy_sync(h, cs.theta, th.data(), sizeof(double) * th.size(), hipMemcpyHostToDevice));
+  // theta[(k (M + 1) + m') P + p] holds nu (m' = 0: K x P) and Phi (m' = m + 1: K x P x M); with covariates,
+  // thetaX[((k (M + 1) + m') D + dd) P + p] holds eta (m' = 0: P x D x K) and xi (m' = m + 1: K arrays P x D x M)
+  const bool mean = s == "nu" || s == "eta", cov = s == "eta" || s == "xi";
+  if (cov ? D > 0 : mean || s == "Phi") {
+    const int64_t DD = cov ? D : 1, nm = mean ? 1 : M;
+    if (need(K * nm * DD * P)) return 1;
+    double* dev = cov ? cs.thetaX : cs.theta;
+    std::vector<double> th((size_t)(K * (M + 1) * DD * P));
+    HIPCHK(copy_sync(h, th.data(), dev, sizeof(double) * th.size(), to_host));
+    for (int64_t k = 0; k < K; ++k)
+      for (int64_t m = 0; m < nm; ++m)
+        for (int64_t dd = 0; dd < DD; ++dd)
+          for (int64_t p = 0; p < P; ++p) {
+            double& t = th[(size_t)(((k * (M + 1) + (mean ? 0 : m + 1)) * DD + dd) * P + p)];
+            double& x = v[cov ? p + P * (dd + D * (m + nm * k)) : k + K * (p + P * m)];
+            if (put) t = x; else x = t;
+          }
+    if (put) HIPCHK(copy_sync(h, dev, th.data(), sizeof(double) * th.size(), to_dev));
     return 0;
   }
-  const int D = d.D;
-  if ((s == "eta" || s == "xi") && D > 0) {
-    std::vector<double> tx((size_t)K * (M + 1) * D * P);
-    HIPCHK(copy_sync(h, tx.data(), cs.thetaX, sizeof(double) * tx.size(), hipMemcpyDeviceToHost));
-    if (s == "eta") {        // P x D x K
-      if (need((int64_t)P * D * K)) return 1;
-      for (int k = 0; k < K; ++k)
-        for (int dd = 0; dd < D; ++dd)
-          for (int p = 0; p < P; ++p) tx[((size_t)(k * (M + 1)) * D + dd) * P + p] = v[p + (size_t)P * (dd + (size_t)D * k)];
-    } else {                 // K arrays P x D x M
-      if (need((int64_t)K * P * D * M)) return 1;
-      for (int k = 0; k < K; ++k)
-        for (int m = 0; m < M; ++m)
-          for (int dd = 0; dd < D; ++dd)
-            for (int p = 0; p < P; ++p)
-              tx[((size_t)(k * (M + 1) + m + 1) * D + dd) * P + p] = v[(size_t)k * P * D * M + p + (size_t)P * (dd + (size_t)D * m)];
-    }
-    HIPCHK(copy_sync(h, cs.thetaX, tx.data(), sizeof(double) * tx.size(), hipMemcpyHostToDevice));
-    return 0;
-  }
-  struct Arr { const char* nm; double* p; int64_t len; };
-  const Arr arrs[] = {{"chi", cs.chi, (int64_t)n * M}, {"Z", cs.Z, (int64_t)n * K}, {"delta", cs.delta, (int64_t)K * M},
-                      {"A", cs.Aa, (int64_t)K * 2}, {"gamma", cs.gamma, (int64_t)K * P * M},
-                      {"tau_eta", cs.tau_eta, (int64_t)K * D}, {"gamma_xi", cs.gamma_xi, (int64_t)K * P * D * M},
-                      {"delta_xi", cs.delta_xi, (int64_t)K * M * D}, {"A_xi", cs.A_xi, (int64_t)K * 2 * D}};
+  // the arrays kept as the reference lays them out (the covariate ones exist once covariates were set)
+  struct Arr { const char* nm; double* p; int64_t len; bool read_only; };
+  const Arr arrs[] = {{"chi", cs.chi, n * M}, {"Z", cs.Z, n * K}, {"delta", cs.delta, K * M}, {"A", cs.Aa, K * 2},
+                      {"gamma", cs.gamma, K * P * M}, {"tau_eta", cs.tau_eta, K * D}, {"gamma_xi", cs.gamma_xi, K * P * D * M},
+                      {"delta_xi", cs.delta_xi, K * M * D}, {"A_xi", cs.A_xi, K * 2 * D}};
   for (const Arr& a : arrs)
     if (s == a.nm && a.p) {
       if (need(a.len)) return 1;
-      HIPCHK(copy_sync(h, a.p, v, sizeof(double) * (size_t)a.len, hipMemcpyHostToDevice));
+      HIPCHK(put ? copy_sync(h, a.p, v, sizeof(double) * (size_t)a.len, to_dev) : copy_sync(h, v, a.p, sizeof(double) * (size_t)a.len, to_host));
       return 0;
     }
+  // the scalars and vectors of Dyn; the read-only ones are unknown names to bfmmm_set_state
   Dyn dyn;
   if (dyn_get(h, dyn)) return 1;
-  if (s == "pi") { if (need(K)) return 1; for (int k = 0; k < K; ++k) dyn.pi[k] = v[k]; }
-  else if (s == "tau") { if (need(K)) return 1; for (int k = 0; k < K; ++k) dyn.tau[k] = v[k]; }
-  else if (s == "alpha_3") { if (need(1)) return 1; dyn.alpha3 = v[0]; }
-  else if (s == "sigma_sq") { if (need(1)) return 1; dyn.sigma2 = v[0]; }
-  else return fail("bfmmm_set_state: unknown name '" + s + "'");
-  return dyn_put(h, dyn);
-}
-
-extern "C" int bfmmm_get_state(bfmmm_handle* h, const char* name, double* out, int64_t capacity) {
-  if (!h || !name || !out) return fail("bfmmm_get_state: null argument");
-  HIPCHK(hipSetDevice(h->device));
-  const Ctx cs = selc(h);       // the selected chain of the batch
-  const Dims& d = cs.d;
-  const int n = d.n, K = d.K, P = d.P, M = d.M;
-  const std::string s(name);
-  auto need = [&](int64_t want) { return capacity >= want ? 0 : fail("bfmmm_get_state(" + s + "): buffer too small"); };
-  HIPCHK(hipStreamSynchronize(h->st));
-  if (s == "nu" || s == "Phi") {
-    std::vector<double> th((size_t)K * (M + 1) * P);
-    HIPCHK(copy_sync(h, th.data(), cs.theta, sizeof(double) * th.size(), hipMemcpyDeviceToHost));
-    if (s == "nu") {
-      if (need((int64_t)K * P)) return 1;
-      for (int j = 0; j < K; ++j)
-        for (int p = 0; p < P; ++p) out[j + (size_t)K * p] = th[((size_t)j * (M + 1)) * P + p];
-    } else {
-      if (need((int64_t)K * P * M)) return 1;
-      for (int j = 0; j < K; ++j)
-        for (int m = 0; m < M; ++m)
-          for (int p = 0; p < P; ++p) out[j + (size_t)K * (p + (size_t)P * m)] = th[((size_t)j * (M + 1) + m + 1) * P + p];
-    }
-    return 0;
-  }
-  const int D = d.D;
-  if ((s == "eta" || s == "xi") && D > 0) {
-    std::vector<double> tx((size_t)K * (M + 1) * D * P);
-    HIPCHK(copy_sync(h, tx.data(), cs.thetaX, sizeof(double) * tx.size(), hipMemcpyDeviceToHost));
-    if (s == "eta") {
-      if (need((int64_t)P * D * K)) return 1;
-      for (int k = 0; k < K; ++k)
-        for (int dd = 0; dd < D; ++dd)
-          for (int p = 0; p < P; ++p) out[p + (size_t)P * (dd + (size_t)D * k)] = tx[((size_t)(k * (M + 1)) * D + dd) * P + p];
-    } else {
-      if (need((int64_t)K * P * D * M)) return 1;
-      for (int k = 0; k < K; ++k)
-        for (int m = 0; m < M; ++m)
-          for (int dd = 0; dd < D; ++dd)
-            for (int p = 0; p < P; ++p)
-              out[(size_t)k * P * D * M + p + (size_t)P * (dd + (size_t)D * m)] = tx[((size_t)(k * (M + 1) + m + 1) * D + dd) * P + p];
-    }
-    return 0;
-  }
-  struct Arr { const char* nm; double* p; int64_t len; };
-  const Arr arrs[] = {{"chi", cs.chi, (int64_t)n * M}, {"Z", cs.Z, (int64_t)n * K}, {"delta", cs.delta, (int64_t)K * M},
-                      {"A", cs.Aa, (int64_t)K * 2}, {"gamma", cs.gamma, (int64_t)K * P * M},
-                      {"tau_eta", cs.tau_eta, (int64_t)K * D}, {"gamma_xi", cs.gamma_xi, (int64_t)K * P * D * M},
-                      {"delta_xi", cs.delta_xi, (int64_t)K * M * D}, {"A_xi", cs.A_xi, (int64_t)K * 2 * D}};
-  for (const Arr& a : arrs)
-    if (s == a.nm && a.p) {
+  double status = (double)dyn.status, stamps[64];
+  for (int q = 0; q < 64; ++q) stamps[q] = (double)(dyn.stamps[q] % 100000000000ULL);
+  const Arr dyns[] = {{"pi", dyn.pi, K}, {"tau", dyn.tau, K}, {"alpha_3", &dyn.alpha3, 1}, {"sigma_sq", &dyn.sigma2, 1},
+                      {"loglik", &dyn.loglik, 1, true}, {"status", &status, 1, true}, {"stamps", stamps, 64, true}};
+  for (const Arr& a : dyns)
+    if (s == a.nm && !(put && a.read_only)) {
       if (need(a.len)) return 1;
-      HIPCHK(copy_sync(h, out, a.p, sizeof(double) * (size_t)a.len, hipMemcpyDeviceToHost));
-      return 0;
+      if (put) std::copy(v, v + a.len, a.p); else std::copy(a.p, a.p + a.len, v);
+      return put ? dyn_put(h, dyn) : 0;
     }
-  Dyn dyn;
-  if (dyn_get(h, dyn)) return 1;
-  if (s == "pi") { if (need(K)) return 1; for (int k = 0; k < K; ++k) out[k] = dyn.pi[k]; }
-  else if (s == "tau") { if (need(K)) return 1; for (int k = 0; k < K; ++k) out[k] = dyn.tau[k]; }
-  else if (s == "alpha_3") { if (need(1)) return 1; out[0] = dyn.alpha3; }
-  else if (s == "sigma_sq") { if (need(1)) return 1; out[0] = dyn.sigma2; }
-  else if (s == "loglik") { if (need(1)) return 1; out[0] = dyn.loglik; }
-  else if (s == "status") { if (need(1)) return 1; out[0] = (double)dyn.status; }
-  else if (s == "stamps") { if (need(64)) return 1; for (int q = 0; q < 64; ++q) out[q] = (double)(dyn.stamps[q] % 100000000000ULL); }
 #ifdef BFMMM_TIMELINE
-  else if (s == "fct") { if (need(8)) return 1; unsigned long long w[8]; fetch_fct(w); for (int q = 0; q < 8; ++q) out[q] = (double)(w[q] % 100000000000ULL); }
-  else if (s == "zphase") { const int N = 8 * 8192; if (need(N)) return 1; std::vector<unsigned long long> w(N); fetch_zphase(w.data()); for (int q = 0; q < N; ++q) out[q] = (double)w[q]; }
-  else if (s == "ztrace") { const int N = 3 * 8192; if (need(N)) return 1; std::vector<unsigned long long> w(N); fetch_ztrace(w.data()); for (int q = 0; q < N; ++q) out[q] = (q % 3 == 1) ? (double)w[q] : (double)(w[q] % 100000000000ULL); }
-  else if (s == "wgtrace") { if (need(3072)) return 1; std::vector<unsigned long long> w(3072); fetch_wgtrace(w.data()); for (int q = 0; q < 3072; ++q) out[q] = (q % 3 == 1) ? (double)w[q] : (double)(w[q] % 100000000000ULL); }
+  // (read-only too) the kernels' timeline words; raw: the words kept as they are (0: none, 1: all, 3: every third from word 1)
+  struct Trace { const char* nm; int len; void (*fetch)(unsigned long long*); int raw; };
+  const Trace traces[] = {{"fct", 8, fetch_fct, 0}, {"zphase", 8 * 8192, fetch_zphase, 1}, {"ztrace", 3 * 8192, fetch_ztrace, 3},
+                          {"wgtrace", 3072, fetch_wgtrace, 3}};
+  for (const Trace& t : traces)
+    if (s == t.nm && !put) {
+      if (need(t.len)) return 1;
+      std::vector<unsigned long long> w(t.len);
+      t.fetch(w.data());
+      for (int q = 0; q < t.len; ++q) v[q] = (double)(t.raw == 1 || (t.raw == 3 && q % 3 == 1) ? w[q] : w[q] % 100000000000ULL);
+      return 0;
+    }
 #endif
-  else return fail("bfmmm_get_state: unknown name '" + s + "'");
-  return 0;
+  return fail(fn + ": unknown name '" + s + "'");
+}
+extern "C" int bfmmm_set_state(bfmmm_handle* h, const char* name, const double* v, int64_t count) {
+  return state_io(h, name, const_cast<double*>(v), count, true);
+}
+extern "C" int bfmmm_get_state(bfmmm_handle* h, const char* name, double* out, int64_t capacity) {
+  return state_io(h, name, out, capacity, false);
 }
 
 // Initial states of BFMMM_Nu_Z (BFMMM.h:1039-1071) and BFMMM_Theta (:1210-1235)
@@ -1131,9 +1073,9 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
     *count = cnt;
     return 0;
   }
-  if (s == "curve_ll_ms") {   // device time of k_chain_curve_ll in the last bfmmm_chain_curve_loglik / _diagnostics / bfmmm_chain_loo
+  if (s == kPostNames[PT_CURVE_LL]) {
     if (capacity < 1) return fail("bfmmm_debug_get: buffer too small");
-    out[0] = h->curve_ll_ms;
+    out[0] = h->post_ms[PT_CURVE_LL];
     *count = 1;
     return 0;
   }
@@ -1168,19 +1110,13 @@ extern "C" int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, i
   if (!h || !name || !ms || !launches) return fail("bfmmm_get_timing: null argument");
   for (int f = 0; f < FAM_COUNT; ++f)
     if (!strcmp(name, kFamNames[f])) { *ms = h->fam_ms[f]; *launches = h->fam_launches[f]; return 0; }
-  // the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands: each kernel family of kernels_curve_fit.hip, and their sum
-  for (int f = 0; f < FIT_T_COUNT; ++f)
-    if (!strcmp(name, kFitNames[f])) { *ms = h->fit_ms[f]; *launches = h->fit_launches[f]; return 0; }
+  for (int f = PT_CURVE_LL + 1; f < PT_COUNT; ++f)
+    if (!strcmp(name, kPostNames[f])) { *ms = h->post_ms[f]; *launches = h->post_launches[f]; return 0; }
   if (!strcmp(name, "curve_fit")) {
     *ms = 0; *launches = 0;
-    for (int f = 0; f < FIT_T_COUNT; ++f) { *ms += h->fit_ms[f]; *launches += h->fit_launches[f]; }
+    for (int f = PT_FIT_PROJECT; f <= PT_FIT_REDUCE; ++f) { *ms += h->post_ms[f]; *launches += h->post_launches[f]; }
     return 0;
   }
-  if (!strcmp(name, "curve_sim")) { *ms = h->band_sim_ms[0]; *launches = h->band_sim_launches[0]; return 0; }      // the last bfmmm_chain_curve_bands_sim
-  if (!strcmp(name, "curve_sim_reduce")) { *ms = h->band_sim_ms[1]; *launches = h->band_sim_launches[1]; return 0; }
-  if (!strcmp(name, "similarity")) { *ms = h->sim_ms; *launches = h->sim_launches; return 0; }      // the last bfmmm_chain_similarity
-  if (!strcmp(name, "curve_cov_project")) { *ms = h->cov_ms[0]; *launches = h->cov_launches[0]; return 0; }      // the last bfmmm_chain_curve_cov
-  if (!strcmp(name, "curve_cov")) { *ms = h->cov_ms[1]; *launches = h->cov_launches[1]; return 0; }
   return fail("bfmmm_get_timing: unknown name");
 }
 

@@ -1,7 +1,8 @@
 // C ABI of the sampler (include/bfmmm.h), what is read off the chain slots after a run: the chain arrays, their convergence
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
 // their simultaneous bands, the pooled co-membership matrix of the curves, the pooled per-curve covariance surfaces.
-// An entry point is its argument checks (SlotCheck), the sizing of its workspace (CallBufs owns it) and one for_chunks.
+// An entry point is its argument checks (SlotCheck: slots, curve selection, workspace plan), its workspace and the event pairs
+// that time its launches into the handle's PT_* timers (CallBufs owns both) and one for_chunks.
 #include "handle.hpp"
 #include "launchers.hpp"
 #include "../../include/bfmmm_entry.h"
@@ -64,18 +65,38 @@ struct SlotCheck {
   int budget_sign(int64_t bytes) const { return bytes < 0 ? fail(fn + ": 'max_workspace_bytes' must not be negative") : 0; }
   int budget_row(size_t budget, size_t row) const { return budget < row ? fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(row) + " bytes of one row") : 0; }
   int capacity(int64_t have, int64_t want, const char* unit = "entries") const { return have < want ? fail(fn + tag + ": 'capacity' below " + std::to_string(want) + " " + unit) : 0; }
+  // a selection of curves (null: all n): every index is one; *m: the curves of the result.  The caller checks n_curves by its own rule.
+  int curve_list(const int32_t* curves, int n_curves, int64_t* m) const {
+    const int n = h->c.d.n;
+    for (int j = 0; curves && j < n_curves; ++j)
+      if (curves[j] < 0 || curves[j] >= n)
+        return fail(fn + ": 'curves'[" + std::to_string(j) + "] = " + std::to_string(curves[j]) + " outside 0 .. " + std::to_string(n - 1));
+    *m = curves ? n_curves : n;
+    return 0;
+  }
+  // a workspace of `shared` bytes for all curves and `per_curve` for every curve of a chunk: *chunk curves fit the budget, at most
+  // m and 2^30 result entries of `cells` a curve
+  int curve_chunk(size_t budget, size_t shared, size_t per_curve, int64_t m, int64_t cells, int64_t* chunk) const {
+    if (budget < shared + per_curve)
+      return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
+                  std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
+    *chunk = std::min<int64_t>(std::min<int64_t>(m, (int64_t)((budget - shared) / per_curve)), std::max<int64_t>(1, (1LL << 30) / cells));
+    return 0;
+  }
 };
 size_t budget_of(int64_t max_workspace_bytes) { return max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20; }
 
 // ---- what a call owns, its chunk loop and its timing ----------------------------------------------------------------------
+// A pair of events around a launch, or a sequence of launches, of a call.
+struct Timer { hipEvent_t from = nullptr, to = nullptr; };
+
 // The device buffers and events of one call: released when the call returns, whichever way.
 struct CallBufs {
   std::vector<void*> p;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // curve fit: project start / end, chunk start / middle / end (/ after the band ends)
+  std::vector<hipEvent_t> ev;
   ~CallBufs() {
     for (void* q : p) (void)hipFree(q);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
   }
   template <typename T>
   hipError_t get(T** out, size_t count) {
@@ -83,6 +104,21 @@ struct CallBufs {
     const hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
     if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
     return e;
+  }
+  // a device copy of the `count` elements at src
+  template <typename T>
+  hipError_t put(bfmmm_handle* h, T** out, const T* src, size_t count) {
+    const hipError_t e = get(out, count);
+    return e != hipSuccess ? e : copy_sync(h, *out, src, sizeof(T) * count, hipMemcpyHostToDevice);
+  }
+  hipError_t timers(std::initializer_list<Timer*> l) {
+    for (Timer* t : l)
+      for (hipEvent_t* e : {&t->from, &t->to}) {
+        const hipError_t err = hipEventCreate(e);
+        if (err != hipSuccess) return err;
+        ev.push_back(*e);
+      }
+    return hipSuccess;
   }
 };
 
@@ -97,23 +133,41 @@ int for_chunks(const SlotCheck& ck, int64_t len, int64_t chunk, Body body) {
   return 0;
 }
 
-// device time between two events of a stream that has been synchronised since: added to *ms and counted
-void add_elapsed(hipEvent_t from, hipEvent_t to, double* ms, int64_t* launches = nullptr) {
-  float t = 0.f;
-  if (hipEventElapsedTime(&t, from, to) != hipSuccess) { (void)hipGetLastError(); return; }
-  *ms += t;
-  if (launches) *launches += 1;
+// launch(), which answers "" or what failed, between the events of t on the stream; once the stream has been synchronised,
+// collect adds the device time between them to timer pt of the handle (handle.hpp) and counts it
+template <typename Launch>
+std::string timed(const Timer& t, hipStream_t st, Launch launch) {
+  (void)hipEventRecord(t.from, st);
+  const std::string err = launch();
+  (void)hipEventRecord(t.to, st);
+  return err;
+}
+void collect(bfmmm_handle* h, const Timer& t, int pt) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, t.from, t.to) != hipSuccess) { (void)hipGetLastError(); return; }
+  h->post_ms[pt] += ms;
+  h->post_launches[pt] += 1;
+}
+void reset_timers(bfmmm_handle* h, int first, int last) {
+  for (int pt = first; pt <= last; ++pt) { h->post_ms[pt] = 0; h->post_launches[pt] = 0; }
 }
 
 // one launch of k_chain_curve_ll between the handle's two events; curve_ll_collect adds its device time after a synchronise
 std::string curve_ll_timed(const SlotCheck& ck, int i0, int rows, double* d_x) {
   bfmmm_handle* h = ck.h;
-  (void)hipEventRecord(h->ev0, h->st);
-  const std::string err = launch_chain_curve_ll(h->c, ck.first_slot, ck.n_slots, i0, rows, d_x, h->st);
-  (void)hipEventRecord(h->ev1, h->st);
-  return err;
+  return timed({h->ev0, h->ev1}, h->st, [&] { return launch_chain_curve_ll(h->c, ck.first_slot, ck.n_slots, i0, rows, d_x, h->st); });
 }
-void curve_ll_collect(bfmmm_handle* h) { add_elapsed(h->ev0, h->ev1, &h->curve_ll_ms); }
+void curve_ll_collect(bfmmm_handle* h) { collect(h, {h->ev0, h->ev1}, PT_CURVE_LL); }
+
+// Rows [r0, r0 + rows) of a call's mean, of its sd and of its C chains' means, the last two where asked for, of `cells` entries a
+// row, from the chunk's device buffers to the host; true: all there, the stream synchronised
+bool stats_to_host(bfmmm_handle* h, int64_t r0, int rows, int64_t cells, int C, double* mean, const double* d_mean, double* sd,
+                   const double* d_sd, double* chain_mean, const double* d_cm) {
+  const size_t cnt = sizeof(double) * (size_t)rows * cells;
+  return !(sd && hipMemcpyAsync(sd + (size_t)r0 * cells, d_sd, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) &&
+         !(chain_mean && hipMemcpyAsync(chain_mean + (size_t)r0 * C * cells, d_cm, cnt * C, hipMemcpyDeviceToHost, h->st) != hipSuccess) &&
+         copy_sync(h, mean + (size_t)r0 * cells, d_mean, cnt, hipMemcpyDeviceToHost) == hipSuccess;
+}
 
 // ---- split R-hat, ESS, MCSE, mean and sd of rows of C S draws (kernels_diag.hip) --------------------------------
 // fill(p0, rows, d_x) puts rows [p0, p0 + rows) of the len rows into the workspace (row-major: draw fastest, then chain),
@@ -127,7 +181,7 @@ int seven_stats(const SlotCheck& ck, int64_t len, int64_t max_workspace_bytes, d
   if (ck.budget_row(budget, per_row)) return 1;
   const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
   HIPCHK(hipSetDevice(h->device));
-  if (ll_timed) h->curve_ll_ms = 0;
+  if (ll_timed) reset_timers(h, PT_CURVE_LL, PT_CURVE_LL);
   CallBufs b;
   double* d_x = nullptr;
   HIPCHK(b.get(&d_x, per_row / sizeof(double) * (size_t)chunk));
@@ -147,14 +201,10 @@ int seven_stats(const SlotCheck& ck, int64_t len, int64_t max_workspace_bytes, d
 }
 
 // ---- the pooled per-curve fitted functions (kernels_curve_fit.hip) -----------------------------------------
-// h->fit_ms[] / fit_launches[] (bfmmm_get_timing names them in this order)
-enum { FIT_T_PROJECT = 0, FIT_T_ROWS, FIT_T_VALUES, FIT_T_REDUCE, FIT_T_COUNT };
-static_assert(FIT_T_COUNT == sizeof(bfmmm_handle::fit_ms) / sizeof(double), "one slot of the handle per kernel family");
-void fit_collect(bfmmm_handle* h, const CallBufs& b, int from, int to, int what) { add_elapsed(b.ev[from], b.ev[to], &h->fit_ms[what], &h->fit_launches[what]); }
-
 struct FitSetup {
   FitCall f;
-  long long m = 0, CS = 0, NJ = 0;       // curves of the result, draws per row, projection directions
+  int64_t m = 0;                    // curves of the result
+  long long CS = 0, NJ = 0;         // draws per row, projection directions
 };
 
 // The checks both calls share, then E, the curve list and the projection table on the device (owned by b) and the table
@@ -165,15 +215,8 @@ int fit_check_args(const SlotCheck& ck, int which, const double* E, int G, const
   if (which != 0 && which != 1) return fail(fn + ": 'which' must be 0 (mean) or 1 (fit), got " + std::to_string(which));
   if (G < 1) return fail(fn + ": 'G' must be at least 1");
   const bfmmm_handle* h = ck.h;
-  const int n = h->c.d.n;
-  if (curves) {
-    if (n_curves < 1) return fail(fn + ": 'n_curves' must be at least 1 where 'curves' is given");
-    for (int j = 0; j < n_curves; ++j)
-      if (curves[j] < 0 || curves[j] >= n)
-        return fail(fn + ": 'curves'[" + std::to_string(j) + "] = " + std::to_string(curves[j]) + " outside 0 .. " + std::to_string(n - 1));
-  }
-  if (ck.range() || ck.row_limit()) return 1;
-  s.m = curves ? n_curves : n;
+  if (curves && n_curves < 1) return fail(fn + ": 'n_curves' must be at least 1 where 'curves' is given");
+  if (ck.curve_list(curves, n_curves, &s.m) || ck.range() || ck.row_limit()) return 1;
   s.CS = ck.CS();
   s.f.which = which; s.f.G = G; s.f.first_slot = ck.first_slot; s.f.n_slots = ck.n_slots;
   const std::string err = fit_check(h->c, s.f);
@@ -187,23 +230,18 @@ size_t fit_shared_bytes(const bfmmm_handle* h, const FitSetup& s) {
 int fit_prepare(const SlotCheck& ck, const double* E, const int32_t* curves, FitSetup& s, CallBufs& b) {
   bfmmm_handle* h = ck.h;
   double *d_E = nullptr, *d_tab = nullptr;
-  int* d_curves = nullptr;
-  for (hipEvent_t& e : b.ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(b.get(&d_E, (size_t)s.f.G * h->c.d.P));
+  int32_t* d_curves = nullptr;
+  Timer project;
+  HIPCHK(b.timers({&project}));
+  HIPCHK(b.put(h, &d_E, E, (size_t)s.f.G * h->c.d.P));
   HIPCHK(b.get(&d_tab, (size_t)s.CS * s.f.G * (size_t)s.NJ));
-  HIPCHK(copy_sync(h, d_E, E, sizeof(double) * (size_t)s.f.G * h->c.d.P, hipMemcpyHostToDevice));
-  if (curves) {
-    HIPCHK(b.get(&d_curves, (size_t)s.m));
-    HIPCHK(copy_sync(h, d_curves, curves, sizeof(int32_t) * (size_t)s.m, hipMemcpyHostToDevice));
-  }
+  if (curves) HIPCHK(b.put(h, &d_curves, curves, (size_t)s.m));
   s.f.E = d_E; s.f.curves = d_curves; s.f.tab = d_tab;
-  for (int q = 0; q < FIT_T_COUNT; ++q) { h->fit_ms[q] = 0; h->fit_launches[q] = 0; }
-  (void)hipEventRecord(b.ev[0], h->st);
-  const std::string err = launch_fit_project(h->c, s.f, h->st);
-  (void)hipEventRecord(b.ev[1], h->st);
+  reset_timers(h, PT_FIT_PROJECT, PT_FIT_REDUCE);
+  const std::string err = timed(project, h->st, [&] { return launch_fit_project(h->c, s.f, h->st); });
   if (!err.empty()) { (void)hipStreamSynchronize(h->st); return fail(ck.fn + ": " + err); }
   HIPCHK(hipStreamSynchronize(h->st));
-  fit_collect(h, b, 0, 1, FIT_T_PROJECT);
+  collect(h, project, PT_FIT_PROJECT);
   return 0;
 }
 
@@ -256,7 +294,7 @@ extern "C" int bfmmm_chain_curve_loglik(bfmmm_handle* h, int first_slot, int n_s
   const int64_t per_row = ck.CS();
   if (ck.capacity(capacity, (int64_t)n * per_row)) return 1;
   HIPCHK(hipSetDevice(h->device));
-  h->curve_ll_ms = 0;
+  reset_timers(h, PT_CURVE_LL, PT_CURVE_LL);
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(((size_t)256 << 20) / (sizeof(double) * (size_t)per_row))));
   CallBufs b;
   double* d_x = nullptr;
@@ -300,7 +338,7 @@ extern "C" int bfmmm_chain_loo(bfmmm_handle* h, int first_slot, int n_slots, int
   if (ck.budget_row(budget, per_row)) return 1;
   const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
   HIPCHK(hipSetDevice(h->device));
-  h->curve_ll_ms = 0;
+  reset_timers(h, PT_CURVE_LL, PT_CURVE_LL);
   CallBufs b;
   double* d_x = nullptr;
   HIPCHK(b.get(&d_x, (size_t)CS * (size_t)chunk));
@@ -331,17 +369,17 @@ extern "C" int bfmmm_chain_curve_fit(bfmmm_handle* h, int which, const double* E
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
   if (fit_prepare(ck, E, curves, s, b)) return 1;
+  Timer values;
+  HIPCHK(b.timers({&values}));
   int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (sizeof(double) * (size_t)per_curve)));
   chunk = std::min<int64_t>(std::min<int64_t>(chunk, s.m), std::max<int64_t>(1, (1LL << 30) / G));
   double* d_v = nullptr;
   HIPCHK(b.get(&d_v, (size_t)chunk * per_curve));
   return for_chunks(ck, s.m, chunk, [&](int64_t r0, int rows) {
-    (void)hipEventRecord(b.ev[2], h->st);
-    std::string err = launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st);
-    (void)hipEventRecord(b.ev[3], h->st);
+    std::string err = timed(values, h->st, [&] { return launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st); });
     if (err.empty() && copy_sync(h, out + (size_t)r0 * per_curve, d_v, sizeof(double) * (size_t)rows * per_curve, hipMemcpyDeviceToHost) != hipSuccess)
       err = "kernel or copy back failed";
-    if (err.empty()) fit_collect(h, b, 2, 3, FIT_T_VALUES);
+    if (err.empty()) collect(h, values, PT_FIT_VALUES);
     return err;
   });
 }
@@ -363,16 +401,13 @@ extern "C" int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double*
   const bool lds_rows = s.CS <= fit_lds_rows() && !g_curve_fit_route;
   const bool sort_ws = s.CS > fit_lds_rows();               // k_bands_quantiles_big sorts in a workspace
   const int NP = sort_ws ? bands_sort_pad((int)s.CS) : 0;
-  const size_t budget = budget_of(max_workspace_bytes);
-  const size_t shared = fit_shared_bytes(h, s);
   const size_t per_curve = sizeof(double) * (size_t)G * ((size_t)(2 + nq) + (lds_rows ? 0 : (size_t)s.CS + (size_t)NP));
-  if (budget < shared + per_curve)
-    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
-                std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
-  int64_t chunk = std::min<int64_t>(s.m, (int64_t)((budget - shared) / per_curve));
-  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (1LL << 30) / G));
+  int64_t chunk = 0;
+  if (ck.curve_chunk(budget_of(max_workspace_bytes), fit_shared_bytes(h, s), per_curve, s.m, G, &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
+  Timer first, reduce;      // k_fit_rows, or k_fit_values and then the sort and the moments of its values
+  HIPCHK(b.timers({&first, &reduce}));
   double *d_probs = nullptr, *d_out = nullptr, *d_v = nullptr, *d_w = nullptr;
   HIPCHK(b.get(&d_probs, 16));
   HIPCHK(b.get(&d_out, (size_t)chunk * G * (2 + nq)));
@@ -385,28 +420,26 @@ extern "C" int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double*
   double* d_q = d_out + 2 * (size_t)chunk * G;
   return for_chunks(ck, s.m, chunk, [&](int64_t r0, int rows) {
     const long long ncol = (long long)rows * G;
-    std::string err;
-    (void)hipEventRecord(b.ev[2], h->st);
-    if (lds_rows) {
-      err = launch_fit_rows(h->c, s.f, (int)r0, rows, d_probs, nq, d_mean, d_sd, d_q, h->st);
-      (void)hipEventRecord(b.ev[3], h->st);
-    } else {
-      err = launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st);
-      (void)hipEventRecord(b.ev[3], h->st);
-      if (err.empty()) err = launch_bands_quantiles(d_v, (int)s.CS, ncol, d_w, d_probs, nq, d_q, h->st);
-      // the sorted rows are in the workspace: the rule again, rounded as k_fit_rows rounds it
-      if (err.empty() && sort_ws) err = launch_fit_quantiles(d_w, NP, (int)s.CS, ncol, d_probs, nq, d_q, h->st);
-      if (err.empty()) err = launch_bands_moments(d_v, (int)s.CS, ncol, d_mean, d_sd, h->st);
-    }
-    (void)hipEventRecord(b.ev[4], h->st);
+    std::string err = timed(first, h->st, [&] {
+      return lds_rows ? launch_fit_rows(h->c, s.f, (int)r0, rows, d_probs, nq, d_mean, d_sd, d_q, h->st)
+                      : launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st);
+    });
+    if (err.empty() && !lds_rows)
+      err = timed(reduce, h->st, [&] {
+        std::string e = launch_bands_quantiles(d_v, (int)s.CS, ncol, d_w, d_probs, nq, d_q, h->st);
+        // the sorted rows are in the workspace: the rule again, rounded as k_fit_rows rounds it
+        if (e.empty() && sort_ws) e = launch_fit_quantiles(d_w, NP, (int)s.CS, ncol, d_probs, nq, d_q, h->st);
+        if (e.empty()) e = launch_bands_moments(d_v, (int)s.CS, ncol, d_mean, d_sd, h->st);
+        return e;
+      });
     if (err.empty() &&
         (hipMemcpyAsync(mean + (size_t)r0 * G, d_mean, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
          hipMemcpyAsync(sd + (size_t)r0 * G, d_sd, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
          copy_sync(h, quantiles + (size_t)r0 * G * nq, d_q, sizeof(double) * (size_t)ncol * nq, hipMemcpyDeviceToHost) != hipSuccess))
       err = "kernel or copy back failed";
     if (!err.empty()) return err;
-    fit_collect(h, b, 2, 3, lds_rows ? FIT_T_ROWS : FIT_T_VALUES);
-    if (!lds_rows) fit_collect(h, b, 3, 4, FIT_T_REDUCE);
+    collect(h, first, lds_rows ? PT_FIT_ROWS : PT_FIT_VALUES);
+    if (!lds_rows) collect(h, reduce, PT_FIT_REDUCE);
     return err;
   });
 }
@@ -426,16 +459,13 @@ extern "C" int bfmmm_chain_curve_bands_sim(bfmmm_handle* h, int which, const dou
     return fail(fn + ": 'G' above " + std::to_string(fit_sim_gmax()) + ": mean and sd of a curve's grid points stay in LDS beside its sort row");
   const bool sort_ws = s.CS > fit_lds_rows();               // C goes to a workspace row that k_bands_quantiles_big sorts
   const int NP = sort_ws ? bands_sort_pad((int)s.CS) : 0;
-  const size_t budget = budget_of(max_workspace_bytes);
-  const size_t shared = fit_shared_bytes(h, s);
   const size_t per_curve = sizeof(double) * (4 * (size_t)G + 1 + (sort_ws ? (size_t)s.CS + (size_t)NP : 0));
-  if (budget < shared + per_curve)
-    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
-                std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
-  int64_t chunk = std::min<int64_t>(s.m, (int64_t)((budget - shared) / per_curve));
-  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (1LL << 30) / G));
+  int64_t chunk = 0;
+  if (ck.curve_chunk(budget_of(max_workspace_bytes), fit_shared_bytes(h, s), per_curve, s.m, G, &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
+  Timer sim, sort, band;      // k_fit_sim; for long rows the sort of their maxima, then k_fit_sim_band
+  HIPCHK(b.timers({&sim, &sort, &band}));
   double *d_p = nullptr, *d_out = nullptr, *d_crit = nullptr, *d_c = nullptr, *d_w = nullptr;
   const double p = 1.0 - alpha;
   HIPCHK(b.get(&d_p, 16));
@@ -446,7 +476,7 @@ extern "C" int bfmmm_chain_curve_bands_sim(bfmmm_handle* h, int which, const dou
     HIPCHK(b.get(&d_w, (size_t)chunk * (size_t)NP));
   }
   HIPCHK(copy_sync(h, d_p, &p, sizeof(double), hipMemcpyHostToDevice));
-  for (int q = 0; q < 2; ++q) { h->band_sim_ms[q] = 0; h->band_sim_launches[q] = 0; }
+  reset_timers(h, PT_SIM, PT_SIM_REDUCE);
   if (fit_prepare(ck, E, curves, s, b)) return 1;
   double* d_mean = d_out;
   double* d_sd = d_out + (size_t)chunk * G;
@@ -454,17 +484,14 @@ extern "C" int bfmmm_chain_curve_bands_sim(bfmmm_handle* h, int which, const dou
   double* d_up = d_out + 3 * (size_t)chunk * G;
   return for_chunks(ck, s.m, chunk, [&](int64_t r0, int rows) {
     const size_t cnt = sizeof(double) * (size_t)rows * G;
-    (void)hipEventRecord(b.ev[2], h->st);
-    std::string err = launch_fit_sim(h->c, s.f, (int)r0, rows, p, d_mean, d_sd, d_crit, d_lo, d_up, d_c, h->st);
-    (void)hipEventRecord(b.ev[3], h->st);
-    if (sort_ws) {
-      if (err.empty()) err = launch_bands_quantiles(d_c, (int)s.CS, rows, d_w, d_p, 1, d_crit, h->st);
-      // the sorted rows are in the workspace: the rule again, rounded as k_fit_sim rounds it
-      if (err.empty()) err = launch_fit_quantiles(d_w, NP, (int)s.CS, rows, d_p, 1, d_crit, h->st);
-      (void)hipEventRecord(b.ev[4], h->st);
-      if (err.empty()) err = launch_fit_sim_band(d_mean, d_sd, d_crit, G, rows, d_lo, d_up, h->st);
-      (void)hipEventRecord(b.ev[5], h->st);
-    }
+    std::string err = timed(sim, h->st, [&] { return launch_fit_sim(h->c, s.f, (int)r0, rows, p, d_mean, d_sd, d_crit, d_lo, d_up, d_c, h->st); });
+    if (err.empty() && sort_ws)
+      err = timed(sort, h->st, [&] {
+        const std::string e = launch_bands_quantiles(d_c, (int)s.CS, rows, d_w, d_p, 1, d_crit, h->st);
+        // the sorted rows are in the workspace: the rule again, rounded as k_fit_sim rounds it
+        return e.empty() ? launch_fit_quantiles(d_w, NP, (int)s.CS, rows, d_p, 1, d_crit, h->st) : e;
+      });
+    if (err.empty() && sort_ws) err = timed(band, h->st, [&] { return launch_fit_sim_band(d_mean, d_sd, d_crit, G, rows, d_lo, d_up, h->st); });
     if (err.empty() &&
         ((mean && hipMemcpyAsync(mean + (size_t)r0 * G, d_mean, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
          (sd && hipMemcpyAsync(sd + (size_t)r0 * G, d_sd, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
@@ -473,10 +500,10 @@ extern "C" int bfmmm_chain_curve_bands_sim(bfmmm_handle* h, int which, const dou
          copy_sync(h, crit + r0, d_crit, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
       err = "kernel or copy back failed";
     if (!err.empty()) return err;
-    add_elapsed(b.ev[2], b.ev[3], &h->band_sim_ms[0], &h->band_sim_launches[0]);
+    collect(h, sim, PT_SIM);
     if (sort_ws) {
-      add_elapsed(b.ev[3], b.ev[4], &h->band_sim_ms[1], &h->band_sim_launches[1]);
-      add_elapsed(b.ev[4], b.ev[5], &h->band_sim_ms[0], &h->band_sim_launches[0]);
+      collect(h, sort, PT_SIM_REDUCE);
+      collect(h, band, PT_SIM);
     }
     return err;
   });
@@ -493,26 +520,21 @@ extern "C" int bfmmm_chain_similarity(bfmmm_handle* h, const int32_t* curves, in
   const std::string& fn = ck.fn;
   if (ck.ptrs({{"h", h}, {"mean", mean}})) return 1;
   const int n = h->c.d.n, C = h->nch;
+  int64_t m = 0;
   if (n_curves < 0) return fail(fn + ": 'n_curves' must not be negative");
-  if (curves)
-    for (int j = 0; j < n_curves; ++j)
-      if (curves[j] < 0 || curves[j] >= n)
-        return fail(fn + ": 'curves'[" + std::to_string(j) + "] = " + std::to_string(curves[j]) + " outside 0 .. " + std::to_string(n - 1));
-  const int64_t m = curves ? n_curves : n;
-  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, m * n) || ck.row_limit()) return 1;
+  if (ck.curve_list(curves, n_curves, &m) || ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, m * n) || ck.row_limit()) return 1;
   // a result row: its n entries of mean, of sd and of every chain's mean, and its curve index
   const size_t per_row = sizeof(double) * (size_t)n * (1 + (sd ? 1 : 0) + (chain_mean ? (size_t)C : 0)) + (curves ? sizeof(int32_t) : 0);
   if (ck.budget_row(budget_of(max_workspace_bytes), per_row)) return 1;
-  h->sim_ms = 0;
-  h->sim_launches = 0;
+  reset_timers(h, PT_SIMILARITY, PT_SIMILARITY);
   if (m == 0) return 0;
   const int64_t chunk = std::min<int64_t>(std::min<int64_t>(m, (int64_t)(budget_of(max_workspace_bytes) / per_row)), 1 << 30);
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
   double *d_mean = nullptr, *d_sd = nullptr, *d_cm = nullptr;
   int* d_curves = nullptr;
-  HIPCHK(hipEventCreate(&b.ev[0]));
-  HIPCHK(hipEventCreate(&b.ev[1]));
+  Timer kernel;
+  HIPCHK(b.timers({&kernel}));
   HIPCHK(b.get(&d_mean, (size_t)chunk * n));
   if (sd) HIPCHK(b.get(&d_sd, (size_t)chunk * n));
   if (chain_mean) HIPCHK(b.get(&d_cm, (size_t)chunk * C * n));
@@ -520,16 +542,9 @@ extern "C" int bfmmm_chain_similarity(bfmmm_handle* h, const int32_t* curves, in
   return for_chunks(ck, m, chunk, [&](int64_t r0, int rows) {
     if (curves && copy_sync(h, d_curves, curves + r0, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess)
       return std::string("copy of the curve list failed");
-    (void)hipEventRecord(b.ev[0], h->st);
-    std::string err = launch_similarity(h->c, first_slot, n_slots, d_curves, (int)r0, rows, d_mean, d_sd, d_cm, h->st);
-    (void)hipEventRecord(b.ev[1], h->st);
-    const size_t cnt = sizeof(double) * (size_t)rows * n;
-    if (err.empty() &&
-        ((sd && hipMemcpyAsync(sd + (size_t)r0 * n, d_sd, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         (chain_mean && hipMemcpyAsync(chain_mean + (size_t)r0 * C * n, d_cm, cnt * C, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         copy_sync(h, mean + (size_t)r0 * n, d_mean, cnt, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
-    if (err.empty()) add_elapsed(b.ev[0], b.ev[1], &h->sim_ms, &h->sim_launches);
+    std::string err = timed(kernel, h->st, [&] { return launch_similarity(h->c, first_slot, n_slots, d_curves, (int)r0, rows, d_mean, d_sd, d_cm, h->st); });
+    if (err.empty() && !stats_to_host(h, r0, rows, n, C, mean, d_mean, sd, d_sd, chain_mean, d_cm)) err = "kernel or copy back failed";
+    if (err.empty()) collect(h, kernel, PT_SIMILARITY);
     return err;
   });
 }
@@ -546,14 +561,11 @@ extern "C" int bfmmm_chain_curve_cov(bfmmm_handle* h, const double* E1, int G1, 
   if (G1 < 1) return fail(fn + ": 'G1' must be at least 1");
   if (E2 && G2 < 1) return fail(fn + ": 'G2' must be at least 1 where 'E2' is given");
   if (diagonal && E2) return fail(fn + ": 'diagonal' requires 'E2' to be null");
-  const int n = h->c.d.n, C = h->nch, P = h->c.d.P;
+  const int C = h->nch, P = h->c.d.P;
   if (!E2) G2 = G1;
+  int64_t m = 0, chunk = 0;
   if (n_curves < 0) return fail(fn + ": 'n_curves' must not be negative");
-  if (curves)
-    for (int j = 0; j < n_curves; ++j)
-      if (curves[j] < 0 || curves[j] >= n)
-        return fail(fn + ": 'curves'[" + std::to_string(j) + "] = " + std::to_string(curves[j]) + " outside 0 .. " + std::to_string(n - 1));
-  const int64_t m = curves ? n_curves : n;
+  if (ck.curve_list(curves, n_curves, &m)) return 1;
   const int64_t cells = diagonal ? (int64_t)G1 : (int64_t)G1 * G2;      // entries of a curve's result
   if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, m * cells) || ck.row_limit()) return 1;
   CovCall f;
@@ -565,53 +577,35 @@ extern "C" int bfmmm_chain_curve_cov(bfmmm_handle* h, const double* E1, int G1, 
   const size_t shared = sizeof(double) * (tab1 + tab2 + (size_t)G1 * P + (E2 ? (size_t)G2 * P : 0)) +
                         (curves ? sizeof(int32_t) * (((size_t)m + 1) & ~(size_t)1) : 0);
   const size_t per_curve = sizeof(double) * (size_t)cells * (1 + (sd ? 1 : 0) + (chain_mean ? (size_t)C : 0));
-  const size_t budget = budget_of(max_workspace_bytes);
-  if (budget < shared + per_curve)
-    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
-                std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
-  for (int q = 0; q < 2; ++q) { h->cov_ms[q] = 0; h->cov_launches[q] = 0; }
+  if (ck.curve_chunk(budget_of(max_workspace_bytes), shared, per_curve, m, cells, &chunk)) return 1;
+  reset_timers(h, PT_COV_PROJECT, PT_COV);
   if (m == 0) return 0;
-  int64_t chunk = std::min<int64_t>(m, (int64_t)((budget - shared) / per_curve));
-  chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, (1LL << 30) / cells));
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
   double *d_E1 = nullptr, *d_E2 = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_cm = nullptr;
-  int* d_curves = nullptr;
-  for (int e = 0; e < 4; ++e) HIPCHK(hipEventCreate(&b.ev[e]));
-  HIPCHK(b.get(&d_E1, (size_t)G1 * P));
+  int32_t* d_curves = nullptr;
+  Timer project, kernel;
+  HIPCHK(b.timers({&project, &kernel}));
+  HIPCHK(b.put(h, &d_E1, E1, (size_t)G1 * P));
   HIPCHK(b.get(&f.tab1, tab1));
-  HIPCHK(copy_sync(h, d_E1, E1, sizeof(double) * (size_t)G1 * P, hipMemcpyHostToDevice));
   if (E2) {
-    HIPCHK(b.get(&d_E2, (size_t)G2 * P));
+    HIPCHK(b.put(h, &d_E2, E2, (size_t)G2 * P));
     HIPCHK(b.get(&f.tab2, tab2));
-    HIPCHK(copy_sync(h, d_E2, E2, sizeof(double) * (size_t)G2 * P, hipMemcpyHostToDevice));
   }
-  if (curves) {
-    HIPCHK(b.get(&d_curves, (size_t)m));
-    HIPCHK(copy_sync(h, d_curves, curves, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice));
-  }
+  if (curves) HIPCHK(b.put(h, &d_curves, curves, (size_t)m));
   HIPCHK(b.get(&d_mean, (size_t)chunk * cells));
   if (sd) HIPCHK(b.get(&d_sd, (size_t)chunk * cells));
   if (chain_mean) HIPCHK(b.get(&d_cm, (size_t)chunk * C * cells));
   f.E1 = d_E1; f.E2 = d_E2; f.curves = d_curves;
-  (void)hipEventRecord(b.ev[0], h->st);
-  const std::string perr = launch_cov_project(h->c, f, h->st);
-  (void)hipEventRecord(b.ev[1], h->st);
+  const std::string perr = timed(project, h->st, [&] { return launch_cov_project(h->c, f, h->st); });
   if (!perr.empty()) { (void)hipStreamSynchronize(h->st); return fail(fn + ": " + perr); }
   HIPCHK(hipStreamSynchronize(h->st));
-  add_elapsed(b.ev[0], b.ev[1], &h->cov_ms[0]);
-  h->cov_launches[0] = E2 ? 2 : 1;
+  collect(h, project, PT_COV_PROJECT);
+  h->post_launches[PT_COV_PROJECT] = E2 ? 2 : 1;      // the tables filled
   return for_chunks(ck, m, chunk, [&](int64_t r0, int rows) {
-    (void)hipEventRecord(b.ev[2], h->st);
-    std::string err = launch_curve_cov(h->c, f, (int)r0, rows, d_mean, d_sd, d_cm, h->st);
-    (void)hipEventRecord(b.ev[3], h->st);
-    const size_t cnt = sizeof(double) * (size_t)rows * cells;
-    if (err.empty() &&
-        ((sd && hipMemcpyAsync(sd + (size_t)r0 * cells, d_sd, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         (chain_mean && hipMemcpyAsync(chain_mean + (size_t)r0 * C * cells, d_cm, cnt * C, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         copy_sync(h, mean + (size_t)r0 * cells, d_mean, cnt, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
-    if (err.empty()) add_elapsed(b.ev[2], b.ev[3], &h->cov_ms[1], &h->cov_launches[1]);
+    std::string err = timed(kernel, h->st, [&] { return launch_curve_cov(h->c, f, (int)r0, rows, d_mean, d_sd, d_cm, h->st); });
+    if (err.empty() && !stats_to_host(h, r0, rows, cells, C, mean, d_mean, sd, d_sd, chain_mean, d_cm)) err = "kernel or copy back failed";
+    if (err.empty()) collect(h, kernel, PT_COV);
     return err;
   });
 }

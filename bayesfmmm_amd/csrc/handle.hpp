@@ -22,6 +22,15 @@
 
 enum { FAM_TOTAL = 0, FAM_Z, FAM_PG, FAM_FACTOR, FAM_SWEEP, FAM_CHI, FAM_LOGLIK, FAM_REDUCE, FAM_COUNT };
 
+// The timers of the chain-slot calls (capi_chain.hip), from HIP events around their launches, and their public names: PT_CURVE_LL
+// is read by bfmmm_debug_get, the others by bfmmm_get_timing ("curve_fit": the sum of the four PT_FIT_*).  PT_SIM: k_fit_sim and
+// k_fit_sim_band, PT_SIM_REDUCE: the long-row sort; PT_COV_PROJECT counts the tables filled (1 or 2), not its launches.
+enum { PT_CURVE_LL = 0, PT_FIT_PROJECT, PT_FIT_ROWS, PT_FIT_VALUES, PT_FIT_REDUCE, PT_SIM, PT_SIM_REDUCE, PT_SIMILARITY,
+       PT_COV_PROJECT, PT_COV, PT_COUNT };
+inline constexpr const char* kPostNames[PT_COUNT] = {"curve_ll_ms", "curve_fit_project", "curve_fit_rows", "curve_fit_values",
+                                                     "curve_fit_reduce", "curve_sim", "curve_sim_reduce", "similarity",
+                                                     "curve_cov_project", "curve_cov"};
+
 struct bfmmm_handle {
   bfmmm_config cfg;
   int device = 0;
@@ -67,15 +76,8 @@ struct bfmmm_handle {
   double fam_ms[FAM_COUNT] = {0};
   int64_t fam_launches[FAM_COUNT] = {0};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double curve_ll_ms = 0;              // bfmmm_debug_get("curve_ll_ms"): device time of k_chain_curve_ll in the last call that ran it
-  double fit_ms[4] = {0};              // bfmmm_get_timing("curve_fit_project" / "_rows" / "_values" / "_reduce"; "curve_fit": their sum):
-  int64_t fit_launches[4] = {0};       // device time of the last bfmmm_chain_curve_fit / bfmmm_chain_curve_bands
-  double band_sim_ms[2] = {0};         // bfmmm_get_timing("curve_sim" / "curve_sim_reduce"): device time and launches of k_fit_sim (and
-  int64_t band_sim_launches[2] = {0};  // k_fit_sim_band) / of the long-row sort in the last bfmmm_chain_curve_bands_sim
-  double sim_ms = 0;                   // bfmmm_get_timing("similarity"): device time and launches of k_similarity in the last
-  int64_t sim_launches = 0;            // bfmmm_chain_similarity
-  double cov_ms[2] = {0};              // bfmmm_get_timing("curve_cov_project" / "curve_cov"): device time and launches of k_cov_project /
-  int64_t cov_launches[2] = {0};       // k_curve_cov in the last bfmmm_chain_curve_cov
+  double post_ms[PT_COUNT] = {0};      // the timers of the chain-slot calls (kPostNames): device time and launches of a kernel
+  int64_t post_launches[PT_COUNT] = {0};   // family in the last call that ran it
 };
 
 namespace bfmmm {

@@ -20,6 +20,14 @@ SWEEP_WARM = SWEEP_NU_Z | SWEEP_THETA
 
 MODEL_FUNCTIONAL, MODEL_MULTIVARIATE = 0, 1
 
+# One draw of every array of the model in the reference's shape: a letter per dimension, n, K, P, M, D of the sampler or 2.
+DRAW_DIMS = {"nu": "KP", "Phi": "KPM", "chi": "nM", "Z": "nK", "pi": "K", "alpha_3": "", "delta": "KM", "A": "K2", "gamma": "KPM",
+             "tau": "K", "sigma_sq": "", "loglik": "", "eta": "PDK", "xi": "PDMK", "gamma_xi": "PDMK", "tau_eta": "KD",
+             "delta_xi": "KMD", "A_xi": "K2D"}
+# what get_state also answers: diagnostic vectors of fixed length
+STATE_ONLY = {"status": (1,), "stamps": (64,), "wgtrace": (3072,), "ztrace": (3 * 8192,), "zphase": (8 * 8192,), "fct": (8,)}
+STAT_NAMES = ("rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd")
+
 
 def _dp(a):
     return a.ctypes.data_as(_lib.c_double_p)
@@ -112,13 +120,22 @@ class Sampler:
             pass
 
     # ---- shapes of the reference's objects ----
+    def _draw_shape(self, name):
+        size = {"n": self.n, "K": self.K, "P": self.P, "M": self.M, "D": self.D, "2": 2}
+        return tuple(size[c] for c in DRAW_DIMS[name])
+
     def _state_shape(self, name):
-        n, K, P, M = self.n, self.K, self.P, self.M
-        return {"nu": (K, P), "Phi": (K, P, M), "chi": (n, M), "Z": (n, K), "pi": (K,), "alpha_3": (1,),
-                "delta": (K, M), "A": (K, 2), "gamma": (K, P, M), "tau": (K,), "sigma_sq": (1,),
-                "loglik": (1,), "status": (1,), "stamps": (64,), "wgtrace": (3072,), "ztrace": (3 * 8192,), "zphase": (8 * 8192,), "fct": (8,),
-                "eta": (P, self.D, K), "xi": (P, self.D, M, K), "gamma_xi": (P, self.D, M, K),
-                "tau_eta": (K, self.D), "delta_xi": (K, M, self.D), "A_xi": (K, 2, self.D)}[name]
+        return STATE_ONLY[name] if name in STATE_ONLY else self._draw_shape(name) or (1,)
+
+    def _slots(self, first_slot, n_slots):
+        return self.T - int(first_slot) if n_slots is None else int(n_slots)
+
+    def _curve_list(self, curves):
+        """(the index array, which must outlive the call; its pointer; the curves of the result), all n where curves is None"""
+        if curves is None:
+            return None, None, self.n
+        idx = np.ascontiguousarray(curves, dtype=np.int32).reshape(-1)
+        return idx, idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size
 
     def set_state(self, **kw):
         for name, v in kw.items():
@@ -156,12 +173,7 @@ class Sampler:
 
     def get_chain(self, name, n_slots=None):
         T = self.T if n_slots is None else n_slots
-        shp = {"nu": (self.K, self.P, T), "chi": (self.n, self.M, T), "Z": (self.n, self.K, T), "pi": (self.K, T),
-               "alpha_3": (T,), "delta": (self.K, self.M, T), "A": (self.K, 2, T), "sigma_sq": (T,),
-               "tau": (T, self.K), "gamma": (self.K, self.P, self.M, T), "Phi": (self.K, self.P, self.M, T),
-               "loglik": (T,), "eta": (self.P, self.D, self.K, T), "xi": (self.P, self.D, self.M, self.K, T),
-               "gamma_xi": (self.P, self.D, self.M, self.K, T), "tau_eta": (self.K, self.D, T),
-               "delta_xi": (self.K, self.M, self.D, T), "A_xi": (self.K, 2, self.D, T)}[name]
+        shp = (T, self.K) if name == "tau" else self._draw_shape(name) + (T,)      # tau: slot fastest
         out = np.zeros(shp, order="F")
         _lib.check(self.lib.bfmmm_get_chain(self.h, name.encode(), T, _dp(out), out.size))
         return out
@@ -170,24 +182,19 @@ class Sampler:
         """Split R-hat, bulk / tail ESS, ESS and MCSE of the mean, mean and sd of chain slots [first_slot, first_slot + n_slots)
         of `name` (a get_chain name) over every chain of the batch, computed on the device (bfmmm_chain_diagnostics).
         Returns a dict of the seven statistics, each shaped like one draw of `name` (Z: (n, K); tau: (K,))."""
-        T = self.T - int(first_slot) if n_slots is None else int(n_slots)
-        shp = {"nu": (self.K, self.P), "chi": (self.n, self.M), "Z": (self.n, self.K), "pi": (self.K,), "alpha_3": (), "delta": (self.K, self.M),
-               "A": (self.K, 2), "sigma_sq": (), "tau": (self.K,), "gamma": (self.K, self.P, self.M), "Phi": (self.K, self.P, self.M),
-               "loglik": (), "eta": (self.P, self.D, self.K), "xi": (self.P, self.D, self.M, self.K),
-               "gamma_xi": (self.P, self.D, self.M, self.K), "tau_eta": (self.K, self.D), "delta_xi": (self.K, self.M, self.D),
-               "A_xi": (self.K, 2, self.D)}.get(name, (1,))
+        T = self._slots(first_slot, n_slots)
+        shp = self._draw_shape(name) if name in DRAW_DIMS else (1,)
         cnt = int(np.prod(shp, dtype=np.int64))
         outs = [np.zeros(cnt) for _ in range(7)]
         _lib.check(self.lib.bfmmm_chain_diagnostics(self.h, name.encode(), int(first_slot), T, int(max_workspace_bytes),
                                                     *[_dp(o) for o in outs], cnt))
-        names = ("rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd")
-        return {k: o.reshape(shp, order="F") for k, o in zip(names, outs)}
+        return {k: o.reshape(shp, order="F") for k, o in zip(STAT_NAMES, outs)}
 
     def curve_loglik(self, first_slot=0, n_slots=None):
         """The marginal log-density (scores integrated out) of every curve under chain slots [first_slot, first_slot + n_slots)
         of every chain of the batch, computed on the device from the resident per-curve statistics (bfmmm_chain_curve_loglik;
         DESIGN.md 7d).  Label- and sign-invariant.  Returns an (n, C, S) array."""
-        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
+        S = self._slots(first_slot, n_slots)
         out = np.zeros((self.n, self.n_chains, max(S, 0)))
         _lib.check(self.lib.bfmmm_chain_curve_loglik(self.h, int(first_slot), S, _dp(out), out.size))
         return out
@@ -196,18 +203,17 @@ class Sampler:
         """The seven statistics of `diagnostics` for each curve's log-density (`curve_loglik`), which never leaves the device
         (bfmmm_chain_curve_diagnostics).  Where the R-hat of nu, Phi or Z reports a label switch between chains, this one
         reports mixing, curve by curve.  Returns a dict of arrays of shape (n,)."""
-        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
+        S = self._slots(first_slot, n_slots)
         outs = [np.zeros(self.n) for _ in range(7)]
         _lib.check(self.lib.bfmmm_chain_curve_diagnostics(self.h, int(first_slot), S, int(max_workspace_bytes),
                                                           *[_dp(o) for o in outs], self.n))
-        names = ("rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd")
-        return dict(zip(names, outs))
+        return dict(zip(STAT_NAMES, outs))
 
     def loo(self, first_slot=0, n_slots=None, max_workspace_bytes=0):
         """PSIS-LOO and WAIC over curves from the chain slots of every chain, pooled (bfmmm_chain_loo): the dict api.psis_loo
         returns for the (n, C * S) matrix `curve_loglik` holds, without that matrix leaving the device."""
         from . import api
-        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
+        S = self._slots(first_slot, n_slots)
         outs = [np.zeros(self.n) for _ in range(6)]
         _lib.check(self.lib.bfmmm_chain_loo(self.h, int(first_slot), S, int(max_workspace_bytes), *[_dp(o) for o in outs], self.n))
         pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs))
@@ -221,12 +227,8 @@ class Sampler:
         Em = np.ascontiguousarray(E, dtype=np.float64)
         if Em.ndim != 2 or Em.shape[1] != self.P:
             raise ValueError(f"E must be a G x {self.P} matrix in the sampler's basis")
-        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
-        if curves is None:
-            idx, pc, m = None, None, self.n
-        else:
-            idx = np.ascontiguousarray(curves, dtype=np.int32).reshape(-1)
-            pc, m = idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size
+        S = self._slots(first_slot, n_slots)
+        idx, pc, m = self._curve_list(curves)
         return w, Em, S, idx, pc, m
 
     def curve_fit(self, E, which="fit", curves=None, first_slot=0, n_slots=None):
@@ -273,12 +275,8 @@ class Sampler:
         in any order (default: all n); columns are all curves.  per_chain: also each chain's own mean, which shows whether the
         chains agree on the clustering where their labels differ.
         Returns {"mean": (m, n), "sd": (m, n) if sd, "chain_mean": (m, C, n) if per_chain}."""
-        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
-        if curves is None:
-            idx, pc, m = None, None, self.n
-        else:
-            idx = np.ascontiguousarray(curves, dtype=np.int32).reshape(-1)
-            pc, m = idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size
+        S = self._slots(first_slot, n_slots)
+        idx, pc, m = self._curve_list(curves)
         out = {"mean": np.zeros((m, self.n))}
         if sd:
             out["sd"] = np.zeros((m, self.n))
@@ -305,12 +303,8 @@ class Sampler:
             return Bm
         E1m = basis(E, "E")
         E2m = None if E2 is None else basis(E2, "E2")
-        S = self.T - int(first_slot) if n_slots is None else int(n_slots)
-        if curves is None:
-            idx, pc, m = None, None, self.n
-        else:
-            idx = np.ascontiguousarray(curves, dtype=np.int32).reshape(-1)
-            pc, m = idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size
+        S = self._slots(first_slot, n_slots)
+        idx, pc, m = self._curve_list(curves)
         G1 = E1m.shape[0]
         G2 = G1 if E2m is None else E2m.shape[0]
         cell = (G1,) if diagonal else (G1, G2)
