@@ -37,6 +37,7 @@ SYMBOLS = {
                                                 C.c_int, c_double_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "bfmmm_select_chain": (C.c_int, [C.c_void_p, C.c_int]),
     "bfmmm_n_chains": (C.c_int, [C.c_void_p]),
+    "bfmmm_selected_chain": (C.c_int, [C.c_void_p]),
     "bfmmm_set_chain_id_stride": (C.c_int, [C.c_void_p, C.c_uint32]),
     "bfmmm_gather_best": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, c_double_p, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "bfmmm_set_covariates": (C.c_int, [C.c_void_p, c_double_p, C.c_int, C.c_int]),
@@ -69,6 +70,9 @@ SYMBOLS = {
     "bfmmm_chain_similarity": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int64, c_double_p, c_double_p,
                                          c_double_p, C.c_int64]),
     "bfmmm_set_similarity_block": (None, [C.c_int]),
+    "bfmmm_chain_similarity_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, c_double_p, C.c_int64, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), c_double_p]),
+    "bfmmm_get_slot": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, c_double_p, C.c_int64]),
     "bfmmm_chain_curve_cov": (C.c_int, [C.c_void_p, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
                                         C.c_int, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int64]),
     "bfmmm_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, c_double_p, C.c_int64, c_int64_p]),

@@ -439,6 +439,7 @@ extern "C" int bfmmm_select_chain(bfmmm_handle* h, int q) {
   return 0;
 }
 extern "C" int bfmmm_n_chains(const bfmmm_handle* h) { return h ? h->nch : 0; }
+extern "C" int bfmmm_selected_chain(const bfmmm_handle* h) { return h ? h->sel : -1; }
 extern "C" int bfmmm_set_chain_id_stride(bfmmm_handle* h, uint32_t stride) {
   if (!h || stride < 1) return fail("bfmmm_set_chain_id_stride: bad arguments");
   h->c.chain_id_stride = stride;

@@ -1,6 +1,7 @@
 // C ABI of the sampler (include/bfmmm.h), what is read off the chain slots after a run: the chain arrays, their convergence
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
-// their simultaneous bands, the pooled co-membership matrix of the curves, the pooled per-curve covariance surfaces.
+// their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
+// per-curve covariance surfaces.
 // An entry point is its argument checks (SlotCheck: slots, curve selection, workspace plan), its workspace and the event pairs
 // that time its launches into the handle's PT_* timers (CallBufs owns both) and one for_chunks.
 #include "handle.hpp"
@@ -81,6 +82,14 @@ struct SlotCheck {
       return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
                   std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
     *chunk = std::min<int64_t>(std::min<int64_t>(m, (int64_t)((budget - shared) / per_curve)), std::max<int64_t>(1, (1LL << 30) / cells));
+    return 0;
+  }
+  // the same for the blocks of bfmmm_chain_similarity_loss: *chunk blocks fit the budget, at most `blocks` and 2^30
+  int block_chunk(size_t budget, size_t shared, size_t per_block, int64_t blocks, int64_t* chunk) const {
+    if (budget < shared + per_block)
+      return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_block) + " bytes one block needs (" +
+                  std::to_string(shared) + " shared by all blocks + " + std::to_string(per_block) + " per block)");
+    *chunk = std::min<int64_t>(std::min<int64_t>(blocks, (int64_t)((budget - shared) / per_block)), 1 << 30);
     return 0;
   }
 };
@@ -547,6 +556,79 @@ extern "C" int bfmmm_chain_similarity(bfmmm_handle* h, const int32_t* curves, in
     if (err.empty()) collect(h, kernel, PT_SIMILARITY);
     return err;
   });
+}
+
+// ---- the least-squares draw of the clustering (kernels_similarity.hip) -------------------------------------------
+// loss(q, t) = sum_ij (d_ij(q, t) - mean_ij)^2 of every draw, in chunks of consecutive 64 x 64 blocks of the upper triangle: a
+// chunk's per-block sums go through k_similarity_loss_reduce into the loss vector, which stays on the device for diag_launch.
+extern "C" int bfmmm_chain_similarity_loss(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes, double* loss,
+                                           int64_t capacity, int32_t* best_chain, int32_t* best_slot, double* stats) {
+  const SlotCheck ck{"bfmmm_chain_similarity_loss", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"loss", loss}}) || ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, ck.CS()) || ck.row_limit())
+    return 1;
+  const int C = h->nch, S = n_slots;
+  const size_t N = (size_t)ck.CS();
+  const int64_t blocks = similarity_loss_blocks(h->c.d.n);
+  // shared by all blocks: the loss vector and, where asked for, the seven statistics and the workspace of their row; a block: its N sums
+  const size_t stat_doubles = stats ? 7 + diag_row_ws_doubles(C, S) : 0;
+  int64_t chunk = 0;
+  if (ck.block_chunk(budget_of(max_workspace_bytes), sizeof(double) * (N + stat_doubles), sizeof(double) * N, blocks, &chunk)) return 1;
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_SIM_LOSS, PT_SIM_LOSS_REDUCE);
+  CallBufs b;
+  double *d_loss = nullptr, *d_part = nullptr, *d_stat = nullptr;
+  Timer kernel, reduce;
+  HIPCHK(b.timers({&kernel, &reduce}));
+  HIPCHK(b.get(&d_loss, N));
+  HIPCHK(b.get(&d_part, (size_t)chunk * N));
+  if (stats) HIPCHK(b.get(&d_stat, stat_doubles));
+  const int rc = for_chunks(ck, blocks, chunk, [&](int64_t b0, int nb) {
+    std::string err = timed(kernel, h->st, [&] { return launch_similarity_loss(h->c, first_slot, n_slots, b0, nb, d_part, h->st); });
+    if (err.empty()) err = timed(reduce, h->st, [&] { return launch_similarity_loss_reduce(h->c, first_slot, n_slots, b0, nb, d_part, d_loss, h->st); });
+    if (err.empty() && (hipStreamSynchronize(h->st) != hipSuccess || hipGetLastError() != hipSuccess)) err = "kernel failed";
+    if (!err.empty()) return err;
+    collect(h, kernel, PT_SIM_LOSS);
+    collect(h, reduce, PT_SIM_LOSS_REDUCE);
+    return err;
+  });
+  if (rc) return rc;
+  if (stats) {
+    const std::string err = diag_launch(d_loss, 1, C, S, d_stat, 1, d_stat + 7, 1, h->st);
+    if (!err.empty()) { (void)hipStreamSynchronize(h->st); return fail(ck.fn + ": " + err); }
+    HIPCHK(copy_sync(h, stats, d_stat, sizeof(double) * 7, hipMemcpyDeviceToHost));
+  }
+  HIPCHK(copy_sync(h, loss, d_loss, sizeof(double) * N, hipMemcpyDeviceToHost));
+  // the first minimum in (chain, slot) order
+  size_t best = 0;
+  for (size_t o = 1; o < N; ++o)
+    if (loss[o] < loss[best]) best = o;
+  if (best_chain) *best_chain = (int32_t)(best / (size_t)S);
+  if (best_slot) *best_slot = first_slot + (int32_t)(best % (size_t)S);
+  return 0;
+}
+
+// One slot of `name` of the selected chain.
+extern "C" int bfmmm_get_slot(bfmmm_handle* h, const char* name, int slot, double* out, int64_t capacity) {
+  const std::string fn = "bfmmm_get_slot";
+  if (!h) return fail(fn + ": 'h' is null");
+  if (!name) return fail(fn + ": 'name' is null");
+  if (!out) return fail(fn + ": 'out' is null");
+  if (slot < 0 || slot >= h->T) return fail(fn + ": 'slot' out of range");
+  HIPCHK(hipSetDevice(h->device));
+  const std::string s(name);
+  const ChainArr a = chain_array(selc(h), h->T, s);
+  if (!a.p) return fail(fn + ": unknown name '" + s + "'");
+  if (capacity < a.len) return fail(fn + "(" + s + "): 'capacity' below " + std::to_string(a.len) + " entries");
+  HIPCHK(hipStreamSynchronize(h->st));
+  if (a.ps == 1) {
+    HIPCHK(copy_sync(h, out, a.p + (size_t)a.ss * slot, sizeof(double) * (size_t)a.len, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  // slot fastest on the device (tau): the slot's len entries lie ps doubles apart, one strided copy
+  HIPCHK(hipMemcpy2DAsync(out, sizeof(double), a.p + (size_t)a.ss * slot, sizeof(double) * (size_t)a.ps, sizeof(double), (size_t)a.len,
+                          hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  return 0;
 }
 
 // ---- pooled per-curve covariance surfaces from the chain slots (kernels_curve_cov.hip) ------------------------

@@ -115,6 +115,15 @@ std::string launch_fit_sim_band(const double* mean, const double* sd, const doub
 std::string launch_similarity(const Ctx& c, int first_slot, int n_slots, const int* curves, int r0, int rows, double* mean, double* sd,
                               double* chain_mean, hipStream_t st);
 extern int g_similarity_block;      // bfmmm_set_similarity_block: 0 the launcher decides, 1 blocks of 64 x 64, 2 of 16 x 64
+// The least-squares loss of every draw against that mean over the 64 x 64 blocks (rb, cb), rb <= cb, of the full
+// matrix, numbered rows first: similarity_loss_blocks(n) of them.  launch_similarity_loss: partial[b N + q S + t], the sum of
+// (d - mean)^2 over block b0 + b of draw (q, t), for b < nb (N = C n_slots; device).  launch_similarity_loss_reduce:
+// loss[q S + t] = sum of w partial over those blocks in order, w = 1 for rb = cb and 2 above, continued from what loss holds
+// where b0 > 0.
+long long similarity_loss_blocks(int n);
+std::string launch_similarity_loss(const Ctx& c, int first_slot, int n_slots, long long b0, long long nb, double* partial, hipStream_t st);
+std::string launch_similarity_loss_reduce(const Ctx& c, int first_slot, int n_slots, long long b0, long long nb, const double* partial,
+                                          double* loss, hipStream_t st);
 
 // ---- kernels_curve_cov.hip ----
 // One call of bfmmm_chain_curve_cov: the evaluation bases E1 (G1 x P) and E2 (G2 x P; null: E2 = E1, G2 = G1), whether only the

@@ -287,6 +287,47 @@ class Sampler:
                                                    _dp(out["chain_mean"]) if per_chain else None, m * self.n))
         return out
 
+    def similarity_loss(self, first_slot=0, n_slots=None, diagnostics=True, max_workspace_bytes=0):
+        """The least-squares loss of every draw of chain slots [first_slot, first_slot + n_slots) of every chain of the batch,
+        loss(q, t) = sum_ij (d_ij(q, t) - m_ij)^2 with m the pooled mean `similarity` returns, computed on the device
+        (bfmmm_chain_similarity_loss), and the draw that minimises it (Dahl 2006).  Label-invariant; with
+        diagnostics, split R-hat, ESS, MCSE, mean and sd of the loss trace tell whether the chains agree on the clustering.
+        Returns {"loss": (C, S), "chain": int, "slot": int (absolute), "min": float} and, with diagnostics, the seven
+        STAT_NAMES as floats."""
+        S = self._slots(first_slot, n_slots)
+        loss = np.zeros((self.n_chains, max(S, 0)))
+        chain, slot = C.c_int32(-1), C.c_int32(-1)
+        stats = np.zeros(7)
+        _lib.check(self.lib.bfmmm_chain_similarity_loss(self.h, int(first_slot), S, int(max_workspace_bytes), _dp(loss), loss.size,
+                                                        C.byref(chain), C.byref(slot), _dp(stats) if diagnostics else None))
+        out = {"loss": loss, "chain": chain.value, "slot": slot.value, "min": float(loss[chain.value, slot.value - int(first_slot)])}
+        if diagnostics:
+            out.update((k, float(v)) for k, v in zip(STAT_NAMES, stats))
+        return out
+
+    def get_slot(self, name, slot, chain=None):
+        """One slot of `name` (a get_chain name): get_chain(name)[..., slot] ("tau": [slot]) without the other slots
+        (bfmmm_get_slot).  chain: the chain to read (default: the selected one); the selection is restored afterwards."""
+        out = np.zeros(self._draw_shape(name) if name in DRAW_DIMS else (1,), order="F")
+        prev = self.lib.bfmmm_selected_chain(self.h)      # the handle's own record, whoever selected last
+        if chain is not None:
+            self.select_chain(chain)
+        try:
+            _lib.check(self.lib.bfmmm_get_slot(self.h, name.encode(), int(slot), _dp(out), out.size))
+        finally:
+            if chain is not None:
+                self.select_chain(prev)
+        return out
+
+    def representative_draw(self, names=("Z",), first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """The least-squares draw of the clustering (`similarity_loss` without its diagnostics) and the arrays `names` of that
+        draw, all in the draw's own consistent labelling.  Returns {"chain", "slot", "loss"} plus one array per name."""
+        r = self.similarity_loss(first_slot, n_slots, diagnostics=False, max_workspace_bytes=max_workspace_bytes)
+        out = {"chain": r["chain"], "slot": r["slot"], "loss": r["min"]}
+        for nm in names:
+            out[nm] = self.get_slot(nm, r["slot"], chain=r["chain"])
+        return out
+
     def curve_cov(self, E, E2=None, curves=None, sd=True, per_chain=False, diagonal=False, first_slot=0, n_slots=None,
                   max_workspace_bytes=0):
         """The pooled covariance surface of every curve: mean (and sd) over chain slots [first_slot, first_slot + n_slots) of

@@ -108,6 +108,7 @@ int bfmmm_create_from_basis_batch(const bfmmm_config* cfg, int device, const dou
                                   int P, int band, const double* Pmat, int pen_band, int n_chains, bfmmm_handle** out);
 int bfmmm_select_chain(bfmmm_handle* h, int q);
 int bfmmm_n_chains(const bfmmm_handle* h);
+int bfmmm_selected_chain(const bfmmm_handle* h);      /* the chain bfmmm_select_chain chose last (0 before any call); -1 for a null handle */
 int bfmmm_set_chain_id_stride(bfmmm_handle* h, uint32_t stride);
 
 /* Final gather of a multi-GPU multi-try (the reference keeps the best of its 1 + n_try chains, src/UserFunctions.cpp:302-325,
@@ -266,6 +267,31 @@ int bfmmm_chain_similarity(bfmmm_handle* h, const int32_t* curves, int n_curves,
                            int64_t max_workspace_bytes, double* mean, double* sd, double* chain_mean, int64_t capacity);
 void bfmmm_set_similarity_block(int block);
 
+/* The least-squares draw of the clustering (Dahl 2006): of the N = C n_slots draws of chain slots [first_slot,
+ * first_slot + n_slots) of EVERY chain of the batch, the one whose own co-membership matrix is closest to the pooled mean,
+ *   loss(q, t) = sum_i sum_j (d_ij(q, t) - m_ij)^2      over all n^2 ordered pairs, the diagonal included,
+ * with d as above and m the mean bfmmm_chain_similarity returns for the full matrix, bit for bit (it is formed again on the
+ * device and never stored).  A sum over k inside a sum over pairs: label-invariant, so the minimiser is a real draw in one
+ * consistent labelling whose nu, Phi and chi can be read next to its Z (bfmmm_get_slot), and loss(q, .) is a scalar trace of the
+ * whole clustering whose split R-hat says whether the chains agree on it.
+ *   loss[q n_slots + (t - first_slot)]   capacity >= C n_slots entries.
+ *   best_chain, best_slot (may be NULL)  the draw of smallest loss, the slot as an absolute slot index; ties go to the lowest
+ *                                        chain, then the lowest slot.
+ *   stats (NULL, or 7 doubles)           rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd of the loss trace over the chains,
+ *                                        as bfmmm_chain_diagnostics computes them, from the copy on the device.
+ * Only the 64 x 64 blocks on and above the diagonal of the matrix are visited; a block's sum counts twice above the diagonal
+ * (d_ij and d_ji are the same bits).  Every sum has a fixed order that depends on the position in the block and on the block's
+ * number alone, so the result does not depend on the chunk or on repeated calls.  Chunks of consecutive blocks keep everything the
+ * call allocates within max_workspace_bytes (0: 256 MiB): 8 N bytes per block, and shared by all blocks the 8 N bytes of the loss
+ * vector and, with stats, 56 bytes and the workspace of its row; a budget below one block is refused with the bytes needed.  At
+ * most 2^22 draws (n_chains x n_slots).  Runs on the sampler's stream and leaves its state and slots untouched. */
+int bfmmm_chain_similarity_loss(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes, double* loss,
+                                int64_t capacity, int32_t* best_chain, int32_t* best_slot, double* stats);
+
+/* One slot of `name` (a bfmmm_get_chain name) of the selected chain: what bfmmm_get_chain returns for that slot, without the
+ * others ("tau": its K entries); capacity >= the entries of one draw. */
+int bfmmm_get_slot(bfmmm_handle* h, const char* name, int slot, double* out, int64_t capacity);
+
 /* Pooled per-curve covariance surfaces under chain slots [first_slot, first_slot + n_slots) of EVERY chain of the batch, on the
  * rows of two evaluation bases E1 (G1 x P) and E2 (G2 x P), row-major in the sampler's basis.  With the scores
  * chi_im ~ N(0, 1), the covariance function of curve i under a draw is
@@ -312,6 +338,8 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * Of the last bfmmm_chain_curve_bands_sim (always measured): "curve_sim", the device time and launches of k_fit_sim (and, for rows
  * above 8192 draws, of the kernel that writes the band ends), and "curve_sim_reduce", those of the long rows' sort.
  * Of the last bfmmm_chain_similarity (always measured): "similarity", the device time and launches of its kernel.
+ * Of the last bfmmm_chain_similarity_loss (always measured): "similarity_loss", the device time and launches (one per chunk) of
+ * k_similarity_loss, and "similarity_loss_reduce", those of the kernel that adds a chunk's blocks into the loss vector.
  * Of the last bfmmm_chain_curve_cov (always measured): "curve_cov", the device time and launches (one per chunk) of k_curve_cov,
  * and "curve_cov_project", those of the projection that precedes them. */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
