@@ -873,6 +873,11 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
     const PgRoute& r0 = subs[0].r;
     const double v[6] = {r0.packed ? 1.0 : 0.0, (double)r0.KS, (double)r0.NKS, (double)r0.body, (double)r0.G, (double)r0.tail};
     memcpy(h->last_route, v, sizeof v);
+    // the sweep kernel every sub-batch launches, for bfmmm_debug_get("sweep_route"): decided from the run's Dims alone, by the
+    // function launch_sweep reads, so the record also holds for a run that only replays cached graphs
+    const SweepRoute sr = sweep_route_decide(c.d);
+    const double w[5] = {(double)sr.kernel, (double)sr.targ, c.d.mv ? 1.0 : 0.0, (double)sr.direct, (double)sr.threads};
+    memcpy(h->last_sweep, w, sizeof w);
   }
   // single chain: the scalar job of k_curve_chi rides the next iteration's k_pair_gram instead (its grid has NKS - 1 idle extra
   // workgroups); the run's flush kernel runs the last one
@@ -1072,6 +1077,21 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
     if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
     memcpy(out, h->last_route, sizeof h->last_route);
     *count = cnt;
+    return 0;
+  }
+  if (s == "sweep_route") {   // host-side record of the last bfmmm_run (run_impl)
+    const int64_t cnt = sizeof h->last_sweep / sizeof h->last_sweep[0];
+    if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
+    memcpy(out, h->last_sweep, sizeof h->last_sweep);
+    *count = cnt;
+    return 0;
+  }
+  if (s == "rss") {           // Dyn::rss of the selected chain: the sweep's RSS after a run whose mask has U_SIGMA and runs no chi pass
+    if (capacity < 1) return fail("bfmmm_debug_get: buffer too small");
+    Dyn dn;
+    if (dyn_get(h, dn)) return 1;
+    out[0] = dn.rss;
+    *count = 1;
     return 0;
   }
   if (s == kPostNames[PT_CURVE_LL]) {

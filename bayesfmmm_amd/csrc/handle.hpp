@@ -67,6 +67,7 @@ struct bfmmm_handle {
   bool g_valid = false;                // the cached graphs were captured for g_key
   int last_md = -1;
   double last_route[6] = {0, 0, 0, -1, 0, 0};  // bfmmm_debug_get("pg_route"): {packed, KS, NKS, body, G, tail} of sub-batch 0 of the last run
+  double last_sweep[5] = {-1, 0, 0, 0, 0};     // bfmmm_debug_get("sweep_route"): {kernel, template argument, mv, direct, block threads} of the last run
   int64_t tab_key = -1;                // (MD, mask) the step tables of k_sweep_chain were built for
   int launch_error = 0;
   int slot_base = 0;                   // chain slot of iteration i is i - slot_base (bfmmm_set_slot_base)

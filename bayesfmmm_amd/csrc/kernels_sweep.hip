@@ -1003,12 +1003,46 @@ __global__ void k_fill_slots(double* chain, const double* cur, size_t len, int s
 }
 
 // ---- host launchers -------------------------------------------------------------------------
+// The one decision of which sweep kernel a run launches (bfmmm_debug_get("sweep_route") reports it).
+SweepRoute sweep_route_decide(const Dims& d) {
+  SweepRoute r;
+  if (d.BW == 0 && d.BWP == 0 && d.A <= 8 * DG_RPL_MAX && d.P <= 64) {        // diagonal model: independent scalar chains per coordinate
+    r.kernel = 0;
+    r.targ = std::min((d.A + 7) / 8, DG_RPL_MAX);
+    r.threads = (8 * d.P + 63) / 64 * 64;
+    r.lds = (16 + (size_t)d.A * d.A) * sizeof(double) + ((size_t)d.A * d.A + (size_t)d.K * (d.M + 1) + 8) * sizeof(int) + 16;
+    return r;
+  }
+  const int swc_ph = (d.P + 1) / 2, swc_lrk = swc_ph <= 4 ? 4 : swc_ph <= 8 ? 8 : 16;      // lanes per rank of the row threads
+  const size_t swc_lds = (5 * (((size_t)d.A * d.P + 1) & ~(size_t)1) + 32 + (size_t)d.A * (32 + 2 * d.BW + 2) + 16) * sizeof(double) + 2 * ((size_t)d.A + 2) * sizeof(int4) +
+                         ((size_t)d.A * d.A + (size_t)d.A + 8) * sizeof(int) + 16;
+  if (d.P <= 32 && d.A * swc_lrk <= SWC_THREADS - 64 && d.BW <= 5 && swc_lds <= 160 * 1024) {      // fast path: the chain in one wave
+    r.kernel = 1;
+    r.targ = d.BW;
+    r.threads = 64 + (d.A * swc_lrk + 63) / 64 * 64;
+    r.lds = swc_lds;       // beyond 64 KB at small P and many directions (P = 8, A >= 71): opted in by prepare_sweep_kernels
+    return r;
+  }
+  const bool diag = (d.BW == 0 && d.BWP == 0);
+  size_t pf_len = (size_t)d.A * d.LG + (diag ? (size_t)d.P : (size_t)d.P * d.P);
+  auto lds_for = [&](size_t pf) {
+    const size_t doubles = (size_t)d.A * (d.P + 2 * d.BW) + 4 * (size_t)d.A * d.P + PMAX + PMAX + 2 * BWWIDE + 32 + 2 * pf;
+    return doubles * sizeof(double) + (size_t)d.A * d.A * sizeof(int) + 16;
+  };
+  if (pf_len > (size_t)NPF * SW_THREADS || lds_for(pf_len) > 160 * 1024) { r.direct = 1; pf_len = 0; }
+  r.lds = lds_for(pf_len);
+  r.threads = SW_THREADS;
+  if (r.lds <= 160 * 1024) r.kernel = 2;
+  return r;
+}
+
 int launch_sweep(const Ctx& c, hipStream_t st) {
   const Dims& d = c.d;
-  if (d.BW == 0 && d.BWP == 0 && d.A <= 8 * DG_RPL_MAX && d.P <= 64) {        // diagonal model: independent scalar chains per coordinate
-    const size_t lds = (16 + (size_t)d.A * d.A) * sizeof(double) + ((size_t)d.A * d.A + (size_t)d.K * (d.M + 1) + 8) * sizeof(int) + 16;
-    const dim3 grid(1, 1, c.nch), block((8 * d.P + 63) / 64 * 64);
-    switch ((d.A + 7) / 8) {
+  const SweepRoute r = sweep_route_decide(d);
+  const dim3 grid(1, 1, c.nch), block(r.threads);
+  const size_t lds = r.lds;
+  if (r.kernel == 0) {
+    switch (r.targ) {
       case 1: if (d.mv) hipLaunchKernelGGL((k_sweep_diag<1, true>), grid, block, lds, st, c); else hipLaunchKernelGGL((k_sweep_diag<1, false>), grid, block, lds, st, c); break;
       case 2: if (d.mv) hipLaunchKernelGGL((k_sweep_diag<2, true>), grid, block, lds, st, c); else hipLaunchKernelGGL((k_sweep_diag<2, false>), grid, block, lds, st, c); break;
       case 3: if (d.mv) hipLaunchKernelGGL((k_sweep_diag<3, true>), grid, block, lds, st, c); else hipLaunchKernelGGL((k_sweep_diag<3, false>), grid, block, lds, st, c); break;
@@ -1020,33 +1054,19 @@ int launch_sweep(const Ctx& c, hipStream_t st) {
     }
     return 0;
   }
-  const int swc_ph = (d.P + 1) / 2, swc_lrk = swc_ph <= 4 ? 4 : swc_ph <= 8 ? 8 : 16;      // lanes per rank of the row threads
-  const size_t swc_lds = (5 * (((size_t)d.A * d.P + 1) & ~(size_t)1) + 32 + (size_t)d.A * (32 + 2 * d.BW + 2) + 16) * sizeof(double) + 2 * ((size_t)d.A + 2) * sizeof(int4) +
-                         ((size_t)d.A * d.A + (size_t)d.A + 8) * sizeof(int) + 16;
-  if (d.P <= 32 && d.A * swc_lrk <= SWC_THREADS - 64 && d.BW <= 5 && swc_lds <= 160 * 1024) {      // fast path: the chain in one wave
-    const int nthr = 64 + (d.A * swc_lrk + 63) / 64 * 64;
-    const size_t lds = swc_lds;       // beyond 64 KB at small P and many directions (P = 8, A >= 71): opted in by prepare_sweep_kernels
-    switch (d.BW) {
-      case 0: hipLaunchKernelGGL(k_sweep_chain<0>, dim3(1, 1, c.nch), dim3(nthr), lds, st, c); break;
-      case 1: hipLaunchKernelGGL(k_sweep_chain<1>, dim3(1, 1, c.nch), dim3(nthr), lds, st, c); break;
-      case 2: hipLaunchKernelGGL(k_sweep_chain<2>, dim3(1, 1, c.nch), dim3(nthr), lds, st, c); break;
-      case 3: hipLaunchKernelGGL(k_sweep_chain<3>, dim3(1, 1, c.nch), dim3(nthr), lds, st, c); break;
-      case 4: hipLaunchKernelGGL(k_sweep_chain<4>, dim3(1, 1, c.nch), dim3(nthr), lds, st, c); break;
-      default: hipLaunchKernelGGL(k_sweep_chain<5>, dim3(1, 1, c.nch), dim3(nthr), lds, st, c); break;
+  if (r.kernel == 1) {
+    switch (r.targ) {
+      case 0: hipLaunchKernelGGL(k_sweep_chain<0>, grid, block, lds, st, c); break;
+      case 1: hipLaunchKernelGGL(k_sweep_chain<1>, grid, block, lds, st, c); break;
+      case 2: hipLaunchKernelGGL(k_sweep_chain<2>, grid, block, lds, st, c); break;
+      case 3: hipLaunchKernelGGL(k_sweep_chain<3>, grid, block, lds, st, c); break;
+      case 4: hipLaunchKernelGGL(k_sweep_chain<4>, grid, block, lds, st, c); break;
+      default: hipLaunchKernelGGL(k_sweep_chain<5>, grid, block, lds, st, c); break;
     }
     return 0;
   }
-  const bool diag = (d.BW == 0 && d.BWP == 0);
-  size_t pf_len = (size_t)d.A * d.LG + (diag ? (size_t)d.P : (size_t)d.P * d.P);
-  auto lds_for = [&](size_t pf) {
-    const size_t doubles = (size_t)d.A * (d.P + 2 * d.BW) + 4 * (size_t)d.A * d.P + PMAX + PMAX + 2 * BWWIDE + 32 + 2 * pf;
-    return doubles * sizeof(double) + (size_t)d.A * d.A * sizeof(int) + 16;
-  };
-  int direct = 0;
-  if (pf_len > (size_t)NPF * SW_THREADS || lds_for(pf_len) > 160 * 1024) { direct = 1; pf_len = 0; }
-  const size_t lds = lds_for(pf_len);
-  if (lds > 160 * 1024) return 1;
-  hipLaunchKernelGGL(k_sweep, dim3(1, 1, c.nch), dim3(SW_THREADS), lds, st, c, direct);
+  if (r.kernel != 2) return 1;
+  hipLaunchKernelGGL(k_sweep, grid, block, lds, st, c, r.direct);
   return 0;
 }
 

@@ -58,6 +58,15 @@ void launch_factor(const Ctx& c, hipStream_t st);
 void prepare_factor_kernels();
 
 // ---- kernels_sweep.hip ----
+// Which sweep kernel a run's Dims (MD set) take: everything sweep_route_decide decides, and all launch_sweep reads.
+struct SweepRoute {
+  int kernel = -1;          // 0 k_sweep_diag, 1 k_sweep_chain, 2 k_sweep; -1: the problem fits none of them
+  int targ = 0;             // k_sweep_diag: RPL (directions per lane); k_sweep_chain: BW; k_sweep: 0
+  int direct = 0;           // k_sweep: the column blocks and C_a are read from L2 at every step (no LDS staging)
+  int threads = 0;          // workgroup size
+  size_t lds = 0;           // dynamic LDS bytes
+};
+SweepRoute sweep_route_decide(const Dims& d);
 int launch_sweep(const Ctx& c, hipStream_t st);
 void launch_sweep_tables(const Ctx& c, hipStream_t st);
 size_t sweep_tab_ints(int A);

@@ -380,6 +380,12 @@ class Sampler:
         d["BWP"] = int(v[14])
         return d
 
+    def sweep_route(self):
+        """Which sweep kernel the last `run` launched (bfmmm_debug_get "sweep_route", recorded on the host)."""
+        v = self.debug("sweep_route", 8)
+        return dict(kernel=("diag", "chain", "general")[int(v[0])] if v[0] >= 0 else None, targ=int(v[1]), mv=bool(v[2]),
+                    direct=bool(v[3]), threads=int(v[4]))
+
     def set_profile(self, enable):
         _lib.check(self.lib.bfmmm_set_profile(self.h, int(enable)))
 

@@ -326,7 +326,14 @@ int bfmmm_chain_curve_cov(bfmmm_handle* h, const double* E1, int G1, const doubl
  * "pg_route": how sub-batch 0 of the last bfmmm_run ran its pair-Gram contraction, {packed (0 / 1), KS, NKS,
  * body (0 general, 1 single-chain, 2 chain loop, 3 chain loop with staged groups; -1 packed), G (chains per group; 0 packed),
  * tail (single-chain body only, a sum of flags: 4 the s-part workgroup runs its single-chain body, 8 the deferred
- * log-likelihood has a workgroup of its own; 0 otherwise)} as doubles, recorded on the host.  Returns the number of doubles written through *count. */
+ * log-likelihood has a workgroup of its own; 0 otherwise)} as doubles, recorded on the host;
+ * "sweep_route": which sweep kernel the last bfmmm_run launched, {kernel (0 k_sweep_diag, 1 k_sweep_chain, 2 k_sweep),
+ * template argument (directions per lane of k_sweep_diag, band half-width of k_sweep_chain, 0 for k_sweep), mv (the model's flag:
+ * k_sweep_diag's second template argument), direct (k_sweep without LDS staging), block threads} as doubles, recorded on the
+ * host from the decision the launcher reads (also right for a run that replays cached graphs); "rss" (1): the residual sum of
+ * squares in the chain's device state -- the sweep's YY - sum_a theta_a'(t_a + r_a) after a run whose mask has U_SIGMA, unless
+ * the run also had a chi pass (U_CHI with n_eigen > 0, or U_LOGLIK without U_SIGMA, or covariates), whose per-curve sums
+ * replace it.  Returns the number of doubles written through *count. */
 int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capacity, int64_t* count);
 
 /* Timing of the last bfmmm_run: milliseconds between HIP events recorded on the sampler's stream

@@ -85,7 +85,7 @@ SEED = 5                           # the run's RNG seed
 # cases
 # ---------------------------------------------------------------------------------------------------------------------
 class Case:
-    def __init__(self, name, kind, P, regime, deg=None, degs=None, n_int=None, K=2, M=2, nch=1, special=None):
+    def __init__(self, name, kind, P, regime, deg=None, degs=None, n_int=None, K=2, M=2, nch=1, special=None, pen_band=0):
         self.name, self.kind, self.P, self.regime, self.K, self.M, self.nch = name, kind, P, regime, K, M, nch
         self.deg, self.degs, self.n_int, self.special = deg, degs, n_int, special
         self.n, self.MD, self.A = 24, M + 1, K * (M + 1)
@@ -100,6 +100,8 @@ class Case:
             self.band, self.pen_band = sum(g * s for g, s in zip(degs, strides)), max(strides)
             self.BW = self.band if self.band <= BWMAX else BWMID if self.band <= BWMID else BWWIDE
             self.BWP = min(max(self.BW, self.pen_band), BWWIDE if self.BW > BWMAX else BWMAX)
+        elif kind == "step":      # a caller-supplied basis with one non-zero per row (B'B diagonal) and a penalty of band pen_band
+            self.band, self.pen_band, self.BW, self.BWP = 0, pen_band, 0, pen_band
         else:
             self.band = self.pen_band = self.BW = self.BWP = 0
         self.diag = self.BW == 0 and self.BWP == 0
@@ -108,7 +110,8 @@ class Case:
 
     @property
     def data_key(self):
-        return (self.kind, self.P, self.deg, tuple(self.degs or ()), self.K, self.M, self.regime == "stiff")
+        key = (self.kind, self.P, self.deg, tuple(self.degs or ()), self.K, self.M, self.regime == "stiff")
+        return key + (self.pen_band,) if self.kind == "step" else key
 
 
 _INST = [  # one per (band class, PP); among them P = 32 (= PP), 33, 64 (the build limit), P % 4 == 1, P % 4 == 2, a small P
@@ -152,7 +155,7 @@ STATE_SALT = {"mid_5x5-stiff": 1, "mid_6x6-stiff": 1, "wide_7x7-stiff": 1}
 
 def case_data(c):
     """n = 24 ragged curves.  spline: y, t lists, internal / boundary knots; tensor: y, basis rows B (the oracle's tensor
-    B-spline), P_mat; multivariate: Y (n x P)."""
+    B-spline), P_mat; multivariate: Y (n x P); step: y, t, one-hot basis rows B, P_mat (RW1, or I for pen_band 0)."""
     key = c.data_key
     if key in _data:
         return _data[key]
@@ -165,6 +168,11 @@ def case_data(c):
     sparse = c.regime == "stiff"
     if c.kind == "mv":
         d = dict(Y=rng.standard_normal((n, c.P)) * 2.0, Pmat=np.eye(c.P))
+    elif c.kind == "step":
+        ni = rng.integers(14, 31, size=n)
+        t = [np.sort(rng.uniform(0.0, 1.0, size=k)) for k in ni]
+        B = [np.eye(c.P)[np.minimum((x * c.P).astype(int), c.P - 1)] for x in t]
+        d = dict(y=[rng.standard_normal(k) * 2.0 for k in ni], t=t, B=B, Pmat=O.pmat_rw1(c.P) if c.pen_band else np.eye(c.P))
     elif c.kind == "spline":
         if sparse:
             sites = (np.arange(G) + rng.uniform(0.0, 1.0, size=G)) / G          # one site in each of G equal intervals
