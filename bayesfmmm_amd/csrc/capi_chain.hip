@@ -1,7 +1,7 @@
 // C ABI of the sampler (include/bfmmm.h), what is read off the chain slots after a run: the chain arrays, their convergence
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
-// per-curve covariance surfaces.
+// per-curve covariance surfaces, the label alignment against a pivot and the pooled cluster summaries under it.
 // An entry point is its argument checks (SlotCheck: slots, curve selection, workspace plan), its workspace and the event pairs
 // that time its launches into the handle's PT_* timers (CallBufs owns both) and one for_chunks.
 #include "handle.hpp"
@@ -9,6 +9,7 @@
 #include "../../include/bfmmm_entry.h"
 
 #include <algorithm>
+#include <cmath>
 #include <initializer_list>
 #include <utility>
 
@@ -688,6 +689,191 @@ extern "C" int bfmmm_chain_curve_cov(bfmmm_handle* h, const double* E1, int G1, 
     std::string err = timed(kernel, h->st, [&] { return launch_curve_cov(h->c, f, (int)r0, rows, d_mean, d_sd, d_cm, h->st); });
     if (err.empty() && !stats_to_host(h, r0, rows, cells, C, mean, d_mean, sd, d_sd, chain_mean, d_cm)) err = "kernel or copy back failed";
     if (err.empty()) collect(h, kernel, PT_COV);
+    return err;
+  });
+}
+
+// ---- label alignment against a pivot and the pooled cluster summaries (kernels_align.hip) ----------------------
+namespace {
+
+// (inner, outer) of the component axis of a chain array: element e = a + inner (k + K b), a < inner, b < outer; inner 0: no
+// component axis.  False: no array of that name.
+bool align_axis(const Dims& d, const std::string& name, int64_t* inner) {
+  const int64_t n = d.n, P = d.P, M = d.M, D = d.D;
+  const struct { const char* nm; int64_t inner; } axes[] = {
+      {"nu", 1}, {"Phi", 1}, {"gamma", 1}, {"Z", n}, {"pi", 1}, {"tau", 1}, {"delta", 1}, {"A", 1}, {"eta", P * D}, {"xi", P * D * M},
+      {"gamma_xi", P * D * M}, {"tau_eta", 1}, {"delta_xi", 1}, {"A_xi", 1}, {"chi", 0}, {"sigma_sq", 0}, {"alpha_3", 0}, {"loglik", 0}};
+  for (const auto& a : axes)
+    if (name == a.nm) { *inner = a.inner; return true; }
+  return false;
+}
+
+// every row perm[(q S + s) K + .] a permutation of 0 .. K - 1, or fail() naming the first draw that is not
+int perm_check(const SlotCheck& ck, const int32_t* perm) {
+  const int K = ck.h->c.d.K, S = ck.n_slots;
+  for (long long o = 0; o < ck.CS(); ++o) {
+    unsigned seen = 0;
+    for (int l = 0; l < K; ++l) {
+      const int32_t v = perm[o * K + l];
+      if (v < 0 || v >= K || (seen >> v & 1u))
+        return fail(ck.fn + ": 'perm' of chain " + std::to_string(o / S) + ", slot " + std::to_string(ck.first_slot + o % S) +
+                    " is not a permutation of 0 .. " + std::to_string(K - 1));
+      seen |= 1u << v;
+    }
+  }
+  return 0;
+}
+
+// nq in 0 .. 16, with probs inside [0, 1] and somewhere to put the quantiles where nq > 0
+int probs_check(const SlotCheck& ck, const double* probs, int nq, const double* quant) {
+  if (nq < 0 || nq > 16) return fail(ck.fn + ": 'nq' outside 0 .. 16");
+  if (nq > 0 && ck.ptrs({{"probs", probs}, {"quant", quant}})) return 1;
+  for (int q = 0; q < nq; ++q)
+    if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail(ck.fn + ": 'probs'[" + std::to_string(q) + "] outside [0, 1]");
+  return 0;
+}
+
+}  // namespace
+
+// perm and score of every draw against the pivot Zref: one launch of k_align_gram, one workgroup per draw.
+extern "C" int bfmmm_chain_align(bfmmm_handle* h, const double* Zref, int first_slot, int n_slots, int32_t* perm, double* score,
+                                 int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_align", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"Zref", Zref}, {"perm", perm}}) || ck.range() || ck.row_limit()) return 1;
+  const Dims& d = h->c.d;
+  const int64_t N = ck.CS();
+  if (ck.capacity(capacity, N * d.K)) return 1;
+  for (int64_t e = 0; e < (int64_t)d.n * d.K; ++e)
+    if (!std::isfinite(Zref[e]))
+      return fail(ck.fn + ": 'Zref'[" + std::to_string(e % d.n) + ", " + std::to_string(e / d.n) + "] is not finite");
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_ALIGN_GRAM, PT_ALIGN_GRAM);
+  CallBufs b;
+  double *d_ref = nullptr, *d_score = nullptr;
+  int32_t* d_perm = nullptr;
+  Timer gram;
+  HIPCHK(b.timers({&gram}));
+  HIPCHK(b.put(h, &d_ref, Zref, (size_t)d.n * d.K));
+  HIPCHK(b.get(&d_perm, (size_t)N * d.K));
+  HIPCHK(b.get(&d_score, (size_t)N));
+  return for_chunks(ck, 1, 1, [&](int64_t, int) {
+    std::string err = timed(gram, h->st, [&] { return launch_align_gram(h->c, d_ref, first_slot, n_slots, d_perm, d_score, h->st); });
+    if (err.empty() &&
+        ((score && hipMemcpyAsync(score, d_score, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         copy_sync(h, perm, d_perm, sizeof(int32_t) * (size_t)N * d.K, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (err.empty()) collect(h, gram, PT_ALIGN_GRAM);
+    return err;
+  });
+}
+
+// bfmmm_chain_diagnostics of `name` with every draw's components relabelled by its row of perm, and the quantiles of the same
+// gathered rows: k_align_gather, then diag_launch and launch_bands_quantiles as they are, in chunks of consecutive elements.
+extern "C" int bfmmm_chain_aligned_summary(bfmmm_handle* h, const char* name, const int32_t* perm, int first_slot, int n_slots,
+                                           const double* probs, int nq, int64_t max_workspace_bytes, double* rhat, double* ess_bulk,
+                                           double* ess_tail, double* ess_mean, double* mcse_mean, double* mean, double* sd, double* quant,
+                                           int64_t capacity) {
+  SlotCheck ck{"bfmmm_chain_aligned_summary", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"name", name}, {"perm", perm}, {"rhat", rhat}, {"ess_bulk", ess_bulk}, {"ess_tail", ess_tail},
+               {"ess_mean", ess_mean}, {"mcse_mean", mcse_mean}, {"mean", mean}, {"sd", sd}}) ||
+      ck.range() || ck.budget_sign(max_workspace_bytes))
+    return 1;
+  const Ctx& c = h->c;          // chain 0 of the batch
+  const ChainArr a = chain_array(c, h->T, name);
+  int64_t inner = 0;
+  if (!a.p || !align_axis(c.d, name, &inner)) return fail(ck.fn + ": unknown name '" + name + "'");
+  ck.tag = std::string("(") + name + ")";
+  if (ck.capacity(capacity, a.len) || ck.row_limit() || probs_check(ck, probs, nq, quant) || perm_check(ck, perm)) return 1;
+  const int C = h->nch, S = n_slots, K = c.d.K;
+  const size_t N = (size_t)ck.CS();
+  const bool sort_ws = nq > 0 && (long long)N > fit_lds_rows();      // k_bands_quantiles_big sorts in a workspace
+  const size_t NP = sort_ws ? (size_t)bands_sort_pad((int)N) : 0;
+  const size_t tier = diag_row_ws_doubles(C, S);
+  const size_t per_row = sizeof(double) * (N + tier + 7 + (size_t)nq + NP);
+  const size_t budget = budget_of(max_workspace_bytes);
+  if (ck.budget_row(budget, per_row)) return 1;
+  const int64_t chunk = std::min<int64_t>(a.len, (int64_t)(budget / per_row));
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_ALIGN_GATHER, PT_ALIGN_GATHER);
+  CallBufs b;
+  double *d_x = nullptr, *d_probs = nullptr;
+  int32_t* d_perm = nullptr;
+  Timer gather;
+  HIPCHK(b.timers({&gather}));
+  HIPCHK(b.get(&d_x, per_row / sizeof(double) * (size_t)chunk));
+  HIPCHK(b.put(h, &d_perm, perm, N * K));
+  HIPCHK(b.get(&d_probs, 16));
+  if (nq) HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
+  double* d_out = d_x + (size_t)chunk * N;
+  double* d_tier = d_out + 7 * (size_t)chunk;
+  double* d_q = d_tier + tier * (size_t)chunk;
+  double* d_w = d_q + (size_t)nq * (size_t)chunk;
+  double* const outs[7] = {rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
+  std::vector<double> hb(7 * (size_t)chunk);
+  return for_chunks(ck, a.len, chunk, [&](int64_t p0, int rows) {
+    std::string err = timed(gather, h->st, [&] {
+      return launch_align_gather(a.p, a.cov ? c.chain_bytes_cov : c.chain_bytes, a.ss, a.ps, first_slot, S, C, (int)p0, rows, d_perm, K, inner,
+                                 d_x, h->st);
+    });
+    if (err.empty()) err = diag_launch(d_x, rows, C, S, d_out, rows, d_tier, rows, h->st);
+    if (err.empty() && nq) err = launch_bands_quantiles(d_x, (int)N, rows, d_w, d_probs, nq, d_q, h->st);
+    if (err.empty() &&
+        ((nq && hipMemcpyAsync(quant + (size_t)p0 * nq, d_q, sizeof(double) * (size_t)rows * nq, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         copy_sync(h, hb.data(), d_out, sizeof(double) * 7 * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (!err.empty()) return err;
+    collect(h, gather, PT_ALIGN_GATHER);
+    for (int q = 0; q < 7; ++q) std::copy(hb.begin() + (size_t)q * rows, hb.begin() + (size_t)(q + 1) * rows, outs[q] + p0);
+    return err;
+  });
+}
+
+// Mean, sd and quantiles over the pooled draws of the K G cluster mean functions E nu_k with the labels aligned: k_align_project
+// into rows of C S values, then launch_bands_moments and launch_bands_quantiles as they are, in chunks of consecutive rows.
+extern "C" int bfmmm_chain_cluster_mean_bands(bfmmm_handle* h, const int32_t* perm, const double* E, int G, int first_slot, int n_slots,
+                                              const double* probs, int nq, int64_t max_workspace_bytes, double* mean, double* sd,
+                                              double* quant, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_cluster_mean_bands", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"perm", perm}, {"E", E}, {"mean", mean}, {"sd", sd}})) return 1;
+  if (G < 1) return fail(ck.fn + ": 'G' must be at least 1");
+  if (ck.range() || ck.budget_sign(max_workspace_bytes)) return 1;
+  const Ctx& c = h->c;
+  const int K = c.d.K, P = c.d.P;
+  const int64_t len = (int64_t)K * G;
+  if (ck.capacity(capacity, len, "rows") || ck.row_limit() || probs_check(ck, probs, nq, quant) || perm_check(ck, perm)) return 1;
+  const size_t N = (size_t)ck.CS();
+  const bool sort_ws = nq > 0 && (long long)N > fit_lds_rows();
+  const size_t NP = sort_ws ? (size_t)bands_sort_pad((int)N) : 0;
+  const size_t per_row = sizeof(double) * (N + 2 + (size_t)nq + NP);
+  const size_t budget = budget_of(max_workspace_bytes);
+  if (ck.budget_row(budget, per_row)) return 1;
+  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(len, (int64_t)(budget / per_row)), 65535);
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_ALIGN_PROJECT, PT_ALIGN_PROJECT);
+  CallBufs b;
+  double *d_v = nullptr, *d_E = nullptr, *d_probs = nullptr;
+  int32_t* d_perm = nullptr;
+  Timer project;
+  HIPCHK(b.timers({&project}));
+  HIPCHK(b.get(&d_v, per_row / sizeof(double) * (size_t)chunk));
+  HIPCHK(b.put(h, &d_E, E, (size_t)G * P));
+  HIPCHK(b.put(h, &d_perm, perm, N * K));
+  HIPCHK(b.get(&d_probs, 16));
+  if (nq) HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
+  double* d_mean = d_v + (size_t)chunk * N;
+  double* d_sd = d_mean + (size_t)chunk;
+  double* d_q = d_sd + (size_t)chunk;
+  double* d_w = d_q + (size_t)nq * (size_t)chunk;
+  return for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
+    std::string err = timed(project, h->st, [&] { return launch_align_project(c, d_E, G, d_perm, first_slot, n_slots, (int)r0, rows, d_v, h->st); });
+    if (err.empty()) err = launch_bands_moments(d_v, (int)N, rows, d_mean, d_sd, h->st);
+    if (err.empty() && nq) err = launch_bands_quantiles(d_v, (int)N, rows, d_w, d_probs, nq, d_q, h->st);
+    if (err.empty() &&
+        ((nq && hipMemcpyAsync(quant + (size_t)r0 * nq, d_q, sizeof(double) * (size_t)rows * nq, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         hipMemcpyAsync(mean + r0, d_mean, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+         copy_sync(h, sd + r0, d_sd, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (err.empty()) collect(h, project, PT_ALIGN_PROJECT);
     return err;
   });
 }

@@ -134,6 +134,19 @@ std::string launch_similarity_loss(const Ctx& c, int first_slot, int n_slots, lo
 std::string launch_similarity_loss_reduce(const Ctx& c, int first_slot, int n_slots, long long b0, long long nb, const double* partial,
                                           double* loss, hipStream_t st);
 
+// ---- kernels_align.hip ----
+// Label alignment against a pivot.  launch_align_gram: of every draw (q, t) of every chain and slots [first_slot,
+// first_slot + n_slots), perm[(q S + s) K + l], the exact maximiser of sum_l A[perm(l)][l], A = Z(q, t)' Zref (Zref n x K
+// column-major), and score[q S + s] (null: not written) that sum (all device).  launch_align_gather: diag_gather with the
+// component index k of element e = a + inner (k + K b) read from perm[k] of the draw (inner 0: no component axis).
+// launch_align_project: rows [r0, r0 + rows) (<= 65535) of the K G cluster mean functions on E (G x P), row = k + K g, into
+// V[q S + s + C S (row - r0)].
+std::string launch_align_gram(const Ctx& c, const double* Zref, int first_slot, int n_slots, int32_t* perm, double* score, hipStream_t st);
+std::string launch_align_gather(const double* base, size_t chain_bytes, long long ss, long long ps, int first, int S, int C, int p0, int P,
+                                const int32_t* perm, int K, long long inner, double* ws, hipStream_t st);
+std::string launch_align_project(const Ctx& c, const double* E, int G, const int32_t* perm, int first_slot, int n_slots, int r0, int rows,
+                                 double* V, hipStream_t st);
+
 // ---- kernels_curve_cov.hip ----
 // One call of bfmmm_chain_curve_cov: the evaluation bases E1 (G1 x P) and E2 (G2 x P; null: E2 = E1, G2 = G1), whether only the
 // diagonal g = h is wanted (E2 null), the curve of every result row of the call (null: curve r), the slot range and the call's

@@ -328,6 +328,82 @@ class Sampler:
             out[nm] = self.get_slot(nm, r["slot"], chain=r["chain"])
         return out
 
+    def align(self, pivot=None, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """Aligns the component labels of every draw of chain slots [first_slot, first_slot + n_slots) of every chain of the batch
+        to a pivot (the pivot method; bfmmm_chain_align): perm maximises sum_l (Z' Zref)[perm[l], l] exactly over
+        all K! permutations, so that Z[:, perm] is the draw in the pivot's labelling.  Labels only: eigenfunction signs are not
+        touched.  pivot: None for the `representative_draw` of the same slots, (chain, slot) for that draw (slot absolute), or an
+        (n, K) array.  Returns {"perm": (C, S, K) int32, "score": (C, S), "pivot": {"chain", "slot", "Z"} or None for an array,
+        "chain_perm": (C, K), each chain's most frequent permutation (the lexicographically smallest of several),
+        "modal_share": (C,), the share of the chain's draws that have it: below 1 the labels switch within the chain}."""
+        S = self._slots(first_slot, n_slots)
+        info = None
+        if pivot is None:
+            r = self.representative_draw(("Z",), first_slot, n_slots, max_workspace_bytes)
+            info = {"chain": r["chain"], "slot": r["slot"], "Z": r["Z"]}
+        elif isinstance(pivot, tuple) and len(pivot) == 2 and all(isinstance(v, (int, np.integer)) for v in pivot):
+            info = {"chain": int(pivot[0]), "slot": int(pivot[1]), "Z": self.get_slot("Z", int(pivot[1]), chain=int(pivot[0]))}
+        Zref = np.asfortranarray(info["Z"] if info is not None else pivot, dtype=np.float64)
+        if Zref.shape != (self.n, self.K):
+            raise ValueError(f"pivot must be None, (chain, slot) or an array of shape ({self.n}, {self.K})")
+        perm = np.zeros((self.n_chains, max(S, 0), self.K), dtype=np.int32)
+        score = np.zeros((self.n_chains, max(S, 0)))
+        _lib.check(self.lib.bfmmm_chain_align(self.h, _dp(Zref), int(first_slot), S, perm.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              _dp(score), perm.size))
+        chain_perm = np.zeros((self.n_chains, self.K), dtype=np.int32)
+        share = np.zeros(self.n_chains)
+        for q in range(self.n_chains):
+            rows, counts = np.unique(perm[q], axis=0, return_counts=True)      # rows in lexicographic order: argmax takes the first
+            chain_perm[q] = rows[int(np.argmax(counts))]
+            share[q] = counts.max() / float(S)
+        return {"perm": perm, "score": score, "pivot": info, "chain_perm": chain_perm, "modal_share": share}
+
+    def _perm_arg(self, perm, S):
+        p = np.ascontiguousarray(perm, dtype=np.int32)
+        if p.shape != (self.n_chains, S, self.K):
+            raise ValueError(f"perm must have shape ({self.n_chains}, {S}, {self.K}): align()['perm'] of the same slots")
+        return p
+
+    def aligned_summary(self, name, perm, probs=(0.025, 0.5, 0.975), first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """`diagnostics(name)` with every draw's components relabelled by its row of perm (`align`'s "perm" of the same slots),
+        and pooled quantiles of the same values, on the device (bfmmm_chain_aligned_summary): memberships with
+        credible intervals for "Z", and an R-hat of nu or Z that measures mixing rather than labelling.  Names without a component
+        axis are summarised as they are.  Returns the seven STAT_NAMES shaped like a draw, plus "quantiles": shape + (nq,) by
+        arma::quantile's rule, and "probs"."""
+        S = self._slots(first_slot, n_slots)
+        p = self._perm_arg(perm, S)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        shp = self._draw_shape(name) if name in DRAW_DIMS else (1,)
+        cnt = int(np.prod(shp, dtype=np.int64))
+        outs = [np.zeros(cnt) for _ in range(7)]
+        qs = np.zeros((cnt, pr.size))
+        _lib.check(self.lib.bfmmm_chain_aligned_summary(self.h, name.encode(), p.ctypes.data_as(C.POINTER(C.c_int32)), int(first_slot), S,
+                                                        _dp(pr) if pr.size else None, pr.size, int(max_workspace_bytes),
+                                                        *[_dp(o) for o in outs], _dp(qs) if pr.size else None, cnt))
+        out = {k: o.reshape(shp, order="F") for k, o in zip(STAT_NAMES, outs)}
+        out["quantiles"] = qs.reshape(shp + (pr.size,), order="F") if shp else qs.reshape((pr.size,))
+        out["probs"] = pr
+        return out
+
+    def cluster_mean_bands(self, E, perm, probs=(0.025, 0.5, 0.975), first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """Pointwise posterior mean, sd and quantiles of the K cluster mean functions E nu_k (E: G x P rows in the sampler's basis,
+        as in `curve_fit`) with the labels aligned by perm (`align`'s "perm" of the same slots) and the chains pooled, on the
+        device (bfmmm_chain_cluster_mean_bands); the reference's FMeanCI without rescale / trans_mats.  With
+        covariates set: the mean function at x = 0.  Returns {"mean": (K, G), "sd": (K, G), "quantiles": (K, G, nq), "probs"}."""
+        Em = np.ascontiguousarray(E, dtype=np.float64)
+        if Em.ndim != 2 or Em.shape[1] != self.P:
+            raise ValueError(f"E must be a G x {self.P} matrix in the sampler's basis")
+        S = self._slots(first_slot, n_slots)
+        p = self._perm_arg(perm, S)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        G, K = Em.shape[0], self.K
+        mean, sd, qs = np.zeros(K * G), np.zeros(K * G), np.zeros((K * G, pr.size))
+        _lib.check(self.lib.bfmmm_chain_cluster_mean_bands(self.h, p.ctypes.data_as(C.POINTER(C.c_int32)), _dp(Em), G, int(first_slot), S,
+                                                           _dp(pr) if pr.size else None, pr.size, int(max_workspace_bytes), _dp(mean),
+                                                           _dp(sd), _dp(qs) if pr.size else None, K * G))
+        return {"mean": mean.reshape((K, G), order="F"), "sd": sd.reshape((K, G), order="F"),
+                "quantiles": qs.reshape((K, G, pr.size), order="F"), "probs": pr}
+
     def curve_cov(self, E, E2=None, curves=None, sd=True, per_chain=False, diagonal=False, first_slot=0, n_slots=None,
                   max_workspace_bytes=0):
         """The pooled covariance surface of every curve: mean (and sd) over chain slots [first_slot, first_slot + n_slots) of

@@ -316,6 +316,45 @@ int bfmmm_chain_curve_cov(bfmmm_handle* h, const double* E1, int G1, const doubl
                           int n_curves, int first_slot, int n_slots, int64_t max_workspace_bytes, double* mean, double* sd,
                           double* chain_mean, int64_t capacity);
 
+/* Label alignment of the draws against a pivot (the pivot method, Marin, Mengersen & Robert 2005).  Independent
+ * chains, and a chain that switches, label the components differently; against one reference membership matrix Zref (host, n x K
+ * column-major: a real draw such as the least-squares one above, or any matrix of that shape, finite) every draw (q, t) of chain
+ * slots [first_slot, first_slot + n_slots) of EVERY chain of the batch gets
+ *   A[c][l] = sum_i Z_ic(q, t) Zref_il,     perm(q, t) = the maximiser over all K! permutations p of sum_l A[p(l)][l],
+ * so that column l of the aligned draw is column perm[l] of the draw; that trace is largest where |Z P - Zref|_F is smallest.  The
+ * maximum is exact over the device's own A (a recursion over the 2^K subsets, not greedy); among equal sums the
+ * lexicographically smallest permutation.  Labels only: signs and rotations of the eigenfunctions are not identified and not touched.
+ *   perm[(q n_slots + s) K + l]   capacity >= C n_slots K entries.
+ *   score[q n_slots + s]          that sum, A[p0][0] + (A[p1][1] + (..)).  NULL: not returned.
+ * The sum over i has a fixed order, so repeated calls give the same bits.  At most 2^22 draws (n_chains x n_slots).  Runs on the
+ * sampler's stream and leaves its state and slots untouched. */
+int bfmmm_chain_align(bfmmm_handle* h, const double* Zref, int first_slot, int n_slots, int32_t* perm, double* score, int64_t capacity);
+
+/* bfmmm_chain_diagnostics of `name` with the components of every draw relabelled by its row of perm (from bfmmm_chain_align, or
+ * any rows that are permutations of 0 .. K - 1): where element e of a draw has component index k, the value is read from
+ * component perm[k] of the same draw.  Arrays without a component axis (chi, sigma_sq, alpha_3, loglik) are summarised as they
+ * are.  The seven arrays are those of bfmmm_chain_diagnostics, capacity >= the entries of one draw; with the identity
+ * permutation they are its results bit for bit.  quant[q + nq e]: the nq <= 16 quantiles probs (inside [0, 1]) of element e over
+ * the pooled C n_slots draws by arma::quantile's rule, as bfmmm_post_col_quantiles computes them; nq = 0: probs and quant may be
+ * NULL.  Chunks of consecutive elements keep the gathered rows, their workspaces and results within max_workspace_bytes (0: 256
+ * MiB; rows of more than 8192 draws sort in a workspace from the same budget); the call also holds the 4 C n_slots K bytes of perm
+ * on the device.  A budget below one row is refused with the bytes needed.  At most 2^22 draws.  The results do not depend on the
+ * chunk.  Runs on the sampler's stream and leaves its state and slots untouched. */
+int bfmmm_chain_aligned_summary(bfmmm_handle* h, const char* name, const int32_t* perm, int first_slot, int n_slots, const double* probs,
+                                int nq, int64_t max_workspace_bytes, double* rhat, double* ess_bulk, double* ess_tail, double* ess_mean,
+                                double* mcse_mean, double* mean, double* sd, double* quant, int64_t capacity);
+
+/* The cluster mean functions on the rows of E (G x P, row-major in the sampler's basis) with the labels aligned and the chains
+ * pooled: of v_kg(q, s) = sum_p E_gp nu_{perm[k], p}(q, s) (p in order from 0) over the C n_slots draws,
+ *   mean[k + K g], sd[k + K g] (N - 1)   and   quant[q + nq (k + K g)]   (arma::quantile's rule; nq = 0: probs, quant may be NULL);
+ * capacity >= K G rows.  The coefficient table of the reference's FMeanCI, without its rescale / trans_mats.  With covariates
+ * set this is the mean function at x = 0 (eta is not added).  Chunks of consecutive rows keep the values, the sort workspace of
+ * rows of more than 8192 draws and the results within max_workspace_bytes (0: 256 MiB); E and perm are held beside them.  At
+ * most 2^22 draws.  Runs on the sampler's stream and leaves its state and slots untouched. */
+int bfmmm_chain_cluster_mean_bands(bfmmm_handle* h, const int32_t* perm, const double* E, int G, int first_slot, int n_slots,
+                                   const double* probs, int nq, int64_t max_workspace_bytes, double* mean, double* sd, double* quant,
+                                   int64_t capacity);
+
 /* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
  * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P: C_a = Prec_a^-1 as k_factor left it), "Lz" (A x P: L_a z_a of the sampled directions),
@@ -348,7 +387,9 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * Of the last bfmmm_chain_similarity_loss (always measured): "similarity_loss", the device time and launches (one per chunk) of
  * k_similarity_loss, and "similarity_loss_reduce", those of the kernel that adds a chunk's blocks into the loss vector.
  * Of the last bfmmm_chain_curve_cov (always measured): "curve_cov", the device time and launches (one per chunk) of k_curve_cov,
- * and "curve_cov_project", those of the projection that precedes them. */
+ * and "curve_cov_project", those of the projection that precedes them.
+ * Of the last bfmmm_chain_align / bfmmm_chain_aligned_summary / bfmmm_chain_cluster_mean_bands (always measured): "align_gram"
+ * (one launch), "align_gather" and "align_project" (one launch per chunk), the device time and launches of their own kernels. */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
