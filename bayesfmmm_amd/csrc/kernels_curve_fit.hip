@@ -12,20 +12,18 @@
 //                   kernels below (one draw each) read it coalesced.
 //   k_fit_rows      C S <= 8192.  A workgroup takes one curve and a tile of GT grid points: lane cs reads Z_i. and chi_i. of
 //                   its draw once, forms the draw's value of each of the tile's rows into LDS (fit_value), then mean and sd
-//                   of every row (k_bands_moments' fixed-order tree, two passes, N - 1), one bitonic sort of all the tile's
-//                   rows at once (padded with +inf) and the quantiles by the rule below.  (2 + nq) numbers per row leave.
+//                   of every row (row_mean_sd), one bitonic sort of all the tile's rows at once (padded with +inf) and the
+//                   quantiles (quantile5).  (2 + nq) numbers per row leave.
 //   k_fit_values    the same fit_value into a workspace out[((r G + g) CS) + cs]: the long rows (k_bands_quantiles_big and
 //                   k_bands_moments reduce them) and the host copy of bfmmm_chain_curve_fit.
-//   k_fit_quantiles the rule read off rows that are already sorted (k_bands_quantiles_big leaves them so in its workspace):
+//   k_fit_quantiles quantile5 read off rows that are already sorted (k_bands_quantiles_big leaves them so in its workspace):
 //                   kernels_bands.hip is compiled with contraction on, this file is not, and both tiers must round alike.
 //   k_fit_sim       simultaneous band of a curve: one workgroup owns one result row and never stores a value.
 //                   Three passes form every value again with the same fit_value: per-lane sums of tiles of FIT_SIM_GT grid
-//                   points in registers and k_fit_rows' tree -> mean(g) in LDS; the squares likewise -> sd(g); then per draw
+//                   points in registers and the block tree -> mean(g) in LDS; the squares likewise -> sd(g); then per draw
 //                   C(cs) = max_g |(v - mean(g)) / sd(g)| over the grid points with sd != 0.  C S <= 8192: C is sorted in LDS
 //                   and crit, lower, upper leave; longer rows: C goes to a workspace row that k_bands_quantiles_big sorts,
 //                   k_fit_quantiles reads crit off it and k_fit_sim_band writes the band ends.
-// Quantile rule (k_bands_quantiles', Hyndman and Fan definition 5): sorted s[0 .. N-1], p < 0.5 / N -> s[0],
-// p > (N - 0.5) / N -> s[N-1], else k = floor(N p + 0.5), w = (p - (k - 0.5) / N) N, (1 - w) s[k-1] + w s[min(k, N-1)].
 // fp64, every sum in a fixed order that depends on (curve, grid point, chain, slot) only, no atomics, no scratch: the bits
 // do not depend on the chunk, the tile or the grid.
 #include "model.hpp"
@@ -37,6 +35,8 @@
 
 // the interpolation of a quantile must round as the restatement does
 #pragma clang fp contract(off)
+
+#include "row_stats.hpp"
 
 namespace bfmmm {
 
@@ -152,31 +152,6 @@ __device__ __forceinline__ void fit_form(const FitArgs& a, int i, int g0, int gn
   }
 }
 
-__device__ inline double fit_quantile(const double* s, int T, double p) {
-  const double N = (double)T;
-  if (p < 0.5 / N) return s[0];
-  if (p > (N - 0.5) / N) return s[T - 1];
-  const int k = (int)floor(N * p + 0.5);
-  const double pk = ((double)k - 0.5) / N, w = (p - pk) * N;
-  return (1.0 - w) * s[k - 1] + w * s[min(k, T - 1)];
-}
-
-// one bitonic network over `rows` rows of NP (a power of two) in LDS at once: pair pr of a step exchanges e and e | jj inside its row
-__device__ __forceinline__ void fit_sort(double* s, int rows, int NP, int tid) {
-  const int half = rows * NP / 2;
-  for (int k = 2; k <= NP; k <<= 1)
-    for (int jj = k >> 1; jj > 0; jj >>= 1) {
-      __syncthreads();
-      for (int pr = tid; pr < half; pr += FIT_NT) {
-        const int e = ((pr & ~(jj - 1)) << 1) | (pr & (jj - 1)), partner = e | jj;
-        const bool up = ((e & (NP - 1)) & k) == 0;
-        const double x = s[e], y = s[partner];
-        if ((x > y) == up) { s[e] = y; s[partner] = x; }
-      }
-    }
-  __syncthreads();
-}
-
 struct FitRowArgs {
   int r0, GT, NP, tiles, nq;                                   // first result row of the chunk, tile, padded row, tiles per curve
   const double* probs;
@@ -199,32 +174,20 @@ __global__ __launch_bounds__(FIT_NT) void k_fit_rows(FitArgs a, FitRowArgs w) {
   __syncthreads();
   fit_form<WHICH>(a, i, g0, gn, sx, tid, [&](int gl, int cs, double v) { s[gl * NP + cs] = v; });
   __syncthreads();
-  // mean and sd of every row before it is sorted: k_bands_moments' order
+  // mean and sd of every row before it is sorted
   for (int gl = 0; gl < gn; ++gl) {
-    const double* v = s + gl * NP;
-    double acc = 0.0;
-    for (int e = tid; e < T; e += FIT_NT) acc += v[e];
-    red[tid] = acc;
-    __syncthreads();
-    for (int h = FIT_NT / 2; h > 0; h >>= 1) { if (tid < h) red[tid] += red[tid + h]; __syncthreads(); }
-    const double m = red[0] / (double)T;
-    __syncthreads();
-    double qq = 0.0;
-    for (int e = tid; e < T; e += FIT_NT) { const double dlt = v[e] - m; qq += dlt * dlt; }
-    red[tid] = qq;
-    __syncthreads();
-    for (int h = FIT_NT / 2; h > 0; h >>= 1) { if (tid < h) red[tid] += red[tid + h]; __syncthreads(); }
+    double m, sdv;
+    rs::row_mean_sd<FIT_NT>(s + gl * NP, T, red, m, sdv);
     if (tid == 0) {
       const size_t o = (size_t)r * a.G + g0 + gl;
       w.mean[o] = m;
-      w.sd[o] = sqrt(red[0] / (double)(T - 1));
+      w.sd[o] = sdv;
     }
-    __syncthreads();
   }
-  fit_sort(s, gn, NP, tid);
+  rs::bitonic_sort<FIT_NT>(rs::Plain<double>{s}, gn, NP);
   if (tid < gn * w.nq) {
     const int gl = tid / w.nq, qi = tid - gl * w.nq;
-    w.quant[((size_t)r * a.G + g0 + gl) * w.nq + qi] = fit_quantile(s + gl * NP, T, w.probs[qi]);
+    w.quant[((size_t)r * a.G + g0 + gl) * w.nq + qi] = rs::quantile5(rs::Plain<double>{s + gl * NP}, T, w.probs[qi]);
   }
 }
 
@@ -249,7 +212,7 @@ __global__ __launch_bounds__(FIT_NT) void k_fit_quantiles(const double* W, int N
   const long long e = (long long)blockIdx.x * FIT_NT + threadIdx.x;
   if (e >= ncol * nq) return;
   const long long col = e / nq;
-  quant[e] = fit_quantile(W + (size_t)col * NP, T, probs[(int)(e - col * nq)]);
+  quant[e] = rs::quantile5(rs::Plain<const double>{W + (size_t)col * NP}, T, probs[(int)(e - col * nq)]);
 }
 
 // ---- simultaneous bands ----
@@ -281,7 +244,7 @@ __global__ __launch_bounds__(FIT_NT) void k_fit_sim(FitArgs a, FitSimArgs w) {
   if (tid < a.D) sx[tid] = a.X[i + (size_t)a.n * tid];
   for (int e = T + tid; e < NP; e += FIT_NT) row[e] = INFINITY;
   __syncthreads();
-  // passes 0 and 1: sum of v, then of (v - mean)^2, per grid point: the lane's draws in order, then k_fit_rows' tree
+  // passes 0 and 1: sum of v, then of (v - mean)^2, per grid point: the lane's draws in order, then the block tree
   for (int pass = 0; pass < 2; ++pass)
     for (int g0 = 0; g0 < G; g0 += FIT_SIM_GT) {
       const int gn = min(FIT_SIM_GT, G - g0);
@@ -309,12 +272,10 @@ __global__ __launch_bounds__(FIT_NT) void k_fit_sim(FitArgs a, FitSimArgs w) {
 #pragma unroll
       for (int gl = 0; gl < FIT_SIM_GT; ++gl)
         if (gl < gn) {
-          red[tid] = acc[gl];
-          __syncthreads();
-          for (int h = FIT_NT / 2; h > 0; h >>= 1) { if (tid < h) red[tid] += red[tid + h]; __syncthreads(); }
+          const double tot = rs::block_tree<FIT_NT>(acc[gl], red, rs::OpSum());
           if (tid == 0) {
-            if (!pass) s_mean[g0 + gl] = red[0] / (double)T;
-            else s_sd[g0 + gl] = sqrt(red[0] / (double)(T - 1));
+            if (!pass) s_mean[g0 + gl] = tot / (double)T;
+            else s_sd[g0 + gl] = sqrt(tot / (double)(T - 1));
           }
           __syncthreads();
         }
@@ -343,8 +304,9 @@ __global__ __launch_bounds__(FIT_NT) void k_fit_sim(FitArgs a, FitSimArgs w) {
     for (int g = tid; g < G; g += FIT_NT) { w.mean[o + g] = s_mean[g]; w.sd[o + g] = s_sd[g]; }
     return;
   }
-  fit_sort(row, 1, NP, tid);
-  const double crit = fit_quantile(row, T, w.p);
+  __syncthreads();
+  rs::bitonic_sort<FIT_NT>(rs::Plain<double>{row}, 1, NP);
+  const double crit = rs::quantile5(rs::Plain<double>{row}, T, w.p);
   if (tid == 0) w.crit[r] = crit;
   for (int g = tid; g < G; g += FIT_NT) {
     const double m = s_mean[g], sg = s_sd[g];
@@ -378,8 +340,6 @@ FitArgs fit_args(const Ctx& c, const FitCall& f) {
   a.NJ = d.K * a.M1 * (1 + d.D);
   return a;
 }
-
-int fit_np(int CS) { int NP = 1; while (NP < CS) NP <<= 1; return NP; }
 
 }  // namespace
 
@@ -421,7 +381,7 @@ std::string launch_fit_rows(const Ctx& c, const FitCall& f, int r0, int rows, co
   if (a.CS > FIT_LDS_ROWS) return "k_fit_rows: rows above 8192 draws";
   if (nq < 1 || nq > 16 || rows < 1) return "k_fit_rows: bad arguments";
   FitRowArgs w;
-  w.NP = fit_np(a.CS);
+  w.NP = rs::pow2_ceil(a.CS);
   const int fit = (int)(FIT_LDS_SOFT / (sizeof(double) * (size_t)w.NP));
   w.GT = std::max(1, std::min(std::min(fit, FIT_GT_MAX), a.G));
   w.tiles = (a.G + w.GT - 1) / w.GT;
@@ -467,7 +427,7 @@ std::string launch_fit_sim(const Ctx& c, const FitCall& f, int r0, int rows, dou
   const bool lds_row = a.CS <= FIT_LDS_ROWS;
   if (!lds_row && !cw) return "k_fit_sim: no workspace";
   FitSimArgs w;
-  w.r0 = r0; w.NP = lds_row ? fit_np(a.CS) : 0; w.fused = lds_row ? 0 : 1; w.p = p;
+  w.r0 = r0; w.NP = lds_row ? rs::pow2_ceil(a.CS) : 0; w.fused = lds_row ? 0 : 1; w.p = p;
   w.mean = mean; w.sd = sd; w.crit = crit; w.lower = lower; w.upper = upper; w.cw = cw;
   const size_t lds = sizeof(double) * (2 * (size_t)a.G + (size_t)w.NP);
   const void* fn = f.which ? (const void*)k_fit_sim<1> : (const void*)k_fit_sim<0>;

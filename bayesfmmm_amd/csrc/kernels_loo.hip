@@ -24,11 +24,12 @@
 
 #include "../../include/bfmmm_post.h"
 #include "launchers.hpp"
-
-int bfmmm_io_fail(const std::string& m);      // entry_points.cpp: sets bfmmm_entry_last_error
-void bfmmm_post_set_kernel_ms(float ms);      // kernels_post.hip
+#include "post_host.hpp"
+#include "row_stats.hpp"
 
 namespace {
+
+using namespace rs;
 
 constexpr int NT = 256;                        // threads per workgroup = histogram bins
 constexpr int CAP_MAX = 8192;                  // largest on-chip table of gathered tail candidates
@@ -38,38 +39,9 @@ struct PsisOut {
   double *lppd, *elpd_loo, *p_loo, *khat, *elpd_waic, *p_waic;
 };
 
-typedef unsigned long long u64;
-
-// order-preserving image of a double (ascending doubles -> ascending unsigned keys) and its inverse
-__device__ inline u64 okey(double x) {
-  const u64 u = (u64)__double_as_longlong(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
-}
-__device__ inline double key_value(u64 k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ULL) : ~k));
-}
 // digit p (0..11) of the 96-bit composite (key, draw index), most significant first
 __device__ inline unsigned digit(u64 key, unsigned idx, int p) {
   return p < 8 ? (unsigned)(key >> (56 - 8 * p)) & 255u : (idx >> (24 - 8 * (p - 8))) & 255u;
-}
-
-struct OpSum { __device__ double operator()(double a, double b) const { return a + b; } };
-struct OpMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
-struct OpMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } };
-
-// fixed-order tree over the workgroup's 256 partials; every thread gets the result
-template <class Op>
-__device__ double block_reduce(double v, double* red, Op op) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] = op(red[tid], red[tid + s]);
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
 }
 
 // histogram count with the adds of a wave's lanes that share a bin merged (a concentrated row puts most lanes in one bin)
@@ -100,9 +72,9 @@ __global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld
   // ---- pass 1 ----
   double mx = -INFINITY, mn = INFINITY, sum = 0.0;
   for (int t = tid; t < S; t += NT) { const double x = row[t]; mx = fmax(mx, x); mn = fmin(mn, x); sum += x; }
-  mx = block_reduce(mx, red, OpMax());
-  mn = block_reduce(mn, red, OpMin());
-  sum = block_reduce(sum, red, OpSum());
+  mx = block_reduce<NT>(mx, red, OpMax());
+  mn = block_reduce<NT>(mn, red, OpMin());
+  sum = block_reduce<NT>(sum, red, OpSum());
   const double mean = sum / (double)S;
   const double rmax = -mn;                             // max_t r_t, r_t = -l_t;  lw_t = r_t - rmax
   const bool select = L >= 5;
@@ -118,8 +90,8 @@ __global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld
     if (on) { se += exp(x - mx); const double d = x - mean; sq += d * d; }
     if (select) hist_add(hist, digit(okey(-x - rmax), (unsigned)t, 0), on);
   }
-  se = block_reduce(se, red, OpSum());
-  sq = block_reduce(sq, red, OpSum());
+  se = block_reduce<NT>(se, red, OpSum());
+  sq = block_reduce<NT>(sq, red, OpSum());
   const double lppd = mx + log(se) - log((double)S);
   const double p_waic = S > 1 ? sq / (double)(S - 1) : 0.0;
 
@@ -177,23 +149,10 @@ __global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld
     }
     __syncthreads();
     const int G = min((int)sI[3], cap);
-    int npow = 1;
-    while (npow < G) npow <<= 1;
+    const int npow = pow2_ceil(G);
     for (int e = G + tid; e < npow; e += NT) { sKey[e] = 0; sIdx[e] = 0; }      // below every finite key
     __syncthreads();
-    for (int k = 2; k <= npow; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int e = tid; e < npow; e += NT) {
-          const int f = e ^ j;
-          if (f > e) {
-            const u64 ka = sKey[e], kb = sKey[f];
-            const unsigned ia = sIdx[e], ib = sIdx[f];
-            const bool gt = ka > kb || (ka == kb && ia > ib);
-            if (gt == ((e & k) == 0)) { sKey[e] = kb; sKey[f] = ka; sIdx[e] = ib; sIdx[f] = ia; }
-          }
-        }
-        __syncthreads();
-      }
+    bitonic_sort<NT>(KeyIdxRows{sKey, sIdx}, 1, npow);
     base = npow - L;
     kc = sKey[base - 1];
     ic = sIdx[base - 1];
@@ -244,7 +203,7 @@ __global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld
       __syncthreads();
       double kp = 0.0;
       for (int l = tid; l < N; l += NT) kp += log1p(-that * e[l]);
-      const double kk = block_reduce(kp, red, OpSum()) / (double)N;
+      const double kk = block_reduce<NT>(kp, red, OpSum()) / (double)N;
       const double sigma = -kk / that;
       khat = ((double)N * kk + 5.0) / ((double)N + 10.0);
       if (isnan(khat)) khat = INFINITY;
@@ -268,8 +227,8 @@ __global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld
       a1 = fmax(a1, w + row[sIdx[base + j]]);
       a2 = fmax(a2, w);
     }
-    sh1 = fmax(mn, block_reduce(a1, red, OpMax()));
-    sh2 = fmax(c, block_reduce(a2, red, OpMax()));
+    sh1 = fmax(mn, block_reduce<NT>(a1, red, OpMax()));
+    sh2 = fmax(c, block_reduce<NT>(a2, red, OpMax()));
   }
   double s1 = 0.0, s2 = 0.0;
   for (int t = tid; t < S; t += NT) {
@@ -288,8 +247,8 @@ __global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld
       s1 += exp(w + row[sIdx[base + j]] - sh1);
       s2 += exp(w - sh2);
     }
-  s1 = block_reduce(s1, red, OpSum());
-  s2 = block_reduce(s2, red, OpSum());
+  s1 = block_reduce<NT>(s1, red, OpSum());
+  s2 = block_reduce<NT>(s2, red, OpSum());
   if (tid == 0) {
     const double elpd = (sh1 + log(s1)) - (sh2 + log(s2));
     o.lppd[i] = lppd;
@@ -312,23 +271,16 @@ int post_psis_device(const double* d_ll, long long ld, int n, int S, double* con
   const int L = (int)std::ceil(std::min(0.2 * S, 3.0 * std::sqrt((double)S)));
   int cap = 256;
   while (cap < 2 * (L + 1) && cap < CAP_MAX) cap <<= 1;
-  double* d_out = nullptr;
-  if (hipMalloc(&d_out, sizeof(double) * 6 * (size_t)n) != hipSuccess) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_psis: device allocation failed"); }
+  DevBufs b;
+  double* d_out;
+  if (!b.put(&d_out, nullptr, 6 * (size_t)n)) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_psis: device allocation failed"); }
   PsisOut o{d_out, d_out + n, d_out + 2 * (size_t)n, d_out + 3 * (size_t)n, d_out + 4 * (size_t)n, d_out + 5 * (size_t)n};
   const size_t lds = (size_t)(NT + 256) * sizeof(double) + (size_t)(3 * NT + 8) * sizeof(unsigned) + (size_t)cap * (sizeof(u64) + sizeof(unsigned));
   (void)hipFuncSetAttribute((const void*)k_post_psis, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  (void)hipEventRecord(e0, 0);
-  hipLaunchKernelGGL(k_post_psis, dim3(n), dim3(NT), lds, 0, d_ll, ld, S, L, cap, o);
-  (void)hipEventRecord(e1, 0);
-  const bool ran = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
-  if (ran) { float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1); bfmmm_post_set_kernel_ms(ms); }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  const bool ran = timed_launch([&] { hipLaunchKernelGGL(k_post_psis, dim3(n), dim3(NT), lds, 0, d_ll, ld, S, L, cap, o); return true; });
   std::vector<double> h(6 * (size_t)n);
-  const bool copied = ran && hipMemcpy(h.data(), d_out, sizeof(double) * h.size(), hipMemcpyDeviceToHost) == hipSuccess;
-  (void)hipFree(d_out);
-  if (!copied) return bfmmm_io_fail("bfmmm_post_psis: kernel launch or copy back failed");
+  if (!ran || hipMemcpy(h.data(), d_out, sizeof(double) * h.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    return bfmmm_io_fail("bfmmm_post_psis: kernel launch or copy back failed");
   for (int q = 0; q < 6; ++q)
     if (out[q]) std::copy(h.begin() + (size_t)q * n, h.begin() + (size_t)(q + 1) * n, out[q]);
   return 0;
@@ -340,15 +292,12 @@ extern "C" int bfmmm_post_psis(const double* ll, int32_t n, int32_t S, int32_t d
   if (n < 1 || S < 1) return bfmmm_io_fail("bfmmm_post_psis: bad dimensions");
   if (S > S_MAX)
     return bfmmm_io_fail("bfmmm_post_psis: at most 4194304 (2^22) kept draws per curve in this build, got " + std::to_string(S));
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return bfmmm_io_fail("bfmmm_post_psis: no HIP device (the MI355X library has no CPU path)");
-  if (hipSetDevice(device) != hipSuccess) return bfmmm_io_fail("bfmmm_post_psis: cannot select the device");
-  double* d_ll = nullptr;
-  const size_t bytes = sizeof(double) * (size_t)n * (size_t)S;
-  if (hipMalloc(&d_ll, bytes) != hipSuccess) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_psis: device allocation failed"); }
-  if (hipMemcpy(d_ll, ll, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_ll); return bfmmm_io_fail("bfmmm_post_psis: copy failed"); }
+  if (select_device(device, "bfmmm_post_psis")) return 1;
+  DevBufs b;
+  double* d_ll;
+  const size_t count = (size_t)n * (size_t)S;
+  if (!b.put(&d_ll, nullptr, count)) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_psis: device allocation failed"); }
+  if (hipMemcpy(d_ll, ll, sizeof(double) * count, hipMemcpyHostToDevice) != hipSuccess) return bfmmm_io_fail("bfmmm_post_psis: copy failed");
   double* const out[6] = {lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic};
-  const int rc = post_psis_device(d_ll, S, n, S, out);
-  (void)hipFree(d_ll);
-  return rc;
+  return post_psis_device(d_ll, S, n, S, out);
 }

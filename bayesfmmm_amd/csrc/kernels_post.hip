@@ -26,9 +26,8 @@
 #include <vector>
 
 #include "../../include/bfmmm_post.h"
+#include "post_host.hpp"
 #include "rng.hpp"
-
-int bfmmm_io_fail(const std::string& m);      // entry_points.cpp: sets bfmmm_entry_last_error
 
 namespace {
 
@@ -451,23 +450,7 @@ __global__ __launch_bounds__(256) void k_post_paths(PostDev a, unsigned long lon
   }
 }
 
-struct DevBufs {
-  std::vector<void*> p;
-  ~DevBufs() { for (void* q : p) (void)hipFree(q); }
-  template <class Tp>
-  bool put(Tp** out, const Tp* host, size_t count) {
-    void* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(count, 1) * sizeof(Tp)) != hipSuccess) return false;
-    p.push_back(d);
-    if (host && count && hipMemcpy(d, host, count * sizeof(Tp), hipMemcpyHostToDevice) != hipSuccess) return false;
-    *out = (Tp*)d;
-    return true;
-  }
-};
-
 }  // namespace
-
-int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]);      // kernels_loo.hip
 
 void bfmmm_post_set_kernel_ms(float ms) { g_last_kernel_ms = ms; }
 
@@ -487,9 +470,7 @@ static int post_impl(const bfmmm_post_input* in, int32_t first_kept, double* lli
   for (int i = 0; i < n; ++i)
     if (in->offsets[i + 1] - in->offsets[i] > 256 * NJ)
       return bfmmm_io_fail("bfmmm_post_pointwise: at most 1024 observations per curve in this build");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return bfmmm_io_fail("bfmmm_post_pointwise: no HIP device (the MI355X library has no CPU path)");
-  if (hipSetDevice(in->device) != hipSuccess) return bfmmm_io_fail("bfmmm_post_pointwise: cannot select the device");
+  if (select_device(in->device, "bfmmm_post_pointwise")) return 1;
   // draws -> theta[t][r = k (M + 1) + mt][p] (+ thetaX[t][r][d][p])
   const int R = K * (M + 1);
   std::vector<double> theta((size_t)T * R * P), thetaX;
@@ -550,10 +531,10 @@ static int post_impl(const bfmmm_post_input* in, int32_t first_kept, double* lli
   bool ok = db.put((long long**)&a.off, off.data(), off.size()) && db.put((double**)&a.y, in->y, (size_t)n_obs) &&
             db.put((double**)&a.Bc, Bc.data(), Bc.size()) && db.put((int**)&a.bstart, first.data(), first.size()) && db.put((double**)&a.theta, theta.data(), theta.size()) &&
             db.put((double**)&a.Z, in->Z, (size_t)n * K * T) && db.put((double**)&a.chi, in->chi, (size_t)n * M * T) &&
-            db.put((double**)&a.sigma, in->sigma, (size_t)T) && db.put(&a.llpart, (const double*)nullptr, (size_t)n * T) &&
-            db.put(&a.pdf_part, (const double*)nullptr, (size_t)NCH * n_obs) && db.put(&a.fit_part, (const double*)nullptr, (size_t)NCH * n_obs) &&
-            db.put(&d_ll, (const double*)nullptr, (size_t)T) && db.put(&d_pdf, (const double*)nullptr, (size_t)n_obs) &&
-            db.put(&d_fit, (const double*)nullptr, (size_t)n_obs) && db.put(&d_joint, (const double*)nullptr, (size_t)n);
+            db.put((double**)&a.sigma, in->sigma, (size_t)T) && db.put(&a.llpart, nullptr, (size_t)n * T) &&
+            db.put(&a.pdf_part, nullptr, (size_t)NCH * n_obs) && db.put(&a.fit_part, nullptr, (size_t)NCH * n_obs) &&
+            db.put(&d_ll, nullptr, (size_t)T) && db.put(&d_pdf, nullptr, (size_t)n_obs) &&
+            db.put(&d_fit, nullptr, (size_t)n_obs) && db.put(&d_joint, nullptr, (size_t)n);
   if (ok && D > 0) ok = db.put((double**)&a.X, in->X, (size_t)n * D) && db.put((double**)&a.thetaX, thetaX.data(), thetaX.size());
   if (!ok) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_pointwise: device allocation or copy failed"); }
   if (cpo || ll_kept || loo) {
@@ -565,19 +546,15 @@ static int post_impl(const bfmmm_post_input* in, int32_t first_kept, double* lli
     const int Gc = std::min(CPO_GMAX, CPO_LDS_BUDGET / per_draw);
     if (Gc < 1) return bfmmm_io_fail("bfmmm_post_cpo: (M + 1) x observations of a curve exceed the on-chip tile in this build");
     double *d_cll, *d_cpo;
-    if (!db.put(&d_cll, (const double*)nullptr, (size_t)n * T) || !db.put(&d_cpo, (const double*)nullptr, (size_t)n))
+    if (!db.put(&d_cll, nullptr, (size_t)n * T) || !db.put(&d_cpo, nullptr, (size_t)n))
       return bfmmm_io_fail("bfmmm_post_cpo: device allocation failed");
     const size_t lds_c = ((size_t)Gc * per_draw + CPO_GMAX * (KMAXP + 1) + BL_MAX + 8 + 8) * sizeof(double);
     (void)hipFuncSetAttribute((const void*)k_post_cpo, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-    hipEvent_t c0, c1;
-    (void)hipEventCreate(&c0); (void)hipEventCreate(&c1);
-    (void)hipEventRecord(c0, 0);
-    hipLaunchKernelGGL(k_post_cpo, dim3(n), dim3(256), lds_c, 0, a, d_cll, Gc, NIPX);
-    if (cpo) hipLaunchKernelGGL(k_post_cpo_reduce, dim3((n + 255) / 256), dim3(256), 0, 0, a, d_cll, d_cpo);
-    (void)hipEventRecord(c1, 0);
-    const bool ran_c = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
-    if (ran_c) (void)hipEventElapsedTime(&g_last_kernel_ms, c0, c1);
-    (void)hipEventDestroy(c0); (void)hipEventDestroy(c1);
+    const bool ran_c = timed_launch([&] {
+      hipLaunchKernelGGL(k_post_cpo, dim3(n), dim3(256), lds_c, 0, a, d_cll, Gc, NIPX);
+      if (cpo) hipLaunchKernelGGL(k_post_cpo_reduce, dim3((n + 255) / 256), dim3(256), 0, 0, a, d_cll, d_cpo);
+      return true;
+    });
     if (!ran_c || (cpo && hipMemcpy(cpo, d_cpo, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess))
       return bfmmm_io_fail("bfmmm_post_cpo: kernel launch or copy back failed");
     const size_t kept = (size_t)(T - first_kept);
@@ -589,16 +566,12 @@ static int post_impl(const bfmmm_post_input* in, int32_t first_kept, double* lli
   }
   const size_t lds = ((size_t)GMAX * (P | 1) + (size_t)GMAX * WMAX + 2048 + 64 + BL_MAX + 8) * sizeof(double);
   (void)hipFuncSetAttribute((const void*)k_post_pointwise, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  (void)hipEventRecord(e0, 0);
-  hipLaunchKernelGGL(k_post_pointwise, dim3(n, NCH), dim3(256), lds, 0, a);
-  const long long tot = std::max<long long>(std::max<long long>(T, n_obs), n);
-  hipLaunchKernelGGL(k_post_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, a, NCH, d_ll, d_pdf, d_fit, mean_joint ? d_joint : (double*)nullptr);
-  (void)hipEventRecord(e1, 0);
-  const bool ran = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
-  if (ran) (void)hipEventElapsedTime(&g_last_kernel_ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  const bool ran = timed_launch([&] {
+    hipLaunchKernelGGL(k_post_pointwise, dim3(n, NCH), dim3(256), lds, 0, a);
+    const long long tot = std::max<long long>(std::max<long long>(T, n_obs), n);
+    hipLaunchKernelGGL(k_post_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, a, NCH, d_ll, d_pdf, d_fit, mean_joint ? d_joint : (double*)nullptr);
+    return true;
+  });
   if (!ran) return bfmmm_io_fail("bfmmm_post_pointwise: kernel launch failed");
   if ((llik && hipMemcpy(llik, d_ll, sizeof(double) * T, hipMemcpyDeviceToHost) != hipSuccess) ||
       (mean_pdf && hipMemcpy(mean_pdf, d_pdf, sizeof(double) * n_obs, hipMemcpyDeviceToHost) != hipSuccess) ||
@@ -645,9 +618,7 @@ extern "C" int bfmmm_post_sample_paths(const bfmmm_post_input* in, int32_t first
     return bfmmm_io_fail("bfmmm_post_sample_paths: bad dimensions");
   if ((double)T * K * (M + 1) * P * std::max(D, 1) >= 5.0e8) return bfmmm_io_fail("bfmmm_post_sample_paths: too many draws for one call: split the draws");
   const long long n_obs = in->offsets[n];
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return bfmmm_io_fail("bfmmm_post_sample_paths: no HIP device (the MI355X library has no CPU path)");
-  if (hipSetDevice(in->device) != hipSuccess) return bfmmm_io_fail("bfmmm_post_sample_paths: cannot select the device");
+  if (select_device(in->device, "bfmmm_post_sample_paths")) return 1;
   const int R = K * (M + 1), kept = T - first_kept;
   std::vector<double> theta((size_t)T * R * P), thetaX;
   for (int t = 0; t < T; ++t)
@@ -695,8 +666,8 @@ extern "C" int bfmmm_post_sample_paths(const bfmmm_post_input* in, int32_t first
   bool ok = db.put((long long**)&a.off, off.data(), off.size()) && db.put((double**)&a.Bc, Bc.data(), Bc.size()) &&
             db.put((int**)&a.bstart, first.data(), first.size()) && db.put((double**)&a.theta, theta.data(), theta.size()) &&
             db.put((double**)&a.Z, in->Z, (size_t)n * K * T) && db.put((double**)&a.chi, in->chi, (size_t)n * M * T) &&
-            db.put((double**)&a.sigma, in->sigma, (size_t)T) && db.put(&d_paths, (const double*)nullptr, (size_t)kept * n_obs) &&
-            db.put(&d_mo, (const double*)nullptr, (size_t)kept * n_obs);
+            db.put((double**)&a.sigma, in->sigma, (size_t)T) && db.put(&d_paths, nullptr, (size_t)kept * n_obs) &&
+            db.put(&d_mo, nullptr, (size_t)kept * n_obs);
   if (ok && D > 0) ok = db.put((double**)&a.X, in->X, (size_t)n * D) && db.put((double**)&a.thetaX, thetaX.data(), thetaX.size());
   if (!ok) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_sample_paths: device allocation or copy failed"); }
   hipLaunchKernelGGL(k_post_paths, dim3(n, NCH), dim3(256), 0, 0, a, (unsigned long long)seed, kept, d_paths, d_mo);

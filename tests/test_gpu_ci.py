@@ -221,6 +221,20 @@ def test_ci_argument_checks_and_quantile_edges():
                                             out.ctypes.data_as(api.c_double_p)) == 0
         for c in range(5):
             np.testing.assert_allclose(out[:, c], R.arma_quantile(V[:, c], probs), rtol=1e-15)
+    # columns of few distinct values, of both zeros and of both infinities, at the shortest odd length and on either side of
+    # the longest column sorted in LDS, by value (an interpolation weight of 0 on an infinity is a NaN on both sides)
+    for T in (7, 8192, 8193):
+        V = np.zeros((T, 3), order="F")
+        V[:, 0] = rng.integers(0, 3, T)
+        V[:, 1] = rng.choice([-0.1, -0.0, 0.0, 0.1], T)
+        V[:, 2] = rng.standard_normal(T)
+        V[rng.choice(T, 3, replace=False), 2] = [-np.inf, np.inf, np.inf]
+        out = np.zeros((len(probs), 3), order="F")
+        assert lib.bfmmm_post_col_quantiles(V.ctypes.data_as(api.c_double_p), T, 3, probs.ctypes.data_as(api.c_double_p), len(probs), 0,
+                                            out.ctypes.data_as(api.c_double_p)) == 0
+        with np.errstate(invalid="ignore"):
+            for c in range(3):
+                np.testing.assert_allclose(out[:, c], R.arma_quantile(V[:, c], probs), rtol=1e-15)
 
 
 def test_bands_over_more_than_8192_draws():
