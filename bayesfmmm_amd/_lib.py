@@ -85,6 +85,7 @@ SYMBOLS = {
     "bfmmm_set_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "bfmmm_get_timing": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), c_int64_p]),
     "bfmmm_set_exact_instances": (None, [C.c_int]),
+    "bfmmm_set_curve_record": (None, [C.c_int]),
     "bfmmm_set_solo_pair_gram": (None, [C.c_int]),
     "bfmmm_set_solo_pair_gram_tail": (None, [C.c_int]),
     "bfmmm_last_error": (C.c_char_p, []),

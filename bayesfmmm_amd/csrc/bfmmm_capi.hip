@@ -241,7 +241,7 @@ static int create_impl(const bfmmm_config* cfg, int device, const double* y, con
   areq(ar, &c.pg_part, h->pg_part_doubles); areq(ar, &c.H, (size_t)d.R * d.LG + 2); areq(ar, &c.H2, (size_t)d.R * P * (2 * d.BW + 2));
   areq(ar, &c.tvec, (size_t)d.A * P); areq(ar, &c.rvec, (size_t)d.A * P); areq(ar, &c.hq, (size_t)d.A * P);
   areq(ar, &c.gstd, (size_t)K * P * M + (size_t)K * M + 13 * K + 8); areq(ar, &c.zprep, (size_t)(3 * K + 5) * n);
-  areq(ar, &c.chi_norm, (size_t)n * M); areq(ar, &c.piprep, 9 * KMAX + 16); areq(ar, &c.Lz, (size_t)d.A * P);
+  areq(ar, &c.chi_norm, (size_t)n * M); areq(ar, &c.zrec, zrec_stride(n, K)); areq(ar, &c.piprep, 9 * KMAX + 16); areq(ar, &c.Lz, (size_t)d.A * P);
   areq(ar, &c.Cmat, (size_t)d.A * P * P + 2);
   {
     const size_t T = (size_t)h->T;
@@ -639,13 +639,21 @@ static int pg_route(bfmmm_handle* h, const Ctx& c, bool pg, int cnt, int slot, P
 // trail_z: the iteration ends with the stand-alone Z update of the NEXT iteration, in its lean form (the proposals were prepared
 // by this iteration's k_factor): sweeps without a chi pass cannot fuse the Z update into k_curve_chi, but they can still run
 // it in the order "first Z of the run, then bodies [pair_gram .. chi, next Z]".
+// launch_curve's third argument for k_curve_chi and k_curve_z: the one derivation launch_iteration, queue_graph, run_impl AND the
+// route record (record_curve_route) share, so the record cannot drift from what is launched
+static int chi_launch_arg(const Plan& p, bool fuse_z) { return (p.chi ? (p.chi_update ? 2 : 1) : 0) | (fuse_z ? 16 : 0); }
+static int z_launch_arg(const Plan& p, bool trail) { return p.z_update | (trail ? 2 : 0); }
+static void launch_curve_checked(bfmmm_handle* h, const Ctx& c, int which, int arg, hipStream_t st) {
+  if (launch_curve(c, which, arg, st)) h->launch_error = 2;
+}
+
 static void launch_iteration(bfmmm_handle* h, const Ctx& c, const Plan& p, const PgRoute& r, hipStream_t st,
                              std::vector<hipEvent_t>* evs, bool skip_z, bool fuse_z, bool trail_z) {
   auto mark = [&]() {
     if (evs) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, st); evs->push_back(e); }
   };
   mark();
-  if (p.z && !skip_z) launch_curve(c, 0, p.z_update, st);
+  if (p.z && !skip_z) launch_curve_checked(h, c, 0, z_launch_arg(p, false), st);
   mark();
   Ctx cf = c;
   cf.pi_in_factor = r.packed ? 1 : 0;      // (the pi / alpha_3 job: an extra workgroup of k_pair_gram, or -- packed path -- of k_factor)
@@ -664,8 +672,8 @@ static void launch_iteration(bfmmm_handle* h, const Ctx& c, const Plan& p, const
   mark();
   // (a trailing lean Z launch carries the scalar job of k_curve_chi as its first workgroup: sweeps without a chi pass -- the
   //  only ones that run deferred -- then need no k_curve_chi launch at all)
-  if (!(trail_z && !p.chi)) launch_curve(c, 1, (p.chi ? (p.chi_update ? 2 : 1) : 0) | (fuse_z ? 16 : 0), st);
-  if (trail_z) launch_curve(c, 0, p.z_update | 2, st);
+  if (!(trail_z && !p.chi)) launch_curve_checked(h, c, 1, chi_launch_arg(p, fuse_z), st);
+  if (trail_z) launch_curve_checked(h, c, 0, z_launch_arg(p, true), st);
   if (c.d.D > 0) launch_cov_block(c, st);      // eta, tau_eta, Xi, delta_xi, A_xi, gamma_xi (+ residual sums)
   mark();
   if (!c.defer_loglik) launch_loglik(c, p.use_rss_part, 0, st);      // otherwise: job_hyper + the next k_pair_gram (scalar_jobs.hpp)
@@ -695,7 +703,7 @@ struct FreshGraph { hipGraphExec_t g; hipStream_t st; };
 // queues the kernels of a graph of `kind` (reps iterations) on the sub-batch's stream
 static void queue_graph(bfmmm_handle* h, const Ctx& c, const Sub& sb, const Plan& plan, int kind, int reps, int body_kind) {
   if (kind == GK_WHOLE) {
-    launch_curve(sb.c, 0, plan.z_update, sb.st);              // Z of the first iteration
+    launch_curve_checked(h, sb.c, 0, z_launch_arg(plan, false), sb.st);              // Z of the first iteration
     queue_graph(h, c, sb, plan, body_kind, reps - 1, body_kind);
     queue_graph(h, c, sb, plan, GK_CLOSING, 1, body_kind);
     launch_loglik_flush(c, sb.st, h->status_dev);
@@ -816,6 +824,7 @@ static int finish_run(bfmmm_handle* h, const Ctx& c, const Plan& plan, uint32_t 
     HIPCHK(hipMemcpy2DAsync(h->status_host, sizeof(uint32_t), &h->c.dyn->status, h->nch > 1 ? h->c.chain_bytes : sizeof(uint32_t), sizeof(uint32_t),
                             (size_t)h->nch, hipMemcpyDeviceToHost, h->st));
   HIPCHK(hipStreamSynchronize(h->st));
+  if (h->launch_error == 2) { h->launch_error = 0; drop_graphs(h); return fail("bfmmm_run: internal error (no per-curve kernel instance is built for the route the launcher chose)"); }
   if (h->launch_error) { h->launch_error = 0; return fail("bfmmm_run: problem size exceeds the sweep kernel's LDS (5 A P doubles + A^2 ints must fit 160 KB)"); }
   HIPCHK(hipGetLastError());
   float ms = 0;
@@ -831,6 +840,27 @@ static int finish_run(bfmmm_handle* h, const Ctx& c, const Plan& plan, uint32_t 
       return fail("bfmmm_run: a conditional precision matrix was not positive definite");
   }
   return 0;
+}
+
+// bfmmm_debug_get("curve_route") (handle.hpp: last_curve): the instances the run's last Z update and its last k_curve_chi launch
+// take, from curve_route_decide, the function launch_curve reads, and chi_launch_arg / z_launch_arg, which every launch passes
+static void record_curve_route(bfmmm_handle* h, const Ctx& c, const Plan& plan, bool fuse, bool defer) {
+  double v[14] = {0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0};
+  const int mode = chi_launch_arg(plan, false);      // of the closing iteration's k_curve_chi
+  const CurveRoute rc = curve_route_decide(c.d, 1, mode);
+  const double w[8] = {(double)rc.BW, (double)rc.LPC, rc.COV ? 1.0 : 0.0, rc.SMALL ? 1.0 : 0.0, (double)rc.KX, (double)rc.MX, (double)mode,
+                       fuse ? 1.0 : 0.0};
+  memcpy(v + 6, w, sizeof w);
+  if (fuse) {      // the Z update inside k_curve_chi<.., KX, MX>: its K bound is that instance's
+    const CurveRoute rf = curve_route_decide(c.d, 1, chi_launch_arg(plan, true));
+    const double z[6] = {3, (double)rf.BW, (double)rf.LPC, 0, (double)(rf.KX ? rf.KX : (rf.SMALL ? 4 : KMAX)), rf.KX ? 1.0 : 0.0};
+    memcpy(v, z, sizeof z);
+  } else if (plan.z) {
+    const CurveRoute rz = curve_route_decide(c.d, 0, z_launch_arg(plan, defer));
+    const double z[6] = {rz.LEAN ? 2.0 : 1.0, (double)rz.BW, (double)rz.LPC, rz.COV ? 1.0 : 0.0, (double)rz.KT, rz.KEX ? 1.0 : 0.0};
+    memcpy(v, z, sizeof z);
+  }
+  memcpy(h->last_curve, v, sizeof v);
 }
 
 static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters, uint64_t seed, uint32_t chain,
@@ -879,6 +909,12 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
     const double w[5] = {(double)sr.kernel, (double)sr.targ, c.d.mv ? 1.0 : 0.0, (double)sr.direct, (double)sr.threads};
     memcpy(h->last_sweep, w, sizeof w);
   }
+  // the Z record (bfmmm_set_curve_record): the launches of this run get the array, or a null pointer
+  const int rec_on = bfmmm::g_curve_record;
+  if (!rec_on) {
+    c.zrec = nullptr;
+    for (int q = 0; q < nsub; ++q) subs[q].c.zrec = nullptr;
+  }
   // single chain: the scalar job of k_curve_chi rides the next iteration's k_pair_gram instead (its grid has NKS - 1 idle extra
   // workgroups); the run's flush kernel runs the last one
   c.defer_hyper = (c.defer_loglik && plan.pg && plan.chi && h->nch == 1 && !subs[0].r.packed && subs[0].r.NKS >= 2) ? 1 : 0;
@@ -891,6 +927,13 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
     h->state_dirty = false;
     for (int f = 0; f < FAM_COUNT; ++f) { h->fam_ms[f] = 0; h->fam_launches[f] = 0; }
   }
+  // sweeps whose Z update rides in k_curve_chi (fused bodies), and those whose Z update cannot (no chi pass: the Nu_Z stage) but
+  // still runs at the END of the previous iteration's body, as the lean stand-alone kernel (deferred bodies; graph path only)
+  const bool fuse = plan.z && plan.z_update && plan.chi && c.d.D == 0 && n_iters >= 2 && tt_step == 0;
+  const bool defer = !h->profile && !fuse && plan.z && plan.z_update && plan.factor && (mask & U_Z) && c.d.D == 0 && c.d.K <= 4 &&
+                     c.d.BW <= 5 && n_iters >= 2 && tt_step == 0;
+  if (n_iters > 0) record_curve_route(h, c, plan, fuse, defer);
+  if (!prepare_only && n_iters > 0) h->zrec_form = (rec_on && plan.z && plan.z_update) ? (fuse ? 2 : 1) : 0;
   if (h->profile) {
     if (prepare_only) return 0;
     HIPCHK(hipEventRecord(h->ev0, h->st));
@@ -898,11 +941,6 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
     return finish_run(h, c, plan, mask, first_iter, n_iters, false);
   }
   // ---- the graphs of the run: one launch sequence per sub-batch ----
-  const bool fuse = plan.z && plan.z_update && plan.chi && c.d.D == 0 && n_iters >= 2 && tt_step == 0;
-  // sweeps whose Z update cannot ride in k_curve_chi (no chi pass: the Nu_Z stage) still run it at the END of the previous
-  // iteration's body, as the lean stand-alone kernel (deferred bodies)
-  const bool defer = !fuse && plan.z && plan.z_update && plan.factor && (mask & U_Z) && c.d.D == 0 && c.d.K <= 4 && c.d.BW <= 5 &&
-                     n_iters >= 2 && tt_step == 0;
   const bool bodies = fuse || defer;
   const int body_kind = fuse ? GK_FUSED : GK_DEFERRED;
   const int nrep = bodies ? n_iters - 1 : n_iters;                // fused / deferred run: n_iters - 1 bodies + the closing iteration
@@ -921,7 +959,7 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
   }
   // (the captured graphs bake in the kernel instances the launchers chose: the key carries the switch that chooses them)
   const bfmmm_handle::GraphKey key{mask, MD, seed, chain, nsub, (bfmmm::g_exact_instances ? 1 : 0) | (bfmmm::g_solo_pair_gram ? 2 : 0) |
-                                                                        (bfmmm::g_solo_pair_gram_tail ? 4 : 0)};
+                                                                        (bfmmm::g_solo_pair_gram_tail ? 4 : 0) | (rec_on ? 8 : 0)};
   if (n_iters > 0 && !(h->g_valid && h->g_key == key)) { drop_graphs(h); h->g_key = key; h->g_valid = true; }
   std::vector<FreshGraph> fresh;      // graphs instantiated by this call
   std::vector<hipGraphExec_t> seq[bfmmm_handle::MAX_SUB];
@@ -938,7 +976,7 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
   if (nsub > 1) HIPCHK(hipEventRecord(h->evA, h->st));      // k_run_begin first
   for (int q = 1; q < nsub; ++q) HIPCHK(hipStreamWaitEvent(subs[q].st, h->evA, 0));
   for (int s = 0; s < nsub && n_iters > 0; ++s) {
-    if (bodies && !whole) launch_curve(subs[s].c, 0, plan.z_update, subs[s].st);      // Z of the first iteration
+    if (bodies && !whole) launch_curve_checked(h, subs[s].c, 0, z_launch_arg(plan, false), subs[s].st);      // Z of the first iteration
     for (hipGraphExec_t g : seq[s]) HIPCHK(hipGraphLaunch(g, subs[s].st));
   }
   for (int q = 1; q < nsub; ++q) { HIPCHK(hipEventRecord(h->sub_ev[q], subs[q].st)); HIPCHK(hipStreamWaitEvent(h->st, h->sub_ev[q], 0)); }
@@ -1086,6 +1124,23 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
     *count = cnt;
     return 0;
   }
+  if (s == "curve_route") {   // host-side record of the last bfmmm_run (run_impl: record_curve_route)
+    const int64_t cnt = sizeof h->last_curve / sizeof h->last_curve[0];
+    if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
+    memcpy(out, h->last_curve, sizeof h->last_curve);
+    *count = cnt;
+    return 0;
+  }
+  if (s == "z_record" || s == "z_prepared") {      // the selected chain's record of the last run's last Z update (z_proposal.hpp)
+    if (!bfmmm::g_curve_record) return fail("bfmmm_debug_get(" + s + "): recording is off (bfmmm_set_curve_record)");
+    if (!h->zrec_form) return fail("bfmmm_debug_get(" + s + "): the last run stored no record (no Z update in its mask, or recording was off)");
+    const int64_t len = (int64_t)(ZREC_SCALARS + d.K) * d.n, cnt = s == "z_record" ? len : 1;
+    if (capacity < cnt) return fail("bfmmm_debug_get(" + s + "): buffer too small");
+    if (s == "z_prepared" && h->zrec_form == 2) out[0] = 1.0;      // (the fused update runs only with prepared proposals: status bit 2 otherwise)
+    else HIPCHK(copy_sync(h, out, c.zrec + (s == "z_record" ? 0 : len), sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
+    *count = cnt;
+    return 0;
+  }
   if (s == "rss") {           // Dyn::rss of the selected chain: the sweep's RSS after a run whose mask has U_SIGMA and runs no chi pass
     if (capacity < 1) return fail("bfmmm_debug_get: buffer too small");
     Dyn dn;
@@ -1105,9 +1160,15 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
                       {"H2", c.H2, (int64_t)d.R * d.P * (2 * d.BW + 2)},
                       {"Cmat", c.Cmat, (int64_t)d.A * d.P * d.P}, {"Lz", c.Lz, (int64_t)d.A * d.P},
                       {"rvec", c.rvec, (int64_t)d.A * d.P}, {"hq", c.hq, (int64_t)d.A * d.P},      // (k_factor's; the sweep keeps its own copies)
-                      {"theta", c.theta, (int64_t)d.K * (d.M + 1) * d.P}};
+                      {"theta", c.theta, (int64_t)d.K * (d.M + 1) * d.P},
+                      // the per-curve kernels' (k_curve_z, k_curve_chi); the last four exist once covariates were set
+                      {"chi_norm", c.chi_norm, (int64_t)d.n * d.M}, {"zprep", c.zprep, (int64_t)(3 * d.K + 5) * d.n},
+                      {"rss_part", c.rss_part, (int64_t)c.nblk_curve}, {"logz_part", c.logz_part, (int64_t)c.nblk_curve * d.K},
+                      {"stil", c.stil, (int64_t)d.n * d.P}, {"yyp_part", c.yyp_part, (int64_t)c.nblk_curve},
+                      {"cfull", c.cfull, (int64_t)d.n * d.P}, {"gfull", c.gfull, (int64_t)d.n * d.P}};
   for (const Arr& a : arrs)
     if (s == a.nm) {
+      if (!a.p) return fail("bfmmm_debug_get(" + s + "): the array exists once covariates are set");
       if (capacity < a.len) return fail("bfmmm_debug_get(" + s + "): buffer too small");
       HIPCHK(copy_sync(h, out, a.p, sizeof(double) * (size_t)a.len, hipMemcpyDeviceToHost));
       *count = a.len;
@@ -1116,7 +1177,8 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
   return fail("bfmmm_debug_get: unknown name '" + s + "'");
 }
 
-namespace bfmmm { int g_exact_instances = 1; int g_solo_pair_gram = 1; int g_solo_pair_gram_tail = 1; }
+namespace bfmmm { int g_exact_instances = 1; int g_solo_pair_gram = 1; int g_solo_pair_gram_tail = 1; int g_curve_record = 0; }
+extern "C" void bfmmm_set_curve_record(int enable) { bfmmm::g_curve_record = enable ? 1 : 0; }
 extern "C" void bfmmm_set_exact_instances(int enable) { bfmmm::g_exact_instances = enable ? 1 : 0; }
 extern "C" void bfmmm_set_solo_pair_gram(int enable) { bfmmm::g_solo_pair_gram = enable ? 1 : 0; }
 extern "C" void bfmmm_set_solo_pair_gram_tail(int enable) { bfmmm::g_solo_pair_gram_tail = enable ? 1 : 0; }

@@ -70,8 +70,14 @@ struct bfmmm_handle {
   int last_md = -1;
   double last_route[6] = {0, 0, 0, -1, 0, 0};  // bfmmm_debug_get("pg_route"): {packed, KS, NKS, body, G, tail} of sub-batch 0 of the last run
   double last_sweep[5] = {-1, 0, 0, 0, 0};     // bfmmm_debug_get("sweep_route"): {kernel, template argument, mv, direct, block threads} of the last run
+  // bfmmm_debug_get("curve_route"): the last Z update of the last run {form (0 none, 1 stand-alone, 2 lean trailing, 3 fused into
+  // k_curve_chi), BW, LPC, COV, KT, KEX}, then its last k_curve_chi launch {BW, LPC, COV, SMALL, KX, MX, mode, whether the
+  // run's earlier chi launches ran the next Z update} (BW -1: no such launch)
+  double last_curve[14] = {0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0};
   int64_t tab_key = -1;                // (MD, mask) the step tables of k_sweep_chain were built for
-  int launch_error = 0;
+  int launch_error = 0;                // set while a run's launches are queued: 1 the sweep does not fit, 2 no per-curve instance
+  int zrec_form = 0;                   // the Z record of the last run (Ctx::zrec): 0 none stored (recording off, or no Z update in the mask),
+                                       // 1 stand-alone or lean update (its "prepared" flag holds), 2 fused update (always prepared)
   int slot_base = 0;                   // chain slot of iteration i is i - slot_base (bfmmm_set_slot_base)
   double* tt_save = nullptr;            // state saved across a tempered-transition block
   std::vector<double> B_host;           // bfmmm_create_from_basis: the caller's basis rows (bfmmm_get_basis)

@@ -251,6 +251,7 @@ __global__ __launch_bounds__(256, LEAN ? 4 : ((KT <= 4 && BW <= 5) ? 3 : 2)) voi
   } else if (valid && do_update) {
     const bool pre = (dh.zprep_valid != 0u) & (dh.zprep_iter == dh.iter) & (dh.zprep_tt == dh.tt_step) &
                      (dh.zprep_chain == c.chain) & (dh.zprep_seed == c.seed);
+    if (c0.zrec != nullptr && i == 0 && lp == 0) z_record_flag(c.zrec, c, pre);
     if (pre) z_proposal_load(c, i, zp, dh.alpha3, dyn->pi);
     else z_proposal<LPC>(c, make_key(c.seed, c.chain, dh.iter, dh.tt_step), i, lp, Zold, dh.alpha3, dyn->pi, zp);
   }
@@ -272,6 +273,7 @@ __global__ __launch_bounds__(256, LEAN ? 4 : ((KT <= 4 && BW <= 5) ? 3 : 2)) voi
     if (valid && do_update) {
       const bool pre = (dh.zprep_valid != 0u) & (dh.zprep_iter == dh.iter_hyper + 1u) & (dh.zprep_tt == dh.tt_step) &
                        (dh.zprep_chain == c.chain) & (dh.zprep_seed == c.seed);
+      if (c0.zrec != nullptr && i == 0 && lp == 0) z_record_flag(c.zrec, c, pre);
       if (pre) z_proposal_prior(c, zp, dh.alpha3, dyn_pi_lds(sDyn));
       else if (lp == 0) atomicOr(&c.dyn->status, 2u);
     }
@@ -389,6 +391,7 @@ __global__ __launch_bounds__(256, LEAN ? 4 : ((KT <= 4 && BW <= 5) ? 3 : 2)) voi
 #pragma unroll
       for (int k = 0; k < KT; ++k)
         if (k < K && lp == k) { c.Z[i + (size_t)n * k] = Zfin[k]; zslot[i + (size_t)n * k] = Zfin[k]; }
+      if (c0.zrec != nullptr) z_record_store<KT>(c.zrec, c, i, lp, acceptance, zp);      // bfmmm_set_curve_record
     }
     if (do_update) {                                      // log Z_ik of the kept state: both were needed by the proposal densities
 #pragma unroll
@@ -805,6 +808,7 @@ __global__ __launch_bounds__(256) void k_curve_chi(Ctx c0, int mode) {
           zslot[i + (size_t)n * k] = zf;
           logz_mine = took_new ? zp.ln[k] : zp.lo[k];
         }
+      if (c0.zrec != nullptr) z_record_store<KT>(c.zrec, c, i, lp, acceptance, zp);      // bfmmm_set_curve_record
     }
   }
   CT();
@@ -834,8 +838,9 @@ __global__ __launch_bounds__(256) void k_curve_chi(Ctx c0, int mode) {
   X(2, 1) X(2, 2) X(2, 3) X(2, 4) X(2, 5) X(2, 6) X(2, 7) X(2, 8)                                               \
   X(3, 1) X(3, 2) X(3, 3) X(3, 4) X(3, 5) X(3, 6) X(3, 7) X(3, 8)                                               \
   X(4, 1) X(4, 2) X(4, 3) X(4, 4) X(4, 5) X(4, 6) X(4, 7) X(4, 8)
+constexpr bool chi_exact_built(int BW, int L, bool CV) { return (BW == 3 && (!CV || L == 32)) || (BW == 0 && !CV); }
 template <int BW, int L, bool CV>
-constexpr bool chi_exact_built() { return (BW == 3 && (!CV || L == 32)) || (BW == 0 && !CV); }
+constexpr bool chi_exact_built() { return chi_exact_built(BW, L, CV); }
 
 // The 120 exact instances of k_curve_chi are compiled in a translation unit of their own (kernels_curve_exact.hip includes this
 // file with BFMMM_CURVE_EXACT_TU defined and gets the kernels plus the two functions below; this file then holds everything else),
@@ -882,31 +887,85 @@ BFMMM_CHI_EXACT_COMBOS(Y)
 #endif
 
 #ifndef BFMMM_CURVE_EXACT_TU
-template <int BW, int L, bool CV>
-static bool try_chi_exact(const Ctx& c, int nblk, size_t lds, hipStream_t st, int mode) {
-  if (!g_exact_instances) return false;
-  if constexpr (chi_exact_built<BW, L, CV>()) return launch_chi_exact<BW, L, CV>(c, nblk, lds, st, mode);
-  else return false;
+static bool chi_exact_listed(int K, int M) {
+#define X(k, m) if (K == k && M == m) return true;
+  BFMMM_CHI_EXACT(X)
+#undef X
+  return false;
+}
+static bool z_exact_listed(int K) { return K == 2 || K == 3 || K == 4; }      // k_curve_z with K exact, same models
+
+// The one place that chooses the instance of a per-curve launch (launchers.hpp: CurveRoute).  launch_curve reads it and nothing
+// else, and bfmmm_run records it (bfmmm_debug_get "curve_route"), so the record also holds for a run that replays cached graphs.
+CurveRoute curve_route_decide(const Dims& d, int which, int arg) {
+  CurveRoute r;
+  r.which = which;
+  const int BW = d.BW;
+  if (!((BW >= 0 && BW <= 5) || BW == BWMID || BW == BWWIDE)) return r;
+  r.BW = BW;
+  r.LPC = (d.P <= 32) ? 32 : 64;
+  r.COV = d.D > 0;
+  const int LPC = r.LPC, GPB = 256 / LPC, K = d.K, M = d.M, D = d.D;
+  r.nblk = (d.n + GPB - 1) / GPB;
+  const bool exact = g_exact_instances && chi_exact_built(BW, LPC, r.COV);
+  if (which == 0) {
+    const bool lean = (arg & 2) != 0 && !r.COV;       // (a lean launch is one without covariates)
+    if (exact && z_exact_listed(K)) { r.KT = K; r.KEX = true; r.LEAN = lean; }
+    else if (K <= 4 && lean && BW <= 5) { r.KT = 4; r.LEAN = true; }
+    else r.KT = (K <= 4) ? 4 : KMAX;
+  } else {
+    r.SMALL = K <= 4 && M <= 8;
+    if (exact && chi_exact_listed(K, M)) { r.KX = K; r.MX = M; }
+  }
+  const int STR = ((LPC + BW) % 2 == 0) ? LPC + BW + 1 : LPC + BW;      // Tile<BW, LPC>::STR
+  const size_t nth = (size_t)K * (M + 1) * d.P;
+  const int TW = d.mv ? 1 : 2;
+  size_t lds;
+  if (which == 0) lds = DYN_LDS_DOUBLES + nth * (1 + D) + GPB * KMAX + GPB + (size_t)GPB * (BW + (TW * K + 3) * STR + MMAX + 48);
+  else lds = DYN_LDS_DOUBLES + nth * (1 + D) + GPB + GPB * KMAX + (size_t)GPB * (BW + (TW * std::max(M, K + 1) + 2) * STR + 3 * M + 1 + std::max(M * (M + 1) / 2 + M + 1, K + K * (K + 1) / 2));
+  if (which == 1 || (arg & 2)) lds = std::max(lds, (size_t)HYPER_LDS_DOUBLES);      // the scalar job's scratch (k_curve_chi, lean k_curve_z)
+  r.lds = (lds + 8) * sizeof(double);
+  return r;
 }
 
-// k_curve_z with K exact (2, 3, 4), same models
+// the launch of route r (BW, L, CV are r's); 3: the route names an instance this build does not hold
 template <int BW, int L, bool CV>
-static bool launch_z_exact(const Ctx& c, int nblk, size_t lds, hipStream_t st, int do_update) {
-  if (!g_exact_instances) return false;
-  if constexpr (chi_exact_built<BW, L, CV>()) {
-    const bool lean = (do_update & 2) != 0 && !CV;       // (a lean launch is one without covariates: see LAUNCH_CURVE)
+static int launch_curve_inst(const Ctx& c, const CurveRoute& r, int arg, hipStream_t st) {
+  const dim3 gz(r.nblk, 1, c.nch), gc(r.nblk + 8, 1, c.nch);
+  const size_t lds = r.lds;
+  if (r.which == 0) {
+    const int du = arg & 1;
+    if (r.KEX) {
+      if constexpr (chi_exact_built<BW, L, CV>()) {
 #define X(k)                                                                                                   \
-    if (c.d.K == k) {                                                                                          \
-      if constexpr (!CV) {                                                                                     \
-        if (lean) { hipLaunchKernelGGL((k_curve_z<BW, L, false, k, true, true>), dim3(nblk + 8, 1, c.nch), dim3(256), lds, st, c, do_update & 1); return true; }  \
-      }                                                                                                        \
-      hipLaunchKernelGGL((k_curve_z<BW, L, CV, k, false, true>), dim3(nblk, 1, c.nch), dim3(256), lds, st, c, do_update & 1);          \
-      return true;                                                                                             \
-    }
-    X(2) X(3) X(4)
+        if (r.KT == k) {                                                                                       \
+          if constexpr (!CV) {                                                                                 \
+            if (r.LEAN) { hipLaunchKernelGGL((k_curve_z<BW, L, false, k, true, true>), gc, dim3(256), lds, st, c, du); return 0; }  \
+          }                                                                                                    \
+          if (r.LEAN) return 3;                                                                                \
+          hipLaunchKernelGGL((k_curve_z<BW, L, CV, k, false, true>), gz, dim3(256), lds, st, c, du);           \
+          return 0;                                                                                            \
+        }
+        X(2) X(3) X(4)
 #undef X
+      }
+      return 3;
+    }
+    if (r.LEAN) {
+      if constexpr (!CV && BW <= 5) { hipLaunchKernelGGL((k_curve_z<BW, L, false, 4, true>), gc, dim3(256), lds, st, c, du); return 0; }
+      return 3;
+    }
+    if (r.KT == 4) hipLaunchKernelGGL((k_curve_z<BW, L, CV, 4>), gz, dim3(256), lds, st, c, du);
+    else hipLaunchKernelGGL((k_curve_z<BW, L, CV, KMAX>), gz, dim3(256), lds, st, c, du);
+    return 0;
   }
-  return false;
+  if (r.KX > 0) {
+    if constexpr (chi_exact_built<BW, L, CV>()) return launch_chi_exact<BW, L, CV>(c, r.nblk, lds, st, arg) ? 0 : 3;
+    return 3;
+  }
+  if (r.SMALL) hipLaunchKernelGGL((k_curve_chi<BW, L, CV, true>), gc, dim3(256), lds, st, c, arg);
+  else hipLaunchKernelGGL((k_curve_chi<BW, L, CV, false>), gc, dim3(256), lds, st, c, arg);
+  return 0;
 }
 
 template <int BW, int L, bool CV>
@@ -920,35 +979,9 @@ static void prepare_chi_exact() {
 }
 
 template <int BW>
-static void launch_curve_bw(const Ctx& c, int which, int do_update, hipStream_t st) {
-  const int LPC = (c.d.P <= 32) ? 32 : 64;
-  const int GPB = 256 / LPC;
-  const int nblk = (c.d.n + GPB - 1) / GPB;
-  const int K = c.d.K, M = c.d.M;
-  const int STR = ((LPC + BW) % 2 == 0) ? LPC + BW + 1 : LPC + BW;      // Tile<BW, LPC>::STR
-  const int D = c.d.D;
-  const size_t nth = (size_t)K * (M + 1) * c.d.P;
-  const size_t tileE = 0;      // (the covariate-adjusted rows are no longer materialised per curve)
-  size_t lds;
-  const int TW = c.d.mv ? 1 : 2;
-  if (which == 0) lds = DYN_LDS_DOUBLES + nth * (1 + D) + GPB * KMAX + GPB + (size_t)GPB * (BW + (TW * K + 3) * STR + MMAX + 48 + tileE);
-  else lds = DYN_LDS_DOUBLES + nth * (1 + D) + GPB + GPB * KMAX + (size_t)GPB * (BW + (TW * std::max(M, K + 1) + 2) * STR + 3 * M + 1 + std::max(M * (M + 1) / 2 + M + 1, K + K * (K + 1) / 2) + tileE);
-  if (which == 1 || (do_update & 2)) lds = std::max(lds, (size_t)HYPER_LDS_DOUBLES);      // the scalar job's scratch (k_curve_chi, lean k_curve_z)
-  lds = (lds + 8) * sizeof(double);
-  const bool cov = D > 0;
-#define LAUNCH_CURVE(L, CV)                                                                                   \
-  do {                                                                                                        \
-    if (which == 0) { if (launch_z_exact<BW, L, CV>(c, nblk, lds, st, do_update)) { }                          \
-                      else if (K <= 4 && (do_update & 2) && !CV && BW <= 5) hipLaunchKernelGGL((k_curve_z<BW, L, false, 4, true>), dim3(nblk + 8, 1, c.nch), dim3(256), lds, st, c, do_update & 1);  \
-                      else if (K <= 4) hipLaunchKernelGGL((k_curve_z<BW, L, CV, 4>), dim3(nblk, 1, c.nch), dim3(256), lds, st, c, do_update & 1);  \
-                      else hipLaunchKernelGGL((k_curve_z<BW, L, CV, KMAX>), dim3(nblk, 1, c.nch), dim3(256), lds, st, c, do_update & 1); }  \
-    else if (try_chi_exact<BW, L, CV>(c, nblk, lds, st, do_update)) { }                                        \
-    else if (K <= 4 && M <= 8) hipLaunchKernelGGL((k_curve_chi<BW, L, CV, true>), dim3(nblk + 8, 1, c.nch), dim3(256), lds, st, c, do_update);      \
-    else hipLaunchKernelGGL((k_curve_chi<BW, L, CV, false>), dim3(nblk + 8, 1, c.nch), dim3(256), lds, st, c, do_update);      \
-  } while (0)
-  if (LPC == 32) { if (cov) LAUNCH_CURVE(32, true); else LAUNCH_CURVE(32, false); }
-  else { if (cov) LAUNCH_CURVE(64, true); else LAUNCH_CURVE(64, false); }
-#undef LAUNCH_CURVE
+static int launch_curve_bw(const Ctx& c, const CurveRoute& r, int arg, hipStream_t st) {
+  if (r.LPC == 32) return r.COV ? launch_curve_inst<BW, 32, true>(c, r, arg, st) : launch_curve_inst<BW, 32, false>(c, r, arg, st);
+  return r.COV ? launch_curve_inst<BW, 64, true>(c, r, arg, st) : launch_curve_inst<BW, 64, false>(c, r, arg, st);
 }
 
 template <int BW>
@@ -979,18 +1012,18 @@ void prepare_curve_kernels() {
 
 int launch_curve(const Ctx& c, int which, int do_update, hipStream_t st) {
   if (c.d.M > MMAX) return 2;
-  switch (c.d.BW) {
-    case 0: launch_curve_bw<0>(c, which, do_update, st); break;
-    case 1: launch_curve_bw<1>(c, which, do_update, st); break;
-    case 2: launch_curve_bw<2>(c, which, do_update, st); break;
-    case 3: launch_curve_bw<3>(c, which, do_update, st); break;
-    case 4: launch_curve_bw<4>(c, which, do_update, st); break;
-    case 5: launch_curve_bw<5>(c, which, do_update, st); break;
-    case BWMID: launch_curve_bw<BWMID>(c, which, do_update, st); break;
-    case BWWIDE: launch_curve_bw<BWWIDE>(c, which, do_update, st); break;
+  const CurveRoute r = curve_route_decide(c.d, which, do_update);
+  switch (r.BW) {
+    case 0: return launch_curve_bw<0>(c, r, do_update, st);
+    case 1: return launch_curve_bw<1>(c, r, do_update, st);
+    case 2: return launch_curve_bw<2>(c, r, do_update, st);
+    case 3: return launch_curve_bw<3>(c, r, do_update, st);
+    case 4: return launch_curve_bw<4>(c, r, do_update, st);
+    case 5: return launch_curve_bw<5>(c, r, do_update, st);
+    case BWMID: return launch_curve_bw<BWMID>(c, r, do_update, st);
+    case BWWIDE: return launch_curve_bw<BWWIDE>(c, r, do_update, st);
     default: return 1;
   }
-  return 0;
 }
 
 int curve_blocks(int n, int P) {

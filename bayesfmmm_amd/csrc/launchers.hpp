@@ -27,6 +27,22 @@ void launch_stats_totals(int n, int LREC, int yy_off, const double* rec, const i
                          long long* out_counts, hipStream_t st);
 
 // ---- kernels_curve.hip ----
+// Which instance of k_curve_z (which 0) or k_curve_chi (which 1) a launch takes: everything curve_route_decide decides, and all
+// launch_curve reads.  arg is launch_curve's third argument: k_curve_z: bit 0 do_update, bit 1 the lean trailing form;
+// k_curve_chi: the mode (0 / 1 / 2) | 16 where it also runs the next iteration's Z update.
+struct CurveRoute {
+  int which = 0;
+  int BW = -1;              // band class (template argument); -1: none is built for Dims::BW
+  int LPC = 0;              // lanes per curve: 32 or 64
+  bool COV = false;
+  int KT = 0;               // k_curve_z: the compile-time bound on K (4 / KMAX; the exact K where KEX)
+  bool LEAN = false, KEX = false;
+  bool SMALL = false;       // k_curve_chi: K <= 4 and M <= 8 (exact instances included)
+  int KX = 0, MX = 0;       // k_curve_chi: the exact (K, M) instance, or 0, 0
+  int nblk = 0;             // curve workgroups (the grid has 8 more in front of them for k_curve_chi and the lean k_curve_z)
+  size_t lds = 0;           // dynamic LDS bytes
+};
+CurveRoute curve_route_decide(const Dims& d, int which, int arg);
 int launch_curve(const Ctx& c, int which, int do_update, hipStream_t st);
 int curve_blocks(int n, int P);
 void prepare_curve_kernels();

@@ -137,6 +137,10 @@ struct Dims {
   int64_t half_sum;     // sum_i floor(n_i / 2)   (UpdateSigma.h:49 integer division)
 };
 
+constexpr int ZREC_SCALARS = 6;      // scalar fields per curve of Ctx::zrec, in front of Znew[0 .. K) (z_proposal.hpp)
+// doubles per chain of Ctx::zrec: the (6 + K) x n record, then one flag (1: the update took PREPARED proposals, 0: it evaluated them in place)
+__host__ __device__ inline size_t zrec_stride(int n, int K) { return (size_t)(ZREC_SCALARS + K) * n + 2; }
+
 // Everything a kernel needs, passed by value (kernarg).
 struct Ctx {
   Dims d;
@@ -216,6 +220,11 @@ struct Ctx {
   // chain storage (slot-major, each slot laid out exactly as the reference returns it)
   double *c_nu, *c_chi, *c_Z, *c_pi, *c_alpha3, *c_delta, *c_A, *c_sigma, *c_tau, *c_gamma, *c_Phi, *c_loglik;
   int nblk_curve;
+  // The Z record of the tests (bfmmm_set_curve_record; z_proposal.hpp: z_record_store), zrec_stride doubles in every chain's arena;
+  // the kernels get a null pointer unless the switch is on (they test the launch's argument, not chain_view's shifted copy).
+  // The LAST member, and addressed like every other per-chain array: every other kernel argument keeps its offset and the
+  // kernels their scalar loads -- a pointer in the middle of Ctx, or a stride of its own, cost some instances scratch.
+  double* zrec;
 };
 
 // geometry of k_pair_gram_pack (kernels_pair_gram.hip), the pair-Gram kernel of chain batches and long curve sets
@@ -234,7 +243,7 @@ struct PgPack {
 // per-chain pointers of Ctx (everything but the shared data rec, ni, Pmat, X)
 #define BFMMM_CHAIN_PTRS(X_)                                                                                         \
   X_(dyn) X_(Z) X_(chi) X_(theta) X_(delta) X_(Aa) X_(gamma) X_(logz_part) X_(rss_part) X_(pg_part) X_(H) X_(H2)       \
-  X_(tvec) X_(rvec) X_(hq) X_(Lz) X_(gstd) X_(zprep) X_(chi_norm) X_(piprep) X_(Cmat)                        \
+  X_(tvec) X_(rvec) X_(hq) X_(Lz) X_(gstd) X_(zprep) X_(chi_norm) X_(zrec) X_(piprep) X_(Cmat)                        \
   X_(c_nu) X_(c_chi) X_(c_Z) X_(c_pi) X_(c_alpha3) X_(c_delta) X_(c_A) X_(c_sigma) X_(c_tau) X_(c_gamma) X_(c_Phi) X_(c_loglik)
 #define BFMMM_CHAIN_PTRS_COV(X_)                                                                                     \
   X_(thetaX) X_(tau_eta) X_(gamma_xi) X_(delta_xi) X_(A_xi) X_(stil) X_(yyp_part) X_(cfull) X_(gfull) X_(w2_part)      \
@@ -265,6 +274,7 @@ __device__ inline Ctx chain_view(const Ctx& c0) { return chain_ctx(c0, blockIdx.
 #endif
 
 extern int g_exact_instances;      // bfmmm_set_exact_instances (bfmmm_capi.hip): 0 = the launchers use only the general instances
+extern int g_curve_record;         // bfmmm_set_curve_record (bfmmm_capi.hip): 1 = the Z updates of a run store their record (Ctx::zrec)
 extern int g_solo_pair_gram;       // bfmmm_set_solo_pair_gram (bfmmm_capi.hip): 0 = single chains keep k_pair_gram's general body
 extern int g_solo_pair_gram_tail;  // bfmmm_set_solo_pair_gram_tail: 0 = the s-part workgroup keeps the general body, the log-likelihood rides with pi / alpha_3
 

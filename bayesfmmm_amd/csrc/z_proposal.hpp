@@ -117,6 +117,29 @@ __device__ inline void z_proposal(const Ctx& c, const RngKey& key, int i, int gl
   out.lpo = dold - lB_new;
 }
 
+// What a Z update decided from, for the tests (bfmmm_set_curve_record; o: the chain's Ctx::zrec, field f of curve i at [f * n + i]):
+// the acceptance value after the "Z_old,k <= 0 -> 1" rule, log_uu, pr_old, pr_new, lpo, lpn, Znew[0 .. K); behind them one flag,
+// whether the update took prepared proposals (z_record_flag: curve 0 stores it where the tag is tested -- carried to the record
+// it cost the covariate instances scratch; the fused update runs only with prepared proposals and stores none).
+// The prepared proposals in zprep cannot serve: by the end of a run k_factor has overwritten them with the next iteration's.
+// Lane 0 of the curve's group stores the scalars, lane k Znew[k]; the three Z bodies call z_record_store behind their Z store,
+// under one uniform test of the kernel-argument pointer.
+__device__ inline void z_record_flag(double* o, const Ctx& c, bool prepared) {      // o: the chain's record
+  o[(unsigned)(ZREC_SCALARS + c.d.K) * (unsigned)c.d.n] = prepared ? 1.0 : 0.0;
+}
+template <int KT>      // (the caller's bound on K: a proposal entry beyond it must not become live for the record's sake)
+__device__ inline void z_record_store(double* o, const Ctx& c, int i, int lp, double acceptance, const ZProposal& zp) {
+  const unsigned n = (unsigned)c.d.n, at = (unsigned)i;      // ((6 + K) n doubles: 32-bit offsets off the uniform base)
+  const int K = c.d.K;
+  if (lp == 0) {
+    o[at] = acceptance; o[n + at] = zp.log_uu; o[2u * n + at] = zp.pr_old; o[3u * n + at] = zp.pr_new; o[4u * n + at] = zp.lpo;
+    o[5u * n + at] = zp.lpn;
+  }
+#pragma unroll
+  for (int k = 0; k < KT; ++k)
+    if (k < K && lp == k) o[(unsigned)(ZREC_SCALARS + k) * n + at] = zp.Znew[k];
+}
+
 // Spare workgroups of k_factor (iteration t): the proposals of iteration t + 1 for 256 / GW curves each (GW lanes per curve:
 // 8 when 2K + 1 <= 8, 16 when 2K + 1 <= 16, else 32 -- zprep_lanes).
 // Z is final for iteration t by then (k_curve_z ran before k_factor), and the keyed RNG makes the variates a function of

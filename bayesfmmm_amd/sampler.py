@@ -462,6 +462,17 @@ class Sampler:
         return dict(kernel=("diag", "chain", "general")[int(v[0])] if v[0] >= 0 else None, targ=int(v[1]), mv=bool(v[2]),
                     direct=bool(v[3]), threads=int(v[4]))
 
+    def curve_route(self):
+        """Which instances of the per-curve kernels the last `run` took (bfmmm_debug_get "curve_route", recorded on the host):
+        {"z": the last Z update, {"form": None / "standalone" / "lean" / "fused", BW, LPC, COV, KT, KEX}, "chi": the last k_curve_chi
+        launch, {BW, LPC, COV, SMALL, KX, MX, mode, fuse}}."""
+        v = self.debug("curve_route", 16)
+        z = dict(form=(None, "standalone", "lean", "fused")[int(v[0])], BW=int(v[1]), LPC=int(v[2]), COV=bool(v[3]), KT=int(v[4]),
+                 KEX=bool(v[5]))
+        chi = dict(BW=int(v[6]), LPC=int(v[7]), COV=bool(v[8]), SMALL=bool(v[9]), KX=int(v[10]), MX=int(v[11]), mode=int(v[12]),
+                   fuse=bool(v[13]))
+        return dict(z=z, chi=chi)
+
     def set_profile(self, enable):
         _lib.check(self.lib.bfmmm_set_profile(self.h, int(enable)))
 

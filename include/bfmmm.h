@@ -372,7 +372,23 @@ int bfmmm_chain_cluster_mean_bands(bfmmm_handle* h, const int32_t* perm, const d
  * host from the decision the launcher reads (also right for a run that replays cached graphs); "rss" (1): the residual sum of
  * squares in the chain's device state -- the sweep's YY - sum_a theta_a'(t_a + r_a) after a run whose mask has U_SIGMA, unless
  * the run also had a chi pass (U_CHI with n_eigen > 0, or U_LOGLIK without U_SIGMA, or covariates), whose per-curve sums
- * replace it.  Returns the number of doubles written through *count. */
+ * replace it;
+ * "curve_route" (14): the per-curve instances of the last bfmmm_run, recorded on the host from the decision the launcher reads:
+ *   its last Z update {form (0 none, 1 stand-alone k_curve_z, 2 its lean trailing form, 3 fused into k_curve_chi), BW, LPC, COV,
+ *   KT, KEX}, then its last k_curve_chi launch {BW, LPC, COV, SMALL, KX, MX, mode (0 scalar job only, 1 residual sums, 2 chi
+ *   update), whether the run's earlier k_curve_chi launches ran the next iteration's Z update};
+ * "chi_norm" (n x M): the standard normals of the chi update as the device holds them;
+ * "zprep" ((3 K + 5) x n): the Z proposals prepared for the NEXT iteration (field-major: Znew, lo, ln, pr_old, pr_new, lpn, lpo, log_uu);
+ * "rss_part" (curve workgroups): k_curve_chi's block sums of the per-curve residual sums of squares;
+ * "logz_part" (curve workgroups x K): the block sums of log Z_ik of the last Z update;
+ * "stil" (n x P): s_i - G_i o_i (covariates set);
+ * "yyp_part" (curve workgroups): block sums of yy_i - 2 o_i's_i + o_i'G_i o_i (covariates set);
+ * "cfull" (n x P): the fitted coefficient c_i (covariates set): k_curve_chi's value, which the eta / Xi steps update when the mask has them;
+ * "gfull" (n x P): G_i c_i likewise (covariates set);
+ * "z_record" ((6 + K) x n, field-major): acceptance, log_uu, pr_old, pr_new, lpo, lpn, Znew of the last Z update of the last run
+ *   (bfmmm_set_curve_record; fails when that run stored none);
+ * "z_prepared" (1): whether that update took the proposals prepared ahead by k_factor (1) or evaluated them in place (0).
+ * Returns the number of doubles written through *count. */
 int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capacity, int64_t* count);
 
 /* Timing of the last bfmmm_run: milliseconds between HIP events recorded on the sampler's stream
@@ -397,6 +413,11 @@ int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* lau
  * the launchers pick when the model's shape is on the list.  0 makes every later launch (of samplers created afterwards) use the
  * general instances instead -- the parity tests run both and compare.  Process-wide; default 1. */
 void bfmmm_set_exact_instances(int enable);
+
+/* 1 makes the Z updates of every later run store, per curve, the values their accept / reject decision was made from (the
+ * acceptance value itself never leaves the kernel otherwise): bfmmm_debug_get "z_record", which fails while this is off.  With
+ * 0 the kernels get a null pointer and skip the stores behind one uniform test.  For the tests.  Process-wide; default 0. */
+void bfmmm_set_curve_record(int enable);
 
 /* Single chains run the G workgroups of the pair-Gram contraction through a body of their own where the shape allows (DESIGN.md
  * section 5); 0 makes later runs use the general body instead -- the parity tests run both and compare bit for bit.
