@@ -908,6 +908,13 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
     const SweepRoute sr = sweep_route_decide(c.d);
     const double w[5] = {(double)sr.kernel, (double)sr.targ, c.d.mv ? 1.0 : 0.0, (double)sr.direct, (double)sr.threads};
     memcpy(h->last_sweep, w, sizeof w);
+    // what launch_cov_block launches in every iteration, for bfmmm_debug_get("cov_route"): from the function it reads
+    if (c.d.D > 0) {
+      const CovRoute cr = cov_route_decide(c);
+      const double x[11] = {(double)cr.BW, (double)cr.LPC, (double)cr.DX, (double)cr.W2D, (double)cr.PP, (double)cr.NB2, (double)cr.NBS,
+                            (double)cr.NPG, (double)cr.launches, cr.do_eta ? 1.0 : 0.0, cr.do_xi ? 1.0 : 0.0};
+      memcpy(h->last_cov, x, sizeof x);
+    }
   }
   // the Z record (bfmmm_set_curve_record): the launches of this run get the array, or a null pointer
   const int rec_on = bfmmm::g_curve_record;
@@ -1131,7 +1138,15 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
     *count = cnt;
     return 0;
   }
-  if (s == "z_record" || s == "z_prepared") {      // the selected chain's record of the last run's last Z update (z_proposal.hpp)
+  if (s == "cov_route") {     // host-side record of the last bfmmm_run (run_impl)
+    if (d.D == 0) return fail("bfmmm_debug_get(" + s + "): the record exists once covariates are set");
+    const int64_t cnt = sizeof h->last_cov / sizeof h->last_cov[0];
+    if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
+    memcpy(out, h->last_cov, sizeof h->last_cov);
+    *count = cnt;
+    return 0;
+  }
+  if (s == "z_record" || s == "z_prepared") {     // the selected chain's record of the last run's last Z update (z_proposal.hpp)
     if (!bfmmm::g_curve_record) return fail("bfmmm_debug_get(" + s + "): recording is off (bfmmm_set_curve_record)");
     if (!h->zrec_form) return fail("bfmmm_debug_get(" + s + "): the last run stored no record (no Z update in its mask, or recording was off)");
     const int64_t len = (int64_t)(ZREC_SCALARS + d.K) * d.n, cnt = s == "z_record" ? len : 1;
@@ -1165,7 +1180,12 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
                       {"chi_norm", c.chi_norm, (int64_t)d.n * d.M}, {"zprep", c.zprep, (int64_t)(3 * d.K + 5) * d.n},
                       {"rss_part", c.rss_part, (int64_t)c.nblk_curve}, {"logz_part", c.logz_part, (int64_t)c.nblk_curve * d.K},
                       {"stil", c.stil, (int64_t)d.n * d.P}, {"yyp_part", c.yyp_part, (int64_t)c.nblk_curve},
-                      {"cfull", c.cfull, (int64_t)d.n * d.P}, {"gfull", c.gfull, (int64_t)d.n * d.P}};
+                      {"cfull", c.cfull, (int64_t)d.n * d.P}, {"gfull", c.gfull, (int64_t)d.n * d.P},
+                      // what the eta / Xi block (kernels_cov.hip) leaves behind; they exist once covariates were set
+                      {"Wdir", c.Wdir, (int64_t)d.n * c.A2}, {"H2aa", c.H2aa, (int64_t)c.NPAIR * d.LG},
+                      {"C2", c.C2, (int64_t)c.A2 * d.P * d.P}, {"Lz2", c.Lz2, (int64_t)c.A2 * d.P},
+                      {"gstd2", c.gstd2, (int64_t)d.K * d.D + (int64_t)d.K * d.M * d.D + (int64_t)d.K * d.D * d.P * d.M},
+                      {"thetaX", c.thetaX, (int64_t)d.K * (d.M + 1) * d.D * d.P}};      // (row (j (M + 1) + mt) D + d: A2 rows with the Xi block)
   for (const Arr& a : arrs)
     if (s == a.nm) {
       if (!a.p) return fail("bfmmm_debug_get(" + s + "): the array exists once covariates are set");

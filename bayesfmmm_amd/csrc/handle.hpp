@@ -74,6 +74,9 @@ struct bfmmm_handle {
   // k_curve_chi), BW, LPC, COV, KT, KEX}, then its last k_curve_chi launch {BW, LPC, COV, SMALL, KX, MX, mode, whether the
   // run's earlier chi launches ran the next Z update} (BW -1: no such launch)
   double last_curve[14] = {0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0};
+  // bfmmm_debug_get("cov_route"): what launch_cov_block launches in every iteration of the last run {BW, LPC, DX (0 general), the D
+  // instance of k_cov_w2, PP of k_cov_factor, NB2, NBS, NPG, k_cov_group launches, do_eta, do_xi} (BW -1: no covariates)
+  double last_cov[11] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   int64_t tab_key = -1;                // (MD, mask) the step tables of k_sweep_chain were built for
   int launch_error = 0;                // set while a run's launches are queued: 1 the sweep does not fit, 2 no per-curve instance
   int zrec_form = 0;                   // the Z record of the last run (Ctx::zrec): 0 none stored (recording off, or no Z update in the mask),

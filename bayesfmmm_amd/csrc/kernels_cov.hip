@@ -766,33 +766,53 @@ __global__ __launch_bounds__(HT) void k_cov_hyper(Ctx c0) {
 // ---- host launchers -------------------------------------------------------------------------
 #define COV_EACH_D(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
 static_assert(DMAX_COV == 8, "COV_EACH_D lists 1 .. DMAX_COV");
+// The one decision of what launch_cov_block launches for a run's Dims and mask (bfmmm_debug_get("cov_route") reports it).
+CovRoute cov_route_decide(const Ctx& c) {
+  const Dims& d = c.d;
+  CovRoute r;
+  r.BW = (d.BW <= 5) ? d.BW : (d.BW == BWMID ? BWMID : BWWIDE);
+  r.LPC = (d.P <= 32) ? 32 : 64;
+  r.DX = (r.BW == 3 && g_exact_instances && d.D >= 1 && d.D <= DMAX_COV) ? d.D : 0;      // instances with D exact
+  r.W2D = d.D;
+  r.PP = (d.P <= 32) ? 32 : 64;
+  r.NB2 = c.NB2; r.NBS = c.NBS; r.NPG = c.NPG;
+  r.do_eta = (c.mask & U_ETA) != 0;
+  r.do_xi = (c.mask & U_XI) != 0 && c.covariance_adj && d.MD > 1;
+  const int n_eta_groups = d.K, n_groups = c.A2 / d.D;
+  r.launches = 1;      // the last group's draws and the residual sums
+  if (r.do_eta) r.launches += n_eta_groups;
+  if (r.do_xi) r.launches += n_groups - n_eta_groups;
+  r.lds_group = ((size_t)c.NPG * d.LG + 2 + (d.P <= 32 ? (size_t)d.D * d.P * d.P + 2 : 0)) * sizeof(double);
+  return r;
+}
+
 template <int BW>
-static void launch_group_bw(const Ctx& c, int g_prev, int g_next, int par_prev, hipStream_t st) {
-  const size_t lds = ((size_t)c.NPG * c.d.LG + 2 + (c.d.P <= 32 ? (size_t)c.d.D * c.d.P * c.d.P + 2 : 0)) * sizeof(double);
+static void launch_group_bw(const Ctx& c, const CovRoute& r, int g_prev, int g_next, int par_prev, hipStream_t st) {
+  const size_t lds = r.lds_group;
   if constexpr (BW == 3) {           // instances with D exact
 #define X(dx)                                                                                                                    \
-    if (g_exact_instances && c.d.D == dx) {                                                                                                           \
-      if (c.d.P <= 32) hipLaunchKernelGGL((k_cov_group<BW, 32, dx>), dim3(c.NBS, 1, c.nch), dim3(GT), lds, st, c, g_prev, g_next, par_prev);   \
+    if (r.DX == dx) {                                                                                                           \
+      if (r.LPC == 32) hipLaunchKernelGGL((k_cov_group<BW, 32, dx>), dim3(c.NBS, 1, c.nch), dim3(GT), lds, st, c, g_prev, g_next, par_prev);   \
       else hipLaunchKernelGGL((k_cov_group<BW, 64, dx>), dim3(c.NBS, 1, c.nch), dim3(GT), lds, st, c, g_prev, g_next, par_prev);  \
       return;                                                                                                                    \
     }
     COV_EACH_D(X)
 #undef X
   }
-  if (c.d.P <= 32) hipLaunchKernelGGL((k_cov_group<BW, 32>), dim3(c.NBS, 1, c.nch), dim3(GT), lds, st, c, g_prev, g_next, par_prev);
+  if (r.LPC == 32) hipLaunchKernelGGL((k_cov_group<BW, 32>), dim3(c.NBS, 1, c.nch), dim3(GT), lds, st, c, g_prev, g_next, par_prev);
   else hipLaunchKernelGGL((k_cov_group<BW, 64>), dim3(c.NBS, 1, c.nch), dim3(GT), lds, st, c, g_prev, g_next, par_prev);
 }
 
-static void launch_group(const Ctx& c, int g_prev, int g_next, int par_prev, hipStream_t st) {
-  switch (c.d.BW) {
-    case 0: launch_group_bw<0>(c, g_prev, g_next, par_prev, st); break;
-    case 1: launch_group_bw<1>(c, g_prev, g_next, par_prev, st); break;
-    case 2: launch_group_bw<2>(c, g_prev, g_next, par_prev, st); break;
-    case 3: launch_group_bw<3>(c, g_prev, g_next, par_prev, st); break;
-    case 4: launch_group_bw<4>(c, g_prev, g_next, par_prev, st); break;
-    case 5: launch_group_bw<5>(c, g_prev, g_next, par_prev, st); break;
-    case BWMID: launch_group_bw<BWMID>(c, g_prev, g_next, par_prev, st); break;
-    default: launch_group_bw<BWWIDE>(c, g_prev, g_next, par_prev, st); break;
+static void launch_group(const Ctx& c, const CovRoute& r, int g_prev, int g_next, int par_prev, hipStream_t st) {
+  switch (r.BW) {
+    case 0: launch_group_bw<0>(c, r, g_prev, g_next, par_prev, st); break;
+    case 1: launch_group_bw<1>(c, r, g_prev, g_next, par_prev, st); break;
+    case 2: launch_group_bw<2>(c, r, g_prev, g_next, par_prev, st); break;
+    case 3: launch_group_bw<3>(c, r, g_prev, g_next, par_prev, st); break;
+    case 4: launch_group_bw<4>(c, r, g_prev, g_next, par_prev, st); break;
+    case 5: launch_group_bw<5>(c, r, g_prev, g_next, par_prev, st); break;
+    case BWMID: launch_group_bw<BWMID>(c, r, g_prev, g_next, par_prev, st); break;
+    default: launch_group_bw<BWWIDE>(c, r, g_prev, g_next, par_prev, st); break;
   }
 }
 
@@ -804,8 +824,8 @@ int cov_w2_chunks(int n) { return (n + W2_CH - 1) / W2_CH; }
 // the eta / Xi part of one iteration (after k_curve_chi has stored c_i, g_i)
 void launch_cov_block(const Ctx& c, hipStream_t st) {
   const Dims& d = c.d;
-  const bool do_eta = (c.mask & U_ETA) != 0;
-  const bool do_xi = (c.mask & U_XI) != 0 && c.covariance_adj && d.MD > 1;
+  const CovRoute r = cov_route_decide(c);
+  const bool do_eta = r.do_eta, do_xi = r.do_xi;
   int g_prev = -1, par = 0;
   {
     const size_t tot = (size_t)d.n * c.A2;
@@ -815,24 +835,24 @@ void launch_cov_block(const Ctx& c, hipStream_t st) {
   }
   if (do_eta || do_xi) {
     const size_t lds_w2 = ((size_t)W2_CH * d.D + (size_t)c.NPG * 128) * sizeof(double);
-    switch (d.D) {
+    switch (r.W2D) {
 #define X(dx) case dx: hipLaunchKernelGGL(k_cov_w2<dx>, dim3(c.A2 / d.D, c.NB2, c.nch), dim3(256), lds_w2, st, c); break;
       COV_EACH_D(X)
 #undef X
     }
-    const int PP = (d.P <= 32) ? 32 : 64;
+    const int PP = r.PP;
     const size_t lds = (2 * (size_t)PP * PP + PP + d.LG + 4 * PP + 2) * sizeof(double);      // + scratch of the pseudo-inverse route
     if (PP == 32) hipLaunchKernelGGL(k_cov_factor<32>, dim3(c.NPAIR, 1, c.nch), dim3(256), lds, st, c);
     else hipLaunchKernelGGL(k_cov_factor<64>, dim3(c.NPAIR, 1, c.nch), dim3(256), lds, st, c);
     const int n_eta_groups = d.K, n_groups = c.A2 / d.D;
     for (int g = 0; g < n_groups; ++g) {
       if (g < n_eta_groups ? !do_eta : !do_xi) continue;
-      launch_group(c, g_prev, g, par, st);      // partial sums of g go to parity par ^ 1
+      launch_group(c, r, g_prev, g, par, st);      // partial sums of g go to parity par ^ 1
       g_prev = g;
       par ^= 1;
     }
   }
-  launch_group(c, g_prev, -1, par, st);      // the last group's draws, and the residual sums for the log-likelihood
+  launch_group(c, r, g_prev, -1, par, st);      // the last group's draws, and the residual sums for the log-likelihood
   const size_t lds_h = ((size_t)d.K * d.D * d.P + (size_t)d.P * d.P + 3 * (size_t)d.D * d.K * d.M) * sizeof(double);
   hipLaunchKernelGGL(k_cov_hyper, dim3(1, 1, c.nch), dim3(HT), lds_h, st, c);
 }

@@ -92,6 +92,20 @@ void launch_fill_slots(const Ctx& c, double* chain, const double* cur, size_t le
 void prepare_sweep_kernels();
 
 // ---- kernels_cov.hip ----
+// What the eta / Xi block of a run's Dims (MD set) and mask launches: everything cov_route_decide decides, and all
+// launch_cov_block reads to choose an instance.
+struct CovRoute {
+  int BW = 0;               // band class of k_cov_group (template argument)
+  int LPC = 0;              // lanes per curve of k_cov_group: 32 or 64
+  int DX = 0;               // its exact-D instance, or 0: the general one
+  int W2D = 0;              // the D instance of k_cov_w2
+  int PP = 0;               // k_cov_factor<PP>
+  int NB2 = 0, NBS = 0, NPG = 0;      // curve chunks of k_cov_w2, workgroups of k_cov_group, in-group pairs
+  int launches = 0;         // k_cov_group launches of one iteration (the closing residual pass included)
+  bool do_eta = false, do_xi = false;
+  size_t lds_group = 0;     // dynamic LDS bytes of k_cov_group
+};
+CovRoute cov_route_decide(const Ctx& c);
 void launch_cov_block(const Ctx& c, hipStream_t st);
 int cov_step_blocks(int nblk_curve);
 int cov_w2_chunks(int n);

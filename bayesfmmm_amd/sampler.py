@@ -473,6 +473,16 @@ class Sampler:
                    fuse=bool(v[13]))
         return dict(z=z, chi=chi)
 
+    def cov_route(self):
+        """What the eta / Xi block of every iteration of the last `run` launches (bfmmm_debug_get "cov_route", recorded on the
+        host; covariates set): BW, LPC and DX (0: the general instance) of k_cov_group, the D instance of k_cov_w2, PP of
+        k_cov_factor, NB2, NBS, NPG, the number of k_cov_group launches, do_eta, do_xi."""
+        v = self.debug("cov_route", 16)
+        names = ("BW", "LPC", "DX", "W2D", "PP", "NB2", "NBS", "NPG", "launches")
+        out = {k: int(x) for k, x in zip(names, v)}
+        out.update(do_eta=bool(v[9]), do_xi=bool(v[10]))
+        return out
+
     def set_profile(self, enable):
         _lib.check(self.lib.bfmmm_set_profile(self.h, int(enable)))
 

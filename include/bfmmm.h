@@ -385,6 +385,18 @@ int bfmmm_chain_cluster_mean_bands(bfmmm_handle* h, const int32_t* perm, const d
  * "yyp_part" (curve workgroups): block sums of yy_i - 2 o_i's_i + o_i'G_i o_i (covariates set);
  * "cfull" (n x P): the fitted coefficient c_i (covariates set): k_curve_chi's value, which the eta / Xi steps update when the mask has them;
  * "gfull" (n x P): G_i c_i likewise (covariates set);
+ * what the eta / Xi block of the last iteration left (covariates set; an error otherwise), A2 = K D (+ K M D with the Xi block)
+ * directions in the order of the sweep (eta: d outer, j inner; then Xi: (j, m, d)), groups of D consecutive directions:
+ *   "Wdir" (n x A2, direction fastest): w_{a,i} = Z_ij x_id (chi_im);
+ *   "H2aa" (NPAIR x LG): sum_i w_u w_v G_i, band rows, of in-group pair (u <= v) of group g at row g D(D+1)/2 + v(v+1)/2 + u
+ *     (only groups the mask updates are written);
+ *   "C2" (A2 x P x P) and "Lz2" (A2 x P): the conditional covariance C_a and L_a z_a of every updated direction;
+ *   "gstd2" (K D + K M D + K D P M): the standard gamma variates of tau_eta, delta_xi, gamma_xi;
+ *   "thetaX" (K (M + 1) D x P, row (j (M + 1) + mt) D + d; A2 x P with the Xi block): the committed eta (mt = 0) and xi rows;
+ * "cov_route" (11): what the eta / Xi block of every iteration of the last bfmmm_run launches, recorded on the host from the
+ *   decision the launcher reads: {BW and LPC of k_cov_group, its exact-D instance (0: general), the D instance of k_cov_w2, PP of
+ *   k_cov_factor, NB2 (curve chunks of k_cov_w2), NBS (workgroups of k_cov_group), NPG (in-group pairs), k_cov_group launches
+ *   (the closing residual pass included), do_eta, do_xi};
  * "z_record" ((6 + K) x n, field-major): acceptance, log_uu, pr_old, pr_new, lpo, lpn, Znew of the last Z update of the last run
  *   (bfmmm_set_curve_record; fails when that run stored none);
  * "z_prepared" (1): whether that update took the proposals prepared ahead by k_factor (1) or evaluated them in place (0).
