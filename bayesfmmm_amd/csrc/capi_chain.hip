@@ -1,7 +1,8 @@
 // C ABI of the sampler (include/bfmmm.h), what is read off the chain slots after a run: the chain arrays, their convergence
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
-// per-curve covariance surfaces, the label alignment against a pivot and the pooled cluster summaries under it.
+// per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it and the cluster
+// covariance surfaces with their bands.
 // An entry point is its argument checks (SlotCheck: slots, curve selection, workspace plan), its workspace and the event pairs
 // that time its launches into the handle's PT_* timers (CallBufs owns both) and one for_chunks.
 #include "handle.hpp"
@@ -876,4 +877,163 @@ extern "C" int bfmmm_chain_cluster_mean_bands(bfmmm_handle* h, const int32_t* pe
     if (err.empty()) collect(h, project, PT_ALIGN_PROJECT);
     return err;
   });
+}
+
+// ---- cluster covariance surfaces with bands under aligned labels (kernels_cluster_cov.hip) ----------------------
+// Mean, sd and quantiles over the pooled draws of c_r(g, h) = sum_m W1_k[g][m] W2_l[h][m] of the aligned pairs r = (k, l), and the
+// simultaneous band per pair: k_ccov_project once per call, then per chunk of consecutive result rows k_ccov_values into rows of
+// C S values and launch_bands_moments and launch_bands_quantiles on them as they are.  The band's deviations need every chunk's
+// mean and sd: with one chunk its values are reused, with several a second sweep forms them again for k_ccov_maxdev.
+extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* perm, const double* E1, int G1, const double* E2, int G2,
+                                             int diagonal, const int32_t* pairs, int n_pairs, const double* x, int first_slot, int n_slots,
+                                             const double* probs, int nq, double alpha, int64_t max_workspace_bytes, double* mean, double* sd,
+                                             double* quant, double* crit, double* lower, double* upper, double* trace, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_cluster_cov_bands", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"h", h}, {"perm", perm}, {"E1", E1}, {"mean", mean}, {"sd", sd}})) return 1;
+  if (G1 < 1) return fail(fn + ": 'G1' must be at least 1");
+  if (E2 && G2 < 1) return fail(fn + ": 'G2' must be at least 1 where 'E2' is given");
+  if (diagonal && E2) return fail(fn + ": 'diagonal' requires 'E2' to be null");
+  if (n_pairs < 0) return fail(fn + ": 'n_pairs' must not be negative");
+  const Ctx& c = h->c;
+  const int K = c.d.K, P = c.d.P, D = c.d.D;
+  for (int r = 0; pairs && r < n_pairs; ++r)
+    if (pairs[2 * r] < 0 || pairs[2 * r] >= K || pairs[2 * r + 1] < 0 || pairs[2 * r + 1] >= K)
+      return fail(fn + ": 'pairs'[" + std::to_string(r) + "] = (" + std::to_string(pairs[2 * r]) + ", " + std::to_string(pairs[2 * r + 1]) +
+                  ") outside 0 .. " + std::to_string(K - 1));
+  if (x && !(c.covariance_adj && D > 0)) return fail(fn + ": 'x' is given but the sampler is not covariance-adjusted");
+  for (int d = 0; x && d < D; ++d)
+    if (!std::isfinite(x[d])) return fail(fn + ": 'x'[" + std::to_string(d) + "] is not finite");
+  if (c.d.M < 1) return fail(fn + ": n_eigen is 0: the model has no covariance surface");
+  if (!E2) G2 = G1;
+  // the pairs of the result: the caller's, or all k <= l
+  std::vector<int32_t> pr;
+  if (pairs) pr.assign(pairs, pairs + 2 * (size_t)n_pairs);
+  else
+    for (int k = 0; k < K; ++k)
+      for (int l = k; l < K; ++l) { pr.push_back(k); pr.push_back(l); }
+  const int64_t m = (int64_t)pr.size() / 2;
+  const int64_t cells = diagonal ? (int64_t)G1 : (int64_t)G1 * G2;      // entries of a pair's result
+  const int64_t len = m * cells;
+  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, len) || ck.row_limit() || probs_check(ck, probs, nq, quant))
+    return 1;
+  const bool band = crit || lower || upper;
+  if (band && !(crit && lower && upper)) return fail(fn + ": 'crit', 'lower' and 'upper' must be all null or all set");
+  if (band && !(alpha > 0.0 && alpha < 1.0)) return fail(fn + ": 'alpha' must be inside (0, 1)");
+  if (perm_check(ck, perm)) return 1;
+  CcovCall f;
+  f.G1 = G1; f.G2 = G2; f.diagonal = diagonal ? 1 : 0; f.first_slot = first_slot; f.n_slots = n_slots; f.n_pairs = m;
+  const std::string bad = ccov_check(c, f);
+  if (!bad.empty()) return fail(fn + ": " + bad);
+  reset_timers(h, PT_CCOV_PROJECT, PT_CCOV_MAXDEV);
+  if (m == 0) return 0;
+  const size_t N = (size_t)ck.CS();
+  const bool long_dev = band && (long long)N > ccov_sort_rows();               // dev's rows are sorted in the workspace too
+  const bool sort_ws = (nq > 0 && (long long)N > fit_lds_rows()) || long_dev;  // k_bands_quantiles_big sorts in a workspace
+  const size_t NP = sort_ws ? (size_t)bands_sort_pad((int)N) : 0;
+  // shared by all rows: the tables, E1, E2, x, probs, perm, the pairs and, for the band, dev and crit; a row: its values, its sort
+  // workspace, its mean, sd and quantiles
+  const size_t tab1 = ccov_table_doubles(c, f, 0), tab2 = E2 ? ccov_table_doubles(c, f, 1) : 0;
+  const size_t shared = sizeof(double) * (tab1 + tab2 + (size_t)G1 * P + (E2 ? (size_t)G2 * P : 0) + (x ? (size_t)D : 0) + 17 +
+                                          (band ? (size_t)m * N + (size_t)m : 0)) +
+                        sizeof(int32_t) * (((N * K + 1) & ~(size_t)1) + 2 * (size_t)m);
+  const size_t per_row = sizeof(double) * (N + 2 + (size_t)nq + NP);
+  const size_t budget = budget_of(max_workspace_bytes);
+  if (budget < shared + per_row)
+    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_row) + " bytes one row needs (" +
+                std::to_string(shared) + " shared by all rows + " + std::to_string(per_row) + " per row)");
+  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(len, (int64_t)((budget - shared) / per_row)), 1 << 30);
+  const int64_t nchunks = (len + chunk - 1) / chunk;
+  HIPCHK(hipSetDevice(h->device));
+  CallBufs b;
+  double *d_v = nullptr, *d_E1 = nullptr, *d_E2 = nullptr, *d_x = nullptr, *d_probs = nullptr, *d_dev = nullptr, *d_crit = nullptr;
+  int32_t *d_perm = nullptr, *d_pairs = nullptr;
+  Timer project, values, maxdev;
+  HIPCHK(b.timers({&project, &values, &maxdev}));
+  HIPCHK(b.get(&d_v, per_row / sizeof(double) * (size_t)chunk));
+  HIPCHK(b.put(h, &d_E1, E1, (size_t)G1 * P));
+  HIPCHK(b.get(&f.tab1, tab1));
+  if (E2) {
+    HIPCHK(b.put(h, &d_E2, E2, (size_t)G2 * P));
+    HIPCHK(b.get(&f.tab2, tab2));
+  }
+  if (x) HIPCHK(b.put(h, &d_x, x, (size_t)D));
+  HIPCHK(b.put(h, &d_perm, perm, N * K));
+  HIPCHK(b.put(h, &d_pairs, (const int32_t*)pr.data(), pr.size()));
+  HIPCHK(b.get(&d_probs, 17));
+  const double p_crit = 1.0 - alpha;
+  if (nq) HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
+  if (band) {
+    HIPCHK(copy_sync(h, d_probs + 16, &p_crit, sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(b.get(&d_dev, (size_t)m * N));
+    HIPCHK(b.get(&d_crit, (size_t)m));
+    HIPCHK(hipMemsetAsync(d_dev, 0, sizeof(double) * (size_t)m * N, h->st));      // the maximum starts from 0.0
+  }
+  f.E1 = d_E1; f.E2 = d_E2; f.x = d_x; f.perm = d_perm; f.pairs = d_pairs;
+  double* d_mean = d_v + (size_t)chunk * N;
+  double* d_sd = d_mean + (size_t)chunk;
+  double* d_q = d_sd + (size_t)chunk;
+  double* d_w = d_q + (size_t)nq * (size_t)chunk;
+  const std::string perr = timed(project, h->st, [&] { return launch_ccov_project(c, f, h->st); });
+  if (!perr.empty()) { (void)hipStreamSynchronize(h->st); return fail(fn + ": " + perr); }
+  HIPCHK(hipStreamSynchronize(h->st));
+  collect(h, project, PT_CCOV_PROJECT);
+  h->post_launches[PT_CCOV_PROJECT] = E2 ? 2 : 1;      // the tables filled
+  int rc = for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
+    const bool dev_now = band && nchunks == 1;
+    std::string err = timed(values, h->st, [&] { return launch_ccov_values(c, f, r0, rows, d_v, h->st); });
+    if (err.empty()) err = launch_bands_moments(d_v, (int)N, rows, d_mean, d_sd, h->st);
+    if (err.empty() && nq) err = launch_bands_quantiles(d_v, (int)N, rows, d_w, d_probs, nq, d_q, h->st);
+    if (err.empty() && dev_now) err = timed(maxdev, h->st, [&] { return launch_ccov_maxdev(f, (long long)N, r0, rows, d_v, d_mean, d_sd, d_dev, h->st); });
+    if (err.empty() &&
+        ((nq && hipMemcpyAsync(quant + (size_t)r0 * nq, d_q, sizeof(double) * (size_t)rows * nq, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         (trace && hipMemcpyAsync(trace + (size_t)r0 * N, d_v, sizeof(double) * (size_t)rows * N, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         hipMemcpyAsync(mean + r0, d_mean, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+         copy_sync(h, sd + r0, d_sd, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (!err.empty()) return err;
+    collect(h, values, PT_CCOV);
+    if (dev_now) collect(h, maxdev, PT_CCOV_MAXDEV);
+    return err;
+  });
+  if (rc || !band) return rc;
+  if (nchunks > 1) {
+    // the second sweep: the same kernel on the same tables gives the same values, now against every chunk's mean and sd
+    rc = for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
+      std::string err = timed(values, h->st, [&] { return launch_ccov_values(c, f, r0, rows, d_v, h->st); });
+      if (err.empty() && (copy_sync(h, d_mean, mean + r0, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess ||
+                          copy_sync(h, d_sd, sd + r0, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess))
+        err = "copy of the chunk's mean and sd failed";
+      if (err.empty()) err = timed(maxdev, h->st, [&] { return launch_ccov_maxdev(f, (long long)N, r0, rows, d_v, d_mean, d_sd, d_dev, h->st); });
+      if (err.empty() && (hipStreamSynchronize(h->st) != hipSuccess || hipGetLastError() != hipSuccess)) err = "kernel failed";
+      if (!err.empty()) return err;
+      collect(h, values, PT_CCOV);
+      collect(h, maxdev, PT_CCOV_MAXDEV);
+      return err;
+    });
+    if (rc) return rc;
+  }
+  // crit[r]: the (1 - alpha) quantile of dev's row r, interpolated without an fma as k_fit_sim's is; long rows are sorted by
+  // k_bands_quantiles_big, in pieces of as many rows as the chunk's sort workspace holds, and the rule read off them again
+  rc = for_chunks(ck, m, long_dev ? std::min<int64_t>(m, chunk) : m, [&](int64_t p0, int cnt) {
+    std::string err;
+    if (!long_dev) err = launch_ccov_crit(d_dev + (size_t)p0 * N, (long long)N, cnt, p_crit, d_crit + p0, h->st);
+    else {
+      err = launch_bands_quantiles(d_dev + (size_t)p0 * N, (int)N, cnt, d_w, d_probs + 16, 1, d_crit + p0, h->st);
+      if (err.empty()) err = launch_fit_quantiles(d_w, (int)NP, (int)N, cnt, d_probs + 16, 1, d_crit + p0, h->st);
+    }
+    if (err.empty() && copy_sync(h, crit + p0, d_crit + p0, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost) != hipSuccess)
+      err = "kernel or copy back failed";
+    return err;
+  });
+  if (rc) return rc;
+  {
+#pragma clang fp contract(off)
+    for (int64_t e = 0; e < len; ++e) {
+      const double w = crit[e / cells] * sd[e];
+      lower[e] = mean[e] - w;
+      upper[e] = mean[e] + w;
+    }
+  }
+  return 0;
 }

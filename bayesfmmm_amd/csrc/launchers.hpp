@@ -194,6 +194,31 @@ std::string launch_cov_project(const Ctx& c, const CovCall& f, hipStream_t st);
 // (r from 0; diagonal: [r G1 + g], [(r C + q) G1 + g]); sd, chain_mean may be null
 std::string launch_curve_cov(const Ctx& c, const CovCall& f, int r0, int rows, double* mean, double* sd, double* chain_mean, hipStream_t st);
 
+// ---- kernels_cluster_cov.hip ----
+// One call of bfmmm_chain_cluster_cov_bands: the evaluation bases E1 (G1 x P) and E2 (G2 x P; null: E2 = E1, G2 =
+// G1), whether only the diagonal g = h is wanted (E2 null), the permutation rows perm[(q S + s) K + .], the n_pairs pairs
+// pairs[2 r], pairs[2 r + 1] of aligned components, the covariate setting x (D entries; null: phi alone), the slot range and the
+// call's projection tables of ccov_table_doubles(.., 0 / 1) doubles (tab2 null where E2 is; all device).
+struct CcovCall {
+  int G1 = 0, G2 = 0, diagonal = 0, first_slot = 0, n_slots = 0;
+  long long n_pairs = 0;
+  const double *E1 = nullptr, *E2 = nullptr, *x = nullptr;
+  const int32_t *perm = nullptr, *pairs = nullptr;
+  double *tab1 = nullptr, *tab2 = nullptr;
+};
+std::string ccov_check(const Ctx& c, const CcovCall& f);
+size_t ccov_table_doubles(const Ctx& c, const CcovCall& f, int which);
+std::string launch_ccov_project(const Ctx& c, const CcovCall& f, hipStream_t st);
+// the values V[cs + N (e - r0)] of result rows e in [r0, r0 + rows), e = (r G1 + g) G2 + h (diagonal: r G1 + g), N = C n_slots
+std::string launch_ccov_values(const Ctx& c, const CcovCall& f, long long r0, long long rows, double* V, hipStream_t st);
+// dev[r N + cs] = max(dev, |(v - mean) / sd|) over the entries of pair r among those rows (sd = 0 skipped, NaN kept); V, mean and
+// sd are the chunk's (entry r0 first), dev the call's
+std::string launch_ccov_maxdev(const CcovCall& f, long long N, long long r0, long long rows, const double* V, const double* mean,
+                               const double* sd, double* dev, hipStream_t st);
+// crit[r] = quantile p of dev[r N + .] for r < m, rows of at most ccov_sort_rows() draws, interpolated without an fma
+int ccov_sort_rows();
+std::string launch_ccov_crit(const double* dev, long long N, long long m, double p, double* crit, hipStream_t st);
+
 // ---- kernels_bands.hip ----
 // The column reductions of the credible-band entry points on device tables V[t + T col], on stream st.  quantiles: LDS sort
 // for T <= 8192 (W unused), else k_bands_quantiles_big over the workspace W of NP ncol doubles, NP = bands_sort_pad(T), which

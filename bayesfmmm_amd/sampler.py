@@ -404,6 +404,59 @@ class Sampler:
         return {"mean": mean.reshape((K, G), order="F"), "sd": sd.reshape((K, G), order="F"),
                 "quantiles": qs.reshape((K, G, pr.size), order="F"), "probs": pr}
 
+    def cluster_cov_bands(self, E, perm, E2=None, pairs=None, x=None, diagonal=False, probs=(0.025, 0.5, 0.975),
+                          simultaneous=None, trace=False, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """The covariance surfaces between clusters, C^(k,l)(g, h) = sum_m (E_g . theta_km)(E2_h . theta_lm), theta_km = phi_km +
+        sum_d x_d xi_kmd, with the labels aligned by perm (`align`'s "perm" of the same slots) and the chains pooled: pointwise
+        mean, sd and quantiles and, with simultaneous=alpha, the simultaneous (1 - alpha) band of every pair by
+        `curve_bands_simultaneous`' rule, on the device (bfmmm_chain_cluster_cov_bands); the reference's FCovCI
+        without rescale / trans_mats.  The sum over m does not see the signs of the eigenfunctions, so labels are all that has
+        to be aligned.  E (G1 x P) and E2 (G2 x P; default: E) are rows in the sampler's basis.  pairs: (k, l) pairs of aligned
+        components in any order (default: all k <= l, (0, 0), (0, 1), ..).  x: one covariate setting of D entries (covariance-
+        adjusted samplers; default: phi alone).  diagonal: only g = h (E2 must be None), the variance function where k = l.
+        trace: also the values of every draw, chain-major.
+        Returns {"mean", "sd": (m, G1, G2), "quantiles": (m, G1, G2, nq), "probs", "pairs": (m, 2)}, with simultaneous also
+        {"crit": (m,), "lower", "upper": (m, G1, G2), "alpha"}, with trace also {"trace": (m, G1, G2, N)}; with diagonal the G2
+        axis is dropped."""
+        def basis(B, name):
+            Bm = np.ascontiguousarray(B, dtype=np.float64)
+            if Bm.ndim != 2 or Bm.shape[1] != self.P:
+                raise ValueError(f"{name} must be a G x {self.P} matrix in the sampler's basis")
+            return Bm
+        ip = C.POINTER(C.c_int32)
+        E1m = basis(E, "E")
+        E2m = None if E2 is None else basis(E2, "E2")
+        S = self._slots(first_slot, n_slots)
+        p = self._perm_arg(perm, S)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        if pairs is None:
+            pl = np.array([(k, l) for k in range(self.K) for l in range(k, self.K)], dtype=np.int32).reshape(-1, 2)
+        else:
+            pl = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        xv = None
+        if x is not None:
+            xv = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            if self.D > 0 and xv.size != self.D:
+                raise ValueError(f"x must have {self.D} entries, one per covariate")
+        m, G1 = pl.shape[0], E1m.shape[0]
+        G2 = G1 if E2m is None else E2m.shape[0]
+        N = self.n_chains * max(S, 0)
+        cell = (G1,) if diagonal else (G1, G2)
+        out = {"mean": np.zeros((m,) + cell), "sd": np.zeros((m,) + cell), "quantiles": np.zeros((m,) + cell + (pr.size,)),
+               "probs": pr, "pairs": pl}
+        if simultaneous is not None:
+            out.update(crit=np.zeros(m), lower=np.zeros((m,) + cell), upper=np.zeros((m,) + cell), alpha=simultaneous)
+        if trace:
+            out["trace"] = np.zeros((m,) + cell + (N,))
+        band = [_dp(out[k]) if simultaneous is not None else None for k in ("crit", "lower", "upper")]
+        _lib.check(self.lib.bfmmm_chain_cluster_cov_bands(
+            self.h, p.ctypes.data_as(ip), _dp(E1m), G1, None if E2m is None else _dp(E2m), G2, int(bool(diagonal)),
+            None if pairs is None else pl.ctypes.data_as(ip), m if pairs is not None else 0, None if xv is None else _dp(xv),
+            int(first_slot), S, _dp(pr) if pr.size else None, pr.size, float(simultaneous) if simultaneous is not None else 0.0,
+            int(max_workspace_bytes), _dp(out["mean"]), _dp(out["sd"]), _dp(out["quantiles"]) if pr.size else None, *band,
+            _dp(out["trace"]) if trace else None, out["mean"].size))
+        return out
+
     def curve_cov(self, E, E2=None, curves=None, sd=True, per_chain=False, diagonal=False, first_slot=0, n_slots=None,
                   max_workspace_bytes=0):
         """The pooled covariance surface of every curve: mean (and sd) over chain slots [first_slot, first_slot + n_slots) of

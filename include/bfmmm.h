@@ -355,6 +355,42 @@ int bfmmm_chain_cluster_mean_bands(bfmmm_handle* h, const int32_t* perm, const d
                                    const double* probs, int nq, int64_t max_workspace_bytes, double* mean, double* sd, double* quant,
                                    int64_t capacity);
 
+/* The cluster covariance surfaces with the labels aligned and the chains pooled, with pointwise and simultaneous credible bands
+ * (the reference's FCovCI, without its rescale / trans_mats).  For draw cs = q n_slots + s of chain slots
+ * [first_slot, first_slot + n_slots) of EVERY chain of the batch, its row perm[cs K + .] (from bfmmm_chain_align, or any rows that
+ * are permutations of 0 .. K - 1), rows E1_g, E2_h of two evaluation bases (G1 x P and G2 x P, row-major in the sampler's basis;
+ * E2 NULL: E2 = E1 and G2 = G1, the argument G2 is ignored) and pair r = (k_r, l_r) of aligned components
+ *   theta_km   = phi_{perm[k], m} + sum_d x_d xi_{perm[k], m, d}       (x: D entries, one covariate setting; NULL: phi alone)
+ *   W1_k[g][m] = sum_p E1_gp theta_km,p,   W2 likewise with E2
+ *   c_r(g, h)  = sum_m W1_k[g][m] W2_l[h][m],
+ * which does not change when the eigenfunctions change sign or are rotated jointly over the components: once the labels are
+ * aligned the chains pool as they are.  pairs: n_pairs >= 0 pairs pairs[2 r], pairs[2 r + 1], 0-based, in any order, repeats
+ * allowed (m = n_pairs; 0: returns at once and writes nothing), or NULL for all m = K (K + 1) / 2 pairs with k <= l in the order
+ * (0, 0), (0, 1), .., (0, K - 1), (1, 1), ...  With e = (r G1 + g) G2 + h and N = C n_slots draws:
+ *   mean[e], sd[e] (N - 1; NaN for one draw)   required;
+ *   quant[q + nq e]                            the nq <= 16 quantiles probs (inside [0, 1]) by arma::quantile's rule, as
+ *                                              bfmmm_post_col_quantiles computes them; nq = 0: probs and quant may be NULL;
+ *   trace[e N + cs]                            the values themselves (the reference's cov_trace).  NULL: not copied;
+ *   crit[r], lower[e], upper[e]                all NULL or all set: the simultaneous (1 - alpha) band of pair r by DESIGN.md 7h's
+ *                                              rule, crit the (1 - alpha) quantile over the draws of the largest |(c - mean) / sd|
+ *                                              over the pair's entries with sd != 0 (from 0.0; a NaN is kept), lower / upper =
+ *                                              mean -/+ crit sd.  alpha inside (0, 1), checked only where the band is asked for.
+ * diagonal != 0 (E2 must be NULL): only the entries g = h, the variance function for k = l, at e = r G1 + g; they are the diagonal
+ * of the surface bit for bit.  capacity >= m G1 G2 entries (diagonal: m G1); trace holds capacity N doubles.
+ * x requires a covariance-adjusted sampler and must be finite.
+ * A value's bits depend on (draw, pair, g, h) alone, so the results do not depend on the chunk or on repeated calls, a selected
+ * pair equals its rows of the full result, and with E2 NULL pair (l, k) is the transpose of pair (k, l), all bit for bit.
+ * Chunks of consecutive result rows keep the values, the sort workspace of rows of more than 8192 draws and the chunk's results
+ * within max_workspace_bytes (0: 256 MiB); the projection tables, E1, E2, x, perm, the pairs and the band's per-draw maxima are
+ * shared by all rows and count against it; a budget below what is shared plus one row is refused with the bytes needed.  With
+ * the band and more than one chunk a second sweep over the chunks forms the values again.  At most 2^22 draws.  Runs on the
+ * sampler's stream and leaves its state and slots untouched. */
+int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* perm, const double* E1, int G1, const double* E2, int G2,
+                                  int diagonal, const int32_t* pairs, int n_pairs, const double* x, int first_slot, int n_slots,
+                                  const double* probs, int nq, double alpha, int64_t max_workspace_bytes,
+                                  double* mean, double* sd, double* quant, double* crit, double* lower, double* upper,
+                                  double* trace, int64_t capacity);
+
 /* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
  * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P: C_a = Prec_a^-1 as k_factor left it), "Lz" (A x P: L_a z_a of the sampled directions),
@@ -417,7 +453,10 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * Of the last bfmmm_chain_curve_cov (always measured): "curve_cov", the device time and launches (one per chunk) of k_curve_cov,
  * and "curve_cov_project", those of the projection that precedes them.
  * Of the last bfmmm_chain_align / bfmmm_chain_aligned_summary / bfmmm_chain_cluster_mean_bands (always measured): "align_gram"
- * (one launch), "align_gather" and "align_project" (one launch per chunk), the device time and launches of their own kernels. */
+ * (one launch), "align_gather" and "align_project" (one launch per chunk), the device time and launches of their own kernels.
+ * Of the last bfmmm_chain_cluster_cov_bands (always measured): "cluster_cov_project", the device time of k_ccov_project and the
+ * tables it filled (1, or 2 with E2); "cluster_cov", the device time and launches of k_ccov_values (one per chunk, and one more
+ * per chunk where the band takes a second sweep); "cluster_cov_maxdev", those of k_ccov_maxdev (one per chunk; 0 without the band). */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
