@@ -1,8 +1,8 @@
 // C ABI of the sampler (include/bfmmm.h), what is read off the chain slots after a run: the chain arrays, their convergence
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
-// per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it and the cluster
-// covariance surfaces with their bands.
+// per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it, the cluster
+// covariance surfaces with their bands and their eigenvalues and eigenfunctions.
 // An entry point is its argument checks (SlotCheck: slots, curve selection, workspace plan), its workspace and the event pairs
 // that time its launches into the handle's PT_* timers (CallBufs owns both) and one for_chunks.
 #include "handle.hpp"
@@ -1036,4 +1036,153 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
     }
   }
   return 0;
+}
+
+// ---- cluster eigenvalues and eigenfunctions under aligned labels (kernels_cluster_eig.hip) --------------------
+// k_ceig_gram and k_ceig_solve once per call: every draw's lambda, pve and total as rows of C S values, its signed b and its status
+// word.  The K M + K M + K small rows are reduced at once by launch_bands_moments and launch_bands_quantiles, the lambda rows also
+// by diag_launch, all as they are; then per chunk of consecutive eigenfunction rows k_ceig_values and the same two launchers.
+extern "C" void bfmmm_set_cluster_eig_form(int form) { bfmmm::g_cluster_eig_form = form == 1 || form == 2 ? form : 0; }
+
+extern "C" int bfmmm_chain_cluster_eigen(bfmmm_handle* h, const int32_t* perm, const double* E, int G, const double* w, const double* x,
+                                         int n_functions, const double* ref, int first_slot, int n_slots, const double* probs, int nq,
+                                         int64_t max_workspace_bytes, double* val_diag, double* val_quant, double* pve_mean, double* pve_sd,
+                                         double* pve_quant, double* tot_mean, double* tot_sd, double* tot_quant, double* fn_mean,
+                                         double* fn_sd, double* fn_quant, double* val_trace, double* fn_trace, int32_t* max_sweeps,
+                                         int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_cluster_eigen", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"h", h}, {"perm", perm}, {"E", E}, {"val_diag", val_diag}, {"pve_mean", pve_mean}, {"pve_sd", pve_sd},
+               {"tot_mean", tot_mean}, {"tot_sd", tot_sd}, {"max_sweeps", max_sweeps}}))
+    return 1;
+  if (G < 1) return fail(fn + ": 'G' must be at least 1");
+  const Ctx& c = h->c;
+  const int K = c.d.K, P = c.d.P, M = c.d.M, D = c.d.D, J = n_functions;
+  if (M < 1) return fail(fn + ": n_eigen is 0: the model has no covariance surface");
+  if (J < 0 || J > M) return fail(fn + ": 'n_functions' = " + std::to_string(J) + " outside 0 .. " + std::to_string(M) + " (n_eigen)");
+  for (int g = 0; w && g < G; ++g)
+    if (!(w[g] >= 0.0) || !std::isfinite(w[g])) return fail(fn + ": 'w'[" + std::to_string(g) + "] is negative or not finite");
+  if (x && !(c.covariance_adj && D > 0)) return fail(fn + ": 'x' is given but the sampler is not covariance-adjusted");
+  for (int d = 0; x && d < D; ++d)
+    if (!std::isfinite(x[d])) return fail(fn + ": 'x'[" + std::to_string(d) + "] is not finite");
+  const int64_t len = (int64_t)K * J * G;      // eigenfunction rows
+  if (J > 0 && ck.ptrs({{"fn_mean", fn_mean}, {"fn_sd", fn_sd}})) return 1;
+  for (int64_t e = 0; ref && e < len; ++e)
+    if (!std::isfinite(ref[e])) return fail(fn + ": 'ref'[" + std::to_string(e) + "] is not finite");
+  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, len, "rows") || ck.row_limit() ||
+      probs_check(ck, probs, nq, val_quant))
+    return 1;
+  if (nq > 0 && (ck.ptrs({{"pve_quant", pve_quant}, {"tot_quant", tot_quant}}) || (J > 0 && ck.ptrs({{"fn_quant", fn_quant}})))) return 1;
+  if (perm_check(ck, perm)) return 1;
+  CeigCall f;
+  f.G = G; f.J = J; f.first_slot = first_slot; f.n_slots = n_slots;
+  const std::string bad = ceig_check(c, f);
+  if (!bad.empty()) return fail(fn + ": " + bad);
+  reset_timers(h, PT_CEIG_GRAM, PT_CEIG_VALUES);
+  const int C = h->nch, S = n_slots;
+  const size_t N = (size_t)ck.CS();
+  const size_t KM = (size_t)K * M, rs = 2 * KM + (size_t)K;                    // the small rows: lambda, pve, total
+  const bool with_ref = ref && J > 0;
+  const bool sort_ws = nq > 0 && (long long)N > fit_lds_rows();                // k_bands_quantiles_big sorts in a workspace
+  const size_t NP = sort_ws ? (size_t)bands_sort_pad((int)N) : 0;
+  const size_t tier = diag_row_ws_doubles(C, S);
+  // shared by all rows: Q, R, E, w, x, ref, probs, the small rows with their results and workspaces, the b of every draw, the
+  // status words and perm; an eigenfunction row: its values, its sort workspace, its mean, sd and quantiles
+  const size_t small_ws = rs * (2 + (size_t)nq + NP) + KM * (7 + tier);
+  const size_t shared = sizeof(double) * ((size_t)P * P + (with_ref ? (size_t)K * J * P + (size_t)len : 0) + (size_t)G * P + (w ? (size_t)G : 0) +
+                                          (x ? (size_t)D : 0) + 16 + N * rs + small_ws + N * K * J * P) +
+                        sizeof(int32_t) * 2 * N * K;
+  const size_t per_row = sizeof(double) * (N + 2 + (size_t)nq + NP);
+  const size_t budget = budget_of(max_workspace_bytes);
+  if (budget < shared + (len > 0 ? per_row : 0))
+    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + (len > 0 ? per_row : 0)) + " bytes one row needs (" +
+                std::to_string(shared) + " shared by all rows + " + std::to_string(len > 0 ? per_row : 0) + " per row)");
+  const int64_t chunk = len > 0 ? std::min<int64_t>(std::min<int64_t>(len, (int64_t)((budget - shared) / per_row)), 1 << 30) : 1;
+  HIPCHK(hipSetDevice(h->device));
+  CallBufs b;
+  double *d_E = nullptr, *d_w = nullptr, *d_x = nullptr, *d_ref = nullptr, *d_probs = nullptr, *d_small = nullptr, *d_sres = nullptr,
+         *d_v = nullptr;
+  int32_t *d_perm = nullptr, *d_status = nullptr;
+  Timer gram, solve, values;
+  HIPCHK(b.timers({&gram, &solve, &values}));
+  HIPCHK(b.put(h, &d_E, E, (size_t)G * P));
+  if (w) HIPCHK(b.put(h, &d_w, w, (size_t)G));
+  if (x) HIPCHK(b.put(h, &d_x, x, (size_t)D));
+  if (with_ref) {
+    HIPCHK(b.put(h, &d_ref, ref, (size_t)len));
+    HIPCHK(b.get(&f.R, (size_t)K * J * P));
+  }
+  HIPCHK(b.put(h, &d_perm, perm, N * K));
+  HIPCHK(b.get(&d_status, N * K));
+  HIPCHK(b.get(&d_probs, 16));
+  if (nq) HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
+  HIPCHK(b.get(&f.Q, (size_t)P * P));
+  HIPCHK(b.get(&d_small, N * rs));
+  HIPCHK(b.get(&d_sres, small_ws));
+  HIPCHK(b.get(&f.b, N * K * J * P));
+  if (len > 0) HIPCHK(b.get(&d_v, per_row / sizeof(double) * (size_t)chunk));
+  f.E = d_E; f.w = d_w; f.x = d_x; f.ref = d_ref; f.perm = d_perm; f.status = d_status;
+  f.lam = d_small; f.pve = d_small + N * KM; f.tot = d_small + 2 * N * KM;
+  double* d_smean = d_sres;
+  double* d_ssd = d_smean + rs;
+  double* d_sq = d_ssd + rs;
+  double* d_sw = d_sq + rs * (size_t)nq;
+  double* d_diag = d_sw + rs * NP;
+  double* d_tier = d_diag + 7 * KM;
+  std::vector<int32_t> st_host(N * K);
+  std::vector<double> sm(2 * rs);
+  // the solve and the small rows
+  int rc = for_chunks(ck, 1, 1, [&](int64_t, int) {
+    std::string err = timed(gram, h->st, [&] { return launch_ceig_gram(c, f, h->st); });
+    if (err.empty()) err = timed(solve, h->st, [&] { return launch_ceig_solve(c, f, h->st); });
+    if (err.empty() && copy_sync(h, st_host.data(), d_status, sizeof(int32_t) * N * K, hipMemcpyDeviceToHost) != hipSuccess)
+      err = "kernel or copy back failed";
+    if (!err.empty()) return err;
+    collect(h, gram, PT_CEIG_GRAM);
+    collect(h, solve, PT_CEIG);
+    int32_t mx = 0;
+    for (size_t o = 0; o < N * K; ++o) {
+      if (st_host[o] & 0x100)
+        return "no convergence in " + std::to_string(ceig_sweep_cap()) + " sweeps: chain " + std::to_string(o / K / S) + ", slot " +
+               std::to_string(first_slot + (int)(o / K % S)) + ", component " + std::to_string(o % K);
+      mx = std::max(mx, st_host[o] & 0xff);
+    }
+    *max_sweeps = mx;
+    err = launch_bands_moments(d_small, (int)N, (long long)rs, d_smean, d_ssd, h->st);
+    if (err.empty() && nq) err = launch_bands_quantiles(d_small, (int)N, (long long)rs, d_sw, d_probs, nq, d_sq, h->st);
+    if (err.empty()) err = diag_launch(d_small, (long long)KM, C, S, d_diag, (long long)KM, d_tier, (long long)KM, h->st);
+    const size_t q1 = sizeof(double) * KM * (size_t)nq;
+    if (err.empty() &&
+        ((nq && (hipMemcpyAsync(val_quant, d_sq, q1, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+                 hipMemcpyAsync(pve_quant, d_sq + KM * nq, q1, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+                 hipMemcpyAsync(tot_quant, d_sq + 2 * KM * nq, sizeof(double) * (size_t)K * nq, hipMemcpyDeviceToHost, h->st) != hipSuccess)) ||
+         (val_trace && hipMemcpyAsync(val_trace, d_small, sizeof(double) * N * KM, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         hipMemcpyAsync(val_diag, d_diag, sizeof(double) * 7 * KM, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+         copy_sync(h, sm.data(), d_smean, sizeof(double) * 2 * rs, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (!err.empty()) return err;
+    std::copy(sm.begin() + KM, sm.begin() + 2 * KM, pve_mean);
+    std::copy(sm.begin() + 2 * KM, sm.begin() + rs, tot_mean);
+    std::copy(sm.begin() + rs + KM, sm.begin() + rs + 2 * KM, pve_sd);
+    std::copy(sm.begin() + rs + 2 * KM, sm.begin() + 2 * rs, tot_sd);
+    return err;
+  });
+  if (rc || len == 0) return rc;
+  double* d_mean = d_v + (size_t)chunk * N;
+  double* d_sd = d_mean + (size_t)chunk;
+  double* d_q = d_sd + (size_t)chunk;
+  double* d_ws = d_q + (size_t)nq * (size_t)chunk;
+  return for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
+    std::string err = timed(values, h->st, [&] { return launch_ceig_values(c, f, r0, rows, d_v, h->st); });
+    if (err.empty()) err = launch_bands_moments(d_v, (int)N, rows, d_mean, d_sd, h->st);
+    if (err.empty() && nq) err = launch_bands_quantiles(d_v, (int)N, rows, d_ws, d_probs, nq, d_q, h->st);
+    if (err.empty() &&
+        ((nq && hipMemcpyAsync(fn_quant + (size_t)r0 * nq, d_q, sizeof(double) * (size_t)rows * nq, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         (fn_trace && hipMemcpyAsync(fn_trace + (size_t)r0 * N, d_v, sizeof(double) * (size_t)rows * N, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
+         hipMemcpyAsync(fn_mean + r0, d_mean, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+         copy_sync(h, fn_sd + r0, d_sd, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
+      err = "kernel or copy back failed";
+    if (err.empty()) collect(h, values, PT_CEIG_VALUES);
+    return err;
+  });
 }

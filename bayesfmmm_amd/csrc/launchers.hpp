@@ -219,6 +219,27 @@ std::string launch_ccov_maxdev(const CcovCall& f, long long N, long long r0, lon
 int ccov_sort_rows();
 std::string launch_ccov_crit(const double* dev, long long N, long long m, double p, double* crit, hipStream_t st);
 
+// ---- kernels_cluster_eig.hip ----
+// One call of bfmmm_chain_cluster_eigen: the grid basis E (G x P), the weights w (G; null: 1), the covariate
+// setting x (D entries; null: phi alone), the reference functions ref (K J G; null: the largest-entry rule), the permutation
+// rows perm[(q S + s) K + .], the J leading eigenfunctions wanted, the slot range, and what the kernels fill: Q (P P), R (K J P;
+// with ref), the rows lam / pve [cs + N (k M + j)] and tot [cs + N k], the signed b [((cs K + k) J + j) P + p] and the status
+// words [cs K + k] (the sweeps; bit 0x100: the cap of ceig_sweep_cap() sweeps was reached).  All device.
+struct CeigCall {
+  int G = 0, J = 0, first_slot = 0, n_slots = 0;
+  const double *E = nullptr, *w = nullptr, *x = nullptr, *ref = nullptr;
+  const int32_t* perm = nullptr;
+  double *Q = nullptr, *R = nullptr, *lam = nullptr, *pve = nullptr, *tot = nullptr, *b = nullptr;
+  int32_t* status = nullptr;
+};
+extern int g_cluster_eig_form;      // bfmmm_set_cluster_eig_form: 0 the launcher decides, 1 plain multiplies and additions, 2 MFMA
+std::string ceig_check(const Ctx& c, const CeigCall& f);
+int ceig_sweep_cap();
+std::string launch_ceig_gram(const Ctx& c, const CeigCall& f, hipStream_t st);
+std::string launch_ceig_solve(const Ctx& c, const CeigCall& f, hipStream_t st);
+// the values V[cs + N (e - r0)] of result rows e in [r0, r0 + rows), e = (k J + j) G + g, N = C n_slots
+std::string launch_ceig_values(const Ctx& c, const CeigCall& f, long long r0, long long rows, double* V, hipStream_t st);
+
 // ---- kernels_bands.hip ----
 // The column reductions of the credible-band entry points on device tables V[t + T col], on stream st.  quantiles: LDS sort
 // for T <= 8192 (W unused), else k_bands_quantiles_big over the workspace W of NP ncol doubles, NP = bands_sort_pad(T), which

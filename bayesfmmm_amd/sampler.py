@@ -457,6 +457,97 @@ class Sampler:
             _dp(out["trace"]) if trace else None, out["mean"].size))
         return out
 
+    def cluster_eigen(self, E, perm, weights=None, n_functions=None, x=None, ref="mean", probs=(0.025, 0.5, 0.975), trace=False,
+                      first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """The principal components of the cluster covariance surfaces of `cluster_cov_bands`: per draw and aligned component k the
+        eigenvalues lambda_k1 >= .. >= lambda_kM >= 0 and the J = n_functions leading eigenfunctions psi_kj on the grid of the
+        operator C^(k,k) discretised with the quadrature weights w, the total variance sum_g w_g C^(k,k)(g, g) and the share
+        lambda_kj / total each component explains, with the labels aligned by perm (`align`'s "perm" of the same slots) and the
+        chains pooled, on the device (bfmmm_chain_cluster_eigen).  These do not see the signs or the joint rotation of
+        the sampler's own eigenfunction blocks, which are not identified.  E (G x P): rows in the sampler's basis (the identity for
+        the multivariate model, where this is PCA of Phi_k Phi_k').  weights: G non-negative quadrature weights (default: 1).
+        n_functions: default M.  x: one covariate setting of D entries (covariance-adjusted samplers; default: phi alone).
+        ref fixes the sign of every eigenfunction, <psi, ref>_w >= 0: "mean" (default) takes the J leading w-eigenfunctions of the
+        posterior mean surfaces (`cluster_cov_bands` and numpy.linalg.eigh on the host), each signed so that its entry of
+        largest |sqrt(w) psi| is positive; an array (K, J, G) is used as it is; None applies that largest-entry rule to every draw.
+        Returns {"values": {"mean", "sd", "rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean": (K, M), "quantiles": (K, M, nq)},
+        "pve": {"mean", "sd": (K, M), "quantiles": (K, M, nq)}, "total": {"mean", "sd": (K,), "quantiles": (K, nq)},
+        "functions": {"mean", "sd": (K, J, G), "quantiles": (K, J, G, nq)}, "ref": (K, J, G) or None, "max_sweeps", "probs"},
+        with trace also {"values_trace": (K, M, N), "functions_trace": (K, J, G, N)}, N = C S chain-major."""
+        Em = np.ascontiguousarray(E, dtype=np.float64)
+        if Em.ndim != 2 or Em.shape[1] != self.P:
+            raise ValueError(f"E must be a G x {self.P} matrix in the sampler's basis")
+        S = self._slots(first_slot, n_slots)
+        p = self._perm_arg(perm, S)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        G, K = Em.shape[0], self.K
+        M = self.M
+        J = M if n_functions is None else int(n_functions)
+        wv = None
+        if weights is not None:
+            wv = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if wv.size != G:
+                raise ValueError(f"weights must have {G} entries, one per row of E")
+        xv = None
+        if x is not None:
+            xv = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            if self.D > 0 and xv.size != self.D:
+                raise ValueError(f"x must have {self.D} entries, one per covariate")
+        rv = None
+        if isinstance(ref, str):
+            if ref != "mean":
+                raise ValueError('ref must be "mean", None or an array of shape (K, n_functions, G)')
+            if 0 < J <= M and (wv is None or (np.all(np.isfinite(wv)) and np.all(wv >= 0))):
+                rv = self._mean_eigenfunctions(Em, p, wv, J, xv, first_slot, n_slots, max_workspace_bytes)
+        elif ref is not None:
+            rv = np.ascontiguousarray(ref, dtype=np.float64)
+            if rv.shape != (K, J, G):
+                raise ValueError(f"ref must have shape ({K}, {J}, {G})")
+        N = self.n_chains * max(S, 0)
+        Jn = max(min(J, M), 0)
+        nqs = pr.size
+        vd = np.zeros((7, K, M))
+        out = {"values": {"quantiles": np.zeros((K, M, nqs))},
+               "pve": {"mean": np.zeros((K, M)), "sd": np.zeros((K, M)), "quantiles": np.zeros((K, M, nqs))},
+               "total": {"mean": np.zeros(K), "sd": np.zeros(K), "quantiles": np.zeros((K, nqs))},
+               "functions": {"mean": np.zeros((K, Jn, G)), "sd": np.zeros((K, Jn, G)), "quantiles": np.zeros((K, Jn, G, nqs))},
+               "ref": rv, "probs": pr}
+        if trace:
+            out["values_trace"] = np.zeros((K, M, N))
+            out["functions_trace"] = np.zeros((K, Jn, G, N))
+        ms = C.c_int32(0)
+        q = (lambda a: _dp(a)) if nqs else (lambda a: None)
+        fnp = (lambda a: _dp(a)) if Jn > 0 else (lambda a: None)
+        _lib.check(self.lib.bfmmm_chain_cluster_eigen(
+            self.h, p.ctypes.data_as(C.POINTER(C.c_int32)), _dp(Em), G, None if wv is None else _dp(wv), None if xv is None else _dp(xv),
+            J, None if rv is None else _dp(rv), int(first_slot), S, _dp(pr) if nqs else None, nqs, int(max_workspace_bytes),
+            _dp(vd), q(out["values"]["quantiles"]), _dp(out["pve"]["mean"]), _dp(out["pve"]["sd"]), q(out["pve"]["quantiles"]),
+            _dp(out["total"]["mean"]), _dp(out["total"]["sd"]), q(out["total"]["quantiles"]), fnp(out["functions"]["mean"]),
+            fnp(out["functions"]["sd"]), fnp(out["functions"]["quantiles"]) if nqs else None,
+            _dp(out["values_trace"]) if trace else None, _dp(out["functions_trace"]) if trace and Jn > 0 else None, C.byref(ms),
+            K * Jn * G))
+        out["values"].update((k, vd[i]) for i, k in enumerate(STAT_NAMES))
+        out["max_sweeps"] = int(ms.value)
+        return out
+
+    def _mean_eigenfunctions(self, Em, perm, wv, J, xv, first_slot, n_slots, max_workspace_bytes):
+        """(K, J, G): the J leading w-eigenfunctions of the posterior mean surfaces C^(k,k), numpy.linalg.eigh of
+        sqrt(w) C sqrt(w)' on the host, each signed so that its entry of largest |sqrt(w) psi| (lowest g on ties) is positive"""
+        K, G = self.K, Em.shape[0]
+        cm = self.cluster_cov_bands(Em, perm, pairs=[(k, k) for k in range(K)], x=xv, probs=(), first_slot=first_slot, n_slots=n_slots,
+                                    max_workspace_bytes=max_workspace_bytes)["mean"]
+        sw = np.ones(G) if wv is None else np.sqrt(wv)
+        out = np.zeros((K, J, G))
+        for k in range(K):
+            A = sw[:, None] * (0.5 * (cm[k] + cm[k].T)) * sw[None, :]
+            _, vec = np.linalg.eigh(A)
+            for j in range(min(J, G)):
+                u = vec[:, G - 1 - j]
+                g = int(np.argmax(np.abs(u)))                # the first of several
+                u = u if u[g] >= 0 else -u
+                out[k, j] = np.divide(u, sw, out=np.zeros(G), where=sw > 0)
+        return out
+
     def curve_cov(self, E, E2=None, curves=None, sd=True, per_chain=False, diagonal=False, first_slot=0, n_slots=None,
                   max_workspace_bytes=0):
         """The pooled covariance surface of every curve: mean (and sd) over chain slots [first_slot, first_slot + n_slots) of

@@ -391,6 +391,54 @@ int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* perm, const do
                                   double* mean, double* sd, double* quant, double* crit, double* lower, double* upper,
                                   double* trace, int64_t capacity);
 
+/* The eigenvalues and eigenfunctions of the cluster covariance operators with the labels aligned and the chains pooled (DESIGN.md
+ * 7l): the principal components of the surfaces of bfmmm_chain_cluster_cov_bands.  For draw cs = q n_slots + s of chain slots
+ * [first_slot, first_slot + n_slots) of EVERY chain of the batch, its row perm[cs K + .], a grid basis E (G x P, row-major in the
+ * sampler's basis; the identity for the multivariate model), quadrature weights w (G entries, finite and >= 0; NULL: all 1) and
+ * aligned component k
+ *   theta_km = phi_{perm[k], m} + sum_d x_d xi_{perm[k], m, d}       (x: D entries, one covariate setting; NULL: phi alone)
+ *   Q        = E' diag(w) E                                          (P x P, once per call, g in order from 0)
+ *   S_k      = Theta_k' Q Theta_k = V diag(lambda) V'                (M x M, Theta_k = [theta_k1 .. theta_kM]; cyclic Jacobi)
+ *              lambda_1 >= .. >= lambda_M >= 0                       (ties in index order; negative rounding noise clamped to 0)
+ *   total_k  = trace S_k = sum_g w_g C^(k,k)(g, g)                   (summed from the diagonal before the rotations)
+ *   pve_kj   = lambda_kj / total_k                                   (0 where total_k == 0)
+ *   b_kj     = Theta_k v_j / sqrt(lambda_kj)                         (0 where lambda_kj <= M 2^-53 lambda_k1)
+ *   psi_kj(g)= sgn_kj E_g . b_kj,   sgn_kj = +1 if b_kj . (E' diag(w) ref_kj) >= 0 else -1,   j < n_functions,
+ * the eigenpairs of the w-discretised covariance operator of cluster k: ordinary PCA of Phi_k Phi_k' with E = I and w = 1.  They do
+ * not change when the eigenfunctions of the sampler change sign or are rotated jointly over m, so once the labels are aligned the
+ * chains pool.  ref (K x n_functions x G, row (k J + j) G + g, finite) fixes the signs; NULL: the sign makes the entry of largest
+ * |sqrt(w_g) psi(g)| positive, lowest g first on ties.  Only the upper triangle of S_k is read.  The Jacobi iteration takes its
+ * pairs in a round-robin order fixed by M alone, skips a pair with |s_pq| <= u max(sqrt(|s_pp s_qq|), u ||S_k||_F of the start),
+ * u = 2^-53, and stops after a sweep without a rotation; a problem still rotating in its 40th sweep makes the call fail naming the
+ * chain, the slot and the component.  With N = C n_slots draws, J = n_functions in 0 .. M and nq <= 16 quantiles probs by
+ * arma::quantile's rule (nq = 0: probs and every *_quant may be NULL):
+ *   val_diag[i K M + k M + j]                    i = 0 .. 6: split R-hat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd of
+ *                                                lambda_kj as bfmmm_chain_diagnostics computes them;  val_quant[q + nq (k M + j)];
+ *   pve_mean, pve_sd [k M + j], pve_quant[q + nq (k M + j)];   tot_mean, tot_sd [k], tot_quant[q + nq k]   (sd: N - 1);
+ *   fn_mean, fn_sd [e], fn_quant[q + nq e]       of psi at row e = (k J + j) G + g; capacity >= K J G rows; J = 0: may be NULL,
+ *                                                and no row, no ref and no values launch is made (E and w are still held for Q);
+ *   val_trace[(k M + j) N + cs], fn_trace[e N + cs]   the values themselves.  NULL: not copied;
+ *   *max_sweeps                                  the largest number of sweeps a problem took, the last, rotation-free one included.
+ * x requires a covariance-adjusted sampler and must be finite.  A value's bits depend on (draw, component) alone (a function's: and
+ * on j, g), so the results do not depend on the chunk or on repeated calls, lambda, pve and total do not depend on n_functions,
+ * ref or trace, and J < M gives the first J functions of J = M, all bit for bit.
+ * Chunks of consecutive eigenfunction rows keep the values, the sort workspace of rows of more than 8192 draws and the chunk's
+ * results within max_workspace_bytes (0: 256 MiB); Q, E, w, x, perm, ref and its projection, and the per-draw outputs of the solve
+ * (lambda, pve, total, the signed b of K J P doubles a draw, the status words) with the results of the lambda, pve and total rows
+ * are shared by all rows and count against it; a budget below what is shared plus one row is refused with the bytes needed.  At
+ * most 2^22 draws.  Runs on the sampler's stream and leaves its state and slots untouched. */
+int bfmmm_chain_cluster_eigen(bfmmm_handle* h, const int32_t* perm, const double* E, int G, const double* w, const double* x,
+                              int n_functions, const double* ref, int first_slot, int n_slots, const double* probs, int nq,
+                              int64_t max_workspace_bytes, double* val_diag, double* val_quant, double* pve_mean, double* pve_sd,
+                              double* pve_quant, double* tot_mean, double* tot_sd, double* tot_quant, double* fn_mean, double* fn_sd,
+                              double* fn_quant, double* val_trace, double* fn_trace, int32_t* max_sweeps, int64_t capacity);
+
+/* k_ceig_solve forms S_k either by plain multiplies and additions or by v_mfma_f64_16x16x4_f64 on zero-padded tiles;
+ * the launcher takes the form that measured faster.  1 makes later calls of bfmmm_chain_cluster_eigen take the plain form, 2 the MFMA
+ * form, 0 (and anything else) the launcher's choice again -- the tests and tests/perf/bench_cluster_eig.py run both.  The two
+ * forms round differently; each keeps every promise of the call.  Process-wide; default 0. */
+void bfmmm_set_cluster_eig_form(int form);
+
 /* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
  * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P: C_a = Prec_a^-1 as k_factor left it), "Lz" (A x P: L_a z_a of the sampled directions),
@@ -456,7 +504,10 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * (one launch), "align_gather" and "align_project" (one launch per chunk), the device time and launches of their own kernels.
  * Of the last bfmmm_chain_cluster_cov_bands (always measured): "cluster_cov_project", the device time of k_ccov_project and the
  * tables it filled (1, or 2 with E2); "cluster_cov", the device time and launches of k_ccov_values (one per chunk, and one more
- * per chunk where the band takes a second sweep); "cluster_cov_maxdev", those of k_ccov_maxdev (one per chunk; 0 without the band). */
+ * per chunk where the band takes a second sweep); "cluster_cov_maxdev", those of k_ccov_maxdev (one per chunk; 0 without the band).
+ * Of the last bfmmm_chain_cluster_eigen (always measured): "cluster_eig_gram", the device time of k_ceig_gram (one launch);
+ * "cluster_eig", that of k_ceig_solve (one launch); "cluster_eig_values", the device time and launches of k_ceig_values (one per
+ * chunk; 0 with n_functions = 0). */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
