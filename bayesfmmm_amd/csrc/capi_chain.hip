@@ -2,7 +2,7 @@
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
 // per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it, the cluster
-// covariance surfaces with their bands and their eigenvalues and eigenfunctions.
+// covariance surfaces with their bands and their eigenvalues and eigenfunctions, and the prediction of held-out curves.
 // An entry point is its argument checks (SlotCheck: slots, curve selection, workspace plan), its workspace and the event pairs
 // that time its launches into the handle's PT_* timers (CallBufs owns both) and one for_chunks.
 #include "handle.hpp"
@@ -1183,6 +1183,165 @@ extern "C" int bfmmm_chain_cluster_eigen(bfmmm_handle* h, const int32_t* perm, c
          copy_sync(h, fn_sd + r0, d_sd, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
       err = "kernel or copy back failed";
     if (err.empty()) collect(h, values, PT_CEIG_VALUES);
+    return err;
+  });
+}
+
+// ---- prediction of held-out curves from the chain slots (kernels_predict.hip) -----------------------------------
+// The records of all new curves once per call (launch_stats_* as they are; a from-basis handle forms them on the host as its
+// creation does), then per chunk of consecutive new curves k_predict into the chunk's traces and k_predict_pool over them.
+extern "C" int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const double* t, const double* B, const int64_t* offsets,
+                                   int n_new, const double* X, const int32_t* perm, int first_slot, int n_slots, int n_samples,
+                                   int n_stages, uint64_t seed, const double* zs, int64_t max_workspace_bytes,
+                                   double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min,
+                                   double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace, double* samples,
+                                   int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_predict", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"h", h}})) return 1;
+  if (n_new < 0) return fail(fn + ": 'n_new' must not be negative");
+  if (n_new == 0) return 0;
+  if (ck.ptrs({{"lpd", lpd}, {"z_mean", z_mean}, {"z_sd", z_sd}, {"ess_mean", ess_mean}, {"ess_min", ess_min}})) return 1;
+  const Ctx& c = h->c;
+  const Dims& d = c.d;
+  const int K = d.K, P = d.P, D = d.D, J = n_samples, R = n_stages;
+  const bool mv = d.mv != 0, from_basis = !h->B_host.empty();
+  if (ck.ptrs({{"y", y}})) return 1;
+  if (mv) {
+    if (t || B || offsets) return fail(fn + ": the multivariate model takes 'y' alone: 't', 'B' and 'offsets' must be null");
+  } else if (from_basis) {
+    if (ck.ptrs({{"B", B}, {"offsets", offsets}})) return 1;
+    if (t) return fail(fn + ": a sampler created from a basis takes 'B', not 't'");
+  } else {
+    if (ck.ptrs({{"t", t}, {"offsets", offsets}})) return 1;
+    if (B) return fail(fn + ": a spline sampler takes 't', not 'B'");
+  }
+  if (!mv) {
+    if (offsets[0] < 0) return fail(fn + ": 'offsets'[0] must not be negative");
+    for (int r = 0; r < n_new; ++r)
+      if (offsets[r + 1] - offsets[r] < 1)
+        return fail(fn + ": new curve " + std::to_string(r) + " is empty (offsets " + std::to_string(offsets[r]) + " .. " + std::to_string(offsets[r + 1]) +
+                    "): at least 1 point a curve");
+  }
+  if (D > 0 && !X) return fail(fn + ": 'X' is null but the sampler has " + std::to_string(D) + " covariates");
+  if (D == 0 && X) return fail(fn + ": 'X' is given but the sampler has no covariates");
+  for (int64_t e = 0; X && e < (int64_t)n_new * D; ++e)
+    if (!std::isfinite(X[e])) return fail(fn + ": 'X'[" + std::to_string(e % n_new) + ", " + std::to_string(e / n_new) + "] is not finite");
+  if (J < 1) return fail(fn + ": 'n_samples' must be at least 1, got " + std::to_string(J));
+  if (R < 1) return fail(fn + ": 'n_stages' must be at least 1, got " + std::to_string(R));
+  if (zs && R != 1) return fail(fn + ": 'zs' takes the place of the stage-0 samples: 'n_stages' must be 1, got " + std::to_string(R));
+  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, n_new, "rows") || ck.row_limit()) return 1;
+  // the RNG index ((r R + st) J + j) K + k is a 32-bit counter word
+  if (!zs && (long double)n_new * (long double)R * (long double)J * (long double)K > 4294967296.0L)
+    return fail(fn + ": n_new x n_stages x n_samples x K = " + std::to_string(n_new) + " x " + std::to_string(R) + " x " + std::to_string(J) + " x " +
+                std::to_string(K) + " exceeds the 4294967296 (2^32) indices of the random number counter");
+  if (perm && perm_check(ck, perm)) return 1;
+  PredictCall f;
+  f.n_new = n_new; f.J = J; f.R = R; f.first_slot = first_slot; f.n_slots = n_slots; f.seed = seed;
+  const std::string bad = predict_check(c, f, nullptr);
+  if (!bad.empty()) return fail(fn + ": " + bad);
+  const size_t N = (size_t)ck.CS();
+  const int64_t n_obs = mv ? (int64_t)n_new * P : offsets[n_new];
+  // shared by all curves: the data (y, and t and the offsets of a spline sampler), the records and counts, X, perm, zs; a curve: its
+  // traces (lpd, ess, m, q, the proposals and the samples where asked for) and its five pooled results
+  const size_t shared = sizeof(double) * ((from_basis ? 0 : (size_t)n_obs * (mv ? 1 : 2)) + (size_t)n_new * d.LREC + (X ? (size_t)n_new * D : 0) +
+                                          (zs ? N * (size_t)J * K : 0) + 2) +
+                        sizeof(int64_t) * (!mv && !from_basis ? (size_t)n_new + 1 : 0) + sizeof(int32_t) * (((size_t)n_new + 1) & ~(size_t)1) +
+                        (perm ? sizeof(int32_t) * ((N * K + 1) & ~(size_t)1) : 0);
+  const size_t per_curve = sizeof(double) * (N * (2 + 2 * (size_t)K + (prop_trace ? (size_t)R * K : 0) + (samples ? (size_t)R * J * K : 0)) + 3 + 2 * (size_t)K);
+  const size_t budget = budget_of(max_workspace_bytes);
+  if (samples && budget < shared + per_curve)
+    return fail(fn + ": 'samples' of one curve (n_chains x n_slots x n_stages x n_samples x K doubles) with the rest need " +
+                std::to_string(shared + per_curve) + " bytes, above 'max_workspace_bytes' = " + std::to_string(budget) + " (" + std::to_string(shared) +
+                " shared by all curves + " + std::to_string(per_curve) + " per curve)");
+  int64_t chunk = 0;
+  if (ck.curve_chunk(budget, shared, per_curve, n_new, (int64_t)std::max<size_t>(1, per_curve / sizeof(double) / std::max<size_t>(N, 1)), &chunk)) return 1;
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_PREDICT_STATS, PT_PREDICT);
+  CallBufs b;
+  double *d_y = nullptr, *d_t = nullptr, *d_rec = nullptr, *d_X = nullptr, *d_zs = nullptr, *d_tr = nullptr, *d_prop = nullptr, *d_smp = nullptr,
+         *d_out = nullptr;
+  int64_t* d_off = nullptr;
+  int *d_ni = nullptr, *d_err = nullptr;
+  int32_t* d_perm = nullptr;
+  Timer stats, kernel, pool;
+  HIPCHK(b.timers({&stats, &kernel, &pool}));
+  HIPCHK(b.get(&d_rec, (size_t)n_new * d.LREC));
+  HIPCHK(b.get(&d_ni, (size_t)n_new));
+  if (from_basis) {
+    // band-packed G = B'B ([dd P + lo] = G(lo, lo + dd), dd <= BW), s = B'y, yy, as bfmmm_create_from_basis forms them
+    std::vector<double> hrec((size_t)n_new * d.LREC, 0.0);
+    std::vector<int> hni((size_t)n_new);
+    for (int r = 0; r < n_new; ++r) {
+      double* rc = hrec.data() + (size_t)r * d.LREC;
+      hni[r] = (int)(offsets[r + 1] - offsets[r]);
+      for (int64_t l = offsets[r]; l < offsets[r + 1]; ++l) {
+        const double* br = B + (size_t)l * P;
+        for (int lo = 0; lo < P; ++lo) {
+          if (br[lo] == 0.0) continue;
+          for (int dd = 0; dd <= d.BW && lo + dd < P; ++dd) rc[dd * P + lo] += br[lo] * br[lo + dd];
+          rc[d.LG + lo] += br[lo] * y[l];
+        }
+        rc[d.LG + P] += y[l] * y[l];
+      }
+    }
+    HIPCHK(copy_sync(h, d_rec, hrec.data(), sizeof(double) * hrec.size(), hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(h, d_ni, hni.data(), sizeof(int) * hni.size(), hipMemcpyHostToDevice));
+  } else {
+    HIPCHK(b.put(h, &d_y, y, (size_t)n_obs));
+    if (!mv) {
+      HIPCHK(b.put(h, &d_t, t, (size_t)n_obs));
+      HIPCHK(b.put(h, &d_off, offsets, (size_t)n_new + 1));
+      HIPCHK(b.get(&d_err, 2));
+      HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int) * 2, h->st));
+    }
+    HIPCHK(hipMemsetAsync(d_rec, 0, sizeof(double) * (size_t)n_new * d.LREC, h->st));
+    int herr = 0;
+    const std::string serr = timed(stats, h->st, [&] {
+      if (mv) { launch_stats_multivariate(n_new, P, d.LREC, d_y, d_rec, d_ni, h->st); return std::string(); }
+      return launch_stats_functional(h->cfg.basis_degree, n_new, P, d.LREC, d_off, d_t, d_y, h->d_knots, h->n_knots, d_rec, d_ni, nullptr, d_err, h->st)
+                 ? std::string("unsupported basis_degree") : std::string();
+    });
+    if (!serr.empty()) { (void)hipStreamSynchronize(h->st); return fail(fn + ": " + serr); }
+    if (!mv) HIPCHK(copy_sync(h, &herr, d_err, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipGetLastError());
+    collect(h, stats, PT_PREDICT_STATS);
+    if (herr) return fail(fn + ": at least one time point of the new curves lies outside 'boundary_knots'");
+  }
+  if (X) HIPCHK(b.put(h, &d_X, X, (size_t)n_new * D));
+  if (perm) HIPCHK(b.put(h, &d_perm, perm, N * K));
+  if (zs) HIPCHK(b.put(h, &d_zs, zs, N * (size_t)J * K));
+  const size_t NK = N * (size_t)K;
+  HIPCHK(b.get(&d_tr, (size_t)chunk * (2 * N + 2 * NK)));
+  HIPCHK(b.get(&d_out, (size_t)chunk * (3 + 2 * (size_t)K)));
+  if (prop_trace) HIPCHK(b.get(&d_prop, (size_t)chunk * NK * R));
+  if (samples) HIPCHK(b.get(&d_smp, (size_t)chunk * NK * R * J));
+  f.rec = d_rec; f.ni = d_ni; f.X = d_X; f.perm = d_perm; f.zs = d_zs;
+  double* d_lpd_t = d_tr;
+  double* d_ess_t = d_lpd_t + (size_t)chunk * N;
+  double* d_m_t = d_ess_t + (size_t)chunk * N;
+  double* d_q_t = d_m_t + (size_t)chunk * NK;
+  double* d_lpd = d_out;
+  double* d_emean = d_lpd + chunk;
+  double* d_emin = d_emean + chunk;
+  double* d_zm = d_emin + chunk;
+  double* d_zsd = d_zm + (size_t)chunk * K;
+  return for_chunks(ck, n_new, chunk, [&](int64_t r0, int rows) {
+    std::string err = timed(kernel, h->st, [&] { return launch_predict(c, f, (int)r0, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_prop, d_smp, h->st); });
+    if (err.empty())
+      err = timed(pool, h->st, [&] { return launch_predict_pool(K, (long long)N, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_lpd, d_zm, d_zsd, d_emean, d_emin, h->st); });
+    auto back = [&](double* dst, const double* src, size_t per_row) {
+      return !dst || hipMemcpyAsync(dst + (size_t)r0 * per_row, src, sizeof(double) * (size_t)rows * per_row, hipMemcpyDeviceToHost, h->st) == hipSuccess;
+    };
+    if (err.empty() &&
+        !(back(lpd_trace, d_lpd_t, N) && back(ess_trace, d_ess_t, N) && back(z_trace, d_m_t, NK) && back(prop_trace, d_prop, NK * R) &&
+          back(samples, d_smp, NK * R * J) && back(lpd, d_lpd, 1) && back(ess_mean, d_emean, 1) && back(ess_min, d_emin, 1) &&
+          back(z_mean, d_zm, K) && back(z_sd, d_zsd, K) && hipStreamSynchronize(h->st) == hipSuccess && hipGetLastError() == hipSuccess))
+      err = "kernel or copy back failed";
+    if (!err.empty()) return err;
+    collect(h, kernel, PT_PREDICT);
+    collect(h, pool, PT_PREDICT);
     return err;
   });
 }

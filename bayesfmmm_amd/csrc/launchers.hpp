@@ -240,6 +240,29 @@ std::string launch_ceig_solve(const Ctx& c, const CeigCall& f, hipStream_t st);
 // the values V[cs + N (e - r0)] of result rows e in [r0, r0 + rows), e = (k J + j) G + g, N = C n_slots
 std::string launch_ceig_values(const Ctx& c, const CeigCall& f, long long r0, long long rows, double* V, hipStream_t st);
 
+// ---- kernels_predict.hip ----
+// One call of bfmmm_chain_predict: the records rec (n_new x LREC) and point counts ni of the new curves, their
+// covariates X (n_new x D column-major; null without covariates), the permutation rows perm[(q S + s) K + .] (null: identity), the
+// sample table zs[(cs J + j) K + k] (null: variates are drawn), J samples in each of R stages, the seed and the slot range.  All
+// device.
+struct PredictCall {
+  int n_new = 0, J = 0, R = 0, first_slot = 0, n_slots = 0;
+  unsigned long long seed = 0;
+  const double *rec = nullptr, *X = nullptr, *zs = nullptr;
+  const int* ni = nullptr;
+  const int32_t* perm = nullptr;
+};
+// "" or what k_predict cannot take; *lds_bytes: the dynamic LDS a workgroup needs
+std::string predict_check(const Ctx& c, const PredictCall& f, size_t* lds_bytes);
+// new curves [r0, r0 + rows) of the call into the chunk's traces (r from 0, N = C n_slots): lpd_t, ess_t [r N + cs], m_t, q_t
+// [(r N + cs) K + l] (relabelled by perm), prop [((r N + cs) R + st) K + k] and samples [(((r N + cs) R + st) J + j) K + k] (either
+// may be null)
+std::string launch_predict(const Ctx& c, const PredictCall& f, int r0, int rows, double* lpd_t, double* ess_t, double* m_t, double* q_t,
+                           double* prop, double* samples, hipStream_t st);
+// the pooled results of the chunk's rows from its traces: lpd, ess_mean, ess_min [r], z_mean, z_sd [r K + l]
+std::string launch_predict_pool(int K, long long N, int rows, const double* lpd_t, const double* ess_t, const double* m_t, const double* q_t,
+                                double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min, hipStream_t st);
+
 // ---- kernels_bands.hip ----
 // The column reductions of the credible-band entry points on device tables V[t + T col], on stream st.  quantiles: LDS sort
 // for T <= 8192 (W unused), else k_bands_quantiles_big over the workspace W of NP ncol doubles, NP = bands_sort_pad(T), which

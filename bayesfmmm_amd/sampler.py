@@ -530,6 +530,82 @@ class Sampler:
         out["max_sweeps"] = int(ms.value)
         return out
 
+    def predict(self, Y_new, time_new=None, basis_new=None, X_new=None, perm=None, n_samples=256, n_stages=3, seed=1,
+                trace=False, z_samples=None, return_samples=False, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """Held-out curves under the fitted model (bfmmm_chain_predict): for every new curve the log predictive
+        density log p(y_new | data) and the predictive law of its memberships Z_new ~ Dir(alpha_3 pi), with the chains pooled over
+        chain slots [first_slot, first_slot + n_slots), on the device.  The integral over Z_new is taken per draw by importance
+        sampling in n_stages rounds of n_samples samples: the first round proposes from the prior, every later one from a Dirichlet
+        fitted to the weighted moments of the round before; the results are the last round's.  K-fold cross-validation is a fit per
+        fold and the sum of the folds' "elpd".
+        Y_new: a list of 1-D arrays with time_new (spline samplers) or basis_new (a list of n_i x P matrices; samplers created from a
+        basis), or an (m, P) matrix (multivariate model).  X_new: (m, D), required exactly when covariates are set.  perm: `align`'s
+        "perm" of the same slots, which relabels the membership columns (default: the labels as they are, which only means something
+        where no chain switches labels); "lpd" and the ESS do not depend on it.  z_samples: (C, S, J, K) memberships that take the
+        place of the stage-0 samples of every curve (n_stages must be 1; the deterministic hook of the tests).
+        Returns {"lpd": (m,), "elpd": sum lpd, "se_elpd": sqrt(m var(lpd)), "Z_mean": (m, K), "Z_sd": (m, K), the sd of the whole
+        predictive law, "ess_mean", "ess_min": (m,), the importance-sampling effective sample size of the last round over the draws,
+        "n_samples", "n_stages"}.  A curve whose ess_min is small against n_samples (below 10, say) is not to be trusted: raise
+        n_stages or n_samples.  trace adds "lpd_trace", "ess_trace": (m, C, S), "Z_trace": (m, C, S, K) and "proposal": (m, C, S, R, K);
+        return_samples adds "samples": (m, C, S, R, J, K), for small shapes."""
+        S = self._slots(first_slot, n_slots)
+        Cn, K, J, R = self.n_chains, self.K, int(n_samples), int(n_stages)
+        ip = C.POINTER(C.c_int32)
+        y = t = B = off = None
+        if self.offsets is None:
+            y = np.asfortranarray(Y_new, dtype=np.float64)
+            if y.ndim != 2 or y.shape[1] != self.P:
+                raise ValueError(f"Y_new must be an (m, {self.P}) matrix")
+            m = y.shape[0]
+            if time_new is not None or basis_new is not None:
+                raise ValueError("the multivariate model takes Y_new alone")
+        else:
+            m = len(Y_new)
+            off = np.zeros(m + 1, dtype=np.int64)
+            off[1:] = np.cumsum([len(v) for v in Y_new])
+            cat = lambda vs, w: np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, w) for v in vs], axis=0)) \
+                if m else np.zeros((0, w))
+            y = cat(Y_new, 1).reshape(-1)
+            if basis_new is not None:
+                if any(np.shape(b) != (len(v), self.P) for b, v in zip(basis_new, Y_new)) or len(basis_new) != m:
+                    raise ValueError(f"basis_new must hold one n_i x {self.P} matrix per new curve")
+                B = cat(basis_new, self.P)
+            if time_new is not None:
+                if len(time_new) != m or any(len(a) != len(v) for a, v in zip(time_new, Y_new)):
+                    raise ValueError("time_new must hold one array per new curve, as long as the curve")
+                t = cat(time_new, 1).reshape(-1)
+        Xm = None
+        if X_new is not None:
+            Xm = np.asfortranarray(X_new, dtype=np.float64)
+            if Xm.ndim != 2 or Xm.shape[0] != m or (self.D > 0 and Xm.shape[1] != self.D):
+                raise ValueError(f"X_new must be an ({m}, {self.D}) matrix")
+        p = None if perm is None else self._perm_arg(perm, S)
+        zs = None
+        if z_samples is not None:
+            zs = np.ascontiguousarray(z_samples, dtype=np.float64)
+            if zs.shape != (Cn, S, J, K):
+                raise ValueError(f"z_samples must have shape ({Cn}, {S}, {J}, {K}): (chains, slots, n_samples, K)")
+        Sn = max(S, 0)
+        out = {"lpd": np.zeros(m), "Z_mean": np.zeros((m, K)), "Z_sd": np.zeros((m, K)), "ess_mean": np.zeros(m), "ess_min": np.zeros(m)}
+        tr = {}
+        if trace:
+            tr = {"lpd_trace": np.zeros((m, Cn, Sn)), "ess_trace": np.zeros((m, Cn, Sn)), "Z_trace": np.zeros((m, Cn, Sn, K)),
+                  "proposal": np.zeros((m, Cn, Sn, max(R, 0), K))}
+        if return_samples:
+            tr["samples"] = np.zeros((m, Cn, Sn, max(R, 0), max(J, 0), K))
+        opt = lambda k: _dp(tr[k]) if k in tr else None
+        _lib.check(self.lib.bfmmm_chain_predict(
+            self.h, None if y is None else _dp(y), None if t is None else _dp(t), None if B is None else _dp(B),
+            None if off is None else off.ctypes.data_as(_lib.c_int64_p), m, None if Xm is None else _dp(Xm),
+            None if p is None else p.ctypes.data_as(ip), int(first_slot), S, J, R, int(seed), None if zs is None else _dp(zs),
+            int(max_workspace_bytes), _dp(out["lpd"]), _dp(out["Z_mean"]), _dp(out["Z_sd"]), _dp(out["ess_mean"]), _dp(out["ess_min"]),
+            opt("lpd_trace"), opt("Z_trace"), opt("ess_trace"), opt("proposal"), opt("samples"), m))
+        out.update(tr)
+        out["elpd"] = float(np.sum(out["lpd"]))
+        out["se_elpd"] = float(np.sqrt(m * np.var(out["lpd"]))) if m > 0 else 0.0
+        out["n_samples"], out["n_stages"] = J, R
+        return out
+
     def _mean_eigenfunctions(self, Em, perm, wv, J, xv, first_slot, n_slots, max_workspace_bytes):
         """(K, J, G): the J leading w-eigenfunctions of the posterior mean surfaces C^(k,k), numpy.linalg.eigh of
         sqrt(w) C sqrt(w)' on the host, each signed so that its entry of largest |sqrt(w) psi| (lowest g on ties) is positive"""

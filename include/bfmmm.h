@@ -439,6 +439,48 @@ int bfmmm_chain_cluster_eigen(bfmmm_handle* h, const int32_t* perm, const double
  * forms round differently; each keeps every promise of the call.  Process-wide; default 0. */
 void bfmmm_set_cluster_eig_form(int form);
 
+/* Prediction of held-out curves from the chain slots: for every new curve r, with the chains pooled, the log
+ * predictive density log p(y_r | data) and the predictive law of its memberships Z_new ~ Dir(alpha_3 pi), integrated over by
+ * staged importance sampling on the device.  For draw cs = q n_slots + s of chain slots [first_slot, first_slot + n_slots) of
+ * EVERY chain of the batch the integrand is the marginal density l(z) of bfmmm_chain_curve_loglik, evaluated from the new
+ * curve's record and the A x A table Gamma_ab = theta_a' G theta_b, tau_a = theta_a' s of the draw's A = K (M + 1) directions
+ * (x folded in), which the kernel forms once per (curve, draw) and keeps on chip.
+ * Input forms.  A spline handle takes y, t, offsets (n_new + 1 entries; curve r is [offsets[r], offsets[r + 1])) with B NULL and
+ * uses the handle's knots and degree; a handle of bfmmm_create_from_basis takes y, B (rows of P, row-major), offsets with t NULL
+ * and the handle's band; the multivariate model takes y as n_new x P column-major with t, B, offsets NULL.  X: n_new x D
+ * column-major, required exactly when the sampler has covariates, finite.  No curve may be empty.
+ * The estimator, per (r, cs), runs n_stages = R rounds of n_samples = J samples; the results are the last round's.
+ *   stage 0 proposes from the prior, a = alpha_3 pi of the draw; stage st draws z_j ~ Dir(a) from gamma variates keyed by
+ *   (seed, the RNG chain id of chain q, the slot) with index ((r R + st) J + j) K + k, r the curve's position in the call, every
+ *   variate clamped below at the smallest normal double;
+ *   lw_j = l(z_j) + sum_k (alpha_3 pi_k - a_k) log z_jk + lB(a) - lB(alpha_3 pi)      (stage 0: lw_j = l(z_j));
+ *   w_j = exp(lw_j - max lw), lpd = max + log(sum w / J), ess = (sum w)^2 / sum w^2, m_k = sum w z_k / sum w,
+ *   q_k = sum w z_k^2 / sum w, v_k = sum w (z_k - m_k)^2 / sum w (a second pass);
+ *   next proposal: r_k = m_k (1 - m_k) / v_k - 1 over v_k > 0, a0 their median (the mean of the middle two of an even count;
+ *   1e4 where no v_k > 0) clipped to [1, 1e4], a_k = max(a0 m_k, 0.5).
+ * ess is a result: rows with a low ess are not to be trusted.  Pooled over the N = C n_slots draws:
+ *   lpd[r] = log mean_cs exp(lpd_trace[r, cs]);  z_mean[r K + l] = mean_cs m_perm[l];  z_sd[r K + l] = sqrt(mean_cs q - z_mean^2),
+ *   the sd of the whole predictive law;  ess_mean[r], ess_min[r];   capacity >= n_new rows, all five required.
+ * perm (N K entries as from bfmmm_chain_align; NULL: the identity) relabels the membership columns of every draw; lpd and ess do
+ * not depend on it.  Optional traces (NULL: not copied): lpd_trace, ess_trace [r N + cs]; z_trace[(r N + cs) K + l], the last
+ * stage's m relabelled; prop_trace[((r N + cs) R + st) K + k], the proposal of every stage; samples[(((r N + cs) R + st) J + j) K + k],
+ * the z of every stage (tests and small shapes).
+ * zs: NULL, or a host table [(cs J + j) K + k] that every curve takes as its stage-0 samples; no variate is drawn, n_stages must be
+ * 1 and lw = l (the deterministic hook).
+ * Refused by name: a null handle or required pointer, n_new < 0 (0 returns at once), an empty curve, n_samples < 1, n_stages < 1,
+ * a slot range outside the storage, more than 2^22 draws, n_new R J K above 2^32 (the RNG index), a perm row that is no
+ * permutation, a shape whose on-chip tables (Gamma, the samples of a stage) exceed 160 KiB of LDS.  A value's bits depend on
+ * (curve, chain, slot, seed, J, R) alone.  Chunks of consecutive new curves keep the traces within max_workspace_bytes (0: 256
+ * MiB); the new curves' data and records, X, perm and zs are shared by all curves and count against it; a budget below what is
+ * shared plus one curve is refused with the bytes needed.  Runs on the sampler's stream and leaves its state, its slots and its
+ * resident records untouched. */
+int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const double* t, const double* B, const int64_t* offsets,
+                        int n_new, const double* X, const int32_t* perm, int first_slot, int n_slots, int n_samples,
+                        int n_stages, uint64_t seed, const double* zs, int64_t max_workspace_bytes,
+                        double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min,
+                        double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace, double* samples,
+                        int64_t capacity);
+
 /* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
  * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P: C_a = Prec_a^-1 as k_factor left it), "Lz" (A x P: L_a z_a of the sampled directions),
@@ -507,7 +549,10 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * per chunk where the band takes a second sweep); "cluster_cov_maxdev", those of k_ccov_maxdev (one per chunk; 0 without the band).
  * Of the last bfmmm_chain_cluster_eigen (always measured): "cluster_eig_gram", the device time of k_ceig_gram (one launch);
  * "cluster_eig", that of k_ceig_solve (one launch); "cluster_eig_values", the device time and launches of k_ceig_values (one per
- * chunk; 0 with n_functions = 0). */
+ * chunk; 0 with n_functions = 0).
+ * Of the last bfmmm_chain_predict (always measured): "predict_stats", the device time and launches of the kernel that forms the
+ * new curves' records (0 launches for a handle of bfmmm_create_from_basis, whose records are formed on the host); "predict", the
+ * device time and launches of k_predict and the pooling kernel after it (two per chunk). */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
