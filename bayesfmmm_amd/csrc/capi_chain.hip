@@ -3,8 +3,12 @@
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
 // per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it, the cluster
 // covariance surfaces with their bands and their eigenvalues and eigenfunctions, and the prediction of held-out curves.
-// An entry point is its argument checks (SlotCheck: slots, curve selection, workspace plan), its workspace and the event pairs
-// that time its launches into the handle's PT_* timers (CallBufs owns both) and one for_chunks.
+// An entry point is its argument checks (SlotCheck: slots, curve selection, the grid pair, x, alpha, probs and `units`, the one
+// budget rule), its workspace and the event pairs that time its launches into the handle's PT_* timers (CallBufs owns both) and
+// one for_chunks.  What several of them do is written once: `once` for a launch that runs once per call (the projections), Back
+// for a chunk's copies to the host, SortWs for the rule that long rows sort in a workspace, and RowReducer for a chunk of rows of
+// C S pooled values: its layout in one allocation, its reduction (moments or the seven statistics, then the quantiles) and its
+// copies back.
 #include "handle.hpp"
 #include "launchers.hpp"
 #include "../../include/bfmmm_entry.h"
@@ -66,7 +70,20 @@ struct SlotCheck {
     return fail(fn + ": at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " + std::to_string(CS()));
   }
   int budget_sign(int64_t bytes) const { return bytes < 0 ? fail(fn + ": 'max_workspace_bytes' must not be negative") : 0; }
-  int budget_row(size_t budget, size_t row) const { return budget < row ? fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(row) + " bytes of one row") : 0; }
+  // The budget rule: a workspace of `shared` bytes for the whole call and `per_unit` for every unit (noun: "curve", "block", "row")
+  // of a chunk; *chunk units fit the budget, at most `count` and `cap`.  No noun: rows with nothing shared.  per_unit 0: nothing
+  // to chunk, the shared part alone has to fit.
+  int units(size_t budget, size_t shared, size_t per_unit, int64_t count, int64_t cap, const char* noun, int64_t* chunk) const {
+    if (budget < shared + per_unit) {
+      const std::string need = fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_unit) + " bytes ";
+      return fail(noun ? need + "one " + noun + " needs " + plan_text(shared, per_unit, noun) : need + "of one row");
+    }
+    *chunk = per_unit ? std::min<int64_t>(std::min<int64_t>(count, (int64_t)((budget - shared) / per_unit)), cap) : 1;
+    return 0;
+  }
+  static std::string plan_text(size_t shared, size_t per_unit, const std::string& noun) {
+    return "(" + std::to_string(shared) + " shared by all " + noun + "s + " + std::to_string(per_unit) + " per " + noun + ")";
+  }
   int capacity(int64_t have, int64_t want, const char* unit = "entries") const { return have < want ? fail(fn + tag + ": 'capacity' below " + std::to_string(want) + " " + unit) : 0; }
   // a selection of curves (null: all n): every index is one; *m: the curves of the result.  The caller checks n_curves by its own rule.
   int curve_list(const int32_t* curves, int n_curves, int64_t* m) const {
@@ -77,24 +94,34 @@ struct SlotCheck {
     *m = curves ? n_curves : n;
     return 0;
   }
-  // a workspace of `shared` bytes for all curves and `per_curve` for every curve of a chunk: *chunk curves fit the budget, at most
-  // m and 2^30 result entries of `cells` a curve
-  int curve_chunk(size_t budget, size_t shared, size_t per_curve, int64_t m, int64_t cells, int64_t* chunk) const {
-    if (budget < shared + per_curve)
-      return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_curve) + " bytes one curve needs (" +
-                  std::to_string(shared) + " shared by all curves + " + std::to_string(per_curve) + " per curve)");
-    *chunk = std::min<int64_t>(std::min<int64_t>(m, (int64_t)((budget - shared) / per_curve)), std::max<int64_t>(1, (1LL << 30) / cells));
+  // the grid pair of a covariance surface: E1 of G1 rows, E2 of G2 rows where given, `diagonal` only without E2
+  int grid_pair(int G1, const double* E2, int G2, int diagonal) const {
+    if (G1 < 1) return fail(fn + ": 'G1' must be at least 1");
+    if (E2 && G2 < 1) return fail(fn + ": 'G2' must be at least 1 where 'E2' is given");
+    if (diagonal && E2) return fail(fn + ": 'diagonal' requires 'E2' to be null");
     return 0;
   }
-  // the same for the blocks of bfmmm_chain_similarity_loss: *chunk blocks fit the budget, at most `blocks` and 2^30
-  int block_chunk(size_t budget, size_t shared, size_t per_block, int64_t blocks, int64_t* chunk) const {
-    if (budget < shared + per_block)
-      return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_block) + " bytes one block needs (" +
-                  std::to_string(shared) + " shared by all blocks + " + std::to_string(per_block) + " per block)");
-    *chunk = std::min<int64_t>(std::min<int64_t>(blocks, (int64_t)((budget - shared) / per_block)), 1 << 30);
+  // a covariate setting x (null: none) of D finite entries, for covariance-adjusted samplers only
+  int covariate_setting(const double* x) const {
+    const int D = h->c.d.D;
+    if (x && !(h->c.covariance_adj && D > 0)) return fail(fn + ": 'x' is given but the sampler is not covariance-adjusted");
+    for (int d = 0; x && d < D; ++d)
+      if (!std::isfinite(x[d])) return fail(fn + ": 'x'[" + std::to_string(d) + "] is not finite");
+    return 0;
+  }
+  int alpha_inside(double alpha) const { return alpha > 0.0 && alpha < 1.0 ? 0 : fail(fn + ": 'alpha' must be inside (0, 1)"); }
+  // nq in nq_min .. 16, with probs inside [0, 1] and somewhere to put the quantiles where nq > 0
+  int probs_list(const double* probs, int nq, int nq_min, const double* quant) const {
+    if (nq < nq_min || nq > 16) return fail(fn + ": 'nq' outside " + std::to_string(nq_min) + " .. 16");
+    if (nq > 0 && ptrs({{"probs", probs}, {"quant", quant}})) return 1;
+    for (int q = 0; q < nq; ++q)
+      if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail(fn + ": 'probs'[" + std::to_string(q) + "] outside [0, 1]");
     return 0;
   }
 };
+constexpr int64_t kNoCap = INT64_MAX;      // SlotCheck::units without a cap of the call's own
+// the cap of a call whose kernels index 2^30 result entries of `cells` a curve
+int64_t cells_cap(int64_t cells) { return std::max<int64_t>(1, (1LL << 30) / cells); }
 size_t budget_of(int64_t max_workspace_bytes) { return max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20; }
 
 // ---- what a call owns, its chunk loop and its timing ----------------------------------------------------------------------
@@ -170,15 +197,103 @@ std::string curve_ll_timed(const SlotCheck& ck, int i0, int rows, double* d_x) {
 }
 void curve_ll_collect(bfmmm_handle* h) { collect(h, {h->ev0, h->ev1}, PT_CURVE_LL); }
 
-// Rows [r0, r0 + rows) of a call's mean, of its sd and of its C chains' means, the last two where asked for, of `cells` entries a
-// row, from the chunk's device buffers to the host; true: all there, the stream synchronised
-bool stats_to_host(bfmmm_handle* h, int64_t r0, int rows, int64_t cells, int C, double* mean, const double* d_mean, double* sd,
-                   const double* d_sd, double* chain_mean, const double* d_cm) {
-  const size_t cnt = sizeof(double) * (size_t)rows * cells;
-  return !(sd && hipMemcpyAsync(sd + (size_t)r0 * cells, d_sd, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) &&
-         !(chain_mean && hipMemcpyAsync(chain_mean + (size_t)r0 * C * cells, d_cm, cnt * C, hipMemcpyDeviceToHost, h->st) != hipSuccess) &&
-         copy_sync(h, mean + (size_t)r0 * cells, d_mean, cnt, hipMemcpyDeviceToHost) == hipSuccess;
+// A launch that runs once per call (the projection tables), between an event pair of its own: launch, synchronise, a failure
+// under the call's name, the device time into timer pt.  count > 0: the timer reports that (the tables filled), not the launch.
+template <typename Launch>
+int once(const SlotCheck& ck, CallBufs& b, int pt, int count, Launch launch) {
+  bfmmm_handle* h = ck.h;
+  Timer t;
+  HIPCHK(b.timers({&t}));
+  const std::string err = timed(t, h->st, launch);
+  if (!err.empty()) { (void)hipStreamSynchronize(h->st); return fail(ck.fn + ": " + err); }
+  HIPCHK(hipStreamSynchronize(h->st));
+  collect(h, t, pt);
+  if (count) h->post_launches[pt] = count;
+  return 0;
 }
+
+// The copies of a chunk to the host: back(dst, src, per_row) queues rows [r0, r0 + rows) of per_row entries each from the chunk's
+// device buffer src to dst + r0 per_row (dst null: not asked for, skipped); done() synchronises the stream and answers "" or what
+// a body of for_chunks reports.
+constexpr const char* kBackFailed = "kernel or copy back failed";
+struct Back {
+  bfmmm_handle* h;
+  int64_t r0;
+  int rows;
+  bool ok = true;
+  template <typename T>
+  Back& operator()(T* dst, const T* src, size_t per_row) {
+    if (ok && dst)
+      ok = hipMemcpyAsync(dst + (size_t)r0 * per_row, src, sizeof(T) * (size_t)rows * per_row, hipMemcpyDeviceToHost, h->st) == hipSuccess;
+    return *this;
+  }
+  std::string done() const { return ok && hipStreamSynchronize(h->st) == hipSuccess ? "" : kBackFailed; }
+};
+
+// 16 doubles on the device (owned by b) with the call's nq probabilities in front, and `extra` more behind them
+hipError_t probs_put(CallBufs& b, bfmmm_handle* h, const double* probs, int nq, double** d_probs, int extra = 0) {
+  const hipError_t e = b.get(d_probs, 16 + (size_t)extra);
+  return e != hipSuccess || !nq ? e : copy_sync(h, *d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice);
+}
+
+// ---- rows of N = C S pooled values (kernels_bands.hip, kernels_diag.hip) ---------------------------------------------------------
+// Where quantiles are wanted, rows of up to fit_lds_rows() draws sort in LDS and longer ones in a workspace of NP doubles a row
+// (k_bands_quantiles_big); `also`: the caller sorts such rows by a threshold of its own.
+struct SortWs {
+  bool on;
+  size_t NP;
+  SortWs(long long N, bool wanted, bool also = false)
+      : on((wanted && N > fit_lds_rows()) || also), NP(on ? (size_t)bands_sort_pad((int)N) : 0) {}
+};
+
+// A chunk of rows of N values in one allocation, their reduction and the copies back.  Two flavours: mean and sd
+// (launch_bands_moments; a row takes N + 2 + nq + NP doubles) or the seven statistics (diag_launch; N + tier + 7 + nq + NP), then
+// the nq quantiles (launch_bands_quantiles) where nq > 0.  The sub-buffers hold `chunk` rows each, in the order of the members.
+struct RowReducer {
+  bfmmm_handle* h;
+  int C, S, nq;
+  bool seven;
+  size_t N, tier;
+  SortWs ws;
+  const double* probs = nullptr;      // the nq probabilities on the device
+  double *x = nullptr, *mean = nullptr, *sd = nullptr, *out7 = nullptr, *tws = nullptr, *q = nullptr, *w = nullptr;
+  std::vector<double> hb;             // the seven statistics of a chunk, statistic by statistic
+
+  RowReducer(const SlotCheck& ck, int nq, bool seven, bool also_sort = false)
+      : h(ck.h), C(ck.h->nch), S(ck.n_slots), nq(nq), seven(seven), N((size_t)ck.CS()), tier(seven ? diag_row_ws_doubles(C, S) : 0),
+        ws(ck.CS(), nq > 0, also_sort) {}
+  size_t res_doubles() const { return (seven ? tier + 7 : 2) + (size_t)nq + ws.NP; }      // of a row, without its values
+  size_t row_bytes() const { return sizeof(double) * (N + res_doubles()); }
+  // the sub-buffers of `chunk` rows: the values at vals, the rest from res on
+  void place(double* vals, double* res, int64_t chunk) {
+    const size_t n = (size_t)chunk;
+    x = vals;
+    if (seven) { out7 = res; tws = out7 + 7 * n; q = tws + tier * n; }
+    else { mean = res; sd = mean + n; q = sd + n; }
+    w = q + (size_t)nq * n;
+  }
+  hipError_t alloc(CallBufs& b, int64_t chunk) {
+    double* p = nullptr;
+    const hipError_t e = b.get(&p, row_bytes() / sizeof(double) * (size_t)chunk);
+    if (e == hipSuccess) place(p, p + (size_t)chunk * N, chunk);
+    return e;
+  }
+  std::string reduce(long long rows) const {
+    std::string err = seven ? diag_launch(x, rows, C, S, out7, rows, tws, rows, h->st) : launch_bands_moments(x, (int)N, rows, mean, sd, h->st);
+    if (err.empty() && nq) err = launch_bands_quantiles(x, (int)N, rows, w, probs, nq, q, h->st);
+    return err;
+  }
+  // rows [r0, r0 + rows) of the results to the host: quant and trace where asked for, then outs: mean and sd, or the seven statistics
+  std::string to_host(int64_t r0, int rows, double* const* outs, double* quant, double* trace) {
+    Back back{h, r0, rows};
+    back(nq ? quant : nullptr, q, (size_t)nq)(trace, x, N);
+    if (!seven) return back(outs[0], mean, 1)(outs[1], sd, 1).done();
+    hb.resize(7 * (size_t)rows);
+    const std::string err = Back{h, 0, 1, back.ok}(hb.data(), out7, 7 * (size_t)rows).done();
+    for (int s = 0; err.empty() && s < 7; ++s) std::copy(hb.begin() + (size_t)s * rows, hb.begin() + (size_t)(s + 1) * rows, outs[s] + r0);
+    return err;
+  }
+};
 
 // ---- split R-hat, ESS, MCSE, mean and sd of rows of C S draws (kernels_diag.hip) --------------------------------
 // fill(p0, rows, d_x) puts rows [p0, p0 + rows) of the len rows into the workspace (row-major: draw fastest, then chain),
@@ -186,27 +301,18 @@ bool stats_to_host(bfmmm_handle* h, int64_t r0, int rows, int64_t cells, int C, 
 template <typename Fill>
 int seven_stats(const SlotCheck& ck, int64_t len, int64_t max_workspace_bytes, double* const (&outs)[7], bool ll_timed, Fill fill) {
   bfmmm_handle* h = ck.h;
-  const int C = h->nch, S = ck.n_slots;
-  const size_t budget = budget_of(max_workspace_bytes);
-  const size_t per_row = sizeof(double) * ((size_t)C * S + diag_row_ws_doubles(C, S)) + 7 * sizeof(double);
-  if (ck.budget_row(budget, per_row)) return 1;
-  const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
+  RowReducer r(ck, 0, true);
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), 0, r.row_bytes(), len, kNoCap, nullptr, &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   if (ll_timed) reset_timers(h, PT_CURVE_LL, PT_CURVE_LL);
   CallBufs b;
-  double* d_x = nullptr;
-  HIPCHK(b.get(&d_x, per_row / sizeof(double) * (size_t)chunk));
-  double* d_out = d_x + (size_t)chunk * C * S;
-  double* d_tier = d_out + 7 * (size_t)chunk;
-  std::vector<double> hb(7 * (size_t)chunk);
+  HIPCHK(r.alloc(b, chunk));
   return for_chunks(ck, len, chunk, [&](int64_t p0, int rows) {
-    std::string err = fill((int)p0, rows, d_x);
-    if (err.empty()) err = diag_launch(d_x, rows, C, S, d_out, rows, d_tier, rows, h->st);
-    if (err.empty() && copy_sync(h, hb.data(), d_out, sizeof(double) * 7 * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess)
-      err = "kernel or copy back failed";
-    if (!err.empty()) return err;
-    if (ll_timed) curve_ll_collect(h);
-    for (int q = 0; q < 7; ++q) std::copy(hb.begin() + (size_t)q * rows, hb.begin() + (size_t)(q + 1) * rows, outs[q] + p0);
+    std::string err = fill((int)p0, rows, r.x);
+    if (err.empty()) err = r.reduce(rows);
+    if (err.empty()) err = r.to_host(p0, rows, outs, nullptr, nullptr);
+    if (err.empty() && ll_timed) curve_ll_collect(h);
     return err;
   });
 }
@@ -242,18 +348,12 @@ int fit_prepare(const SlotCheck& ck, const double* E, const int32_t* curves, Fit
   bfmmm_handle* h = ck.h;
   double *d_E = nullptr, *d_tab = nullptr;
   int32_t* d_curves = nullptr;
-  Timer project;
-  HIPCHK(b.timers({&project}));
   HIPCHK(b.put(h, &d_E, E, (size_t)s.f.G * h->c.d.P));
   HIPCHK(b.get(&d_tab, (size_t)s.CS * s.f.G * (size_t)s.NJ));
   if (curves) HIPCHK(b.put(h, &d_curves, curves, (size_t)s.m));
   s.f.E = d_E; s.f.curves = d_curves; s.f.tab = d_tab;
   reset_timers(h, PT_FIT_PROJECT, PT_FIT_REDUCE);
-  const std::string err = timed(project, h->st, [&] { return launch_fit_project(h->c, s.f, h->st); });
-  if (!err.empty()) { (void)hipStreamSynchronize(h->st); return fail(ck.fn + ": " + err); }
-  HIPCHK(hipStreamSynchronize(h->st));
-  collect(h, project, PT_FIT_PROJECT);
-  return 0;
+  return once(ck, b, PT_FIT_PROJECT, 0, [&] { return launch_fit_project(h->c, s.f, h->st); });
 }
 
 }  // namespace
@@ -312,8 +412,7 @@ extern "C" int bfmmm_chain_curve_loglik(bfmmm_handle* h, int first_slot, int n_s
   HIPCHK(b.get(&d_x, (size_t)chunk * (size_t)per_row));
   return for_chunks(ck, n, chunk, [&](int64_t i0, int rows) {
     std::string err = curve_ll_timed(ck, (int)i0, rows, d_x);
-    if (err.empty() && copy_sync(h, out + (size_t)i0 * per_row, d_x, sizeof(double) * (size_t)rows * per_row, hipMemcpyDeviceToHost) != hipSuccess)
-      err = "kernel or copy back failed";
+    if (err.empty()) err = Back{h, i0, rows}(out, d_x, (size_t)per_row).done();
     if (err.empty()) curve_ll_collect(h);
     return err;
   });
@@ -344,10 +443,8 @@ extern "C" int bfmmm_chain_loo(bfmmm_handle* h, int first_slot, int n_slots, int
     return 1;
   const int64_t len = h->c.d.n;
   const long long CS = ck.CS();
-  const size_t budget = budget_of(max_workspace_bytes);
-  const size_t per_row = sizeof(double) * (size_t)CS;
-  if (ck.budget_row(budget, per_row)) return 1;
-  const int64_t chunk = std::min<int64_t>(len, (int64_t)(budget / per_row));
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), 0, sizeof(double) * (size_t)CS, len, kNoCap, nullptr, &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   reset_timers(h, PT_CURVE_LL, PT_CURVE_LL);
   CallBufs b;
@@ -388,8 +485,7 @@ extern "C" int bfmmm_chain_curve_fit(bfmmm_handle* h, int which, const double* E
   HIPCHK(b.get(&d_v, (size_t)chunk * per_curve));
   return for_chunks(ck, s.m, chunk, [&](int64_t r0, int rows) {
     std::string err = timed(values, h->st, [&] { return launch_fit_values(h->c, s.f, (int)r0, rows, d_v, h->st); });
-    if (err.empty() && copy_sync(h, out + (size_t)r0 * per_curve, d_v, sizeof(double) * (size_t)rows * per_curve, hipMemcpyDeviceToHost) != hipSuccess)
-      err = "kernel or copy back failed";
+    if (err.empty()) err = Back{h, r0, rows}(out, d_v, (size_t)per_curve).done();
     if (err.empty()) collect(h, values, PT_FIT_VALUES);
     return err;
   });
@@ -400,31 +496,27 @@ extern "C" int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double*
                                        int first_slot, int n_slots, const double* probs, int nq, int64_t max_workspace_bytes,
                                        double* mean, double* sd, double* quantiles, int64_t capacity) {
   const SlotCheck ck{"bfmmm_chain_curve_bands", h, first_slot, n_slots};
-  const std::string& fn = ck.fn;
   FitSetup s;
   if (ck.ptrs({{"h", h}, {"probs", probs}, {"mean", mean}, {"sd", sd}, {"quantiles", quantiles}}) ||
-      fit_check_args(ck, which, E, G, curves, n_curves, s))
+      fit_check_args(ck, which, E, G, curves, n_curves, s) || ck.probs_list(probs, nq, 1, quantiles) || ck.budget_sign(max_workspace_bytes) ||
+      ck.capacity(capacity, (int64_t)s.m * G, "rows"))
     return 1;
-  if (nq < 1 || nq > 16) return fail(fn + ": 'nq' outside 1 .. 16");
-  for (int q = 0; q < nq; ++q)
-    if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail(fn + ": 'probs'[" + std::to_string(q) + "] outside [0, 1]");
-  if (ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, (int64_t)s.m * G, "rows")) return 1;
   const bool lds_rows = s.CS <= fit_lds_rows() && !g_curve_fit_route;
-  const bool sort_ws = s.CS > fit_lds_rows();               // k_bands_quantiles_big sorts in a workspace
-  const int NP = sort_ws ? bands_sort_pad((int)s.CS) : 0;
+  const SortWs ws(s.CS, true);                              // k_bands_quantiles_big sorts in a workspace
+  const bool sort_ws = ws.on;
+  const int NP = (int)ws.NP;
   const size_t per_curve = sizeof(double) * (size_t)G * ((size_t)(2 + nq) + (lds_rows ? 0 : (size_t)s.CS + (size_t)NP));
   int64_t chunk = 0;
-  if (ck.curve_chunk(budget_of(max_workspace_bytes), fit_shared_bytes(h, s), per_curve, s.m, G, &chunk)) return 1;
+  if (ck.units(budget_of(max_workspace_bytes), fit_shared_bytes(h, s), per_curve, s.m, cells_cap(G), "curve", &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
   Timer first, reduce;      // k_fit_rows, or k_fit_values and then the sort and the moments of its values
   HIPCHK(b.timers({&first, &reduce}));
   double *d_probs = nullptr, *d_out = nullptr, *d_v = nullptr, *d_w = nullptr;
-  HIPCHK(b.get(&d_probs, 16));
+  HIPCHK(probs_put(b, h, probs, nq, &d_probs));
   HIPCHK(b.get(&d_out, (size_t)chunk * G * (2 + nq)));
   if (!lds_rows) HIPCHK(b.get(&d_v, (size_t)chunk * G * (size_t)s.CS));
   if (sort_ws) HIPCHK(b.get(&d_w, (size_t)chunk * G * (size_t)NP));
-  HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
   if (fit_prepare(ck, E, curves, s, b)) return 1;
   double* d_mean = d_out;
   double* d_sd = d_out + (size_t)chunk * G;
@@ -443,11 +535,7 @@ extern "C" int bfmmm_chain_curve_bands(bfmmm_handle* h, int which, const double*
         if (e.empty()) e = launch_bands_moments(d_v, (int)s.CS, ncol, d_mean, d_sd, h->st);
         return e;
       });
-    if (err.empty() &&
-        (hipMemcpyAsync(mean + (size_t)r0 * G, d_mean, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-         hipMemcpyAsync(sd + (size_t)r0 * G, d_sd, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-         copy_sync(h, quantiles + (size_t)r0 * G * nq, d_q, sizeof(double) * (size_t)ncol * nq, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
+    if (err.empty()) err = Back{h, r0, rows}(mean, d_mean, (size_t)G)(sd, d_sd, (size_t)G)(quantiles, d_q, (size_t)G * nq).done();
     if (!err.empty()) return err;
     collect(h, first, lds_rows ? PT_FIT_ROWS : PT_FIT_VALUES);
     if (!lds_rows) collect(h, reduce, PT_FIT_REDUCE);
@@ -464,15 +552,15 @@ extern "C" int bfmmm_chain_curve_bands_sim(bfmmm_handle* h, int which, const dou
   const std::string& fn = ck.fn;
   FitSetup s;
   if (ck.ptrs({{"h", h}, {"crit", crit}, {"lower", lower}, {"upper", upper}}) || fit_check_args(ck, which, E, G, curves, n_curves, s)) return 1;
-  if (!(alpha > 0.0 && alpha < 1.0)) return fail(fn + ": 'alpha' must be inside (0, 1)");
-  if (ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, (int64_t)s.m * G, "rows")) return 1;
+  if (ck.alpha_inside(alpha) || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, (int64_t)s.m * G, "rows")) return 1;
   if (G > fit_sim_gmax())
     return fail(fn + ": 'G' above " + std::to_string(fit_sim_gmax()) + ": mean and sd of a curve's grid points stay in LDS beside its sort row");
-  const bool sort_ws = s.CS > fit_lds_rows();               // C goes to a workspace row that k_bands_quantiles_big sorts
-  const int NP = sort_ws ? bands_sort_pad((int)s.CS) : 0;
+  const SortWs ws(s.CS, true);                              // C goes to a workspace row that k_bands_quantiles_big sorts
+  const bool sort_ws = ws.on;
+  const int NP = (int)ws.NP;
   const size_t per_curve = sizeof(double) * (4 * (size_t)G + 1 + (sort_ws ? (size_t)s.CS + (size_t)NP : 0));
   int64_t chunk = 0;
-  if (ck.curve_chunk(budget_of(max_workspace_bytes), fit_shared_bytes(h, s), per_curve, s.m, G, &chunk)) return 1;
+  if (ck.units(budget_of(max_workspace_bytes), fit_shared_bytes(h, s), per_curve, s.m, cells_cap(G), "curve", &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
   Timer sim, sort, band;      // k_fit_sim; for long rows the sort of their maxima, then k_fit_sim_band
@@ -494,7 +582,6 @@ extern "C" int bfmmm_chain_curve_bands_sim(bfmmm_handle* h, int which, const dou
   double* d_lo = d_out + 2 * (size_t)chunk * G;
   double* d_up = d_out + 3 * (size_t)chunk * G;
   return for_chunks(ck, s.m, chunk, [&](int64_t r0, int rows) {
-    const size_t cnt = sizeof(double) * (size_t)rows * G;
     std::string err = timed(sim, h->st, [&] { return launch_fit_sim(h->c, s.f, (int)r0, rows, p, d_mean, d_sd, d_crit, d_lo, d_up, d_c, h->st); });
     if (err.empty() && sort_ws)
       err = timed(sort, h->st, [&] {
@@ -503,13 +590,8 @@ extern "C" int bfmmm_chain_curve_bands_sim(bfmmm_handle* h, int which, const dou
         return e.empty() ? launch_fit_quantiles(d_w, NP, (int)s.CS, rows, d_p, 1, d_crit, h->st) : e;
       });
     if (err.empty() && sort_ws) err = timed(band, h->st, [&] { return launch_fit_sim_band(d_mean, d_sd, d_crit, G, rows, d_lo, d_up, h->st); });
-    if (err.empty() &&
-        ((mean && hipMemcpyAsync(mean + (size_t)r0 * G, d_mean, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         (sd && hipMemcpyAsync(sd + (size_t)r0 * G, d_sd, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         hipMemcpyAsync(lower + (size_t)r0 * G, d_lo, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-         hipMemcpyAsync(upper + (size_t)r0 * G, d_up, cnt, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-         copy_sync(h, crit + r0, d_crit, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
+    if (err.empty())
+      err = Back{h, r0, rows}(mean, d_mean, (size_t)G)(sd, d_sd, (size_t)G)(lower, d_lo, (size_t)G)(upper, d_up, (size_t)G)(crit, d_crit, 1).done();
     if (!err.empty()) return err;
     collect(h, sim, PT_SIM);
     if (sort_ws) {
@@ -536,10 +618,10 @@ extern "C" int bfmmm_chain_similarity(bfmmm_handle* h, const int32_t* curves, in
   if (ck.curve_list(curves, n_curves, &m) || ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, m * n) || ck.row_limit()) return 1;
   // a result row: its n entries of mean, of sd and of every chain's mean, and its curve index
   const size_t per_row = sizeof(double) * (size_t)n * (1 + (sd ? 1 : 0) + (chain_mean ? (size_t)C : 0)) + (curves ? sizeof(int32_t) : 0);
-  if (ck.budget_row(budget_of(max_workspace_bytes), per_row)) return 1;
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), 0, per_row, m, 1 << 30, nullptr, &chunk)) return 1;
   reset_timers(h, PT_SIMILARITY, PT_SIMILARITY);
   if (m == 0) return 0;
-  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(m, (int64_t)(budget_of(max_workspace_bytes) / per_row)), 1 << 30);
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
   double *d_mean = nullptr, *d_sd = nullptr, *d_cm = nullptr;
@@ -554,7 +636,7 @@ extern "C" int bfmmm_chain_similarity(bfmmm_handle* h, const int32_t* curves, in
     if (curves && copy_sync(h, d_curves, curves + r0, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess)
       return std::string("copy of the curve list failed");
     std::string err = timed(kernel, h->st, [&] { return launch_similarity(h->c, first_slot, n_slots, d_curves, (int)r0, rows, d_mean, d_sd, d_cm, h->st); });
-    if (err.empty() && !stats_to_host(h, r0, rows, n, C, mean, d_mean, sd, d_sd, chain_mean, d_cm)) err = "kernel or copy back failed";
+    if (err.empty()) err = Back{h, r0, rows}(sd, d_sd, (size_t)n)(chain_mean, d_cm, (size_t)C * n)(mean, d_mean, (size_t)n).done();
     if (err.empty()) collect(h, kernel, PT_SIMILARITY);
     return err;
   });
@@ -574,7 +656,7 @@ extern "C" int bfmmm_chain_similarity_loss(bfmmm_handle* h, int first_slot, int 
   // shared by all blocks: the loss vector and, where asked for, the seven statistics and the workspace of their row; a block: its N sums
   const size_t stat_doubles = stats ? 7 + diag_row_ws_doubles(C, S) : 0;
   int64_t chunk = 0;
-  if (ck.block_chunk(budget_of(max_workspace_bytes), sizeof(double) * (N + stat_doubles), sizeof(double) * N, blocks, &chunk)) return 1;
+  if (ck.units(budget_of(max_workspace_bytes), sizeof(double) * (N + stat_doubles), sizeof(double) * N, blocks, 1 << 30, "block", &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   reset_timers(h, PT_SIM_LOSS, PT_SIM_LOSS_REDUCE);
   CallBufs b;
@@ -641,10 +723,7 @@ extern "C" int bfmmm_chain_curve_cov(bfmmm_handle* h, const double* E1, int G1, 
                                      double* mean, double* sd, double* chain_mean, int64_t capacity) {
   const SlotCheck ck{"bfmmm_chain_curve_cov", h, first_slot, n_slots};
   const std::string& fn = ck.fn;
-  if (ck.ptrs({{"h", h}, {"E1", E1}, {"mean", mean}})) return 1;
-  if (G1 < 1) return fail(fn + ": 'G1' must be at least 1");
-  if (E2 && G2 < 1) return fail(fn + ": 'G2' must be at least 1 where 'E2' is given");
-  if (diagonal && E2) return fail(fn + ": 'diagonal' requires 'E2' to be null");
+  if (ck.ptrs({{"h", h}, {"E1", E1}, {"mean", mean}}) || ck.grid_pair(G1, E2, G2, diagonal)) return 1;
   const int C = h->nch, P = h->c.d.P;
   if (!E2) G2 = G1;
   int64_t m = 0, chunk = 0;
@@ -661,15 +740,15 @@ extern "C" int bfmmm_chain_curve_cov(bfmmm_handle* h, const double* E1, int G1, 
   const size_t shared = sizeof(double) * (tab1 + tab2 + (size_t)G1 * P + (E2 ? (size_t)G2 * P : 0)) +
                         (curves ? sizeof(int32_t) * (((size_t)m + 1) & ~(size_t)1) : 0);
   const size_t per_curve = sizeof(double) * (size_t)cells * (1 + (sd ? 1 : 0) + (chain_mean ? (size_t)C : 0));
-  if (ck.curve_chunk(budget_of(max_workspace_bytes), shared, per_curve, m, cells, &chunk)) return 1;
+  if (ck.units(budget_of(max_workspace_bytes), shared, per_curve, m, cells_cap(cells), "curve", &chunk)) return 1;
   reset_timers(h, PT_COV_PROJECT, PT_COV);
   if (m == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
   double *d_E1 = nullptr, *d_E2 = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_cm = nullptr;
   int32_t* d_curves = nullptr;
-  Timer project, kernel;
-  HIPCHK(b.timers({&project, &kernel}));
+  Timer kernel;
+  HIPCHK(b.timers({&kernel}));
   HIPCHK(b.put(h, &d_E1, E1, (size_t)G1 * P));
   HIPCHK(b.get(&f.tab1, tab1));
   if (E2) {
@@ -681,14 +760,10 @@ extern "C" int bfmmm_chain_curve_cov(bfmmm_handle* h, const double* E1, int G1, 
   if (sd) HIPCHK(b.get(&d_sd, (size_t)chunk * cells));
   if (chain_mean) HIPCHK(b.get(&d_cm, (size_t)chunk * C * cells));
   f.E1 = d_E1; f.E2 = d_E2; f.curves = d_curves;
-  const std::string perr = timed(project, h->st, [&] { return launch_cov_project(h->c, f, h->st); });
-  if (!perr.empty()) { (void)hipStreamSynchronize(h->st); return fail(fn + ": " + perr); }
-  HIPCHK(hipStreamSynchronize(h->st));
-  collect(h, project, PT_COV_PROJECT);
-  h->post_launches[PT_COV_PROJECT] = E2 ? 2 : 1;      // the tables filled
+  if (once(ck, b, PT_COV_PROJECT, E2 ? 2 : 1, [&] { return launch_cov_project(h->c, f, h->st); })) return 1;
   return for_chunks(ck, m, chunk, [&](int64_t r0, int rows) {
     std::string err = timed(kernel, h->st, [&] { return launch_curve_cov(h->c, f, (int)r0, rows, d_mean, d_sd, d_cm, h->st); });
-    if (err.empty() && !stats_to_host(h, r0, rows, cells, C, mean, d_mean, sd, d_sd, chain_mean, d_cm)) err = "kernel or copy back failed";
+    if (err.empty()) err = Back{h, r0, rows}(sd, d_sd, (size_t)cells)(chain_mean, d_cm, (size_t)C * cells)(mean, d_mean, (size_t)cells).done();
     if (err.empty()) collect(h, kernel, PT_COV);
     return err;
   });
@@ -725,14 +800,6 @@ int perm_check(const SlotCheck& ck, const int32_t* perm) {
   return 0;
 }
 
-// nq in 0 .. 16, with probs inside [0, 1] and somewhere to put the quantiles where nq > 0
-int probs_check(const SlotCheck& ck, const double* probs, int nq, const double* quant) {
-  if (nq < 0 || nq > 16) return fail(ck.fn + ": 'nq' outside 0 .. 16");
-  if (nq > 0 && ck.ptrs({{"probs", probs}, {"quant", quant}})) return 1;
-  for (int q = 0; q < nq; ++q)
-    if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail(ck.fn + ": 'probs'[" + std::to_string(q) + "] outside [0, 1]");
-  return 0;
-}
 
 }  // namespace
 
@@ -759,10 +826,7 @@ extern "C" int bfmmm_chain_align(bfmmm_handle* h, const double* Zref, int first_
   HIPCHK(b.get(&d_score, (size_t)N));
   return for_chunks(ck, 1, 1, [&](int64_t, int) {
     std::string err = timed(gram, h->st, [&] { return launch_align_gram(h->c, d_ref, first_slot, n_slots, d_perm, d_score, h->st); });
-    if (err.empty() &&
-        ((score && hipMemcpyAsync(score, d_score, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         copy_sync(h, perm, d_perm, sizeof(int32_t) * (size_t)N * d.K, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
+    if (err.empty()) err = Back{h, 0, 1}(score, d_score, (size_t)N)(perm, d_perm, (size_t)N * d.K).done();
     if (err.empty()) collect(h, gram, PT_ALIGN_GRAM);
     return err;
   });
@@ -784,47 +848,31 @@ extern "C" int bfmmm_chain_aligned_summary(bfmmm_handle* h, const char* name, co
   int64_t inner = 0;
   if (!a.p || !align_axis(c.d, name, &inner)) return fail(ck.fn + ": unknown name '" + name + "'");
   ck.tag = std::string("(") + name + ")";
-  if (ck.capacity(capacity, a.len) || ck.row_limit() || probs_check(ck, probs, nq, quant) || perm_check(ck, perm)) return 1;
+  if (ck.capacity(capacity, a.len) || ck.row_limit() || ck.probs_list(probs, nq, 0, quant) || perm_check(ck, perm)) return 1;
   const int C = h->nch, S = n_slots, K = c.d.K;
-  const size_t N = (size_t)ck.CS();
-  const bool sort_ws = nq > 0 && (long long)N > fit_lds_rows();      // k_bands_quantiles_big sorts in a workspace
-  const size_t NP = sort_ws ? (size_t)bands_sort_pad((int)N) : 0;
-  const size_t tier = diag_row_ws_doubles(C, S);
-  const size_t per_row = sizeof(double) * (N + tier + 7 + (size_t)nq + NP);
-  const size_t budget = budget_of(max_workspace_bytes);
-  if (ck.budget_row(budget, per_row)) return 1;
-  const int64_t chunk = std::min<int64_t>(a.len, (int64_t)(budget / per_row));
+  RowReducer r(ck, nq, true);
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), 0, r.row_bytes(), a.len, kNoCap, nullptr, &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   reset_timers(h, PT_ALIGN_GATHER, PT_ALIGN_GATHER);
   CallBufs b;
-  double *d_x = nullptr, *d_probs = nullptr;
+  double* d_probs = nullptr;
   int32_t* d_perm = nullptr;
   Timer gather;
   HIPCHK(b.timers({&gather}));
-  HIPCHK(b.get(&d_x, per_row / sizeof(double) * (size_t)chunk));
-  HIPCHK(b.put(h, &d_perm, perm, N * K));
-  HIPCHK(b.get(&d_probs, 16));
-  if (nq) HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
-  double* d_out = d_x + (size_t)chunk * N;
-  double* d_tier = d_out + 7 * (size_t)chunk;
-  double* d_q = d_tier + tier * (size_t)chunk;
-  double* d_w = d_q + (size_t)nq * (size_t)chunk;
+  HIPCHK(r.alloc(b, chunk));
+  HIPCHK(b.put(h, &d_perm, perm, r.N * K));
+  HIPCHK(probs_put(b, h, probs, nq, &d_probs));
+  r.probs = d_probs;
   double* const outs[7] = {rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
-  std::vector<double> hb(7 * (size_t)chunk);
   return for_chunks(ck, a.len, chunk, [&](int64_t p0, int rows) {
     std::string err = timed(gather, h->st, [&] {
       return launch_align_gather(a.p, a.cov ? c.chain_bytes_cov : c.chain_bytes, a.ss, a.ps, first_slot, S, C, (int)p0, rows, d_perm, K, inner,
-                                 d_x, h->st);
+                                 r.x, h->st);
     });
-    if (err.empty()) err = diag_launch(d_x, rows, C, S, d_out, rows, d_tier, rows, h->st);
-    if (err.empty() && nq) err = launch_bands_quantiles(d_x, (int)N, rows, d_w, d_probs, nq, d_q, h->st);
-    if (err.empty() &&
-        ((nq && hipMemcpyAsync(quant + (size_t)p0 * nq, d_q, sizeof(double) * (size_t)rows * nq, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         copy_sync(h, hb.data(), d_out, sizeof(double) * 7 * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
-    if (!err.empty()) return err;
-    collect(h, gather, PT_ALIGN_GATHER);
-    for (int q = 0; q < 7; ++q) std::copy(hb.begin() + (size_t)q * rows, hb.begin() + (size_t)(q + 1) * rows, outs[q] + p0);
+    if (err.empty()) err = r.reduce(rows);
+    if (err.empty()) err = r.to_host(p0, rows, outs, quant, nullptr);
+    if (err.empty()) collect(h, gather, PT_ALIGN_GATHER);
     return err;
   });
 }
@@ -841,39 +889,27 @@ extern "C" int bfmmm_chain_cluster_mean_bands(bfmmm_handle* h, const int32_t* pe
   const Ctx& c = h->c;
   const int K = c.d.K, P = c.d.P;
   const int64_t len = (int64_t)K * G;
-  if (ck.capacity(capacity, len, "rows") || ck.row_limit() || probs_check(ck, probs, nq, quant) || perm_check(ck, perm)) return 1;
-  const size_t N = (size_t)ck.CS();
-  const bool sort_ws = nq > 0 && (long long)N > fit_lds_rows();
-  const size_t NP = sort_ws ? (size_t)bands_sort_pad((int)N) : 0;
-  const size_t per_row = sizeof(double) * (N + 2 + (size_t)nq + NP);
-  const size_t budget = budget_of(max_workspace_bytes);
-  if (ck.budget_row(budget, per_row)) return 1;
-  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(len, (int64_t)(budget / per_row)), 65535);
+  if (ck.capacity(capacity, len, "rows") || ck.row_limit() || ck.probs_list(probs, nq, 0, quant) || perm_check(ck, perm)) return 1;
+  RowReducer r(ck, nq, false);
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), 0, r.row_bytes(), len, 65535, nullptr, &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   reset_timers(h, PT_ALIGN_PROJECT, PT_ALIGN_PROJECT);
   CallBufs b;
-  double *d_v = nullptr, *d_E = nullptr, *d_probs = nullptr;
+  double *d_E = nullptr, *d_probs = nullptr;
   int32_t* d_perm = nullptr;
   Timer project;
   HIPCHK(b.timers({&project}));
-  HIPCHK(b.get(&d_v, per_row / sizeof(double) * (size_t)chunk));
+  HIPCHK(r.alloc(b, chunk));
   HIPCHK(b.put(h, &d_E, E, (size_t)G * P));
-  HIPCHK(b.put(h, &d_perm, perm, N * K));
-  HIPCHK(b.get(&d_probs, 16));
-  if (nq) HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
-  double* d_mean = d_v + (size_t)chunk * N;
-  double* d_sd = d_mean + (size_t)chunk;
-  double* d_q = d_sd + (size_t)chunk;
-  double* d_w = d_q + (size_t)nq * (size_t)chunk;
+  HIPCHK(b.put(h, &d_perm, perm, r.N * K));
+  HIPCHK(probs_put(b, h, probs, nq, &d_probs));
+  r.probs = d_probs;
+  double* const outs[2] = {mean, sd};
   return for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
-    std::string err = timed(project, h->st, [&] { return launch_align_project(c, d_E, G, d_perm, first_slot, n_slots, (int)r0, rows, d_v, h->st); });
-    if (err.empty()) err = launch_bands_moments(d_v, (int)N, rows, d_mean, d_sd, h->st);
-    if (err.empty() && nq) err = launch_bands_quantiles(d_v, (int)N, rows, d_w, d_probs, nq, d_q, h->st);
-    if (err.empty() &&
-        ((nq && hipMemcpyAsync(quant + (size_t)r0 * nq, d_q, sizeof(double) * (size_t)rows * nq, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         hipMemcpyAsync(mean + r0, d_mean, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-         copy_sync(h, sd + r0, d_sd, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
+    std::string err = timed(project, h->st, [&] { return launch_align_project(c, d_E, G, d_perm, first_slot, n_slots, (int)r0, rows, r.x, h->st); });
+    if (err.empty()) err = r.reduce(rows);
+    if (err.empty()) err = r.to_host(r0, rows, outs, quant, nullptr);
     if (err.empty()) collect(h, project, PT_ALIGN_PROJECT);
     return err;
   });
@@ -890,10 +926,7 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
                                              double* quant, double* crit, double* lower, double* upper, double* trace, int64_t capacity) {
   const SlotCheck ck{"bfmmm_chain_cluster_cov_bands", h, first_slot, n_slots};
   const std::string& fn = ck.fn;
-  if (ck.ptrs({{"h", h}, {"perm", perm}, {"E1", E1}, {"mean", mean}, {"sd", sd}})) return 1;
-  if (G1 < 1) return fail(fn + ": 'G1' must be at least 1");
-  if (E2 && G2 < 1) return fail(fn + ": 'G2' must be at least 1 where 'E2' is given");
-  if (diagonal && E2) return fail(fn + ": 'diagonal' requires 'E2' to be null");
+  if (ck.ptrs({{"h", h}, {"perm", perm}, {"E1", E1}, {"mean", mean}, {"sd", sd}}) || ck.grid_pair(G1, E2, G2, diagonal)) return 1;
   if (n_pairs < 0) return fail(fn + ": 'n_pairs' must not be negative");
   const Ctx& c = h->c;
   const int K = c.d.K, P = c.d.P, D = c.d.D;
@@ -901,9 +934,7 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
     if (pairs[2 * r] < 0 || pairs[2 * r] >= K || pairs[2 * r + 1] < 0 || pairs[2 * r + 1] >= K)
       return fail(fn + ": 'pairs'[" + std::to_string(r) + "] = (" + std::to_string(pairs[2 * r]) + ", " + std::to_string(pairs[2 * r + 1]) +
                   ") outside 0 .. " + std::to_string(K - 1));
-  if (x && !(c.covariance_adj && D > 0)) return fail(fn + ": 'x' is given but the sampler is not covariance-adjusted");
-  for (int d = 0; x && d < D; ++d)
-    if (!std::isfinite(x[d])) return fail(fn + ": 'x'[" + std::to_string(d) + "] is not finite");
+  if (ck.covariate_setting(x)) return 1;
   if (c.d.M < 1) return fail(fn + ": n_eigen is 0: the model has no covariance surface");
   if (!E2) G2 = G1;
   // the pairs of the result: the caller's, or all k <= l
@@ -915,12 +946,11 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
   const int64_t m = (int64_t)pr.size() / 2;
   const int64_t cells = diagonal ? (int64_t)G1 : (int64_t)G1 * G2;      // entries of a pair's result
   const int64_t len = m * cells;
-  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, len) || ck.row_limit() || probs_check(ck, probs, nq, quant))
+  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, len) || ck.row_limit() || ck.probs_list(probs, nq, 0, quant))
     return 1;
   const bool band = crit || lower || upper;
   if (band && !(crit && lower && upper)) return fail(fn + ": 'crit', 'lower' and 'upper' must be all null or all set");
-  if (band && !(alpha > 0.0 && alpha < 1.0)) return fail(fn + ": 'alpha' must be inside (0, 1)");
-  if (perm_check(ck, perm)) return 1;
+  if ((band && ck.alpha_inside(alpha)) || perm_check(ck, perm)) return 1;
   CcovCall f;
   f.G1 = G1; f.G2 = G2; f.diagonal = diagonal ? 1 : 0; f.first_slot = first_slot; f.n_slots = n_slots; f.n_pairs = m;
   const std::string bad = ccov_check(c, f);
@@ -929,28 +959,23 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
   if (m == 0) return 0;
   const size_t N = (size_t)ck.CS();
   const bool long_dev = band && (long long)N > ccov_sort_rows();               // dev's rows are sorted in the workspace too
-  const bool sort_ws = (nq > 0 && (long long)N > fit_lds_rows()) || long_dev;  // k_bands_quantiles_big sorts in a workspace
-  const size_t NP = sort_ws ? (size_t)bands_sort_pad((int)N) : 0;
+  RowReducer r(ck, nq, false, long_dev);
   // shared by all rows: the tables, E1, E2, x, probs, perm, the pairs and, for the band, dev and crit; a row: its values, its sort
   // workspace, its mean, sd and quantiles
   const size_t tab1 = ccov_table_doubles(c, f, 0), tab2 = E2 ? ccov_table_doubles(c, f, 1) : 0;
   const size_t shared = sizeof(double) * (tab1 + tab2 + (size_t)G1 * P + (E2 ? (size_t)G2 * P : 0) + (x ? (size_t)D : 0) + 17 +
                                           (band ? (size_t)m * N + (size_t)m : 0)) +
                         sizeof(int32_t) * (((N * K + 1) & ~(size_t)1) + 2 * (size_t)m);
-  const size_t per_row = sizeof(double) * (N + 2 + (size_t)nq + NP);
-  const size_t budget = budget_of(max_workspace_bytes);
-  if (budget < shared + per_row)
-    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_row) + " bytes one row needs (" +
-                std::to_string(shared) + " shared by all rows + " + std::to_string(per_row) + " per row)");
-  const int64_t chunk = std::min<int64_t>(std::min<int64_t>(len, (int64_t)((budget - shared) / per_row)), 1 << 30);
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), shared, r.row_bytes(), len, 1 << 30, "row", &chunk)) return 1;
   const int64_t nchunks = (len + chunk - 1) / chunk;
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
-  double *d_v = nullptr, *d_E1 = nullptr, *d_E2 = nullptr, *d_x = nullptr, *d_probs = nullptr, *d_dev = nullptr, *d_crit = nullptr;
+  double *d_E1 = nullptr, *d_E2 = nullptr, *d_x = nullptr, *d_probs = nullptr, *d_dev = nullptr, *d_crit = nullptr;
   int32_t *d_perm = nullptr, *d_pairs = nullptr;
-  Timer project, values, maxdev;
-  HIPCHK(b.timers({&project, &values, &maxdev}));
-  HIPCHK(b.get(&d_v, per_row / sizeof(double) * (size_t)chunk));
+  Timer values, maxdev;
+  HIPCHK(b.timers({&values, &maxdev}));
+  HIPCHK(r.alloc(b, chunk));
   HIPCHK(b.put(h, &d_E1, E1, (size_t)G1 * P));
   HIPCHK(b.get(&f.tab1, tab1));
   if (E2) {
@@ -960,9 +985,9 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
   if (x) HIPCHK(b.put(h, &d_x, x, (size_t)D));
   HIPCHK(b.put(h, &d_perm, perm, N * K));
   HIPCHK(b.put(h, &d_pairs, (const int32_t*)pr.data(), pr.size()));
-  HIPCHK(b.get(&d_probs, 17));
+  HIPCHK(probs_put(b, h, probs, nq, &d_probs, 1));      // [16]: 1 - alpha
+  r.probs = d_probs;
   const double p_crit = 1.0 - alpha;
-  if (nq) HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
   if (band) {
     HIPCHK(copy_sync(h, d_probs + 16, &p_crit, sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(b.get(&d_dev, (size_t)m * N));
@@ -970,27 +995,17 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
     HIPCHK(hipMemsetAsync(d_dev, 0, sizeof(double) * (size_t)m * N, h->st));      // the maximum starts from 0.0
   }
   f.E1 = d_E1; f.E2 = d_E2; f.x = d_x; f.perm = d_perm; f.pairs = d_pairs;
-  double* d_mean = d_v + (size_t)chunk * N;
-  double* d_sd = d_mean + (size_t)chunk;
-  double* d_q = d_sd + (size_t)chunk;
-  double* d_w = d_q + (size_t)nq * (size_t)chunk;
-  const std::string perr = timed(project, h->st, [&] { return launch_ccov_project(c, f, h->st); });
-  if (!perr.empty()) { (void)hipStreamSynchronize(h->st); return fail(fn + ": " + perr); }
-  HIPCHK(hipStreamSynchronize(h->st));
-  collect(h, project, PT_CCOV_PROJECT);
-  h->post_launches[PT_CCOV_PROJECT] = E2 ? 2 : 1;      // the tables filled
+  if (once(ck, b, PT_CCOV_PROJECT, E2 ? 2 : 1, [&] { return launch_ccov_project(c, f, h->st); })) return 1;
+  double* const outs[2] = {mean, sd};
+  auto dev_launch = [&](int64_t r0, int rows) {
+    return timed(maxdev, h->st, [&] { return launch_ccov_maxdev(f, (long long)N, r0, rows, r.x, r.mean, r.sd, d_dev, h->st); });
+  };
   int rc = for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
     const bool dev_now = band && nchunks == 1;
-    std::string err = timed(values, h->st, [&] { return launch_ccov_values(c, f, r0, rows, d_v, h->st); });
-    if (err.empty()) err = launch_bands_moments(d_v, (int)N, rows, d_mean, d_sd, h->st);
-    if (err.empty() && nq) err = launch_bands_quantiles(d_v, (int)N, rows, d_w, d_probs, nq, d_q, h->st);
-    if (err.empty() && dev_now) err = timed(maxdev, h->st, [&] { return launch_ccov_maxdev(f, (long long)N, r0, rows, d_v, d_mean, d_sd, d_dev, h->st); });
-    if (err.empty() &&
-        ((nq && hipMemcpyAsync(quant + (size_t)r0 * nq, d_q, sizeof(double) * (size_t)rows * nq, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         (trace && hipMemcpyAsync(trace + (size_t)r0 * N, d_v, sizeof(double) * (size_t)rows * N, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         hipMemcpyAsync(mean + r0, d_mean, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-         copy_sync(h, sd + r0, d_sd, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
+    std::string err = timed(values, h->st, [&] { return launch_ccov_values(c, f, r0, rows, r.x, h->st); });
+    if (err.empty()) err = r.reduce(rows);
+    if (err.empty() && dev_now) err = dev_launch(r0, rows);
+    if (err.empty()) err = r.to_host(r0, rows, outs, quant, trace);
     if (!err.empty()) return err;
     collect(h, values, PT_CCOV);
     if (dev_now) collect(h, maxdev, PT_CCOV_MAXDEV);
@@ -1000,11 +1015,11 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
   if (nchunks > 1) {
     // the second sweep: the same kernel on the same tables gives the same values, now against every chunk's mean and sd
     rc = for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
-      std::string err = timed(values, h->st, [&] { return launch_ccov_values(c, f, r0, rows, d_v, h->st); });
-      if (err.empty() && (copy_sync(h, d_mean, mean + r0, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess ||
-                          copy_sync(h, d_sd, sd + r0, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess))
+      std::string err = timed(values, h->st, [&] { return launch_ccov_values(c, f, r0, rows, r.x, h->st); });
+      if (err.empty() && (copy_sync(h, r.mean, mean + r0, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess ||
+                          copy_sync(h, r.sd, sd + r0, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess))
         err = "copy of the chunk's mean and sd failed";
-      if (err.empty()) err = timed(maxdev, h->st, [&] { return launch_ccov_maxdev(f, (long long)N, r0, rows, d_v, d_mean, d_sd, d_dev, h->st); });
+      if (err.empty()) err = dev_launch(r0, rows);
       if (err.empty() && (hipStreamSynchronize(h->st) != hipSuccess || hipGetLastError() != hipSuccess)) err = "kernel failed";
       if (!err.empty()) return err;
       collect(h, values, PT_CCOV);
@@ -1019,12 +1034,10 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
     std::string err;
     if (!long_dev) err = launch_ccov_crit(d_dev + (size_t)p0 * N, (long long)N, cnt, p_crit, d_crit + p0, h->st);
     else {
-      err = launch_bands_quantiles(d_dev + (size_t)p0 * N, (int)N, cnt, d_w, d_probs + 16, 1, d_crit + p0, h->st);
-      if (err.empty()) err = launch_fit_quantiles(d_w, (int)NP, (int)N, cnt, d_probs + 16, 1, d_crit + p0, h->st);
+      err = launch_bands_quantiles(d_dev + (size_t)p0 * N, (int)N, cnt, r.w, d_probs + 16, 1, d_crit + p0, h->st);
+      if (err.empty()) err = launch_fit_quantiles(r.w, (int)r.ws.NP, (int)N, cnt, d_probs + 16, 1, d_crit + p0, h->st);
     }
-    if (err.empty() && copy_sync(h, crit + p0, d_crit + p0, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost) != hipSuccess)
-      err = "kernel or copy back failed";
-    return err;
+    return err.empty() ? Back{h, p0, cnt}(crit, d_crit + p0, 1).done() : err;
   });
   if (rc) return rc;
   {
@@ -1062,15 +1075,13 @@ extern "C" int bfmmm_chain_cluster_eigen(bfmmm_handle* h, const int32_t* perm, c
   if (J < 0 || J > M) return fail(fn + ": 'n_functions' = " + std::to_string(J) + " outside 0 .. " + std::to_string(M) + " (n_eigen)");
   for (int g = 0; w && g < G; ++g)
     if (!(w[g] >= 0.0) || !std::isfinite(w[g])) return fail(fn + ": 'w'[" + std::to_string(g) + "] is negative or not finite");
-  if (x && !(c.covariance_adj && D > 0)) return fail(fn + ": 'x' is given but the sampler is not covariance-adjusted");
-  for (int d = 0; x && d < D; ++d)
-    if (!std::isfinite(x[d])) return fail(fn + ": 'x'[" + std::to_string(d) + "] is not finite");
+  if (ck.covariate_setting(x)) return 1;
   const int64_t len = (int64_t)K * J * G;      // eigenfunction rows
   if (J > 0 && ck.ptrs({{"fn_mean", fn_mean}, {"fn_sd", fn_sd}})) return 1;
   for (int64_t e = 0; ref && e < len; ++e)
     if (!std::isfinite(ref[e])) return fail(fn + ": 'ref'[" + std::to_string(e) + "] is not finite");
   if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, len, "rows") || ck.row_limit() ||
-      probs_check(ck, probs, nq, val_quant))
+      ck.probs_list(probs, nq, 0, val_quant))
     return 1;
   if (nq > 0 && (ck.ptrs({{"pve_quant", pve_quant}, {"tot_quant", tot_quant}}) || (J > 0 && ck.ptrs({{"fn_quant", fn_quant}})))) return 1;
   if (perm_check(ck, perm)) return 1;
@@ -1079,29 +1090,24 @@ extern "C" int bfmmm_chain_cluster_eigen(bfmmm_handle* h, const int32_t* perm, c
   const std::string bad = ceig_check(c, f);
   if (!bad.empty()) return fail(fn + ": " + bad);
   reset_timers(h, PT_CEIG_GRAM, PT_CEIG_VALUES);
-  const int C = h->nch, S = n_slots;
+  const int S = n_slots;
   const size_t N = (size_t)ck.CS();
   const size_t KM = (size_t)K * M, rs = 2 * KM + (size_t)K;                    // the small rows: lambda, pve, total
   const bool with_ref = ref && J > 0;
-  const bool sort_ws = nq > 0 && (long long)N > fit_lds_rows();                // k_bands_quantiles_big sorts in a workspace
-  const size_t NP = sort_ws ? (size_t)bands_sort_pad((int)N) : 0;
-  const size_t tier = diag_row_ws_doubles(C, S);
+  // the eigenfunction rows in chunks; all rs small rows at once: their mean, sd and quantiles (sm) and the seven statistics of
+  // the KM lambda rows in front (sv), on the values the solve leaves in d_small
+  RowReducer r(ck, nq, false), sm(ck, nq, false), sv(ck, 0, true);
   // shared by all rows: Q, R, E, w, x, ref, probs, the small rows with their results and workspaces, the b of every draw, the
   // status words and perm; an eigenfunction row: its values, its sort workspace, its mean, sd and quantiles
-  const size_t small_ws = rs * (2 + (size_t)nq + NP) + KM * (7 + tier);
+  const size_t small_ws = rs * sm.res_doubles() + KM * sv.res_doubles();
   const size_t shared = sizeof(double) * ((size_t)P * P + (with_ref ? (size_t)K * J * P + (size_t)len : 0) + (size_t)G * P + (w ? (size_t)G : 0) +
                                           (x ? (size_t)D : 0) + 16 + N * rs + small_ws + N * K * J * P) +
                         sizeof(int32_t) * 2 * N * K;
-  const size_t per_row = sizeof(double) * (N + 2 + (size_t)nq + NP);
-  const size_t budget = budget_of(max_workspace_bytes);
-  if (budget < shared + (len > 0 ? per_row : 0))
-    return fail(fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + (len > 0 ? per_row : 0)) + " bytes one row needs (" +
-                std::to_string(shared) + " shared by all rows + " + std::to_string(len > 0 ? per_row : 0) + " per row)");
-  const int64_t chunk = len > 0 ? std::min<int64_t>(std::min<int64_t>(len, (int64_t)((budget - shared) / per_row)), 1 << 30) : 1;
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), shared, len > 0 ? r.row_bytes() : 0, len, 1 << 30, "row", &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
-  double *d_E = nullptr, *d_w = nullptr, *d_x = nullptr, *d_ref = nullptr, *d_probs = nullptr, *d_small = nullptr, *d_sres = nullptr,
-         *d_v = nullptr;
+  double *d_E = nullptr, *d_w = nullptr, *d_x = nullptr, *d_ref = nullptr, *d_probs = nullptr, *d_small = nullptr, *d_sres = nullptr;
   int32_t *d_perm = nullptr, *d_status = nullptr;
   Timer gram, solve, values;
   HIPCHK(b.timers({&gram, &solve, &values}));
@@ -1114,29 +1120,24 @@ extern "C" int bfmmm_chain_cluster_eigen(bfmmm_handle* h, const int32_t* perm, c
   }
   HIPCHK(b.put(h, &d_perm, perm, N * K));
   HIPCHK(b.get(&d_status, N * K));
-  HIPCHK(b.get(&d_probs, 16));
-  if (nq) HIPCHK(copy_sync(h, d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice));
+  HIPCHK(probs_put(b, h, probs, nq, &d_probs));
+  r.probs = sm.probs = d_probs;
   HIPCHK(b.get(&f.Q, (size_t)P * P));
   HIPCHK(b.get(&d_small, N * rs));
   HIPCHK(b.get(&d_sres, small_ws));
   HIPCHK(b.get(&f.b, N * K * J * P));
-  if (len > 0) HIPCHK(b.get(&d_v, per_row / sizeof(double) * (size_t)chunk));
+  if (len > 0) HIPCHK(r.alloc(b, chunk));
   f.E = d_E; f.w = d_w; f.x = d_x; f.ref = d_ref; f.perm = d_perm; f.status = d_status;
   f.lam = d_small; f.pve = d_small + N * KM; f.tot = d_small + 2 * N * KM;
-  double* d_smean = d_sres;
-  double* d_ssd = d_smean + rs;
-  double* d_sq = d_ssd + rs;
-  double* d_sw = d_sq + rs * (size_t)nq;
-  double* d_diag = d_sw + rs * NP;
-  double* d_tier = d_diag + 7 * KM;
+  sm.place(d_small, d_sres, (int64_t)rs);
+  sv.place(d_small, d_sres + rs * sm.res_doubles(), (int64_t)KM);
   std::vector<int32_t> st_host(N * K);
-  std::vector<double> sm(2 * rs);
+  std::vector<double> smh(2 * rs);      // mean and sd of the small rows
   // the solve and the small rows
   int rc = for_chunks(ck, 1, 1, [&](int64_t, int) {
     std::string err = timed(gram, h->st, [&] { return launch_ceig_gram(c, f, h->st); });
     if (err.empty()) err = timed(solve, h->st, [&] { return launch_ceig_solve(c, f, h->st); });
-    if (err.empty() && copy_sync(h, st_host.data(), d_status, sizeof(int32_t) * N * K, hipMemcpyDeviceToHost) != hipSuccess)
-      err = "kernel or copy back failed";
+    if (err.empty()) err = Back{h, 0, 1}(st_host.data(), d_status, N * K).done();
     if (!err.empty()) return err;
     collect(h, gram, PT_CEIG_GRAM);
     collect(h, solve, PT_CEIG);
@@ -1148,40 +1149,28 @@ extern "C" int bfmmm_chain_cluster_eigen(bfmmm_handle* h, const int32_t* perm, c
       mx = std::max(mx, st_host[o] & 0xff);
     }
     *max_sweeps = mx;
-    err = launch_bands_moments(d_small, (int)N, (long long)rs, d_smean, d_ssd, h->st);
-    if (err.empty() && nq) err = launch_bands_quantiles(d_small, (int)N, (long long)rs, d_sw, d_probs, nq, d_sq, h->st);
-    if (err.empty()) err = diag_launch(d_small, (long long)KM, C, S, d_diag, (long long)KM, d_tier, (long long)KM, h->st);
-    const size_t q1 = sizeof(double) * KM * (size_t)nq;
-    if (err.empty() &&
-        ((nq && (hipMemcpyAsync(val_quant, d_sq, q1, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-                 hipMemcpyAsync(pve_quant, d_sq + KM * nq, q1, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-                 hipMemcpyAsync(tot_quant, d_sq + 2 * KM * nq, sizeof(double) * (size_t)K * nq, hipMemcpyDeviceToHost, h->st) != hipSuccess)) ||
-         (val_trace && hipMemcpyAsync(val_trace, d_small, sizeof(double) * N * KM, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         hipMemcpyAsync(val_diag, d_diag, sizeof(double) * 7 * KM, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-         copy_sync(h, sm.data(), d_smean, sizeof(double) * 2 * rs, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
+    err = sm.reduce((long long)rs);
+    if (err.empty()) err = sv.reduce((long long)KM);
+    // the results lie statistic by statistic over all rs rows: lambda's KM rows, pve's KM, total's K.  Mean and sd of lambda are
+    // among the seven statistics.
+    const size_t q1 = KM * (size_t)nq;
+    double* const nul = nullptr;
+    if (err.empty())
+      err = Back{h, 0, 1}(nq ? val_quant : nul, sm.q, q1)(nq ? pve_quant : nul, sm.q + q1, q1)(nq ? tot_quant : nul, sm.q + 2 * q1, (size_t)K * nq)(
+                val_trace, d_small, N * KM)(val_diag, sv.out7, 7 * KM)(smh.data(), sm.mean, 2 * rs).done();
     if (!err.empty()) return err;
-    std::copy(sm.begin() + KM, sm.begin() + 2 * KM, pve_mean);
-    std::copy(sm.begin() + 2 * KM, sm.begin() + rs, tot_mean);
-    std::copy(sm.begin() + rs + KM, sm.begin() + rs + 2 * KM, pve_sd);
-    std::copy(sm.begin() + rs + 2 * KM, sm.begin() + 2 * rs, tot_sd);
+    std::copy(smh.begin() + KM, smh.begin() + 2 * KM, pve_mean);
+    std::copy(smh.begin() + 2 * KM, smh.begin() + rs, tot_mean);
+    std::copy(smh.begin() + rs + KM, smh.begin() + rs + 2 * KM, pve_sd);
+    std::copy(smh.begin() + rs + 2 * KM, smh.begin() + 2 * rs, tot_sd);
     return err;
   });
   if (rc || len == 0) return rc;
-  double* d_mean = d_v + (size_t)chunk * N;
-  double* d_sd = d_mean + (size_t)chunk;
-  double* d_q = d_sd + (size_t)chunk;
-  double* d_ws = d_q + (size_t)nq * (size_t)chunk;
+  double* const outs[2] = {fn_mean, fn_sd};
   return for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
-    std::string err = timed(values, h->st, [&] { return launch_ceig_values(c, f, r0, rows, d_v, h->st); });
-    if (err.empty()) err = launch_bands_moments(d_v, (int)N, rows, d_mean, d_sd, h->st);
-    if (err.empty() && nq) err = launch_bands_quantiles(d_v, (int)N, rows, d_ws, d_probs, nq, d_q, h->st);
-    if (err.empty() &&
-        ((nq && hipMemcpyAsync(fn_quant + (size_t)r0 * nq, d_q, sizeof(double) * (size_t)rows * nq, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         (fn_trace && hipMemcpyAsync(fn_trace + (size_t)r0 * N, d_v, sizeof(double) * (size_t)rows * N, hipMemcpyDeviceToHost, h->st) != hipSuccess) ||
-         hipMemcpyAsync(fn_mean + r0, d_mean, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-         copy_sync(h, fn_sd + r0, d_sd, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess))
-      err = "kernel or copy back failed";
+    std::string err = timed(values, h->st, [&] { return launch_ceig_values(c, f, r0, rows, r.x, h->st); });
+    if (err.empty()) err = r.reduce(rows);
+    if (err.empty()) err = r.to_host(r0, rows, outs, fn_quant, fn_trace);
     if (err.empty()) collect(h, values, PT_CEIG_VALUES);
     return err;
   });
@@ -1252,10 +1241,11 @@ extern "C" int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const doubl
   const size_t budget = budget_of(max_workspace_bytes);
   if (samples && budget < shared + per_curve)
     return fail(fn + ": 'samples' of one curve (n_chains x n_slots x n_stages x n_samples x K doubles) with the rest need " +
-                std::to_string(shared + per_curve) + " bytes, above 'max_workspace_bytes' = " + std::to_string(budget) + " (" + std::to_string(shared) +
-                " shared by all curves + " + std::to_string(per_curve) + " per curve)");
+                std::to_string(shared + per_curve) + " bytes, above 'max_workspace_bytes' = " + std::to_string(budget) + " " +
+                SlotCheck::plan_text(shared, per_curve, "curve"));
   int64_t chunk = 0;
-  if (ck.curve_chunk(budget, shared, per_curve, n_new, (int64_t)std::max<size_t>(1, per_curve / sizeof(double) / std::max<size_t>(N, 1)), &chunk)) return 1;
+  const int64_t cells = (int64_t)std::max<size_t>(1, per_curve / sizeof(double) / std::max<size_t>(N, 1));
+  if (ck.units(budget, shared, per_curve, n_new, cells_cap(cells), "curve", &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
   reset_timers(h, PT_PREDICT_STATS, PT_PREDICT);
   CallBufs b;
@@ -1331,14 +1321,10 @@ extern "C" int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const doubl
     std::string err = timed(kernel, h->st, [&] { return launch_predict(c, f, (int)r0, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_prop, d_smp, h->st); });
     if (err.empty())
       err = timed(pool, h->st, [&] { return launch_predict_pool(K, (long long)N, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_lpd, d_zm, d_zsd, d_emean, d_emin, h->st); });
-    auto back = [&](double* dst, const double* src, size_t per_row) {
-      return !dst || hipMemcpyAsync(dst + (size_t)r0 * per_row, src, sizeof(double) * (size_t)rows * per_row, hipMemcpyDeviceToHost, h->st) == hipSuccess;
-    };
-    if (err.empty() &&
-        !(back(lpd_trace, d_lpd_t, N) && back(ess_trace, d_ess_t, N) && back(z_trace, d_m_t, NK) && back(prop_trace, d_prop, NK * R) &&
-          back(samples, d_smp, NK * R * J) && back(lpd, d_lpd, 1) && back(ess_mean, d_emean, 1) && back(ess_min, d_emin, 1) &&
-          back(z_mean, d_zm, K) && back(z_sd, d_zsd, K) && hipStreamSynchronize(h->st) == hipSuccess && hipGetLastError() == hipSuccess))
-      err = "kernel or copy back failed";
+    if (err.empty())
+      err = Back{h, r0, rows}(lpd_trace, d_lpd_t, N)(ess_trace, d_ess_t, N)(z_trace, d_m_t, NK)(prop_trace, d_prop, NK * R)(samples, d_smp, NK * R * J)(
+                lpd, d_lpd, 1)(ess_mean, d_emean, 1)(ess_min, d_emin, 1)(z_mean, d_zm, K)(z_sd, d_zsd, K).done();
+    if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
     if (!err.empty()) return err;
     collect(h, kernel, PT_PREDICT);
     collect(h, pool, PT_PREDICT);

@@ -33,6 +33,14 @@ def _dp(a):
     return a.ctypes.data_as(_lib.c_double_p)
 
 
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _probs_arg(probs):
+    return np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+
+
 def default_config(**kw):
     cfg = _lib.BfmmmConfig()
     _lib.load().bfmmm_config_defaults(C.byref(cfg))
@@ -130,12 +138,28 @@ class Sampler:
     def _slots(self, first_slot, n_slots):
         return self.T - int(first_slot) if n_slots is None else int(n_slots)
 
+    def _basis_arg(self, E, name):
+        """E as a contiguous G x P matrix of rows in the sampler's basis"""
+        Em = np.ascontiguousarray(E, dtype=np.float64)
+        if Em.ndim != 2 or Em.shape[1] != self.P:
+            raise ValueError(f"{name} must be a G x {self.P} matrix in the sampler's basis")
+        return Em
+
+    def _x_arg(self, x):
+        """one covariate setting of D entries, or None"""
+        if x is None:
+            return None
+        xv = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if self.D > 0 and xv.size != self.D:
+            raise ValueError(f"x must have {self.D} entries, one per covariate")
+        return xv
+
     def _curve_list(self, curves):
         """(the index array, which must outlive the call; its pointer; the curves of the result), all n where curves is None"""
         if curves is None:
             return None, None, self.n
         idx = np.ascontiguousarray(curves, dtype=np.int32).reshape(-1)
-        return idx, idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size
+        return idx, _ip(idx), idx.size
 
     def set_state(self, **kw):
         for name, v in kw.items():
@@ -224,9 +248,7 @@ class Sampler:
         if isinstance(w, str):
             raise ValueError("which must be 'mean' or 'fit'")
         w = int(w)
-        Em = np.ascontiguousarray(E, dtype=np.float64)
-        if Em.ndim != 2 or Em.shape[1] != self.P:
-            raise ValueError(f"E must be a G x {self.P} matrix in the sampler's basis")
+        Em = self._basis_arg(E, "E")
         S = self._slots(first_slot, n_slots)
         idx, pc, m = self._curve_list(curves)
         return w, Em, S, idx, pc, m
@@ -247,7 +269,7 @@ class Sampler:
         without the values leaving it (bfmmm_chain_curve_bands).  Quantiles follow arma::quantile's rule, as the single-chain
         credible bands do.  Returns {"mean": (m, G), "sd": (m, G), "quantiles": (m, G, nq), "probs": (nq,)}."""
         w, Em, S, idx, pc, m = self._fit_args(E, which, curves, first_slot, n_slots)
-        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        pr = _probs_arg(probs)
         G = Em.shape[0]
         mean, sd, qs = np.zeros((m, G)), np.zeros((m, G)), np.zeros((m, G, pr.size))
         _lib.check(self.lib.bfmmm_chain_curve_bands(self.h, w, _dp(Em), G, pc, m, int(first_slot), S, _dp(pr), pr.size,
@@ -348,7 +370,7 @@ class Sampler:
             raise ValueError(f"pivot must be None, (chain, slot) or an array of shape ({self.n}, {self.K})")
         perm = np.zeros((self.n_chains, max(S, 0), self.K), dtype=np.int32)
         score = np.zeros((self.n_chains, max(S, 0)))
-        _lib.check(self.lib.bfmmm_chain_align(self.h, _dp(Zref), int(first_slot), S, perm.ctypes.data_as(C.POINTER(C.c_int32)),
+        _lib.check(self.lib.bfmmm_chain_align(self.h, _dp(Zref), int(first_slot), S, _ip(perm),
                                               _dp(score), perm.size))
         chain_perm = np.zeros((self.n_chains, self.K), dtype=np.int32)
         share = np.zeros(self.n_chains)
@@ -372,12 +394,12 @@ class Sampler:
         arma::quantile's rule, and "probs"."""
         S = self._slots(first_slot, n_slots)
         p = self._perm_arg(perm, S)
-        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        pr = _probs_arg(probs)
         shp = self._draw_shape(name) if name in DRAW_DIMS else (1,)
         cnt = int(np.prod(shp, dtype=np.int64))
         outs = [np.zeros(cnt) for _ in range(7)]
         qs = np.zeros((cnt, pr.size))
-        _lib.check(self.lib.bfmmm_chain_aligned_summary(self.h, name.encode(), p.ctypes.data_as(C.POINTER(C.c_int32)), int(first_slot), S,
+        _lib.check(self.lib.bfmmm_chain_aligned_summary(self.h, name.encode(), _ip(p), int(first_slot), S,
                                                         _dp(pr) if pr.size else None, pr.size, int(max_workspace_bytes),
                                                         *[_dp(o) for o in outs], _dp(qs) if pr.size else None, cnt))
         out = {k: o.reshape(shp, order="F") for k, o in zip(STAT_NAMES, outs)}
@@ -390,15 +412,13 @@ class Sampler:
         as in `curve_fit`) with the labels aligned by perm (`align`'s "perm" of the same slots) and the chains pooled, on the
         device (bfmmm_chain_cluster_mean_bands); the reference's FMeanCI without rescale / trans_mats.  With
         covariates set: the mean function at x = 0.  Returns {"mean": (K, G), "sd": (K, G), "quantiles": (K, G, nq), "probs"}."""
-        Em = np.ascontiguousarray(E, dtype=np.float64)
-        if Em.ndim != 2 or Em.shape[1] != self.P:
-            raise ValueError(f"E must be a G x {self.P} matrix in the sampler's basis")
+        Em = self._basis_arg(E, "E")
         S = self._slots(first_slot, n_slots)
         p = self._perm_arg(perm, S)
-        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        pr = _probs_arg(probs)
         G, K = Em.shape[0], self.K
         mean, sd, qs = np.zeros(K * G), np.zeros(K * G), np.zeros((K * G, pr.size))
-        _lib.check(self.lib.bfmmm_chain_cluster_mean_bands(self.h, p.ctypes.data_as(C.POINTER(C.c_int32)), _dp(Em), G, int(first_slot), S,
+        _lib.check(self.lib.bfmmm_chain_cluster_mean_bands(self.h, _ip(p), _dp(Em), G, int(first_slot), S,
                                                            _dp(pr) if pr.size else None, pr.size, int(max_workspace_bytes), _dp(mean),
                                                            _dp(sd), _dp(qs) if pr.size else None, K * G))
         return {"mean": mean.reshape((K, G), order="F"), "sd": sd.reshape((K, G), order="F"),
@@ -418,26 +438,16 @@ class Sampler:
         Returns {"mean", "sd": (m, G1, G2), "quantiles": (m, G1, G2, nq), "probs", "pairs": (m, 2)}, with simultaneous also
         {"crit": (m,), "lower", "upper": (m, G1, G2), "alpha"}, with trace also {"trace": (m, G1, G2, N)}; with diagonal the G2
         axis is dropped."""
-        def basis(B, name):
-            Bm = np.ascontiguousarray(B, dtype=np.float64)
-            if Bm.ndim != 2 or Bm.shape[1] != self.P:
-                raise ValueError(f"{name} must be a G x {self.P} matrix in the sampler's basis")
-            return Bm
-        ip = C.POINTER(C.c_int32)
-        E1m = basis(E, "E")
-        E2m = None if E2 is None else basis(E2, "E2")
+        E1m = self._basis_arg(E, "E")
+        E2m = None if E2 is None else self._basis_arg(E2, "E2")
         S = self._slots(first_slot, n_slots)
         p = self._perm_arg(perm, S)
-        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        pr = _probs_arg(probs)
         if pairs is None:
             pl = np.array([(k, l) for k in range(self.K) for l in range(k, self.K)], dtype=np.int32).reshape(-1, 2)
         else:
             pl = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        xv = None
-        if x is not None:
-            xv = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-            if self.D > 0 and xv.size != self.D:
-                raise ValueError(f"x must have {self.D} entries, one per covariate")
+        xv = self._x_arg(x)
         m, G1 = pl.shape[0], E1m.shape[0]
         G2 = G1 if E2m is None else E2m.shape[0]
         N = self.n_chains * max(S, 0)
@@ -450,8 +460,8 @@ class Sampler:
             out["trace"] = np.zeros((m,) + cell + (N,))
         band = [_dp(out[k]) if simultaneous is not None else None for k in ("crit", "lower", "upper")]
         _lib.check(self.lib.bfmmm_chain_cluster_cov_bands(
-            self.h, p.ctypes.data_as(ip), _dp(E1m), G1, None if E2m is None else _dp(E2m), G2, int(bool(diagonal)),
-            None if pairs is None else pl.ctypes.data_as(ip), m if pairs is not None else 0, None if xv is None else _dp(xv),
+            self.h, _ip(p), _dp(E1m), G1, None if E2m is None else _dp(E2m), G2, int(bool(diagonal)),
+            None if pairs is None else _ip(pl), m if pairs is not None else 0, None if xv is None else _dp(xv),
             int(first_slot), S, _dp(pr) if pr.size else None, pr.size, float(simultaneous) if simultaneous is not None else 0.0,
             int(max_workspace_bytes), _dp(out["mean"]), _dp(out["sd"]), _dp(out["quantiles"]) if pr.size else None, *band,
             _dp(out["trace"]) if trace else None, out["mean"].size))
@@ -474,12 +484,10 @@ class Sampler:
         "pve": {"mean", "sd": (K, M), "quantiles": (K, M, nq)}, "total": {"mean", "sd": (K,), "quantiles": (K, nq)},
         "functions": {"mean", "sd": (K, J, G), "quantiles": (K, J, G, nq)}, "ref": (K, J, G) or None, "max_sweeps", "probs"},
         with trace also {"values_trace": (K, M, N), "functions_trace": (K, J, G, N)}, N = C S chain-major."""
-        Em = np.ascontiguousarray(E, dtype=np.float64)
-        if Em.ndim != 2 or Em.shape[1] != self.P:
-            raise ValueError(f"E must be a G x {self.P} matrix in the sampler's basis")
+        Em = self._basis_arg(E, "E")
         S = self._slots(first_slot, n_slots)
         p = self._perm_arg(perm, S)
-        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        pr = _probs_arg(probs)
         G, K = Em.shape[0], self.K
         M = self.M
         J = M if n_functions is None else int(n_functions)
@@ -488,11 +496,7 @@ class Sampler:
             wv = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
             if wv.size != G:
                 raise ValueError(f"weights must have {G} entries, one per row of E")
-        xv = None
-        if x is not None:
-            xv = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-            if self.D > 0 and xv.size != self.D:
-                raise ValueError(f"x must have {self.D} entries, one per covariate")
+        xv = self._x_arg(x)
         rv = None
         if isinstance(ref, str):
             if ref != "mean":
@@ -519,7 +523,7 @@ class Sampler:
         q = (lambda a: _dp(a)) if nqs else (lambda a: None)
         fnp = (lambda a: _dp(a)) if Jn > 0 else (lambda a: None)
         _lib.check(self.lib.bfmmm_chain_cluster_eigen(
-            self.h, p.ctypes.data_as(C.POINTER(C.c_int32)), _dp(Em), G, None if wv is None else _dp(wv), None if xv is None else _dp(xv),
+            self.h, _ip(p), _dp(Em), G, None if wv is None else _dp(wv), None if xv is None else _dp(xv),
             J, None if rv is None else _dp(rv), int(first_slot), S, _dp(pr) if nqs else None, nqs, int(max_workspace_bytes),
             _dp(vd), q(out["values"]["quantiles"]), _dp(out["pve"]["mean"]), _dp(out["pve"]["sd"]), q(out["pve"]["quantiles"]),
             _dp(out["total"]["mean"]), _dp(out["total"]["sd"]), q(out["total"]["quantiles"]), fnp(out["functions"]["mean"]),
@@ -550,7 +554,6 @@ class Sampler:
         return_samples adds "samples": (m, C, S, R, J, K), for small shapes."""
         S = self._slots(first_slot, n_slots)
         Cn, K, J, R = self.n_chains, self.K, int(n_samples), int(n_stages)
-        ip = C.POINTER(C.c_int32)
         y = t = B = off = None
         if self.offsets is None:
             y = np.asfortranarray(Y_new, dtype=np.float64)
@@ -597,7 +600,7 @@ class Sampler:
         _lib.check(self.lib.bfmmm_chain_predict(
             self.h, None if y is None else _dp(y), None if t is None else _dp(t), None if B is None else _dp(B),
             None if off is None else off.ctypes.data_as(_lib.c_int64_p), m, None if Xm is None else _dp(Xm),
-            None if p is None else p.ctypes.data_as(ip), int(first_slot), S, J, R, int(seed), None if zs is None else _dp(zs),
+            None if p is None else _ip(p), int(first_slot), S, J, R, int(seed), None if zs is None else _dp(zs),
             int(max_workspace_bytes), _dp(out["lpd"]), _dp(out["Z_mean"]), _dp(out["Z_sd"]), _dp(out["ess_mean"]), _dp(out["ess_min"]),
             opt("lpd_trace"), opt("Z_trace"), opt("ess_trace"), opt("proposal"), opt("samples"), m))
         out.update(tr)
@@ -633,13 +636,8 @@ class Sampler:
         (default: all n).  diagonal: only g = h, the curve's variance function (E2 must be None).  per_chain: also each chain's
         own mean.  Returns {"mean": (m, G1, G2), "sd": (m, G1, G2) if sd, "chain_mean": (m, C, G1, G2) if per_chain}; with
         diagonal the shapes are (m, G1) and (m, C, G1)."""
-        def basis(B, name):
-            Bm = np.ascontiguousarray(B, dtype=np.float64)
-            if Bm.ndim != 2 or Bm.shape[1] != self.P:
-                raise ValueError(f"{name} must be a G x {self.P} matrix in the sampler's basis")
-            return Bm
-        E1m = basis(E, "E")
-        E2m = None if E2 is None else basis(E2, "E2")
+        E1m = self._basis_arg(E, "E")
+        E2m = None if E2 is None else self._basis_arg(E2, "E2")
         S = self._slots(first_slot, n_slots)
         idx, pc, m = self._curve_list(curves)
         G1 = E1m.shape[0]

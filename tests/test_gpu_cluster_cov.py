@@ -7,7 +7,7 @@ byte; mean and sd, for which no public entry runs k_bands_moments on a host tabl
 values (N 2^-52 mean|v|, relative 4 N 2^-52); crit, lower and upper are tests/curve_sim_ref.py's rule per pair on the trace with
 the device's own mean and sd, byte for byte.  Then what the layout promises bit for bit (symmetry, transposition, the diagonal,
 pair selection, chunking, repeatability), one and two draws, the empty pair list, untouched state, refusals and timers.  A row
-above 8192 draws is left to tests/test_gpu_ci.py: the long tier is the unchanged k_bands_quantiles_big."""
+above 8192 draws: tests/test_gpu_long_rows.py."""
 import ctypes as C
 import re
 
