@@ -2,7 +2,8 @@
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
 // per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it, the cluster
-// covariance surfaces with their bands and their eigenvalues and eigenfunctions, and the prediction of held-out curves.
+// covariance surfaces with their bands and their eigenvalues and eigenfunctions, and the prediction of held-out curves with
+// their fitted functions.
 // An entry point is its argument checks (SlotCheck: slots, curve selection, the grid pair, x, alpha, probs and `units`, the one
 // budget rule), its workspace and the event pairs that time its launches into the handle's PT_* timers (CallBufs owns both) and
 // one for_chunks.  What several of them do is written once: `once` for a launch that runs once per call (the projections), Back
@@ -228,6 +229,7 @@ struct Back {
     return *this;
   }
   std::string done() const { return ok && hipStreamSynchronize(h->st) == hipSuccess ? "" : kBackFailed; }
+  std::string queued() const { return ok ? "" : kBackFailed; }      // more copies of the chunk follow: their done() synchronises
 };
 
 // 16 doubles on the device (owned by b) with the call's nq probabilities in front, and `extra` more behind them
@@ -1179,19 +1181,40 @@ extern "C" int bfmmm_chain_cluster_eigen(bfmmm_handle* h, const int32_t* perm, c
 // ---- prediction of held-out curves from the chain slots (kernels_predict.hip) -----------------------------------
 // The records of all new curves once per call (launch_stats_* as they are; a from-basis handle forms them on the host as its
 // creation does), then per chunk of consecutive new curves k_predict into the chunk's traces and k_predict_pool over them.
-extern "C" int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const double* t, const double* B, const int64_t* offsets,
-                                   int n_new, const double* X, const int32_t* perm, int first_slot, int n_slots, int n_samples,
-                                   int n_stages, uint64_t seed, const double* zs, int64_t max_workspace_bytes,
-                                   double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min,
-                                   double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace, double* samples,
-                                   int64_t capacity) {
-  const SlotCheck ck{"bfmmm_chain_predict", h, first_slot, n_slots};
+// bfmmm_chain_predict_fit (kernels_predict_fit.hip) is the same call with a FitAsk: every check under its own name,
+// k_predict_fit in k_predict's place, and behind the pooling the moments of the fitted function and the quantiles of its paths.
+namespace {
+struct FitAsk {
+  const double* E;
+  int G, noise;
+  const double* probs;
+  int nq;
+  double *fit_mean, *fit_sd, *fit_q, *mean_trace, *var_trace, *path_trace;
+  int32_t* path_index;
+  double *path_u, *path_xi;
+};
+
+int predict_call(const char* name, const FitAsk* fit, bfmmm_handle* h, const double* y, const double* t, const double* B,
+                 const int64_t* offsets, int n_new, const double* X, const int32_t* perm, int first_slot, int n_slots, int n_samples,
+                 int n_stages, uint64_t seed, const double* zs, int64_t max_workspace_bytes, double* lpd, double* z_mean, double* z_sd,
+                 double* ess_mean, double* ess_min, double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace,
+                 double* samples, int64_t capacity) {
+  const SlotCheck ck{name, h, first_slot, n_slots};
   const std::string& fn = ck.fn;
   if (ck.ptrs({{"h", h}})) return 1;
   if (n_new < 0) return fail(fn + ": 'n_new' must not be negative");
   if (n_new == 0) return 0;
   if (ck.ptrs({{"lpd", lpd}, {"z_mean", z_mean}, {"z_sd", z_sd}, {"ess_mean", ess_mean}, {"ess_min", ess_min}})) return 1;
   const Ctx& c = h->c;
+  const int G = fit ? fit->G : 0, nq = fit ? fit->nq : 0;
+  if (fit) {
+    if (ck.ptrs({{"E", fit->E}, {"fit_mean", fit->fit_mean}, {"fit_sd", fit->fit_sd}})) return 1;
+    if (G < 1) return fail(fn + ": 'G' must be at least 1");
+    for (int64_t e = 0; e < (int64_t)G * c.d.P; ++e)
+      if (!std::isfinite(fit->E[e])) return fail(fn + ": 'E'[" + std::to_string(e / c.d.P) + ", " + std::to_string(e % c.d.P) + "] is not finite");
+    if (nq > 0 && ck.ptrs({{"probs", fit->probs}, {"fit_q", fit->fit_q}})) return 1;
+    if (ck.probs_list(fit->probs, nq, 0, fit->fit_q)) return 1;
+  }
   const Dims& d = c.d;
   const int K = d.K, P = d.P, D = d.D, J = n_samples, R = n_stages;
   const bool mv = d.mv != 0, from_basis = !h->B_host.empty();
@@ -1227,17 +1250,27 @@ extern "C" int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const doubl
   if (perm && perm_check(ck, perm)) return 1;
   PredictCall f;
   f.n_new = n_new; f.J = J; f.R = R; f.first_slot = first_slot; f.n_slots = n_slots; f.seed = seed;
-  const std::string bad = predict_check(c, f, nullptr);
+  PredictFitCall ff;
+  if (fit) { ff.G = G; ff.noise = fit->noise; }
+  ff.p = f;
+  const std::string bad = fit ? predict_fit_check(c, ff, nullptr) : predict_check(c, f, nullptr);
   if (!bad.empty()) return fail(fn + ": " + bad);
   const size_t N = (size_t)ck.CS();
+  const int Mn = d.M;
+  // the fit of a curve: mu_t, v_t and the paths (3 G N), U and j* (N + N / 2), xi (N M), mean, sd and quantiles (G (2 + nq)) and,
+  // for rows too long for the LDS sort, their workspace
+  const SortWs sws((long long)N, fit && nq > 0);
+  const size_t fit_curve = fit ? (size_t)G * (3 * N + 2 + (size_t)nq + sws.NP) + N + (N + 1) / 2 + N * (size_t)Mn : 0;
+  const size_t fit_shared = fit ? sizeof(double) * ((size_t)G * P + 16) : 0;
   const int64_t n_obs = mv ? (int64_t)n_new * P : offsets[n_new];
   // shared by all curves: the data (y, and t and the offsets of a spline sampler), the records and counts, X, perm, zs; a curve: its
   // traces (lpd, ess, m, q, the proposals and the samples where asked for) and its five pooled results
   const size_t shared = sizeof(double) * ((from_basis ? 0 : (size_t)n_obs * (mv ? 1 : 2)) + (size_t)n_new * d.LREC + (X ? (size_t)n_new * D : 0) +
                                           (zs ? N * (size_t)J * K : 0) + 2) +
                         sizeof(int64_t) * (!mv && !from_basis ? (size_t)n_new + 1 : 0) + sizeof(int32_t) * (((size_t)n_new + 1) & ~(size_t)1) +
-                        (perm ? sizeof(int32_t) * ((N * K + 1) & ~(size_t)1) : 0);
-  const size_t per_curve = sizeof(double) * (N * (2 + 2 * (size_t)K + (prop_trace ? (size_t)R * K : 0) + (samples ? (size_t)R * J * K : 0)) + 3 + 2 * (size_t)K);
+                        (perm ? sizeof(int32_t) * ((N * K + 1) & ~(size_t)1) : 0) + fit_shared;
+  const size_t per_curve = sizeof(double) * (N * (2 + 2 * (size_t)K + (prop_trace ? (size_t)R * K : 0) + (samples ? (size_t)R * J * K : 0)) + 3 + 2 * (size_t)K +
+                                             fit_curve);
   const size_t budget = budget_of(max_workspace_bytes);
   if (samples && budget < shared + per_curve)
     return fail(fn + ": 'samples' of one curve (n_chains x n_slots x n_stages x n_samples x K doubles) with the rest need " +
@@ -1247,15 +1280,17 @@ extern "C" int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const doubl
   const int64_t cells = (int64_t)std::max<size_t>(1, per_curve / sizeof(double) / std::max<size_t>(N, 1));
   if (ck.units(budget, shared, per_curve, n_new, cells_cap(cells), "curve", &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
-  reset_timers(h, PT_PREDICT_STATS, PT_PREDICT);
+  const int pt = fit ? PT_PREDICT_FIT : PT_PREDICT;
+  reset_timers(h, PT_PREDICT_STATS, PT_PREDICT_STATS);
+  reset_timers(h, pt, pt);
   CallBufs b;
   double *d_y = nullptr, *d_t = nullptr, *d_rec = nullptr, *d_X = nullptr, *d_zs = nullptr, *d_tr = nullptr, *d_prop = nullptr, *d_smp = nullptr,
          *d_out = nullptr;
   int64_t* d_off = nullptr;
   int *d_ni = nullptr, *d_err = nullptr;
   int32_t* d_perm = nullptr;
-  Timer stats, kernel, pool;
-  HIPCHK(b.timers({&stats, &kernel, &pool}));
+  Timer stats, kernel, pool, fpool, quant;
+  HIPCHK(b.timers({&stats, &kernel, &pool, &fpool, &quant}));
   HIPCHK(b.get(&d_rec, (size_t)n_new * d.LREC));
   HIPCHK(b.get(&d_ni, (size_t)n_new));
   if (from_basis) {
@@ -1317,8 +1352,50 @@ extern "C" int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const doubl
   double* d_emin = d_emean + chunk;
   double* d_zm = d_emin + chunk;
   double* d_zsd = d_zm + (size_t)chunk * K;
+  // the fit's buffers of a chunk: mu_t, v_t, paths; U, xi; mean, sd, quantiles, sort workspace; j*
+  double *d_E = nullptr, *d_probs = nullptr, *d_fit = nullptr, *d_fres = nullptr;
+  int32_t* d_pidx = nullptr;
+  const size_t GN = (size_t)G * N;
+  if (fit) {
+    HIPCHK(b.put(h, &d_E, fit->E, (size_t)G * P));
+    HIPCHK(probs_put(b, h, fit->probs, nq, &d_probs));
+    HIPCHK(b.get(&d_fit, (size_t)chunk * (3 * GN + N + N * (size_t)Mn)));
+    HIPCHK(b.get(&d_fres, (size_t)chunk * G * (2 + (size_t)nq + sws.NP)));
+    HIPCHK(b.get(&d_pidx, (size_t)chunk * N));
+    ff.p = f; ff.E = d_E;
+  }
+  double *d_mu_t = nullptr, *d_var_t = nullptr, *d_path_t = nullptr, *d_pu = nullptr, *d_pxi = nullptr, *d_fmean = nullptr, *d_fsd = nullptr,
+         *d_fq = nullptr, *d_fw = nullptr;
+  if (fit) {
+    d_mu_t = d_fit;
+    d_var_t = d_mu_t + (size_t)chunk * GN;
+    d_path_t = d_var_t + (size_t)chunk * GN;
+    d_pu = d_path_t + (size_t)chunk * GN;
+    d_pxi = d_pu + (size_t)chunk * N;
+    d_fmean = d_fres;
+    d_fsd = d_fmean + (size_t)chunk * G;
+    d_fq = d_fsd + (size_t)chunk * G;
+    d_fw = d_fq + (size_t)chunk * G * nq;
+  }
   return for_chunks(ck, n_new, chunk, [&](int64_t r0, int rows) {
-    std::string err = timed(kernel, h->st, [&] { return launch_predict(c, f, (int)r0, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_prop, d_smp, h->st); });
+    std::string err = timed(kernel, h->st, [&] {
+      return fit ? launch_predict_fit(c, ff, (int)r0, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_prop, d_smp, d_mu_t, d_var_t, d_path_t, d_pidx, d_pu,
+                                      d_pxi, h->st)
+                 : launch_predict(c, f, (int)r0, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_prop, d_smp, h->st);
+    });
+    if (err.empty() && fit) {
+      // (the pooled rows of the chunk are consecutive from 0 in every buffer: launch_predict_fit wrote rows of G N)
+      err = timed(fpool, h->st, [&] { return launch_predict_fit_pool((long long)N, (long long)rows * G, d_mu_t, d_var_t, d_fmean, d_fsd, h->st); });
+      if (err.empty() && nq)
+        err = timed(quant, h->st, [&] { return launch_bands_quantiles(d_path_t, (int)N, (long long)rows * G, d_fw, d_probs, nq, d_fq, h->st); });
+      if (err.empty())
+        err = Back{h, r0, rows, true}(fit->mean_trace, d_mu_t, GN)(fit->var_trace, d_var_t, GN)(fit->path_trace, d_path_t, GN)(
+                  fit->path_u, d_pu, N)(fit->path_xi, d_pxi, N * (size_t)Mn)(fit->fit_mean, d_fmean, (size_t)G)(fit->fit_sd, d_fsd, (size_t)G)(
+                  nq ? fit->fit_q : nullptr, d_fq, (size_t)G * nq).queued();
+      if (err.empty() && fit->path_index &&
+          hipMemcpyAsync(fit->path_index + (size_t)r0 * N, d_pidx, sizeof(int32_t) * (size_t)rows * N, hipMemcpyDeviceToHost, h->st) != hipSuccess)
+        err = kBackFailed;
+    }
     if (err.empty())
       err = timed(pool, h->st, [&] { return launch_predict_pool(K, (long long)N, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_lpd, d_zm, d_zsd, d_emean, d_emin, h->st); });
     if (err.empty())
@@ -1326,8 +1403,35 @@ extern "C" int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const doubl
                 lpd, d_lpd, 1)(ess_mean, d_emean, 1)(ess_min, d_emin, 1)(z_mean, d_zm, K)(z_sd, d_zsd, K).done();
     if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
     if (!err.empty()) return err;
-    collect(h, kernel, PT_PREDICT);
-    collect(h, pool, PT_PREDICT);
+    collect(h, kernel, pt);
+    collect(h, pool, pt);
+    if (fit) collect(h, fpool, pt);
+    if (fit && nq) collect(h, quant, pt);
     return err;
   });
+}
+}  // namespace
+
+extern "C" int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const double* t, const double* B, const int64_t* offsets,
+                                   int n_new, const double* X, const int32_t* perm, int first_slot, int n_slots, int n_samples,
+                                   int n_stages, uint64_t seed, const double* zs, int64_t max_workspace_bytes,
+                                   double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min,
+                                   double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace, double* samples,
+                                   int64_t capacity) {
+  return predict_call("bfmmm_chain_predict", nullptr, h, y, t, B, offsets, n_new, X, perm, first_slot, n_slots, n_samples, n_stages, seed, zs,
+                      max_workspace_bytes, lpd, z_mean, z_sd, ess_mean, ess_min, lpd_trace, z_trace, ess_trace, prop_trace, samples, capacity);
+}
+
+extern "C" int bfmmm_chain_predict_fit(bfmmm_handle* h, const double* y, const double* t, const double* B, const int64_t* offsets,
+                                       int n_new, const double* X, const int32_t* perm, int first_slot, int n_slots, int n_samples,
+                                       int n_stages, uint64_t seed, const double* zs, const double* E, int G, int noise,
+                                       const double* probs, int nq, int64_t max_workspace_bytes,
+                                       double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min,
+                                       double* fit_mean, double* fit_sd, double* fit_q,
+                                       double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace, double* samples,
+                                       double* mean_trace, double* var_trace, double* path_trace, int32_t* path_index, double* path_u,
+                                       double* path_xi, int64_t capacity) {
+  const FitAsk fit{E, G, noise ? 1 : 0, probs, nq, fit_mean, fit_sd, fit_q, mean_trace, var_trace, path_trace, path_index, path_u, path_xi};
+  return predict_call("bfmmm_chain_predict_fit", &fit, h, y, t, B, offsets, n_new, X, perm, first_slot, n_slots, n_samples, n_stages, seed, zs,
+                      max_workspace_bytes, lpd, z_mean, z_sd, ess_mean, ess_min, lpd_trace, z_trace, ess_trace, prop_trace, samples, capacity);
 }

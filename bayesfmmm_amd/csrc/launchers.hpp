@@ -263,6 +263,24 @@ std::string launch_predict(const Ctx& c, const PredictCall& f, int r0, int rows,
 std::string launch_predict_pool(int K, long long N, int rows, const double* lpd_t, const double* ess_t, const double* m_t, const double* q_t,
                                 double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min, hipStream_t st);
 
+// ---- kernels_predict_fit.hip ----
+// One call of bfmmm_chain_predict_fit: the call of 7m, the evaluation basis E (G x P, device) and whether the
+// observation noise is added to the variance and the paths.
+struct PredictFitCall {
+  PredictCall p;
+  const double* E = nullptr;
+  int G = 0, noise = 0;
+};
+// "" or what k_predict_fit cannot take (what k_predict cannot take included, under its name); *lds_bytes: the dynamic LDS of a workgroup
+std::string predict_fit_check(const Ctx& c, const PredictFitCall& f, size_t* lds_bytes);
+// launch_predict's traces of the chunk, bit for bit, and with them mu_t, var_t, path_t [(r G + g) N + cs], path_idx, path_u [r N + cs]
+// and path_xi [(r N + cs) M + m]
+std::string launch_predict_fit(const Ctx& c, const PredictFitCall& f, int r0, int rows, double* lpd_t, double* ess_t, double* m_t, double* q_t,
+                               double* prop, double* samples, double* mu_t, double* var_t, double* path_t, int32_t* path_idx, double* path_u,
+                               double* path_xi, hipStream_t st);
+// mean and sd [col] of the ncol = rows G columns of N draws: the draws pooled with equal weights, sd of the whole mixture (N, not N - 1)
+std::string launch_predict_fit_pool(long long N, long long ncol, const double* mu_t, const double* var_t, double* mean, double* sd, hipStream_t st);
+
 // ---- kernels_bands.hip ----
 // The column reductions of the credible-band entry points on device tables V[t + T col], on stream st.  quantiles: LDS sort
 // for T <= 8192 (W unused), else k_bands_quantiles_big over the workspace W of NP ncol doubles, NP = bands_sort_pad(T), which

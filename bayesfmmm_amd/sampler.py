@@ -552,6 +552,31 @@ class Sampler:
         "n_samples", "n_stages"}.  A curve whose ess_min is small against n_samples (below 10, say) is not to be trusted: raise
         n_stages or n_samples.  trace adds "lpd_trace", "ess_trace": (m, C, S), "Z_trace": (m, C, S, K) and "proposal": (m, C, S, R, K);
         return_samples adds "samples": (m, C, S, R, J, K), for small shapes."""
+        return self._predict_call(None, Y_new, time_new, basis_new, X_new, perm, n_samples, n_stages, seed, trace, z_samples,
+                                  return_samples, first_slot, n_slots, max_workspace_bytes)
+
+    def predict_fit(self, Y_new, E, time_new=None, basis_new=None, X_new=None, perm=None, probs=(0.025, 0.5, 0.975), noise=False,
+                    n_samples=256, n_stages=3, seed=1, trace=False, z_samples=None, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """Held-out, partly observed curves completed (bfmmm_chain_predict_fit): `predict` with the same arguments --
+        the same samples and the same "lpd", "Z_mean", "Z_sd" and ESS, bit for bit -- and, on the rows of the evaluation basis E
+        (G x P, rows in the sampler's basis as in `curve_bands`; the identity for the multivariate model), where each new curve runs
+        given the points it was observed at: the predictive mean function, the sd of its predictive law and pointwise quantile
+        bands, with the chains pooled on the device.  For K-fold cross-validation E holds the basis rows of the left-out points.
+        The parameter draws are pooled with equal weights, as "Z_mean" pools them: the new curve does not reweight them.  noise
+        adds the observation noise sigma^2 to the variance and sigma eps to the paths (bands for a new observation, not for the
+        function).  probs: up to 16 probabilities, () for none.
+        Returns `predict`'s dict and "mean", "sd": (m, G), "quantiles": (m, G, nq), "probs"; trace adds `predict`'s traces and
+        "mean_trace", "var_trace", "path_trace": (m, G, C, S), the per-draw mean, variance and sampled path; "path_index", "path_u":
+        (m, C, S), the sample j* the path took and the uniform that chose it; "path_xi": (m, C, S, M), its standard normals."""
+        Em = self._basis_arg(E, "E")
+        fit = {"E": Em, "probs": _probs_arg(probs), "noise": bool(noise)}
+        return self._predict_call(fit, Y_new, time_new, basis_new, X_new, perm, n_samples, n_stages, seed, trace, z_samples, False,
+                                  first_slot, n_slots, max_workspace_bytes)
+
+    def _predict_call(self, fit, Y_new, time_new, basis_new, X_new, perm, n_samples, n_stages, seed, trace, z_samples, return_samples,
+                      first_slot, n_slots, max_workspace_bytes):
+        """The arguments of `predict` marshalled and bfmmm_chain_predict called, or with fit = {"E", "probs", "noise"}
+        bfmmm_chain_predict_fit"""
         S = self._slots(first_slot, n_slots)
         Cn, K, J, R = self.n_chains, self.K, int(n_samples), int(n_stages)
         y = t = B = off = None
@@ -597,12 +622,25 @@ class Sampler:
         if return_samples:
             tr["samples"] = np.zeros((m, Cn, Sn, max(R, 0), max(J, 0), K))
         opt = lambda k: _dp(tr[k]) if k in tr else None
-        _lib.check(self.lib.bfmmm_chain_predict(
-            self.h, None if y is None else _dp(y), None if t is None else _dp(t), None if B is None else _dp(B),
-            None if off is None else off.ctypes.data_as(_lib.c_int64_p), m, None if Xm is None else _dp(Xm),
-            None if p is None else _ip(p), int(first_slot), S, J, R, int(seed), None if zs is None else _dp(zs),
-            int(max_workspace_bytes), _dp(out["lpd"]), _dp(out["Z_mean"]), _dp(out["Z_sd"]), _dp(out["ess_mean"]), _dp(out["ess_min"]),
-            opt("lpd_trace"), opt("Z_trace"), opt("ess_trace"), opt("proposal"), opt("samples"), m))
+        head = (self.h, None if y is None else _dp(y), None if t is None else _dp(t), None if B is None else _dp(B),
+                None if off is None else off.ctypes.data_as(_lib.c_int64_p), m, None if Xm is None else _dp(Xm),
+                None if p is None else _ip(p), int(first_slot), S, J, R, int(seed), None if zs is None else _dp(zs))
+        pooled = (_dp(out["lpd"]), _dp(out["Z_mean"]), _dp(out["Z_sd"]), _dp(out["ess_mean"]), _dp(out["ess_min"]))
+        traces = (opt("lpd_trace"), opt("Z_trace"), opt("ess_trace"), opt("proposal"), opt("samples"))
+        if fit is None:
+            _lib.check(self.lib.bfmmm_chain_predict(*head, int(max_workspace_bytes), *pooled, *traces, m))
+        else:
+            Em, pr = fit["E"], fit["probs"]
+            G = Em.shape[0]
+            out.update(mean=np.zeros((m, G)), sd=np.zeros((m, G)), quantiles=np.zeros((m, G, pr.size)), probs=pr)
+            if trace:
+                tr.update(mean_trace=np.zeros((m, G, Cn, Sn)), var_trace=np.zeros((m, G, Cn, Sn)), path_trace=np.zeros((m, G, Cn, Sn)),
+                          path_index=np.zeros((m, Cn, Sn), dtype=np.int32), path_u=np.zeros((m, Cn, Sn)),
+                          path_xi=np.zeros((m, Cn, Sn, self.M)))
+            _lib.check(self.lib.bfmmm_chain_predict_fit(
+                *head, _dp(Em), G, int(fit["noise"]), _dp(pr) if pr.size else None, pr.size, int(max_workspace_bytes), *pooled,
+                _dp(out["mean"]), _dp(out["sd"]), _dp(out["quantiles"]) if pr.size else None, *traces, opt("mean_trace"),
+                opt("var_trace"), opt("path_trace"), _ip(tr["path_index"]) if trace else None, opt("path_u"), opt("path_xi"), m))
         out.update(tr)
         out["elpd"] = float(np.sum(out["lpd"]))
         out["se_elpd"] = float(np.sqrt(m * np.var(out["lpd"]))) if m > 0 else 0.0

@@ -481,6 +481,42 @@ int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const double* t, const
                         double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace, double* samples,
                         int64_t capacity);
 
+/* The fitted function of held-out, partly observed curves from the chain slots: bfmmm_chain_predict with the same
+ * arguments -- the same samples, and lpd, z_mean, z_sd, ess_mean, ess_min and their traces bit for bit -- and, on the G rows of an
+ * evaluation basis E (G x P row-major, rows in the sampler's basis as in bfmmm_chain_curve_bands; the identity for the
+ * multivariate model), where the new curve runs: its predictive mean function, the sd of its predictive law and quantile bands.
+ * Per (curve r, draw cs) and last-stage sample z_j with weight w_j, the curve's scores have the law
+ *   chi | y_r, z_j, draw ~ N(A^-1 u, sigma^2 A^-1),  A = sigma^2 I_M + W (u, W of bfmmm_chain_predict's l(z_j)), so with
+ *   e_g,(k,mt) = E_g . theta_(k,mt):  c_j(g) = sum_k z_jk e_g,(k0),  v_j(g)_m = sum_k z_jk e_g,(km),
+ *   mu_j(g) = c_j(g) + (A^-1 u)' v_j(g),  s_j(g) = sigma^2 v_j(g)' A^-1 v_j(g)  (+ sigma^2 with noise != 0),
+ *   mean_trace = mu_t(g) = sum_j w_j mu_j(g) / sum w,  var_trace = v_t(g) = sum_j w_j [s_j(g) + (mu_j(g) - mu_t(g))^2] / sum w.
+ * The N = C n_slots draws are pooled with equal weights, as z_mean pools them: the new curve does not reweight the parameter
+ * draws.  fit_mean[r G + g] = mean_cs mu_t(g);  fit_sd[r G + g] = sqrt(mean_cs v_t(g) + mean_cs (mu_t(g) - fit_mean)^2), in two passes.
+ * Every (curve, draw) also gives one path from the mixture: j* the first j with sum_{i <= j} w_i > U sum w (the sum in sample
+ * order; the last j should rounding leave none), xi ~ N(0, I_M),
+ *   path_trace(g) = c_j*(g) + (A^-1 u + sigma L^-T xi)' v_j*(g)  (+ sigma eps_g with noise),  A = L L',
+ * and fit_q[(r G + g) nq + q] is quantile probs[q] of the N paths at (r, g) by the rule of bfmmm_chain_curve_bands (nq 0 .. 16).
+ * Variates: the key of bfmmm_chain_predict (seed, the RNG chain id of chain q, the slot) under an update id of this call, index
+ * r (1 + M + G) + i with r the curve's position in the call: i = 0 the uniform U, i = 1 + m the normal xi_m, i = 1 + M + g the
+ * normal eps_g.
+ * Outputs: the five pooled arrays of bfmmm_chain_predict, fit_mean, fit_sd (required), fit_q (required where nq > 0); optional
+ * traces (NULL: not copied): those of bfmmm_chain_predict, mean_trace, var_trace, path_trace [(r G + g) N + cs], path_index (j*)
+ * and path_u (U) [r N + cs], path_xi [(r N + cs) M + m].
+ * Refused by name: everything bfmmm_chain_predict refuses, a null or non-finite E, G < 1, nq outside 0 .. 16 or a probability
+ * outside [0, 1], n_new (1 + M + G) above 2^32, a shape whose on-chip tables (those of bfmmm_chain_predict, e of G rounded up to 16
+ * rows, M x 256 values where M > 8) exceed 160 KiB of LDS, with the bytes.  A value's bits depend on (curve, chain, slot, seed, J, R, E, noise)
+ * alone, not on the chunk or a repeated call.  The fit's traces of a chunk count against max_workspace_bytes.  Multivariate rows
+ * are fully observed; missing coordinates, simultaneous bands and reweighting the draws by p(y_r | draw) are not provided. */
+int bfmmm_chain_predict_fit(bfmmm_handle* h, const double* y, const double* t, const double* B, const int64_t* offsets,
+                            int n_new, const double* X, const int32_t* perm, int first_slot, int n_slots, int n_samples,
+                            int n_stages, uint64_t seed, const double* zs, const double* E, int G, int noise,
+                            const double* probs, int nq, int64_t max_workspace_bytes,
+                            double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min,
+                            double* fit_mean, double* fit_sd, double* fit_q,
+                            double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace, double* samples,
+                            double* mean_trace, double* var_trace, double* path_trace, int32_t* path_index, double* path_u,
+                            double* path_xi, int64_t capacity);
+
 /* Diagnostics for the parity tests, of the selected chain after the last bfmmm_run: "rec" (n x LREC per-curve statistics),
  * "H" (R x LG pair-weighted Gram blocks, band-packed), "H2" (the same blocks as the factorisation and the sweep read them:
  * R x P x (2 BW + 2), piece-major), "tvec" (A x P), "Cmat" (A x P x P: C_a = Prec_a^-1 as k_factor left it), "Lz" (A x P: L_a z_a of the sampled directions),
@@ -552,7 +588,9 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * chunk; 0 with n_functions = 0).
  * Of the last bfmmm_chain_predict (always measured): "predict_stats", the device time and launches of the kernel that forms the
  * new curves' records (0 launches for a handle of bfmmm_create_from_basis, whose records are formed on the host); "predict", the
- * device time and launches of k_predict and the pooling kernel after it (two per chunk). */
+ * device time and launches of k_predict and the pooling kernel after it (two per chunk).
+ * Of the last bfmmm_chain_predict_fit (always measured): "predict_stats" as above; "predict_fit", the device time and launches of
+ * k_predict_fit, the two pooling kernels and, where nq > 0, the quantiles of the paths (three or four per chunk). */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
