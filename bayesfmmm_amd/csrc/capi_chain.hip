@@ -2,8 +2,8 @@
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
 // per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it, the cluster
-// covariance surfaces with their bands and their eigenvalues and eigenfunctions, and the prediction of held-out curves with
-// their fitted functions.
+// covariance surfaces with their bands and their eigenvalues and eigenfunctions, the prediction of held-out curves with
+// their fitted functions, and the marginal PSIS-LOO over the training curves with the memberships integrated out.
 // An entry point is its argument checks (SlotCheck: slots, curve selection, the grid pair, x, alpha, probs and `units`, the one
 // budget rule), its workspace and the event pairs that time its launches into the handle's PT_* timers (CallBufs owns both) and
 // one for_chunks.  What several of them do is written once: `once` for a launch that runs once per call (the projections), Back
@@ -1434,4 +1434,148 @@ extern "C" int bfmmm_chain_predict_fit(bfmmm_handle* h, const double* y, const d
   const FitAsk fit{E, G, noise ? 1 : 0, probs, nq, fit_mean, fit_sd, fit_q, mean_trace, var_trace, path_trace, path_index, path_u, path_xi};
   return predict_call("bfmmm_chain_predict_fit", &fit, h, y, t, B, offsets, n_new, X, perm, first_slot, n_slots, n_samples, n_stages, seed, zs,
                       max_workspace_bytes, lpd, z_mean, z_sd, ess_mean, ess_min, lpd_trace, z_trace, ess_trace, prop_trace, samples, capacity);
+}
+
+// ---- marginal PSIS-LOO over curves, the memberships integrated out (kernels_loo_marginal.hip) ------------------------
+// Per chunk of consecutive curves: k_predict on the resident records (the call of 7m with f.rec = c.rec, r = the curve's index, no
+// stats launch and no copy) into lpd_t, ess_t and a_last; with `refine` the count of the selected pairs, their list at the
+// prefix of the counts formed here, and k_lz_refine over the list; then k_lz_count once more for what is reported and
+// post_psis_device on the chunk's lpd_t, as bfmmm_chain_loo calls it.
+extern "C" int bfmmm_chain_loo_marginal(bfmmm_handle* h, int first_slot, int n_slots, int n_samples, int n_stages, uint64_t seed, int refine,
+                                        double ess_floor, int refine_samples, int refine_stages, int64_t max_workspace_bytes,
+                                        double* lppd, double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic,
+                                        double* ess_mean, double* ess_min, int32_t* n_refined, int32_t* n_below,
+                                        double* lpd_trace, double* ess_trace, double* ess_trace_first,
+                                        int32_t* refined_index, double* refine_prop, double* refine_samples_out, int64_t* n_ref,
+                                        int64_t capacity, int64_t ref_capacity) {
+  const SlotCheck ck{"bfmmm_chain_loo_marginal", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"h", h}, {"lppd", lppd}, {"elpd_loo", elpd_loo}, {"p_loo", p_loo}, {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic},
+               {"p_waic", p_waic}, {"ess_mean", ess_mean}, {"ess_min", ess_min}, {"n_refined", n_refined}, {"n_below", n_below}}))
+    return 1;
+  const bool ref_out = refined_index || refine_prop || refine_samples_out;
+  if (ref_out && ck.ptrs({{"n_ref", n_ref}})) return 1;
+  const int J = n_samples, R = n_stages, J2 = refine_samples, R2 = refine_stages;
+  if (J < 1) return fail(fn + ": 'n_samples' must be at least 1, got " + std::to_string(J));
+  if (R < 1) return fail(fn + ": 'n_stages' must be at least 1, got " + std::to_string(R));
+  if (J2 < 1) return fail(fn + ": 'refine_samples' must be at least 1, got " + std::to_string(J2));
+  if (R2 < 1) return fail(fn + ": 'refine_stages' must be at least 1, got " + std::to_string(R2));
+  if (!(std::isfinite(ess_floor) && ess_floor >= 0.0)) return fail(fn + ": 'ess_floor' must be finite and not negative, got " + std::to_string(ess_floor));
+  const Ctx& c = h->c;
+  const Dims& d = c.d;
+  const int n = d.n, K = d.K;
+  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, n, "rows") || ck.row_limit()) return 1;
+  if (ref_out && ref_capacity < 0) return fail(fn + ": 'ref_capacity' must not be negative");
+  // the RNG indices ((i R + st) J + j) K + k and ((i R2 + st) J2 + j) K + k are 32-bit counter words
+  if ((long double)n * (long double)R * (long double)J * (long double)K > 4294967296.0L)
+    return fail(fn + ": n x n_stages x n_samples x K = " + std::to_string(n) + " x " + std::to_string(R) + " x " + std::to_string(J) + " x " +
+                std::to_string(K) + " exceeds the 4294967296 (2^32) indices of the random number counter");
+  if (refine && (long double)n * (long double)R2 * (long double)J2 * (long double)K > 4294967296.0L)
+    return fail(fn + ": n x refine_stages x refine_samples x K = " + std::to_string(n) + " x " + std::to_string(R2) + " x " + std::to_string(J2) +
+                " x " + std::to_string(K) + " exceeds the 4294967296 (2^32) indices of the random number counter");
+  PredictCall f;
+  f.n_new = n; f.J = J; f.R = R; f.first_slot = first_slot; f.n_slots = n_slots; f.seed = seed;
+  f.rec = c.rec; f.ni = c.ni; f.X = c.X;
+  PredictCall f2 = f;
+  f2.J = J2; f2.R = R2;
+  std::string bad = predict_check(c, f, nullptr);
+  if (bad.empty() && refine) bad = lz_check(c, J2, R2, nullptr);
+  if (!bad.empty()) return fail(fn + ": " + bad);
+  const size_t N = (size_t)ck.CS(), NK = N * (size_t)K;
+  double* const want_prop = refine ? refine_prop : nullptr;
+  double* const want_smp = refine ? refine_samples_out : nullptr;
+  // a curve: lpd_t, ess_t and a_last (N (2 + K)), ess_mean and ess_min, the two counts and the offset; with `refine` the list (three
+  // ints a pair) and, where asked for, the proposals and the samples of the refinement, as if every pair were refined
+  const size_t per_curve = sizeof(double) * (N * (2 + (size_t)K) + 2 + (want_prop ? NK * R2 : 0) + (want_smp ? NK * R2 * (size_t)J2 : 0)) +
+                           sizeof(int32_t) * (2 + (refine ? 3 * N + 1 : 0)) + sizeof(int64_t);
+  const size_t budget = budget_of(max_workspace_bytes);
+  if (want_smp && budget < per_curve)
+    return fail(fn + ": 'refine_samples_out' of one curve (n_chains x n_slots x refine_stages x refine_samples x K doubles) with the rest need " +
+                std::to_string(per_curve) + " bytes, above 'max_workspace_bytes' = " + std::to_string(budget) + " " +
+                SlotCheck::plan_text(0, per_curve, "curve"));
+  int64_t chunk = 0;
+  const int64_t cells = (int64_t)std::max<size_t>(1, per_curve / sizeof(double) / std::max<size_t>(N, 1));
+  if (ck.units(budget, 0, per_curve, n, cells_cap(cells), "curve", &chunk)) return 1;
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_LOO_MARGINAL, PT_LOO_MARGINAL_PSIS);
+  CallBufs b;
+  double *d_tr = nullptr, *d_out = nullptr, *d_prop = nullptr, *d_smp = nullptr;
+  int32_t *d_cnt = nullptr, *d_list = nullptr;
+  int64_t* d_off = nullptr;
+  Timer first, count, list, refk, pool, psis;
+  HIPCHK(b.timers({&first, &count, &list, &refk, &pool, &psis}));
+  HIPCHK(b.get(&d_tr, (size_t)chunk * (2 * N + NK)));
+  HIPCHK(b.get(&d_out, 2 * (size_t)chunk));
+  HIPCHK(b.get(&d_cnt, 2 * (size_t)chunk));
+  if (refine) {
+    HIPCHK(b.get(&d_off, (size_t)chunk));
+    HIPCHK(b.get(&d_list, 3 * (size_t)chunk * N));
+  }
+  if (want_prop) HIPCHK(b.get(&d_prop, (size_t)chunk * NK * R2));
+  if (want_smp) HIPCHK(b.get(&d_smp, (size_t)chunk * NK * R2 * J2));
+  double* d_lpd_t = d_tr;
+  double* d_ess_t = d_lpd_t + (size_t)chunk * N;
+  double* d_alast = d_ess_t + (size_t)chunk * N;
+  double* d_emean = d_out;
+  double* d_emin = d_emean + chunk;
+  int32_t* d_below = d_cnt + chunk;
+  std::vector<int32_t> hcnt((size_t)chunk);
+  std::vector<int64_t> hoff((size_t)chunk);
+  int64_t total_ref = 0;
+  const int rc = for_chunks(ck, n, chunk, [&](int64_t r0, int rows) {
+    std::string err = timed(first, h->st, [&] {
+      return launch_predict(c, f, (int)r0, rows, d_lpd_t, d_ess_t, nullptr, nullptr, nullptr, nullptr, h->st, refine ? d_alast : nullptr);
+    });
+    if (err.empty()) err = Back{h, r0, rows}(ess_trace_first, d_ess_t, N).queued();
+    int64_t n_list = 0;
+    std::fill(n_refined + r0, n_refined + r0 + rows, 0);
+    if (err.empty() && refine) {
+      err = timed(count, h->st, [&] { return launch_lz_count((long long)N, rows, d_lpd_t, d_ess_t, ess_floor, d_cnt, nullptr, nullptr, h->st); });
+      if (err.empty() && copy_sync(h, hcnt.data(), d_cnt, sizeof(int32_t) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess) err = kBackFailed;
+      if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
+      if (!err.empty()) return err;
+      for (int r = 0; r < rows; ++r) {
+        if (hcnt[r] < 0 || (size_t)hcnt[r] > N) return std::string("k_lz_count: a count outside 0 .. n_chains x n_slots");
+        hoff[r] = n_list;
+        n_list += hcnt[r];
+        n_refined[r0 + r] = hcnt[r];
+      }
+      if (n_list > 0) {
+        if (ref_out && total_ref + n_list > ref_capacity)
+          return "'ref_capacity' below the " + std::to_string(total_ref + n_list) + " pairs refined up to curve " + std::to_string(r0 + rows - 1);
+        if (copy_sync(h, d_off, hoff.data(), sizeof(int64_t) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess) return std::string(kBackFailed);
+        err = timed(list, h->st, [&] {
+          return launch_lz_list((long long)N, n_slots, (int)r0, rows, d_lpd_t, d_ess_t, ess_floor, d_off, (long long)n_list, d_list, h->st);
+        });
+        if (err.empty())
+          err = timed(refk, h->st, [&] {
+            return launch_lz_refine(c, f2, (int)r0, rows, d_list, (long long)n_list, d_lpd_t, d_ess_t, d_alast, d_prop, d_smp, h->st);
+          });
+        if (err.empty())
+          err = Back{h, total_ref, (int)n_list}(refined_index, d_list, 3)(want_prop, d_prop, (size_t)K * R2)(want_smp, d_smp, (size_t)K * R2 * J2).queued();
+      }
+    }
+    if (err.empty())
+      err = timed(pool, h->st, [&] { return launch_lz_count((long long)N, rows, d_lpd_t, d_ess_t, ess_floor, d_below, d_emean, d_emin, h->st); });
+    if (err.empty())
+      err = Back{h, r0, rows}(lpd_trace, d_lpd_t, N)(ess_trace, d_ess_t, N)(ess_mean, d_emean, 1)(ess_min, d_emin, 1)(n_below, d_below, 1).done();
+    if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
+    if (!err.empty()) return err;
+    collect(h, first, PT_LOO_MARGINAL);
+    if (refine) collect(h, count, PT_LOO_MARGINAL);
+    if (n_list > 0) { collect(h, list, PT_LOO_MARGINAL); collect(h, refk, PT_LOO_MARGINAL); }
+    collect(h, pool, PT_LOO_MARGINAL);
+    total_ref += n_list;
+    // post_psis_device runs on the device's default stream: done() has drained the sampler's
+    double* const outs[6] = {lppd + r0, elpd_loo + r0, p_loo + r0, pareto_k + r0, elpd_waic + r0, p_waic + r0};
+    (void)hipEventRecord(psis.from, nullptr);
+    const int prc = post_psis_device(d_lpd_t, (long long)N, rows, (int)N, outs);
+    (void)hipEventRecord(psis.to, nullptr);
+    if (prc) return std::string(bfmmm_entry_last_error());
+    if (hipEventSynchronize(psis.to) != hipSuccess) return std::string(kBackFailed);
+    collect(h, psis, PT_LOO_MARGINAL_PSIS);
+    return err;
+  });
+  if (n_ref) *n_ref = total_ref;
+  return rc;
 }

@@ -31,18 +31,21 @@ enum { FAM_TOTAL = 0, FAM_Z, FAM_PG, FAM_FACTOR, FAM_SWEEP, FAM_CHI, FAM_LOGLIK,
 // over the chunks, PT_CCOV_MAXDEV: k_ccov_maxdev, one launch per chunk; PT_CEIG_GRAM: k_ceig_gram, PT_CEIG: k_ceig_solve, one launch
 // each per call, PT_CEIG_VALUES: k_ceig_values, one launch per chunk; PT_PREDICT_STATS: the records of the new curves (one launch,
 // none for a from-basis handle), PT_PREDICT: k_predict and k_predict_pool, one launch each per chunk; PT_PREDICT_FIT: what
-// bfmmm_chain_predict_fit launches in their place, k_predict_fit, k_predict_pool, k_predict_fit_pool and the quantiles of the paths.
+// bfmmm_chain_predict_fit launches in their place, k_predict_fit, k_predict_pool, k_predict_fit_pool and the quantiles of the paths;
+// PT_LOO_MARGINAL: what bfmmm_chain_loo_marginal launches on the sampler's stream, per chunk k_predict, k_lz_count twice and, where
+// pairs are refined, k_lz_list and k_lz_refine; PT_LOO_MARGINAL_PSIS: its PSIS pass, one launch per chunk.
 enum { PT_CURVE_LL = 0, PT_FIT_PROJECT, PT_FIT_ROWS, PT_FIT_VALUES, PT_FIT_REDUCE, PT_SIM, PT_SIM_REDUCE, PT_SIMILARITY,
        PT_COV_PROJECT, PT_COV, PT_SIM_LOSS, PT_SIM_LOSS_REDUCE, PT_ALIGN_GRAM, PT_ALIGN_GATHER, PT_ALIGN_PROJECT,
        PT_CCOV_PROJECT, PT_CCOV, PT_CCOV_MAXDEV, PT_CEIG_GRAM, PT_CEIG, PT_CEIG_VALUES, PT_PREDICT_STATS, PT_PREDICT, PT_PREDICT_FIT,
-       PT_COUNT };
+       PT_LOO_MARGINAL, PT_LOO_MARGINAL_PSIS, PT_COUNT };
 inline constexpr const char* kPostNames[PT_COUNT] = {"curve_ll_ms", "curve_fit_project", "curve_fit_rows", "curve_fit_values",
                                                      "curve_fit_reduce", "curve_sim", "curve_sim_reduce", "similarity",
                                                      "curve_cov_project", "curve_cov", "similarity_loss", "similarity_loss_reduce",
                                                      "align_gram", "align_gather", "align_project",
                                                      "cluster_cov_project", "cluster_cov", "cluster_cov_maxdev",
                                                      "cluster_eig_gram", "cluster_eig", "cluster_eig_values",
-                                                     "predict_stats", "predict", "predict_fit"};
+                                                     "predict_stats", "predict", "predict_fit",
+                                                     "loo_marginal", "loo_marginal_psis"};
 
 struct bfmmm_handle {
   bfmmm_config cfg;

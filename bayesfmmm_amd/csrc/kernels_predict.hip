@@ -114,13 +114,14 @@ std::string predict_check(const Ctx& c, const PredictCall& f, size_t* lds_bytes)
 }
 
 PredArgs pred_args(const Ctx& c, const PredictCall& f, int r0, int rows, double* lpd_t, double* ess_t, double* m_t, double* q_t, double* prop,
-                   double* samples) {
+                   double* samples, double* a_last) {
   const Dims& d = c.d;
   PredArgs a;
   a.c_nu = c.c_nu; a.c_Phi = c.c_Phi; a.c_sigma = c.c_sigma; a.c_pi = c.c_pi; a.c_alpha3 = c.c_alpha3;
   a.c_eta = d.D > 0 ? c.c_eta : nullptr; a.c_xi = d.D > 0 ? c.c_xi : nullptr;
   a.rec = f.rec; a.X = d.D > 0 ? f.X : nullptr; a.zs = f.zs; a.ni = f.ni; a.perm = f.perm;
   a.lpd_t = lpd_t; a.ess_t = ess_t; a.m_t = m_t; a.q_t = q_t; a.prop = prop; a.samples = samples;
+  a.a_last = a_last; a.a_start = nullptr;
   a.chain_bytes = c.chain_bytes; a.chain_bytes_cov = c.chain_bytes_cov;
   a.seed = f.seed; a.chain0 = c.chain; a.chain_stride = c.chain_id_stride;
   a.n_new = f.n_new; a.K = d.K; a.P = d.P; a.M = d.M; a.D = d.D; a.BW = d.BW; a.LG = d.LG; a.LREC = d.LREC;
@@ -135,12 +136,13 @@ PredArgs pred_args(const Ctx& c, const PredictCall& f, int r0, int rows, double*
 }
 
 std::string launch_predict(const Ctx& c, const PredictCall& f, int r0, int rows, double* lpd_t, double* ess_t, double* m_t, double* q_t,
-                           double* prop, double* samples, hipStream_t st) {
+                           double* prop, double* samples, hipStream_t st, double* a_last) {
   size_t lds = 0;
   const std::string bad = predict_check(c, f, &lds);
   if (!bad.empty()) return bad;
   if (rows < 1 || r0 < 0 || (long long)r0 + rows > f.n_new) return "k_predict: curves outside the call";
-  const PredArgs a = pred_args(c, f, r0, rows, lpd_t, ess_t, m_t, q_t, prop, samples);
+  if (!m_t != !q_t) return "k_predict: m_t and q_t go together";
+  const PredArgs a = pred_args(c, f, r0, rows, lpd_t, ess_t, m_t, q_t, prop, samples, a_last);
   const dim3 grid((unsigned)rows, (unsigned)((f.n_slots + a.SCH - 1) / a.SCH), (unsigned)c.nch);
   void (*fn)(PredArgs) = pred_kt(c.d.K) == 4 ? k_predict<4> : k_predict<KMAX>;
   if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {

@@ -256,9 +256,9 @@ struct PredictCall {
 std::string predict_check(const Ctx& c, const PredictCall& f, size_t* lds_bytes);
 // new curves [r0, r0 + rows) of the call into the chunk's traces (r from 0, N = C n_slots): lpd_t, ess_t [r N + cs], m_t, q_t
 // [(r N + cs) K + l] (relabelled by perm), prop [((r N + cs) R + st) K + k] and samples [(((r N + cs) R + st) J + j) K + k] (either
-// may be null)
+// may be null; so may m_t and q_t, together) and a_last [(r N + cs) K + k], the proposal of the last stage (null: not stored)
 std::string launch_predict(const Ctx& c, const PredictCall& f, int r0, int rows, double* lpd_t, double* ess_t, double* m_t, double* q_t,
-                           double* prop, double* samples, hipStream_t st);
+                           double* prop, double* samples, hipStream_t st, double* a_last = nullptr);
 // the pooled results of the chunk's rows from its traces: lpd, ess_mean, ess_min [r], z_mean, z_sd [r K + l]
 std::string launch_predict_pool(int K, long long N, int rows, const double* lpd_t, const double* ess_t, const double* m_t, const double* q_t,
                                 double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min, hipStream_t st);
@@ -280,6 +280,24 @@ std::string launch_predict_fit(const Ctx& c, const PredictFitCall& f, int r0, in
                                double* path_xi, hipStream_t st);
 // mean and sd [col] of the ncol = rows G columns of N draws: the draws pooled with equal weights, sd of the whole mixture (N, not N - 1)
 std::string launch_predict_fit_pool(long long N, long long ncol, const double* mu_t, const double* var_t, double* mean, double* sd, hipStream_t st);
+
+// ---- kernels_loo_marginal.hip ----
+// The refinement of bfmmm_chain_loo_marginal over a chunk of `rows` curves from r0 on, whose traces lpd_t, ess_t
+// [r N + cs] and a_last [(r N + cs) K + k] launch_predict left (r from 0, N = C n_slots).  A pair is selected where ess_t < floor
+// or lpd_t is not finite.
+// "" or what k_lz_refine cannot take with J2 samples in each of R2 stages; *lds_bytes: the dynamic LDS of a workgroup
+std::string lz_check(const Ctx& c, int J2, int R2, size_t* lds_bytes);
+// cnt[r]: the selected pairs of row r; where given, ess_mean[r] and ess_min[r] of the row
+std::string launch_lz_count(long long N, int rows, const double* lpd_t, const double* ess_t, double ess_floor, int32_t* cnt, double* ess_mean,
+                            double* ess_min, hipStream_t st);
+// the selected pairs of row r as (curve r0 + r, chain, slot relative to first_slot) at list + 3 off[r], in increasing cs; off: the
+// exclusive prefix of the counts, n_list their sum, the entries the list holds
+std::string launch_lz_list(long long N, int S, int r0, int rows, const double* lpd_t, const double* ess_t, double ess_floor, const int64_t* off,
+                           long long n_list, int32_t* list, hipStream_t st);
+// One workgroup per listed pair runs pred_draw once more with f.J = J2 and f.R = R2 from the pair's a_last and overwrites its lpd_t
+// and ess_t; prop [(e R2 + st) K + k] and samples [((e R2 + st) J2 + j) K + k] of list entry e (either may be null)
+std::string launch_lz_refine(const Ctx& c, const PredictCall& f, int r0, int rows, const int32_t* list, long long n_list, double* lpd_t,
+                             double* ess_t, const double* a_last, double* prop, double* samples, hipStream_t st);
 
 // ---- kernels_bands.hip ----
 // The column reductions of the credible-band entry points on device tables V[t + T col], on stream st.  quantiles: LDS sort

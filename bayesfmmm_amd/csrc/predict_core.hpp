@@ -1,7 +1,8 @@
 // What k_predict (kernels_predict.hip) and k_predict_fit (kernels_predict_fit.hip; 7n) share: the arguments and the LDS
 // layout of a workgroup, its sums, l(z) from the tables in LDS, the set-up of a workgroup and the whole of a draw -- steps (1) to (4)
 // of kernels_predict.hip's header, the tables Gamma and tau and the R stages of the importance sampler.  Written once, so that the two
-// kernels draw the same samples and return the same lpd, ess and memberships bit for bit.
+// kernels draw the same samples and return the same lpd, ess and memberships bit for bit.  k_lz_refine (kernels_loo_marginal.hip;
+// 7o) runs the same set-up and draw once more for a listed (curve, draw) pair, from a given starting proposal (pred_draw<KT, true>).
 #pragma once
 #include "model.hpp"
 #include "launchers.hpp"
@@ -22,7 +23,9 @@ struct PredArgs {
   const double *rec, *X, *zs;
   const int* ni;
   const int32_t* perm;
-  double *lpd_t, *ess_t, *m_t, *q_t, *prop, *samples;
+  double *lpd_t, *ess_t, *m_t, *q_t, *prop, *samples;      // m_t and q_t go together; they, prop and samples may be null
+  double* a_last;              // [row K + k]: the proposal of the draw's last stage (null: not stored)
+  const double* a_start;       // [row K + k]: the proposal stage 0 starts from (pred_draw<KT, true> alone reads it)
   size_t chain_bytes, chain_bytes_cov;
   unsigned long long seed;
   uint32_t chain0, chain_stride;
@@ -189,9 +192,12 @@ __device__ inline void pred_setup(const PredArgs& a, const PredLds& L, double* s
 // [k J + j] and their weights w_j = exp(lw_j - max) (sm + L.lw), and in the lanes' Q columns what pred_ell left for the samples of
 // the last pass of the lanes (j >= J - J % 256, or the last 256).  Returns the sum of those weights, the same bits on every thread.
 // KT: the compile-time bound on K (4 or KMAX), so that a lane's z stays in registers.
-template <int KT>
+// START (k_lz_refine of kernels_loo_marginal.hip): stage 0 proposes from a.a_start of the draw's row in place of the
+// prior, so the Dirichlet correction applies in stage 0 as well; the variates come under UPD_LOO_REFINE, and the proposals and
+// samples go to row prow of a.prop and a.samples, the pair's place in the list, not to the draw's row of the traces.
+template <int KT, bool START = false>
 __device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* sm, const PredSlots& ch, int r, int rr, int q_chain, int s,
-                                   double yy, int ni) {
+                                   double yy, int ni, size_t prow = 0) {
   constexpr int NV = 2 + 2 * KT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K, P = a.P, M = a.M, D = a.D, M1 = M + 1, BW = a.BW, LG = a.LG, J = a.J, R = a.R;
@@ -213,6 +219,8 @@ __device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* 
   const size_t t = (size_t)(a.first_slot + s);
   const long long cs = (long long)q_chain * a.S + s;
   const size_t row = (size_t)rr * (size_t)N + (size_t)cs;
+  if (!START) prow = row;
+  constexpr uint32_t upd = START ? UPD_LOO_REFINE : UPD_PREDICT;
   double sw_last = 0.0;
   __syncthreads();                            // the previous draw's readers are done (and the set-up)
   // (1) theta, directions-major, x folded in (nu: [k + K p], Phi: [k + K (p + P m)], eta: [p + P (d + D k)], xi: [p + P (d + D (m + M k))])
@@ -274,10 +282,10 @@ __device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* 
   const double sig = sPar[PP_SIG];
   const RngKey key = make_key(a.seed, a.chain0 + (uint32_t)q_chain * a.chain_stride, (uint32_t)t);
   for (int st = 0; st < R; ++st) {
-    if (st == 0 && tid < K) sPar[PP_A + tid] = sPar[PP_PRIOR + tid];
+    if (st == 0 && tid < K) sPar[PP_A + tid] = START ? a.a_start[row * K + tid] : sPar[PP_PRIOR + tid];
     __syncthreads();
-    if (tid == 0) sPar[PP_LBC] = st > 0 ? calc_lB(K, sPar + PP_A) - calc_lB(K, sPar + PP_PRIOR) : 0.0;
-    if (a.prop && tid < K) a.prop[(row * R + st) * K + tid] = sPar[PP_A + tid];
+    if (tid == 0) sPar[PP_LBC] = (START || st > 0) ? calc_lB(K, sPar + PP_A) - calc_lB(K, sPar + PP_PRIOR) : 0.0;
+    if (a.prop && tid < K) a.prop[(prow * R + st) * K + tid] = sPar[PP_A + tid];
     __syncthreads();
     const double lbc = sPar[PP_LBC];
     double lmax = -INFINITY;
@@ -292,7 +300,7 @@ __device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* 
         double sum = 0.0;
 #pragma nounroll
         for (int k = 0; k < K; ++k) {
-          const double g = fmax(rgamma(key, UPD_PREDICT, (uint32_t)(i0 + k), sPar[PP_A + k], 1.0), DBL_MIN);
+          const double g = fmax(rgamma(key, upd, (uint32_t)(i0 + k), sPar[PP_A + k], 1.0), DBL_MIN);
           sZ[k * J + j] = g;
           sum += g;
         }
@@ -300,7 +308,7 @@ __device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* 
         for (int k = 0; k < KT; ++k) { const double gv = sZ[min(k, K - 1) * J + j]; z[k] = k < K ? gv / sum : 0.0; }
       }
       double lw = pred_ell<KT>(z, K, M, sGam, GS, sTau, sQ, yy, sig, ni);
-      if (st > 0) {
+      if (START || st > 0) {
         double corr = lbc;
 #pragma unroll
         for (int k = 0; k < KT; ++k) {      // (k >= K: log 1 = 0 times a difference that is there)
@@ -313,7 +321,7 @@ __device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* 
       for (int k = 0; k < KT; ++k)
         if (k < K) {
           sZ[k * J + j] = z[k];
-          if (a.samples) a.samples[((row * R + st) * J + j) * K + k] = z[k];
+          if (a.samples) a.samples[((prow * R + st) * J + j) * K + k] = z[k];
         }
       sLw[j] = lw;
       lmax = fmax(lmax, lw);
@@ -383,17 +391,18 @@ __device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* 
     }
   }
   __syncthreads();
-  if (tid < K) {
+  if (a.m_t && tid < K) {
     const int src = a.perm ? a.perm[(size_t)cs * K + tid] : tid;
     a.m_t[row * K + tid] = sPar[PP_M + src];
     a.q_t[row * K + tid] = sPar[PP_Q + src];
   }
+  if (a.a_last && tid < K) a.a_last[row * K + tid] = sPar[PP_A + tid];
   return sw_last;
 }
 
 inline int pred_kt(int K) { return K <= 4 ? 4 : KMAX; }
-// the arguments of a launch over new curves [r0, r0 + rows) of call f, SCH included (kernels_predict.hip)
+// the arguments of a launch over new curves [r0, r0 + rows) of call f, SCH included (kernels_predict.hip); a_start null
 PredArgs pred_args(const Ctx& c, const PredictCall& f, int r0, int rows, double* lpd_t, double* ess_t, double* m_t, double* q_t, double* prop,
-                   double* samples);
+                   double* samples, double* a_last = nullptr);
 
 }  // namespace bfmmm

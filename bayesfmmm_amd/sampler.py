@@ -243,6 +243,57 @@ class Sampler:
         pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs))
         return api.loo_totals(pw, self.n_chains * S)
 
+    REFINE_TRACE_BYTES = 512 << 20      # loo_marginal(trace=True): the most "refine_prop" and "refine_samples" may take on the host
+
+    def loo_marginal(self, first_slot=0, n_slots=None, n_samples=256, n_stages=3, seed=1, refine=True, ess_floor=10.0,
+                     refine_samples=None, refine_stages=2, trace=False, max_workspace_bytes=0):
+        """PSIS-LOO and WAIC over curves with the memberships integrated out (bfmmm_chain_loo_marginal).  `loo` runs
+        PSIS on log p(y_i | Z_i, draw), which is conditional on the draw's memberships of curve i; leaving the curve out sends them
+        back to their prior, so that estimate is the conditional LOO and its importance ratios are heavy-tailed.  This call runs PSIS
+        on log p(y_i | draw), the integral over Z_i ~ Dir(alpha_3 pi) that `predict` estimates per (curve, draw), taken here from the
+        resident records of the training curves: n_stages rounds of n_samples samples, the traces of predict(Y, time, trace=True)
+        with the same seed bit for bit.  With refine, every (curve, draw) pair whose importance-sampling ess is below ess_floor (or
+        whose estimate is not finite) is run once more from the last proposal of its first pass: refine_stages rounds of
+        refine_samples samples (default 4 * n_samples).  Such a pair would otherwise carry the largest weight of its curve.
+        Returns the dict of `loo` and "ess_mean", "ess_min": (n,), after the refinement; "n_refined": (n,), the pairs of the curve
+        that were refined; "n_below": (n,), the pairs still below the floor afterwards -- reported, never dropped: read it and
+        "pareto_k" before the totals; and the six call parameters.  trace adds "lpd_trace", "ess_trace": (n, C, S) after the
+        refinement, "ess_trace_first": (n, C, S) before it, "refined_index": (n_ref, 3), the (curve, chain, slot relative to
+        first_slot) of the refined pairs in increasing order, and, for tests and small shapes (where they would take no more than
+        REFINE_TRACE_BYTES if every pair were refined), "refine_prop": (n_ref, R2, K) and "refine_samples": (n_ref, R2, J2, K), which then
+        takes the place of the parameter of that name.  All chains of the batch, pooled, on one device."""
+        from . import api
+        S = self._slots(first_slot, n_slots)
+        n, Cn, K, Sn = self.n, self.n_chains, self.K, max(S, 0)
+        J, R, R2 = int(n_samples), int(n_stages), int(refine_stages)
+        J2 = 4 * J if refine_samples is None else int(refine_samples)
+        outs = [np.zeros(n) for _ in range(8)]
+        n_refined, n_below = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        tr, idx, prop, smp, cap = {}, None, None, None, 0
+        if trace:
+            tr = {k: np.zeros((n, Cn, Sn)) for k in ("lpd_trace", "ess_trace", "ess_trace_first")}
+            cap = n * Cn * Sn
+            idx = np.zeros((cap, 3), dtype=np.int32)
+            if refine and 8 * cap * max(R2, 0) * (1 + max(J2, 0)) * K <= self.REFINE_TRACE_BYTES:
+                prop, smp = np.zeros((cap, max(R2, 0), K)), np.zeros((cap, max(R2, 0), max(J2, 0), K))
+        n_ref = C.c_int64(0)
+        opt = lambda a: None if a is None else _dp(a)
+        _lib.check(self.lib.bfmmm_chain_loo_marginal(
+            self.h, int(first_slot), S, J, R, int(seed), int(bool(refine)), float(ess_floor), J2, R2, int(max_workspace_bytes),
+            *[_dp(o) for o in outs], _ip(n_refined), _ip(n_below), opt(tr.get("lpd_trace")), opt(tr.get("ess_trace")),
+            opt(tr.get("ess_trace_first")), None if idx is None else _ip(idx), opt(prop), opt(smp), C.byref(n_ref), n, cap))
+        pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs[:6]))
+        out = api.loo_totals(pw, Cn * S)
+        out.update(ess_mean=outs[6], ess_min=outs[7], n_refined=n_refined, n_below=n_below, n_samples=J, n_stages=R, refine=bool(refine),
+                   ess_floor=float(ess_floor), refine_samples=J2, refine_stages=R2)
+        out.update(tr)
+        if trace:
+            m = n_ref.value
+            out["refined_index"] = idx[:m].copy()
+            if prop is not None:
+                out["refine_prop"], out["refine_samples"] = prop[:m].copy(), smp[:m].copy()
+        return out
+
     def _fit_args(self, E, which, curves, first_slot, n_slots):
         w = {"mean": 0, "fit": 1}.get(which, which)
         if isinstance(w, str):

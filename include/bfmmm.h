@@ -481,6 +481,39 @@ int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const double* t, const
                         double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace, double* samples,
                         int64_t capacity);
 
+/* Marginal PSIS-LOO over the training curves with the memberships integrated out.  bfmmm_chain_loo runs PSIS on
+ * log p(y_i | Z_i, draw); this call runs it on log p(y_i | draw) = log of the integral of exp l_i(z) Dir(z; alpha_3 pi) dz, which
+ * bfmmm_chain_predict estimates per (curve, draw), here from the resident records of the n training curves (nothing is copied or
+ * recomputed): the first pass is bfmmm_chain_predict's with n_samples = J, n_stages = R and r = the curve's index in the data,
+ * so its traces are that call's on the same data, seed, J and R, bit for bit.
+ * Refinement (refine != 0).  A pair (curve, draw) is selected where its ess < ess_floor or its lpd is not finite.  Each selected
+ * pair runs once more: refine_stages = R2 rounds of refine_samples = J2 samples by the rule of bfmmm_chain_predict, except that
+ * stage 0 proposes from the last proposal a of the pair's first pass in place of the prior, so that
+ *   lw_j = l(z_j) + sum_k (alpha_3 pi_k - a_k) log z_jk + lB(a) - lB(alpha_3 pi)   in stage 0 as well (zero where a is the prior);
+ * variates keyed by (seed, the RNG chain id of the chain, the slot) under an update id of its own, index ((i R2 + st) J2 + j) K + k
+ * with i the curve's index.  The pair's lpd and ess are overwritten; there is one such run, not a loop until the floor is met.
+ * Then PSIS-LOO and WAIC as bfmmm_chain_loo on the n x N matrix of lpd, N = C n_slots (the chains pooled).
+ * Outputs (capacity >= n rows): the six pointwise arrays of bfmmm_chain_loo; ess_mean, ess_min [i] over the curve's N pairs
+ * after refinement; n_refined [i], the pairs of the curve that were refined; n_below [i], the pairs the selection rule still
+ * picks afterwards (reported, not dropped).  Optional (NULL: not copied): lpd_trace, ess_trace [i N + cs] after refinement,
+ * ess_trace_first [i N + cs] before it; and for the *n_ref refined pairs in increasing (curve, chain, slot) order, e their
+ * position: refined_index [3 e + .] = (curve, chain, slot relative to first_slot), refine_prop [(e R2 + st) K + k] the proposal
+ * of every refinement stage, refine_samples_out [((e R2 + st) J2 + j) K + k] its samples (tests and small shapes); these three
+ * hold ref_capacity pairs, and a call that refines more is refused.  n_ref may be NULL where none of the three is given.
+ * Refused by name: a null handle or required pointer, a slot range outside the storage, more than 2^22 draws, n_samples,
+ * n_stages, refine_samples or refine_stages below 1, ess_floor negative or not finite, n R J K or n R2 J2 K above 2^32 (the RNG
+ * index), what bfmmm_chain_predict's kernel cannot take, J2 samples whose on-chip tables exceed 160 KiB of LDS (with the bytes),
+ * a negative max_workspace_bytes or one below what one curve needs.  A value's bits depend on (curve, chain, slot, seed, J, R,
+ * J2, R2, ess_floor) alone.  Chunks of consecutive curves keep the traces, the list and the optional outputs within
+ * max_workspace_bytes (0: 256 MiB).  All chains of the batch, on one device; leaves the sampler's state and slots untouched. */
+int bfmmm_chain_loo_marginal(bfmmm_handle* h, int first_slot, int n_slots, int n_samples, int n_stages, uint64_t seed, int refine,
+                             double ess_floor, int refine_samples, int refine_stages, int64_t max_workspace_bytes,
+                             double* lppd, double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic,
+                             double* ess_mean, double* ess_min, int32_t* n_refined, int32_t* n_below,
+                             double* lpd_trace, double* ess_trace, double* ess_trace_first,
+                             int32_t* refined_index, double* refine_prop, double* refine_samples_out, int64_t* n_ref,
+                             int64_t capacity, int64_t ref_capacity);
+
 /* The fitted function of held-out, partly observed curves from the chain slots: bfmmm_chain_predict with the same
  * arguments -- the same samples, and lpd, z_mean, z_sd, ess_mean, ess_min and their traces bit for bit -- and, on the G rows of an
  * evaluation basis E (G x P row-major, rows in the sampler's basis as in bfmmm_chain_curve_bands; the identity for the
@@ -590,7 +623,10 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * new curves' records (0 launches for a handle of bfmmm_create_from_basis, whose records are formed on the host); "predict", the
  * device time and launches of k_predict and the pooling kernel after it (two per chunk).
  * Of the last bfmmm_chain_predict_fit (always measured): "predict_stats" as above; "predict_fit", the device time and launches of
- * k_predict_fit, the two pooling kernels and, where nq > 0, the quantiles of the paths (three or four per chunk). */
+ * k_predict_fit, the two pooling kernels and, where nq > 0, the quantiles of the paths (three or four per chunk).
+ * Of the last bfmmm_chain_loo_marginal (always measured): "loo_marginal", the device time and launches of the first pass, the
+ * counting kernel (twice) and, where pairs are refined, the list and refinement kernels (three to five per chunk);
+ * "loo_marginal_psis", those of the PSIS pass (one per chunk). */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
