@@ -1193,8 +1193,14 @@ struct FitAsk {
   int32_t* path_index;
   double *path_u, *path_xi;
 };
+// bfmmm_chain_predict_laplace (kernels_predict_laplace.hip): the same call with k_predict_lap in k_predict's place, one
+// round and no sample table; what it returns besides (each may be null)
+struct LapAsk {
+  int32_t* n_modes;
+  double *components, *eta_samples;
+};
 
-int predict_call(const char* name, const FitAsk* fit, bfmmm_handle* h, const double* y, const double* t, const double* B,
+int predict_call(const char* name, const FitAsk* fit, const LapAsk* lap, bfmmm_handle* h, const double* y, const double* t, const double* B,
                  const int64_t* offsets, int n_new, const double* X, const int32_t* perm, int first_slot, int n_slots, int n_samples,
                  int n_stages, uint64_t seed, const double* zs, int64_t max_workspace_bytes, double* lpd, double* z_mean, double* z_sd,
                  double* ess_mean, double* ess_min, double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace,
@@ -1244,16 +1250,20 @@ int predict_call(const char* name, const FitAsk* fit, bfmmm_handle* h, const dou
   if (zs && R != 1) return fail(fn + ": 'zs' takes the place of the stage-0 samples: 'n_stages' must be 1, got " + std::to_string(R));
   if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, n_new, "rows") || ck.row_limit()) return 1;
   // the RNG index ((r R + st) J + j) K + k is a 32-bit counter word
-  if (!zs && (long double)n_new * (long double)R * (long double)J * (long double)K > 4294967296.0L)
+  if (!zs && !lap && (long double)n_new * (long double)R * (long double)J * (long double)K > 4294967296.0L)
     return fail(fn + ": n_new x n_stages x n_samples x K = " + std::to_string(n_new) + " x " + std::to_string(R) + " x " + std::to_string(J) + " x " +
                 std::to_string(K) + " exceeds the 4294967296 (2^32) indices of the random number counter");
+  // (the mixture proposal: index (r J + j)(K + 1) + i)
+  if (lap && (long double)n_new * (long double)J * (long double)(K + 1) > 4294967296.0L)
+    return fail(fn + ": n_new x n_samples x (K + 1) = " + std::to_string(n_new) + " x " + std::to_string(J) + " x " + std::to_string(K + 1) +
+                " exceeds the 4294967296 (2^32) indices of the random number counter");
   if (perm && perm_check(ck, perm)) return 1;
   PredictCall f;
   f.n_new = n_new; f.J = J; f.R = R; f.first_slot = first_slot; f.n_slots = n_slots; f.seed = seed;
   PredictFitCall ff;
   if (fit) { ff.G = G; ff.noise = fit->noise; }
   ff.p = f;
-  const std::string bad = fit ? predict_fit_check(c, ff, nullptr) : predict_check(c, f, nullptr);
+  const std::string bad = fit ? predict_fit_check(c, ff, nullptr) : lap ? predict_lap_check(c, f, nullptr) : predict_check(c, f, nullptr);
   if (!bad.empty()) return fail(fn + ": " + bad);
   const size_t N = (size_t)ck.CS();
   const int Mn = d.M;
@@ -1269,8 +1279,11 @@ int predict_call(const char* name, const FitAsk* fit, bfmmm_handle* h, const dou
                                           (zs ? N * (size_t)J * K : 0) + 2) +
                         sizeof(int64_t) * (!mv && !from_basis ? (size_t)n_new + 1 : 0) + sizeof(int32_t) * (((size_t)n_new + 1) & ~(size_t)1) +
                         (perm ? sizeof(int32_t) * ((N * K + 1) & ~(size_t)1) : 0) + fit_shared;
+  // the mixture proposal of a curve: n_modes (an int a draw, counted as a double), the components and the samples where asked for
+  const size_t CD = (size_t)predict_lap_comp_doubles(K);
+  const size_t lap_curve = lap ? N * (1 + (lap->components ? (size_t)(K + 2) * CD : 0) + (lap->eta_samples ? (size_t)J * (K - 1) : 0)) : 0;
   const size_t per_curve = sizeof(double) * (N * (2 + 2 * (size_t)K + (prop_trace ? (size_t)R * K : 0) + (samples ? (size_t)R * J * K : 0)) + 3 + 2 * (size_t)K +
-                                             fit_curve);
+                                             fit_curve + lap_curve);
   const size_t budget = budget_of(max_workspace_bytes);
   if (samples && budget < shared + per_curve)
     return fail(fn + ": 'samples' of one curve (n_chains x n_slots x n_stages x n_samples x K doubles) with the rest need " +
@@ -1280,7 +1293,7 @@ int predict_call(const char* name, const FitAsk* fit, bfmmm_handle* h, const dou
   const int64_t cells = (int64_t)std::max<size_t>(1, per_curve / sizeof(double) / std::max<size_t>(N, 1));
   if (ck.units(budget, shared, per_curve, n_new, cells_cap(cells), "curve", &chunk)) return 1;
   HIPCHK(hipSetDevice(h->device));
-  const int pt = fit ? PT_PREDICT_FIT : PT_PREDICT;
+  const int pt = fit ? PT_PREDICT_FIT : lap ? PT_PREDICT_LAPLACE : PT_PREDICT;
   reset_timers(h, PT_PREDICT_STATS, PT_PREDICT_STATS);
   reset_timers(h, pt, pt);
   CallBufs b;
@@ -1343,6 +1356,13 @@ int predict_call(const char* name, const FitAsk* fit, bfmmm_handle* h, const dou
   if (prop_trace) HIPCHK(b.get(&d_prop, (size_t)chunk * NK * R));
   if (samples) HIPCHK(b.get(&d_smp, (size_t)chunk * NK * R * J));
   f.rec = d_rec; f.ni = d_ni; f.X = d_X; f.perm = d_perm; f.zs = d_zs;
+  int32_t* d_nm = nullptr;
+  double *d_comp = nullptr, *d_eta = nullptr;
+  if (lap) {
+    HIPCHK(b.get(&d_nm, (size_t)chunk * N));
+    if (lap->components) HIPCHK(b.get(&d_comp, (size_t)chunk * N * (K + 2) * CD));
+    if (lap->eta_samples) HIPCHK(b.get(&d_eta, (size_t)chunk * N * J * (K - 1)));
+  }
   double* d_lpd_t = d_tr;
   double* d_ess_t = d_lpd_t + (size_t)chunk * N;
   double* d_m_t = d_ess_t + (size_t)chunk * N;
@@ -1381,7 +1401,8 @@ int predict_call(const char* name, const FitAsk* fit, bfmmm_handle* h, const dou
     std::string err = timed(kernel, h->st, [&] {
       return fit ? launch_predict_fit(c, ff, (int)r0, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_prop, d_smp, d_mu_t, d_var_t, d_path_t, d_pidx, d_pu,
                                       d_pxi, h->st)
-                 : launch_predict(c, f, (int)r0, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_prop, d_smp, h->st);
+             : lap ? launch_predict_lap(c, f, (int)r0, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_nm, d_comp, d_eta, h->st)
+                   : launch_predict(c, f, (int)r0, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_prop, d_smp, h->st);
     });
     if (err.empty() && fit) {
       // (the pooled rows of the chunk are consecutive from 0 in every buffer: launch_predict_fit wrote rows of G N)
@@ -1398,6 +1419,9 @@ int predict_call(const char* name, const FitAsk* fit, bfmmm_handle* h, const dou
     }
     if (err.empty())
       err = timed(pool, h->st, [&] { return launch_predict_pool(K, (long long)N, rows, d_lpd_t, d_ess_t, d_m_t, d_q_t, d_lpd, d_zm, d_zsd, d_emean, d_emin, h->st); });
+    if (err.empty() && lap)
+      err = Back{h, r0, rows}(lap->n_modes, (const int32_t*)d_nm, N)(lap->components, (const double*)d_comp, N * (K + 2) * CD)(
+                lap->eta_samples, (const double*)d_eta, N * (size_t)J * (K - 1)).queued();
     if (err.empty())
       err = Back{h, r0, rows}(lpd_trace, d_lpd_t, N)(ess_trace, d_ess_t, N)(z_trace, d_m_t, NK)(prop_trace, d_prop, NK * R)(samples, d_smp, NK * R * J)(
                 lpd, d_lpd, 1)(ess_mean, d_emean, 1)(ess_min, d_emin, 1)(z_mean, d_zm, K)(z_sd, d_zsd, K).done();
@@ -1418,7 +1442,7 @@ extern "C" int bfmmm_chain_predict(bfmmm_handle* h, const double* y, const doubl
                                    double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min,
                                    double* lpd_trace, double* z_trace, double* ess_trace, double* prop_trace, double* samples,
                                    int64_t capacity) {
-  return predict_call("bfmmm_chain_predict", nullptr, h, y, t, B, offsets, n_new, X, perm, first_slot, n_slots, n_samples, n_stages, seed, zs,
+  return predict_call("bfmmm_chain_predict", nullptr, nullptr, h, y, t, B, offsets, n_new, X, perm, first_slot, n_slots, n_samples, n_stages, seed, zs,
                       max_workspace_bytes, lpd, z_mean, z_sd, ess_mean, ess_min, lpd_trace, z_trace, ess_trace, prop_trace, samples, capacity);
 }
 
@@ -1432,8 +1456,19 @@ extern "C" int bfmmm_chain_predict_fit(bfmmm_handle* h, const double* y, const d
                                        double* mean_trace, double* var_trace, double* path_trace, int32_t* path_index, double* path_u,
                                        double* path_xi, int64_t capacity) {
   const FitAsk fit{E, G, noise ? 1 : 0, probs, nq, fit_mean, fit_sd, fit_q, mean_trace, var_trace, path_trace, path_index, path_u, path_xi};
-  return predict_call("bfmmm_chain_predict_fit", &fit, h, y, t, B, offsets, n_new, X, perm, first_slot, n_slots, n_samples, n_stages, seed, zs,
+  return predict_call("bfmmm_chain_predict_fit", &fit, nullptr, h, y, t, B, offsets, n_new, X, perm, first_slot, n_slots, n_samples, n_stages, seed, zs,
                       max_workspace_bytes, lpd, z_mean, z_sd, ess_mean, ess_min, lpd_trace, z_trace, ess_trace, prop_trace, samples, capacity);
+}
+
+extern "C" int bfmmm_chain_predict_laplace(bfmmm_handle* h, const double* y, const double* t, const double* B, const int64_t* offsets,
+                                           int n_new, const double* X, const int32_t* perm, int first_slot, int n_slots, int n_samples,
+                                           uint64_t seed, int64_t max_workspace_bytes,
+                                           double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min,
+                                           double* lpd_trace, double* z_trace, double* ess_trace,
+                                           int32_t* n_modes, double* components, double* eta_samples, int64_t capacity) {
+  const LapAsk lap{n_modes, components, eta_samples};
+  return predict_call("bfmmm_chain_predict_laplace", nullptr, &lap, h, y, t, B, offsets, n_new, X, perm, first_slot, n_slots, n_samples, 1, seed,
+                      nullptr, max_workspace_bytes, lpd, z_mean, z_sd, ess_mean, ess_min, lpd_trace, z_trace, ess_trace, nullptr, nullptr, capacity);
 }
 
 // ---- marginal PSIS-LOO over curves, the memberships integrated out (kernels_loo_marginal.hip) ------------------------
@@ -1578,4 +1613,89 @@ extern "C" int bfmmm_chain_loo_marginal(bfmmm_handle* h, int first_slot, int n_s
   });
   if (n_ref) *n_ref = total_ref;
   return rc;
+}
+
+// ---- the marginal PSIS-LOO under the Laplace mixture proposal (kernels_predict_laplace.hip) --------------------------
+// Per chunk of consecutive curves: k_predict_lap on the resident records as the first and only pass (as bfmmm_chain_loo_marginal
+// runs k_predict on them), k_lz_count for what is reported and post_psis_device on the chunk's lpd_t.  There is no refinement.
+extern "C" int bfmmm_chain_loo_marginal_laplace(bfmmm_handle* h, int first_slot, int n_slots, int n_samples, uint64_t seed, double ess_floor,
+                                                int64_t max_workspace_bytes,
+                                                double* lppd, double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic,
+                                                double* p_waic, double* ess_mean, double* ess_min, int32_t* n_below,
+                                                double* lpd_trace, double* ess_trace, int32_t* n_modes, double* components,
+                                                double* eta_samples, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_loo_marginal_laplace", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"h", h}, {"lppd", lppd}, {"elpd_loo", elpd_loo}, {"p_loo", p_loo}, {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic},
+               {"p_waic", p_waic}, {"ess_mean", ess_mean}, {"ess_min", ess_min}, {"n_below", n_below}}))
+    return 1;
+  const int J = n_samples;
+  if (J < 1) return fail(fn + ": 'n_samples' must be at least 1, got " + std::to_string(J));
+  if (!(std::isfinite(ess_floor) && ess_floor >= 0.0)) return fail(fn + ": 'ess_floor' must be finite and not negative, got " + std::to_string(ess_floor));
+  const Ctx& c = h->c;
+  const Dims& d = c.d;
+  const int n = d.n, K = d.K;
+  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, n, "rows") || ck.row_limit()) return 1;
+  // the RNG index (i J + j)(K + 1) + . is a 32-bit counter word
+  if ((long double)n * (long double)J * (long double)(K + 1) > 4294967296.0L)
+    return fail(fn + ": n x n_samples x (K + 1) = " + std::to_string(n) + " x " + std::to_string(J) + " x " + std::to_string(K + 1) +
+                " exceeds the 4294967296 (2^32) indices of the random number counter");
+  PredictCall f;
+  f.n_new = n; f.J = J; f.R = 1; f.first_slot = first_slot; f.n_slots = n_slots; f.seed = seed;
+  f.rec = c.rec; f.ni = c.ni; f.X = c.X;
+  const std::string bad = predict_lap_check(c, f, nullptr);
+  if (!bad.empty()) return fail(fn + ": " + bad);
+  const size_t N = (size_t)ck.CS(), CD = (size_t)predict_lap_comp_doubles(K);
+  // a curve: lpd_t and ess_t (2 N), n_modes (an int a draw, counted as a double), ess_mean and ess_min, the count; the components
+  // and the samples where asked for
+  const size_t per_curve = sizeof(double) * (N * (3 + (components ? (size_t)(K + 2) * CD : 0) + (eta_samples ? (size_t)J * (K - 1) : 0)) + 2) +
+                           sizeof(int32_t) * 2;
+  const size_t budget = budget_of(max_workspace_bytes);
+  int64_t chunk = 0;
+  const int64_t cells = (int64_t)std::max<size_t>(1, per_curve / sizeof(double) / std::max<size_t>(N, 1));
+  if (ck.units(budget, 0, per_curve, n, cells_cap(cells), "curve", &chunk)) return 1;
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_LOO_MARGINAL_PSIS, PT_LOO_MARGINAL_PSIS);
+  reset_timers(h, PT_LOO_MARGINAL_LAPLACE, PT_LOO_MARGINAL_LAPLACE);
+  CallBufs b;
+  double *d_tr = nullptr, *d_out = nullptr, *d_comp = nullptr, *d_eta = nullptr;
+  int32_t *d_below = nullptr, *d_nm = nullptr;
+  Timer first, pool, psis;
+  HIPCHK(b.timers({&first, &pool, &psis}));
+  HIPCHK(b.get(&d_tr, (size_t)chunk * 2 * N));
+  HIPCHK(b.get(&d_out, 2 * (size_t)chunk));
+  HIPCHK(b.get(&d_below, (size_t)chunk));
+  HIPCHK(b.get(&d_nm, (size_t)chunk * N));
+  if (components) HIPCHK(b.get(&d_comp, (size_t)chunk * N * (K + 2) * CD));
+  if (eta_samples) HIPCHK(b.get(&d_eta, (size_t)chunk * N * J * (K - 1)));
+  double* d_lpd_t = d_tr;
+  double* d_ess_t = d_lpd_t + (size_t)chunk * N;
+  double* d_emean = d_out;
+  double* d_emin = d_emean + chunk;
+  return for_chunks(ck, n, chunk, [&](int64_t r0, int rows) {
+    std::string err = timed(first, h->st, [&] {
+      return launch_predict_lap(c, f, (int)r0, rows, d_lpd_t, d_ess_t, nullptr, nullptr, d_nm, d_comp, d_eta, h->st);
+    });
+    if (err.empty())
+      err = timed(pool, h->st, [&] { return launch_lz_count((long long)N, rows, d_lpd_t, d_ess_t, ess_floor, d_below, d_emean, d_emin, h->st); });
+    if (err.empty())
+      err = Back{h, r0, rows}(n_modes, (const int32_t*)d_nm, N)(components, (const double*)d_comp, N * (K + 2) * CD)(
+                eta_samples, (const double*)d_eta, N * (size_t)J * (K - 1)).queued();
+    if (err.empty())
+      err = Back{h, r0, rows}(lpd_trace, (const double*)d_lpd_t, N)(ess_trace, (const double*)d_ess_t, N)(ess_mean, (const double*)d_emean, 1)(
+                ess_min, (const double*)d_emin, 1)(n_below, (const int32_t*)d_below, 1).done();
+    if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
+    if (!err.empty()) return err;
+    collect(h, first, PT_LOO_MARGINAL_LAPLACE);
+    collect(h, pool, PT_LOO_MARGINAL_LAPLACE);
+    // post_psis_device runs on the device's default stream: done() has drained the sampler's
+    double* const outs[6] = {lppd + r0, elpd_loo + r0, p_loo + r0, pareto_k + r0, elpd_waic + r0, p_waic + r0};
+    (void)hipEventRecord(psis.from, nullptr);
+    const int prc = post_psis_device(d_lpd_t, (long long)N, rows, (int)N, outs);
+    (void)hipEventRecord(psis.to, nullptr);
+    if (prc) return std::string(bfmmm_entry_last_error());
+    if (hipEventSynchronize(psis.to) != hipSuccess) return std::string(kBackFailed);
+    collect(h, psis, PT_LOO_MARGINAL_PSIS);
+    return err;
+  });
 }

@@ -37,7 +37,7 @@ enum { FAM_TOTAL = 0, FAM_Z, FAM_PG, FAM_FACTOR, FAM_SWEEP, FAM_CHI, FAM_LOGLIK,
 enum { PT_CURVE_LL = 0, PT_FIT_PROJECT, PT_FIT_ROWS, PT_FIT_VALUES, PT_FIT_REDUCE, PT_SIM, PT_SIM_REDUCE, PT_SIMILARITY,
        PT_COV_PROJECT, PT_COV, PT_SIM_LOSS, PT_SIM_LOSS_REDUCE, PT_ALIGN_GRAM, PT_ALIGN_GATHER, PT_ALIGN_PROJECT,
        PT_CCOV_PROJECT, PT_CCOV, PT_CCOV_MAXDEV, PT_CEIG_GRAM, PT_CEIG, PT_CEIG_VALUES, PT_PREDICT_STATS, PT_PREDICT, PT_PREDICT_FIT,
-       PT_LOO_MARGINAL, PT_LOO_MARGINAL_PSIS, PT_COUNT };
+       PT_LOO_MARGINAL, PT_LOO_MARGINAL_PSIS, PT_PREDICT_LAPLACE, PT_LOO_MARGINAL_LAPLACE, PT_COUNT };
 inline constexpr const char* kPostNames[PT_COUNT] = {"curve_ll_ms", "curve_fit_project", "curve_fit_rows", "curve_fit_values",
                                                      "curve_fit_reduce", "curve_sim", "curve_sim_reduce", "similarity",
                                                      "curve_cov_project", "curve_cov", "similarity_loss", "similarity_loss_reduce",
@@ -45,7 +45,8 @@ inline constexpr const char* kPostNames[PT_COUNT] = {"curve_ll_ms", "curve_fit_p
                                                      "cluster_cov_project", "cluster_cov", "cluster_cov_maxdev",
                                                      "cluster_eig_gram", "cluster_eig", "cluster_eig_values",
                                                      "predict_stats", "predict", "predict_fit",
-                                                     "loo_marginal", "loo_marginal_psis"};
+                                                     "loo_marginal", "loo_marginal_psis", "predict_laplace",
+                                                     "loo_marginal_laplace"};
 
 struct bfmmm_handle {
   bfmmm_config cfg;

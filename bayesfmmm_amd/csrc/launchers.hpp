@@ -299,6 +299,17 @@ std::string launch_lz_list(long long N, int S, int r0, int rows, const double* l
 std::string launch_lz_refine(const Ctx& c, const PredictCall& f, int r0, int rows, const int32_t* list, long long n_list, double* lpd_t,
                              double* ess_t, const double* a_last, double* prop, double* samples, hipStream_t st);
 
+// ---- kernels_predict_laplace.hip ----
+// The Laplace mixture proposal for the integral of bfmmm_chain_predict: f.R and f.zs are not read.
+// "" or what k_predict_lap cannot take; *lds_bytes: the dynamic LDS a workgroup needs
+std::string predict_lap_check(const Ctx& c, const PredictCall& f, size_t* lds_bytes);
+// the doubles of one slot of `comps`: the centre (K - 1), the packed lower L ((K - 1) K / 2), g_c and J_c
+int predict_lap_comp_doubles(int K);
+// launch_predict's lpd_t, ess_t, m_t and q_t of the chunk under the mixture proposal, and n_modes [r N + cs], comps
+// [((r N + cs)(K + 2) + c) predict_lap_comp_doubles(K) + .] and eta [((r N + cs) J + j)(K - 1) + i] (the last two may be null)
+std::string launch_predict_lap(const Ctx& c, const PredictCall& f, int r0, int rows, double* lpd_t, double* ess_t, double* m_t, double* q_t,
+                               int32_t* n_modes, double* comps, double* eta, hipStream_t st);
+
 // ---- kernels_bands.hip ----
 // The column reductions of the credible-band entry points on device tables V[t + T col], on stream st.  quantiles: LDS sort
 // for T <= 8192 (W unused), else k_bands_quantiles_big over the workspace W of NP ncol doubles, NP = bands_sort_pad(T), which

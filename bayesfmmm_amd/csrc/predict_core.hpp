@@ -3,6 +3,7 @@
 // of kernels_predict.hip's header, the tables Gamma and tau and the R stages of the importance sampler.  Written once, so that the two
 // kernels draw the same samples and return the same lpd, ess and memberships bit for bit.  k_lz_refine (kernels_loo_marginal.hip;
 // 7o) runs the same set-up and draw once more for a listed (curve, draw) pair, from a given starting proposal (pred_draw<KT, true>).
+// k_predict_lap (kernels_predict_laplace.hip; 7p) shares the set-up and steps (1) to (3), pred_tables, and has stages of its own.
 #pragma once
 #include "model.hpp"
 #include "launchers.hpp"
@@ -187,20 +188,12 @@ __device__ inline void pred_setup(const PredArgs& a, const PredLds& L, double* s
   for (int e = tid; e < L.AP * L.PS; e += PR_NT) { sTh[e] = 0.0; sH[e] = 0.0; }
 }
 
-// One draw of new curve r (row rr of the chunk), chain q_chain, slot s (relative to first_slot): steps (1) to (4) into the chunk's
-// traces.  It leaves in LDS theta (sm + L.th, rows and columns padded with zeros), sigma^2 (PP_SIG), the last stage's samples z
-// [k J + j] and their weights w_j = exp(lw_j - max) (sm + L.lw), and in the lanes' Q columns what pred_ell left for the samples of
-// the last pass of the lanes (j >= J - J % 256, or the last 256).  Returns the sum of those weights, the same bits on every thread.
-// KT: the compile-time bound on K (4 or KMAX), so that a lane's z stays in registers.
-// START (k_lz_refine of kernels_loo_marginal.hip; DESIGN.md 7o): stage 0 proposes from a.a_start of the draw's row in place of the
-// prior, so the Dirichlet correction applies in stage 0 as well; the variates come under UPD_LOO_REFINE, and the proposals and
-// samples go to row prow of a.prop and a.samples, the pair's place in the list, not to the draw's row of the traces.
-template <int KT, bool START = false>
-__device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* sm, const PredSlots& ch, int r, int rr, int q_chain, int s,
-                                   double yy, int ni, size_t prow = 0) {
-  constexpr int NV = 2 + 2 * KT;
+// Steps (1) to (3) of a draw at slot t of the workgroup's chain: theta, H, tau and Gamma into LDS, the draw's prior alpha_3 pi
+// (PP_PRIOR) and sigma^2 (PP_SIG) into L.par.  It opens with the barrier that ends the previous draw's reads (and the set-up) and
+// closes with the one behind Gamma.  pred_draw and k_predict_lap (kernels_predict_laplace.hip) both run it.
+__device__ inline void pred_tables(const PredArgs& a, const PredLds& L, double* sm, const PredSlots& ch, size_t t) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = a.K, P = a.P, M = a.M, D = a.D, M1 = M + 1, BW = a.BW, LG = a.LG, J = a.J, R = a.R;
+  const int K = a.K, P = a.P, M = a.M, D = a.D, M1 = M + 1, BW = a.BW, LG = a.LG;
   const int A = L.A, AP = L.AP, PS = L.PS, GS = L.GS;
   double* sRec = sm + L.rec;
   double* sX = sm + L.x;
@@ -208,20 +201,8 @@ __device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* 
   double* sH = sm + L.h;
   double* sTau = sm + L.tau;
   double* sGam = sm + L.gam;
-  double* sQ = sm + L.q + tid;
-  double* sZ = sm + L.z;           // [k J + j]
-  double* sLw = sm + L.lw;
-  double* sRed = sm + L.red;
   double* sPar = sm + L.par;
-  const long long N = (long long)a.C * a.S;
   const double *c_nu = ch.c_nu, *c_Phi = ch.c_Phi, *c_eta = ch.c_eta, *c_xi = ch.c_xi;
-
-  const size_t t = (size_t)(a.first_slot + s);
-  const long long cs = (long long)q_chain * a.S + s;
-  const size_t row = (size_t)rr * (size_t)N + (size_t)cs;
-  if (!START) prow = row;
-  constexpr uint32_t upd = START ? UPD_LOO_REFINE : UPD_PREDICT;
-  double sw_last = 0.0;
   __syncthreads();                            // the previous draw's readers are done (and the set-up)
   // (1) theta, directions-major, x folded in (nu: [k + K p], Phi: [k + K (p + P m)], eta: [p + P (d + D k)], xi: [p + P (d + D (m + M k))])
   for (int e = tid; e < A * P; e += PR_NT) {
@@ -277,6 +258,39 @@ __device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* 
     }
   }
   __syncthreads();
+}
+
+// One draw of new curve r (row rr of the chunk), chain q_chain, slot s (relative to first_slot): steps (1) to (4) into the chunk's
+// traces.  It leaves in LDS theta (sm + L.th, rows and columns padded with zeros), sigma^2 (PP_SIG), the last stage's samples z
+// [k J + j] and their weights w_j = exp(lw_j - max) (sm + L.lw), and in the lanes' Q columns what pred_ell left for the samples of
+// the last pass of the lanes (j >= J - J % 256, or the last 256).  Returns the sum of those weights, the same bits on every thread.
+// KT: the compile-time bound on K (4 or KMAX), so that a lane's z stays in registers.
+// START (k_lz_refine of kernels_loo_marginal.hip; DESIGN.md 7o): stage 0 proposes from a.a_start of the draw's row in place of the
+// prior, so the Dirichlet correction applies in stage 0 as well; the variates come under UPD_LOO_REFINE, and the proposals and
+// samples go to row prow of a.prop and a.samples, the pair's place in the list, not to the draw's row of the traces.
+template <int KT, bool START = false>
+__device__ inline double pred_draw(const PredArgs& a, const PredLds& L, double* sm, const PredSlots& ch, int r, int rr, int q_chain, int s,
+                                   double yy, int ni, size_t prow = 0) {
+  constexpr int NV = 2 + 2 * KT;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = a.K, M = a.M, J = a.J, R = a.R;
+  const int GS = L.GS;
+  double* sTau = sm + L.tau;
+  double* sGam = sm + L.gam;
+  double* sQ = sm + L.q + tid;
+  double* sZ = sm + L.z;           // [k J + j]
+  double* sLw = sm + L.lw;
+  double* sRed = sm + L.red;
+  double* sPar = sm + L.par;
+  const long long N = (long long)a.C * a.S;
+
+  const size_t t = (size_t)(a.first_slot + s);
+  const long long cs = (long long)q_chain * a.S + s;
+  const size_t row = (size_t)rr * (size_t)N + (size_t)cs;
+  if (!START) prow = row;
+  constexpr uint32_t upd = START ? UPD_LOO_REFINE : UPD_PREDICT;
+  double sw_last = 0.0;
+  pred_tables(a, L, sm, ch, t);
 
   // (4) the stages
   const double sig = sPar[PP_SIG];

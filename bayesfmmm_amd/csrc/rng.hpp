@@ -28,7 +28,8 @@ enum UpdId : uint32_t {
   UPD_SAMPLE_PATH = 41,     // posterior-predictive draws of FSamplePaths (kernels_post.hip)
   UPD_PREDICT = 42,         // membership samples of held-out curves (kernels_predict.hip)
   UPD_PREDICT_FIT = 43,     // the sampled path of a held-out curve's fitted function (kernels_predict_fit.hip)
-  UPD_LOO_REFINE = 44       // membership samples of the refined (curve, draw) pairs of the marginal LOO (kernels_loo_marginal.hip)
+  UPD_LOO_REFINE = 44,      // membership samples of the refined (curve, draw) pairs of the marginal LOO (kernels_loo_marginal.hip)
+  UPD_PREDICT_LAPLACE = 45  // the normals and uniforms of the Laplace mixture proposal (kernels_predict_laplace.hip)
 };
 
 struct RngKey {

@@ -4,6 +4,8 @@ All arrays cross the boundary in the reference's layouts (column-major, R/Armadi
 numpy arrays returned here are Fortran-ordered with the reference's shapes.
 """
 import ctypes as C
+import functools
+import inspect
 
 import numpy as np
 
@@ -35,6 +37,32 @@ def _dp(a):
 
 def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _proposal_option(laplace, refused):
+    """Gives a method the keyword-only option proposal="dirichlet" | "laplace" (DESIGN.md 7p).  "dirichlet", the default, calls the
+    method as it is, with its own parameters and defaults, which are what inspect.signature shows.  "laplace" calls the method named
+    `laplace` with the same arguments, once every parameter of refused = {name: test} that the caller gave, and whose value the test
+    marks as without meaning there, has been refused by name: a wrapper sees which arguments were given, where the method itself
+    could not tell a given refine=True from its default."""
+    def deco(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def call(self, *args, proposal="dirichlet", **kw):
+            if proposal == "dirichlet":
+                return fn(self, *args, **kw)
+            if proposal != "laplace":
+                raise ValueError(f"{fn.__name__}: proposal must be 'dirichlet' or 'laplace', got {proposal!r}")
+            b = sig.bind(self, *args, **kw)
+            for name, without_meaning in refused.items():
+                if name in b.arguments and without_meaning(b.arguments[name]):
+                    raise ValueError(f"{fn.__name__}: '{name}' has no meaning with proposal='laplace' (one round, no sample table, no "
+                                     f"refinement): leave it at its default")
+            b.apply_defaults()
+            return getattr(self, laplace)(**{k: v for k, v in b.arguments.items() if k != "self" and k not in refused})
+        return call
+    return deco
 
 
 def _probs_arg(probs):
@@ -245,6 +273,8 @@ class Sampler:
 
     REFINE_TRACE_BYTES = 512 << 20      # loo_marginal(trace=True): the most "refine_prop" and "refine_samples" may take on the host
 
+    @_proposal_option("_loo_marginal_laplace", {"n_stages": lambda v: v != 3, "refine": bool, "refine_samples": lambda v: v is not None,
+                                                "refine_stages": lambda v: v != 2})
     def loo_marginal(self, first_slot=0, n_slots=None, n_samples=256, n_stages=3, seed=1, refine=True, ess_floor=10.0,
                      refine_samples=None, refine_stages=2, trace=False, max_workspace_bytes=0):
         """PSIS-LOO and WAIC over curves with the memberships integrated out (bfmmm_chain_loo_marginal).  `loo` runs
@@ -261,7 +291,12 @@ class Sampler:
         refinement, "ess_trace_first": (n, C, S) before it, "refined_index": (n_ref, 3), the (curve, chain, slot relative to
         first_slot) of the refined pairs in increasing order, and, for tests and small shapes (where they would take no more than
         REFINE_TRACE_BYTES if every pair were refined), "refine_prop": (n_ref, R2, K) and "refine_samples": (n_ref, R2, J2, K), which then
-        takes the place of the parameter of that name.  All chains of the batch, pooled, on one device."""
+        takes the place of the parameter of that name.  All chains of the batch, pooled, on one device.
+        The keyword proposal="laplace" (bfmmm_chain_loo_marginal_laplace) takes the integral in one round from `predict`'s mixture of
+        Student-t components at the modes of the integrand: the traces of predict(Y, time, proposal="laplace", trace=True) bit for bit,
+        no stages and no refinement -- n_stages other than its default and refine=True, refine_samples or refine_stages given
+        explicitly are refused.  The result then holds "n_modes_mean": (n,) in place of "n_refined" and the refinement's parameters,
+        and trace adds "n_modes", "components" and "eta_samples" as `predict` does."""
         from . import api
         S = self._slots(first_slot, n_slots)
         n, Cn, K, Sn = self.n, self.n_chains, self.K, max(S, 0)
@@ -292,6 +327,31 @@ class Sampler:
             out["refined_index"] = idx[:m].copy()
             if prop is not None:
                 out["refine_prop"], out["refine_samples"] = prop[:m].copy(), smp[:m].copy()
+        return out
+
+    def _loo_marginal_laplace(self, first_slot, n_slots, n_samples, seed, ess_floor, trace, max_workspace_bytes):
+        """loo_marginal(proposal="laplace")"""
+        from . import api
+        S = self._slots(first_slot, n_slots)
+        n, Cn, K, Sn, J = self.n, self.n_chains, self.K, max(S, 0), int(n_samples)
+        d = K - 1
+        outs = [np.zeros(n) for _ in range(8)]
+        n_below, n_modes = np.zeros(n, dtype=np.int32), np.zeros((n, Cn, Sn), dtype=np.int32)
+        tr = {}
+        if trace:
+            tr = {"lpd_trace": np.zeros((n, Cn, Sn)), "ess_trace": np.zeros((n, Cn, Sn)),
+                  "components": np.zeros((n, Cn, Sn, K + 2, d + d * (d + 1) // 2 + 2)), "eta_samples": np.zeros((n, Cn, Sn, max(J, 0), d))}
+        opt = lambda k: _dp(tr[k]) if k in tr else None
+        _lib.check(self.lib.bfmmm_chain_loo_marginal_laplace(
+            self.h, int(first_slot), S, J, int(seed), float(ess_floor), int(max_workspace_bytes), *[_dp(o) for o in outs], _ip(n_below),
+            opt("lpd_trace"), opt("ess_trace"), _ip(n_modes), opt("components"), opt("eta_samples"), n))
+        pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs[:6]))
+        out = api.loo_totals(pw, Cn * S)
+        out.update(ess_mean=outs[6], ess_min=outs[7], n_below=n_below, n_modes_mean=n_modes.mean(axis=(1, 2)), n_samples=J,
+                   ess_floor=float(ess_floor), proposal="laplace")
+        out.update(tr)
+        if trace:
+            out["n_modes"] = n_modes
         return out
 
     def _fit_args(self, E, which, curves, first_slot, n_slots):
@@ -585,6 +645,7 @@ class Sampler:
         out["max_sweeps"] = int(ms.value)
         return out
 
+    @_proposal_option("_predict_laplace", {"n_stages": lambda v: v != 3, "z_samples": lambda v: v is not None, "return_samples": bool})
     def predict(self, Y_new, time_new=None, basis_new=None, X_new=None, perm=None, n_samples=256, n_stages=3, seed=1,
                 trace=False, z_samples=None, return_samples=False, first_slot=0, n_slots=None, max_workspace_bytes=0):
         """Held-out curves under the fitted model (bfmmm_chain_predict): for every new curve the log predictive
@@ -602,9 +663,20 @@ class Sampler:
         predictive law, "ess_mean", "ess_min": (m,), the importance-sampling effective sample size of the last round over the draws,
         "n_samples", "n_stages"}.  A curve whose ess_min is small against n_samples (below 10, say) is not to be trusted: raise
         n_stages or n_samples.  trace adds "lpd_trace", "ess_trace": (m, C, S), "Z_trace": (m, C, S, K) and "proposal": (m, C, S, R, K);
-        return_samples adds "samples": (m, C, S, R, J, K), for small shapes."""
+        return_samples adds "samples": (m, C, S, R, J, K), for small shapes.
+        The keyword proposal="laplace" (bfmmm_chain_predict_laplace) takes the same integral in one round of n_samples samples from
+        a mixture of Student-t components at the modes of the integrand over the log-ratios of Z_new, found by a damped Newton search
+        from K + 1 starts, with a defensive component at the prior: n_stages other than its default, z_samples and return_samples are
+        refused.  The result then holds "n_modes_mean": (m,), the modes kept per draw ("n_stages" is 1), and trace adds "n_modes":
+        (m, C, S), "components": (m, C, S, K + 2, d + d (d + 1) / 2 + 2) -- centre, L packed by rows, g_c and J_c of component c, d = K - 1
+        -- and "eta_samples": (m, C, S, J, d) in place of "proposal"."""
         return self._predict_call(None, Y_new, time_new, basis_new, X_new, perm, n_samples, n_stages, seed, trace, z_samples,
                                   return_samples, first_slot, n_slots, max_workspace_bytes)
+
+    def _predict_laplace(self, Y_new, time_new, basis_new, X_new, perm, n_samples, seed, trace, first_slot, n_slots, max_workspace_bytes):
+        """predict(..., proposal="laplace")"""
+        return self._predict_call(None, Y_new, time_new, basis_new, X_new, perm, n_samples, 1, seed, trace, None, False, first_slot, n_slots,
+                                  max_workspace_bytes, laplace=True)
 
     def predict_fit(self, Y_new, E, time_new=None, basis_new=None, X_new=None, perm=None, probs=(0.025, 0.5, 0.975), noise=False,
                     n_samples=256, n_stages=3, seed=1, trace=False, z_samples=None, first_slot=0, n_slots=None, max_workspace_bytes=0):
@@ -625,7 +697,7 @@ class Sampler:
                                   first_slot, n_slots, max_workspace_bytes)
 
     def _predict_call(self, fit, Y_new, time_new, basis_new, X_new, perm, n_samples, n_stages, seed, trace, z_samples, return_samples,
-                      first_slot, n_slots, max_workspace_bytes):
+                      first_slot, n_slots, max_workspace_bytes, laplace=False):
         """The arguments of `predict` marshalled and bfmmm_chain_predict called, or with fit = {"E", "probs", "noise"}
         bfmmm_chain_predict_fit"""
         S = self._slots(first_slot, n_slots)
@@ -668,8 +740,9 @@ class Sampler:
         out = {"lpd": np.zeros(m), "Z_mean": np.zeros((m, K)), "Z_sd": np.zeros((m, K)), "ess_mean": np.zeros(m), "ess_min": np.zeros(m)}
         tr = {}
         if trace:
-            tr = {"lpd_trace": np.zeros((m, Cn, Sn)), "ess_trace": np.zeros((m, Cn, Sn)), "Z_trace": np.zeros((m, Cn, Sn, K)),
-                  "proposal": np.zeros((m, Cn, Sn, max(R, 0), K))}
+            tr = {"lpd_trace": np.zeros((m, Cn, Sn)), "ess_trace": np.zeros((m, Cn, Sn)), "Z_trace": np.zeros((m, Cn, Sn, K))}
+            if not laplace:
+                tr["proposal"] = np.zeros((m, Cn, Sn, max(R, 0), K))
         if return_samples:
             tr["samples"] = np.zeros((m, Cn, Sn, max(R, 0), max(J, 0), K))
         opt = lambda k: _dp(tr[k]) if k in tr else None
@@ -678,7 +751,18 @@ class Sampler:
                 None if p is None else _ip(p), int(first_slot), S, J, R, int(seed), None if zs is None else _dp(zs))
         pooled = (_dp(out["lpd"]), _dp(out["Z_mean"]), _dp(out["Z_sd"]), _dp(out["ess_mean"]), _dp(out["ess_min"]))
         traces = (opt("lpd_trace"), opt("Z_trace"), opt("ess_trace"), opt("proposal"), opt("samples"))
-        if fit is None:
+        if laplace:
+            d = K - 1
+            n_modes = np.zeros((m, Cn, Sn), dtype=np.int32)
+            if trace:
+                tr["components"] = np.zeros((m, Cn, Sn, K + 2, d + d * (d + 1) // 2 + 2))
+                tr["eta_samples"] = np.zeros((m, Cn, Sn, max(J, 0), d))
+            _lib.check(self.lib.bfmmm_chain_predict_laplace(*head[:11], int(seed), int(max_workspace_bytes), *pooled, *traces[:3], _ip(n_modes),
+                                                            opt("components"), opt("eta_samples"), m))
+            out["n_modes_mean"] = n_modes.mean(axis=(1, 2)) if Cn * Sn > 0 else np.zeros(m)
+            if trace:
+                tr["n_modes"] = n_modes
+        elif fit is None:
             _lib.check(self.lib.bfmmm_chain_predict(*head, int(max_workspace_bytes), *pooled, *traces, m))
         else:
             Em, pr = fit["E"], fit["probs"]

@@ -514,6 +514,39 @@ int bfmmm_chain_loo_marginal(bfmmm_handle* h, int first_slot, int n_slots, int n
                              int32_t* refined_index, double* refine_prop, double* refine_samples_out, int64_t* n_ref,
                              int64_t capacity, int64_t ref_capacity);
 
+/* The Laplace mixture proposal for the same integral.  bfmmm_chain_predict_laplace is bfmmm_chain_predict without
+ * n_stages and zs: per (curve r, chain q, slot t) log p(y_r | draw) = log int exp g(eta) d eta over the log-ratios eta (d = K - 1,
+ * z_k = e^eta_k / (1 + sum e^eta), z_K = 1 / (1 + sum e^eta)) of g(eta) = l(z) + sum_k alpha_k log z_k - lB(alpha), alpha = alpha_3 pi,
+ * by one round of n_samples = J importance samples from a mixture of Student-t components with 4 degrees of freedom.  Component 0 is
+ * always there: centre the log-ratios of alpha / alpha_0, scale [alpha_0 (diag p - p p')]^-1, J_0 = max(1, J / 16) samples.  The
+ * others are the modes a damped Newton ascent finds from K + 1 starts (alpha / alpha_0, and for each k 0.9 at k with 0.1 / (K - 1)
+ * elsewhere; a start counts where -H is positive definite and grad'(-H)^-1 grad < 1e-6 within 40 steps; a mode within 1e-3 of an
+ * earlier one is dropped): centre eta_c, scale (-H_c)^-1 = L_c L_c', J_c = floor((J - J_0) w_c) with w_c ~ exp(g_c) prod diag L_c and
+ * the remainder to the heaviest.  Samples are contiguous by component: eta_j = eta_c + L_c eps_j sqrt(4 / chi2_j), chi2 = -2 log(U1
+ * U2), keyed by (seed, the RNG chain id, the slot) under an update id of its own, index (r J + j)(d + 2) + i.  lw_j = g(eta_j) - log
+ * sum_c (J_c / J) t4(eta_j; eta_c, L_c); lpd, ess, z_mean and z_sd as bfmmm_chain_predict forms them.  Where no start converges only
+ * component 0 is left (J_0 = J): a valid estimate with a low ess, which ess_min shows.
+ * Outputs of bfmmm_chain_predict (without prop_trace and samples) and, optional (NULL: not copied): n_modes [r N + cs], the modes
+ * kept; components [((r N + cs)(K + 2) + c) CD + .], CD = d + d (d + 1) / 2 + 2: centre, L packed by rows, g_c and J_c of slot c
+ * (unused slots are zero); eta_samples [((r N + cs) J + j) d + i].
+ * Refused by name: what bfmmm_chain_predict refuses, n_new J (K + 1) above 2^32 (the RNG index) and tables, search scratch and
+ * samples above 160 KiB of LDS (with the bytes).  A value's bits depend on (curve, chain, slot, seed, J) alone.
+ * bfmmm_chain_loo_marginal_laplace is bfmmm_chain_loo_marginal with that kernel on the resident records as its only pass: no
+ * stages and no refinement; ess_mean, ess_min and n_below (pairs with ess < ess_floor or a lpd that is not finite) by the same
+ * counting kernel, then the same PSIS pass.  Its lpd_trace is bfmmm_chain_predict_laplace's on the same data, seed and J. */
+int bfmmm_chain_predict_laplace(bfmmm_handle* h, const double* y, const double* t, const double* B, const int64_t* offsets,
+                                int n_new, const double* X, const int32_t* perm, int first_slot, int n_slots, int n_samples,
+                                uint64_t seed, int64_t max_workspace_bytes,
+                                double* lpd, double* z_mean, double* z_sd, double* ess_mean, double* ess_min,
+                                double* lpd_trace, double* z_trace, double* ess_trace,
+                                int32_t* n_modes, double* components, double* eta_samples, int64_t capacity);
+int bfmmm_chain_loo_marginal_laplace(bfmmm_handle* h, int first_slot, int n_slots, int n_samples, uint64_t seed, double ess_floor,
+                                     int64_t max_workspace_bytes,
+                                     double* lppd, double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic,
+                                     double* p_waic, double* ess_mean, double* ess_min, int32_t* n_below,
+                                     double* lpd_trace, double* ess_trace, int32_t* n_modes, double* components,
+                                     double* eta_samples, int64_t capacity);
+
 /* The fitted function of held-out, partly observed curves from the chain slots: bfmmm_chain_predict with the same
  * arguments -- the same samples, and lpd, z_mean, z_sd, ess_mean, ess_min and their traces bit for bit -- and, on the G rows of an
  * evaluation basis E (G x P row-major, rows in the sampler's basis as in bfmmm_chain_curve_bands; the identity for the
@@ -626,7 +659,10 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * k_predict_fit, the two pooling kernels and, where nq > 0, the quantiles of the paths (three or four per chunk).
  * Of the last bfmmm_chain_loo_marginal (always measured): "loo_marginal", the device time and launches of the first pass, the
  * counting kernel (twice) and, where pairs are refined, the list and refinement kernels (three to five per chunk);
- * "loo_marginal_psis", those of the PSIS pass (one per chunk). */
+ * "loo_marginal_psis", those of the PSIS pass (one per chunk).
+ * Of the last bfmmm_chain_predict_laplace: "predict_stats" as above; "predict_laplace", k_predict_lap and the pooling kernel (two
+ * per chunk).  Of the last bfmmm_chain_loo_marginal_laplace: "loo_marginal_laplace", k_predict_lap and the counting kernel (two per
+ * chunk); "loo_marginal_psis" as above. */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
