@@ -119,6 +119,7 @@ POST_SYMBOLS = {
     "bfmmm_post_curve_loglik": (C.c_int, [C.POINTER(PostInput), C.c_int32, c_double_p]),
     "bfmmm_post_psis": (C.c_int, [c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                   c_double_p, c_double_p]),
+    "bfmmm_post_psis_expect": (C.c_int, [c_double_p, c_double_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [c_double_p] * 7),
     "bfmmm_FLOO": (C.c_int, [C.POINTER(PostArgs), C.POINTER(C.c_void_p)]),
     "bfmmm_post_diagnostics": (C.c_int, [c_double_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p,
                                          c_double_p, c_double_p, c_double_p, c_double_p]),
@@ -860,6 +861,29 @@ def psis_loo(ll, device=0):
     _check(lib.bfmmm_post_psis(m.ctypes.data_as(c_double_p), n, S, device, *[o.ctypes.data_as(c_double_p) for o in outs]))
     pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs))
     return loo_totals(pw, S)
+
+
+def psis_expect(ll, h, device=0):
+    """`psis_loo(ll)`, bit for bit, and "expect": the expectation of every auxiliary matrix of h -- (n, S), or (n_aux, n, S) -- under
+    each row's Pareto-smoothed weights, sum_t w_it h[a, i, t] / sum_t w_it, of shape h.shape[:-1] (bfmmm_post_psis_expect; DESIGN.md
+    7q).  With h = exp(ll) the logarithm of "expect" is "pointwise_elpd_loo"."""
+    lib = _lib_entry()
+    m = np.ascontiguousarray(ll, dtype=np.float64)
+    if m.ndim != 2:
+        raise ValueError("'ll' must be an n x S matrix")
+    n, S = m.shape
+    hm = np.ascontiguousarray(h, dtype=np.float64)
+    if hm.ndim not in (2, 3) or hm.shape[-2:] != (n, S) or hm.shape[0] < 1:
+        raise ValueError("'h' must be an n x S matrix, or n_aux of them, of the shape of 'll'")
+    n_aux = 1 if hm.ndim == 2 else hm.shape[0]
+    outs = [np.zeros(n) for _ in range(6)]
+    expect = np.zeros((n_aux, n))
+    _check(lib.bfmmm_post_psis_expect(m.ctypes.data_as(c_double_p), hm.ctypes.data_as(c_double_p), n, S, n_aux, device,
+                                      *[o.ctypes.data_as(c_double_p) for o in outs], expect.ctypes.data_as(c_double_p)))
+    pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs))
+    out = loo_totals(pw, S)
+    out["expect"] = expect[0] if hm.ndim == 2 else expect
+    return out
 
 
 # ---- convergence diagnostics (include/bfmmm_post.h; DESIGN.md 7c) -----------------------------------------------------

@@ -3,7 +3,8 @@
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
 // per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it, the cluster
 // covariance surfaces with their bands and their eigenvalues and eigenfunctions, the prediction of held-out curves with
-// their fitted functions, and the marginal PSIS-LOO over the training curves with the memberships integrated out.
+// their fitted functions, the marginal PSIS-LOO over the training curves with the memberships integrated out, and the
+// observation-level PSIS-LOO with its LOO-PIT.
 // An entry point is its argument checks (SlotCheck: slots, curve selection, the grid pair, x, alpha, probs and `units`, the one
 // budget rule), its workspace and the event pairs that time its launches into the handle's PT_* timers (CallBufs owns both) and
 // one for_chunks.  What several of them do is written once: `once` for a launch that runs once per call (the projections), Back
@@ -1696,6 +1697,137 @@ extern "C" int bfmmm_chain_loo_marginal_laplace(bfmmm_handle* h, int first_slot,
     if (prc) return std::string(bfmmm_entry_last_error());
     if (hipEventSynchronize(psis.to) != hipSuccess) return std::string(kBackFailed);
     collect(h, psis, PT_LOO_MARGINAL_PSIS);
+    return err;
+  });
+}
+
+// ---- observation-level PSIS-LOO and LOO-PIT of the chain slots (kernels_loo_pointwise.hip) ---------------------------
+// The unit of a chunk is a row tile: up to LP_ROWS consecutive observations of one curve, listed on the host in the order of the
+// result (the curves as selected, then the observations).  Per chunk k_loo_pointwise fills the four matrices of the chunk's rows
+// (log-likelihood, PIT, conditional mean, second moment; draw fastest, then chain), post_psis_expect_device takes PSIS on the first
+// with the other three as auxiliaries, and the traces go to the host where asked for.  The dense basis rows: one
+// launch_stats_functional for the whole call where the handle has the spline inputs, the chunk's rows from the handle's host copy
+// where it was created from a basis, none for the multivariate model.
+extern "C" int bfmmm_chain_loo_pointwise(bfmmm_handle* h, const int32_t* curves, int n_curves, int first_slot, int n_slots,
+                                         int64_t max_workspace_bytes, double* lppd, double* elpd_loo, double* p_loo, double* pareto_k,
+                                         double* elpd_waic, double* p_waic, double* pit, double* mean, double* sd, double* loglik_trace,
+                                         double* pit_trace, double* mean_trace, double* var_trace, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_loo_pointwise", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"h", h}, {"lppd", lppd}, {"elpd_loo", elpd_loo}, {"p_loo", p_loo}, {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic},
+               {"p_waic", p_waic}, {"pit", pit}, {"mean", mean}, {"sd", sd}}))
+    return 1;
+  if (curves && n_curves < 1) return fail(fn + ": 'n_curves' must be at least 1 where 'curves' is given");
+  int64_t m = 0;
+  if (ck.curve_list(curves, n_curves, &m) || ck.range() || ck.budget_sign(max_workspace_bytes) || ck.row_limit()) return 1;
+  const Ctx& c = h->c;
+  const Dims& d = c.d;
+  const int n = d.n, P = d.P;
+  const std::string bad = loo_pointwise_check(c);
+  if (!bad.empty()) return fail(fn + ": " + bad);
+  HIPCHK(hipSetDevice(h->device));
+  // the tile list, from the curves' observation counts
+  std::vector<int> hni((size_t)n);
+  HIPCHK(hipStreamSynchronize(h->st));
+  HIPCHK(copy_sync(h, hni.data(), c.ni, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+  std::vector<int64_t> off((size_t)n + 1, 0);
+  for (int i = 0; i < n; ++i) off[i + 1] = off[i] + hni[i];
+  std::vector<LpTile> tiles;
+  int64_t total = 0;
+  for (int64_t j = 0; j < m; ++j) {
+    const int i = curves ? curves[j] : (int)j;
+    for (int r0 = 0; r0 < hni[i]; r0 += LP_ROWS) {
+      const int rows = std::min(LP_ROWS, hni[i] - r0);
+      tiles.push_back({i, rows, off[i] + r0, off[i] + r0, total});
+      total += rows;
+    }
+  }
+  if (ck.capacity(capacity, total, "rows")) return 1;
+  if (tiles.empty()) return 0;
+  const bool from_basis = !h->B_host.empty(), spline = !d.mv && !from_basis;
+  const size_t N = (size_t)ck.CS();
+  // shared: the dense basis rows of every observation with the scratch record of their launch; a tile: its rows of the four matrices,
+  // the nine results a row, its entry of the list and, from a host basis, its basis rows
+  const size_t shared = spline ? sizeof(double) * ((size_t)h->n_obs * P + (size_t)n * d.LREC) + sizeof(int) * ((size_t)n + 1) : 0;
+  const size_t per_tile = sizeof(double) * (size_t)LP_ROWS * (4 * N + 9 + (from_basis ? (size_t)P : 0)) + sizeof(LpTile);
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), shared, per_tile, (int64_t)tiles.size(), (int64_t)1 << 24, "tile", &chunk)) return 1;
+  reset_timers(h, PT_LOO_POINTWISE, PT_LOO_POINTWISE_PSIS);
+  CallBufs b;
+  double *d_x = nullptr, *d_B = nullptr;
+  LpTile* d_tiles = nullptr;
+  Timer kern, vark, psis;
+  HIPCHK(b.timers({&kern, &vark, &psis}));
+  const size_t stride = (size_t)chunk * LP_ROWS * N;
+  HIPCHK(b.get(&d_x, 4 * stride));
+  HIPCHK(b.get(&d_tiles, (size_t)chunk));
+  if (spline) {
+    double* rec_tmp = nullptr;
+    int *ni_tmp = nullptr, *d_err = nullptr;
+    HIPCHK(b.get(&d_B, (size_t)h->n_obs * P));
+    HIPCHK(b.get(&rec_tmp, (size_t)n * d.LREC));
+    HIPCHK(b.get(&ni_tmp, (size_t)n));
+    HIPCHK(b.get(&d_err, 1));
+    HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int), h->st));
+    if (once(ck, b, PT_LOO_POINTWISE, 0, [&] {
+          return launch_stats_functional(h->cfg.basis_degree, n, P, d.LREC, h->d_off, h->d_t, h->d_y, h->d_knots, h->n_knots, rec_tmp, ni_tmp,
+                                         d_B, d_err, h->st)
+                     ? std::string("unsupported basis_degree")
+                     : std::string();
+        }))
+      return 1;
+  } else if (from_basis) {
+    HIPCHK(b.get(&d_B, (size_t)chunk * LP_ROWS * P));
+  }
+  std::vector<LpTile> ht((size_t)chunk);
+  std::vector<double> hB(from_basis ? (size_t)chunk * LP_ROWS * P : 0), hexp;
+  return for_chunks(ck, (int64_t)tiles.size(), chunk, [&](int64_t p0, int cnt) {
+    const int64_t base = tiles[(size_t)p0].out_row;
+    int64_t rows64 = 0;
+    for (int q = 0; q < cnt; ++q) {
+      LpTile t = tiles[(size_t)p0 + q];
+      t.out_row -= base;
+      if (from_basis) {
+        std::copy(h->B_host.begin() + (size_t)t.b0 * P, h->B_host.begin() + (size_t)(t.b0 + t.rows) * P, hB.begin() + (size_t)t.out_row * P);
+        t.b0 = t.out_row;
+      }
+      ht[(size_t)q] = t;
+      rows64 = t.out_row + t.rows;
+    }
+    const int rows = (int)rows64;
+    if (copy_sync(h, d_tiles, ht.data(), sizeof(LpTile) * (size_t)cnt, hipMemcpyHostToDevice) != hipSuccess ||
+        (from_basis && copy_sync(h, d_B, hB.data(), sizeof(double) * (size_t)rows * P, hipMemcpyHostToDevice) != hipSuccess))
+      return std::string(kBackFailed);
+    std::string err = timed(kern, h->st, [&] {
+      return launch_loo_pointwise(c, d_tiles, cnt, d_B, h->d_y, first_slot, n_slots, d_x, stride, h->st);
+    });
+    if (err.empty())
+      err = Back{h, base, rows}(loglik_trace, (const double*)d_x, N)(pit_trace, (const double*)(d_x + stride), N)(
+                mean_trace, (const double*)(d_x + 2 * stride), N).done();
+    if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
+    if (!err.empty()) return err;
+    collect(h, kern, PT_LOO_POINTWISE);
+    // post_psis_expect_device runs on the device's default stream: done() has drained the sampler's
+    double* const outs[6] = {lppd + base, elpd_loo + base, p_loo + base, pareto_k + base, elpd_waic + base, p_waic + base};
+    hexp.resize(3 * (size_t)rows);
+    (void)hipEventRecord(psis.from, nullptr);
+    const int prc = post_psis_expect_device(d_x, (long long)N, rows, (int)N, d_x + stride, 3, (long long)stride, outs, hexp.data());
+    (void)hipEventRecord(psis.to, nullptr);
+    if (prc) return std::string(bfmmm_entry_last_error());
+    if (hipEventSynchronize(psis.to) != hipSuccess) return std::string(kBackFailed);
+    collect(h, psis, PT_LOO_POINTWISE_PSIS);
+    for (int r = 0; r < rows; ++r) {
+      const double e1 = hexp[(size_t)rows + r];
+      pit[base + r] = hexp[(size_t)r];
+      mean[base + r] = e1;
+      sd[base + r] = std::sqrt(std::max(0.0, hexp[2 * (size_t)rows + r] - e1 * e1));
+    }
+    if (var_trace) {
+      err = timed(vark, h->st, [&] { return launch_loo_pointwise_var(d_x + 2 * stride, d_x + 3 * stride, (size_t)rows * N, h->st); });
+      if (err.empty()) err = Back{h, base, rows}(var_trace, (const double*)(d_x + 3 * stride), N).done();
+      if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
+      if (err.empty()) collect(h, vark, PT_LOO_POINTWISE);
+    }
     return err;
   });
 }

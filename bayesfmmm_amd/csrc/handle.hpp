@@ -32,12 +32,15 @@ enum { FAM_TOTAL = 0, FAM_Z, FAM_PG, FAM_FACTOR, FAM_SWEEP, FAM_CHI, FAM_LOGLIK,
 // each per call, PT_CEIG_VALUES: k_ceig_values, one launch per chunk; PT_PREDICT_STATS: the records of the new curves (one launch,
 // none for a from-basis handle), PT_PREDICT: k_predict and k_predict_pool, one launch each per chunk; PT_PREDICT_FIT: what
 // bfmmm_chain_predict_fit launches in their place, k_predict_fit, k_predict_pool, k_predict_fit_pool and the quantiles of the paths;
+// PT_LOO_POINTWISE: what bfmmm_chain_loo_pointwise launches on the sampler's stream (the dense basis rows once, k_loo_pointwise and,
+// where the variance trace is asked for, k_loo_pointwise_var per chunk), PT_LOO_POINTWISE_PSIS: its PSIS pass, one per chunk;
 // PT_LOO_MARGINAL: what bfmmm_chain_loo_marginal launches on the sampler's stream, per chunk k_predict, k_lz_count twice and, where
 // pairs are refined, k_lz_list and k_lz_refine; PT_LOO_MARGINAL_PSIS: its PSIS pass, one launch per chunk.
 enum { PT_CURVE_LL = 0, PT_FIT_PROJECT, PT_FIT_ROWS, PT_FIT_VALUES, PT_FIT_REDUCE, PT_SIM, PT_SIM_REDUCE, PT_SIMILARITY,
        PT_COV_PROJECT, PT_COV, PT_SIM_LOSS, PT_SIM_LOSS_REDUCE, PT_ALIGN_GRAM, PT_ALIGN_GATHER, PT_ALIGN_PROJECT,
        PT_CCOV_PROJECT, PT_CCOV, PT_CCOV_MAXDEV, PT_CEIG_GRAM, PT_CEIG, PT_CEIG_VALUES, PT_PREDICT_STATS, PT_PREDICT, PT_PREDICT_FIT,
-       PT_LOO_MARGINAL, PT_LOO_MARGINAL_PSIS, PT_PREDICT_LAPLACE, PT_LOO_MARGINAL_LAPLACE, PT_COUNT };
+       PT_LOO_MARGINAL, PT_LOO_MARGINAL_PSIS, PT_PREDICT_LAPLACE, PT_LOO_MARGINAL_LAPLACE, PT_LOO_POINTWISE, PT_LOO_POINTWISE_PSIS,
+       PT_COUNT };
 inline constexpr const char* kPostNames[PT_COUNT] = {"curve_ll_ms", "curve_fit_project", "curve_fit_rows", "curve_fit_values",
                                                      "curve_fit_reduce", "curve_sim", "curve_sim_reduce", "similarity",
                                                      "curve_cov_project", "curve_cov", "similarity_loss", "similarity_loss_reduce",
@@ -46,7 +49,7 @@ inline constexpr const char* kPostNames[PT_COUNT] = {"curve_ll_ms", "curve_fit_p
                                                      "cluster_eig_gram", "cluster_eig", "cluster_eig_values",
                                                      "predict_stats", "predict", "predict_fit",
                                                      "loo_marginal", "loo_marginal_psis", "predict_laplace",
-                                                     "loo_marginal_laplace"};
+                                                     "loo_marginal_laplace", "loo_pointwise", "loo_pointwise_psis"};
 
 struct bfmmm_handle {
   bfmmm_config cfg;

@@ -15,11 +15,15 @@
 //   fit     the generalized Pareto fit of the tail: the m <= 30 + sqrt(L) candidate thetas over lanes (a few lanes per
 //           candidate, fixed segments), the weights and k in one thread / one reduction; the smoothed tail -> LDS
 //   last    elpd_loo = logsumexp(lw + l) - logsumexp(lw): non-tail draws from the row, tail draws from the LDS table
+// k_post_psis<NAUX>, NAUX > 0: the last pass also takes the expectation of NAUX auxiliary rows h_a (the layout and leading
+// dimension of the log-likelihood matrix, aux_stride doubles from one matrix to the next) under the smoothed weights,
+// E_a = sum_t exp(w_t - sh2) h_a(t) / s2, the terms in the order of s2.  NAUX = 0 is the kernel without them, bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 #include <cmath>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/bfmmm_post.h"
@@ -35,8 +39,16 @@ constexpr int NT = 256;                        // threads per workgroup = histog
 constexpr int CAP_MAX = 8192;                  // largest on-chip table of gathered tail candidates
 constexpr long long S_MAX = 1LL << 22;         // kept draws per row in this build (L <= 6144 < CAP_MAX)
 
+constexpr int NAUX_MAX = 4;                    // auxiliary matrices of one launch (more: further launches)
+
 struct PsisOut {
   double *lppd, *elpd_loo, *p_loo, *khat, *elpd_waic, *p_waic;
+};
+struct PsisAux {
+  const double* h;       // matrix a at h + a * stride, row i at + i * ld
+  long long stride;
+  double* expect;        // E_a of row i at [a * n + i]
+  int n;
 };
 
 // digit p (0..11) of the 96-bit composite (key, draw index), most significant first
@@ -56,7 +68,8 @@ __device__ inline void hist_add(unsigned* hist, unsigned d, bool on) {
   }
 }
 
-__global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld, int S, int L, int cap, PsisOut o) {
+template <int NAUX>
+__global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld, int S, int L, int cap, PsisOut o, PsisAux ax) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int tid = threadIdx.x, i = blockIdx.x;
   double* red = sm;                                    // NT
@@ -231,6 +244,8 @@ __global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld
     sh2 = fmax(c, block_reduce<NT>(a2, red, OpMax()));
   }
   double s1 = 0.0, s2 = 0.0;
+  double sa[NAUX > 0 ? NAUX : 1] = {};
+  const double* hrow = NAUX > 0 ? ax.h + (size_t)i * (size_t)ld : nullptr;
   for (int t = tid; t < S; t += NT) {
     const double x = row[t], lw = -x - rmax;
     if (smooth) {
@@ -239,16 +254,33 @@ __global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld
     }
     const double w = fmin(lw, 0.0);
     s1 += exp(w + x - sh1);
-    s2 += exp(w - sh2);
+    const double e2 = exp(w - sh2);
+    s2 += e2;
+    if constexpr (NAUX > 0) {
+#pragma unroll
+      for (int a = 0; a < NAUX; ++a) sa[a] += e2 * hrow[(size_t)a * (size_t)ax.stride + t];
+    }
   }
   if (smooth)
     for (int j = tid; j < L; j += NT) {
       const double w = fmin(sE[base + j], 0.0);
       s1 += exp(w + row[sIdx[base + j]] - sh1);
-      s2 += exp(w - sh2);
+      const double e2 = exp(w - sh2);
+      s2 += e2;
+      if constexpr (NAUX > 0) {
+#pragma unroll
+        for (int a = 0; a < NAUX; ++a) sa[a] += e2 * hrow[(size_t)a * (size_t)ax.stride + sIdx[base + j]];
+      }
     }
   s1 = block_reduce<NT>(s1, red, OpSum());
   s2 = block_reduce<NT>(s2, red, OpSum());
+  if constexpr (NAUX > 0) {
+#pragma unroll
+    for (int a = 0; a < NAUX; ++a) {
+      const double v = block_reduce<NT>(sa[a], red, OpSum());
+      if (tid == 0) ax.expect[(size_t)a * ax.n + i] = v / s2;
+    }
+  }
   if (tid == 0) {
     const double elpd = (sh1 + log(s1)) - (sh2 + log(s2));
     o.lppd[i] = lppd;
@@ -262,28 +294,67 @@ __global__ __launch_bounds__(NT) void k_post_psis(const double* ll, long long ld
 
 }  // namespace
 
-// the PSIS / WAIC pass over n rows of S values on the current device (row i at d_ll + i * ld); out: six host arrays of n
-// (lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic).  Shared by bfmmm_post_psis and the file-based entry points, which
-// keep the matrix on the device.
-int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]) {
-  if (S > S_MAX)
-    return bfmmm_io_fail("bfmmm_post_psis: at most 4194304 (2^22) kept draws per curve in this build, got " + std::to_string(S));
+namespace {
+
+using PsisKernel = void (*)(const double*, long long, int, int, int, PsisOut, PsisAux);
+PsisKernel psis_pick(int n_aux) {
+  switch (n_aux) {
+    case 0: return k_post_psis<0>;
+    case 1: return k_post_psis<1>;
+    case 2: return k_post_psis<2>;
+    case 3: return k_post_psis<3>;
+    default: return k_post_psis<4>;
+  }
+}
+
+// one launch per group of up to NAUX_MAX auxiliary matrices (one without any); the six arrays of every launch are the same
+int psis_run(const char* who, const double* d_ll, long long ld, int n, int S, const double* d_aux, int n_aux, long long aux_stride,
+             double* const out[6], double* expect_host) {
+  const std::string fn(who);
+  if (S > S_MAX) return bfmmm_io_fail(fn + ": at most 4194304 (2^22) kept draws per curve in this build, got " + std::to_string(S));
   const int L = (int)std::ceil(std::min(0.2 * S, 3.0 * std::sqrt((double)S)));
   int cap = 256;
   while (cap < 2 * (L + 1) && cap < CAP_MAX) cap <<= 1;
   DevBufs b;
   double* d_out;
-  if (!b.put(&d_out, nullptr, 6 * (size_t)n)) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_psis: device allocation failed"); }
+  if (!b.put(&d_out, nullptr, (6 + (size_t)n_aux) * (size_t)n)) { (void)hipGetLastError(); return bfmmm_io_fail(fn + ": device allocation failed"); }
   PsisOut o{d_out, d_out + n, d_out + 2 * (size_t)n, d_out + 3 * (size_t)n, d_out + 4 * (size_t)n, d_out + 5 * (size_t)n};
   const size_t lds = (size_t)(NT + 256) * sizeof(double) + (size_t)(3 * NT + 8) * sizeof(unsigned) + (size_t)cap * (sizeof(u64) + sizeof(unsigned));
-  (void)hipFuncSetAttribute((const void*)k_post_psis, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const bool ran = timed_launch([&] { hipLaunchKernelGGL(k_post_psis, dim3(n), dim3(NT), lds, 0, d_ll, ld, S, L, cap, o); return true; });
-  std::vector<double> h(6 * (size_t)n);
-  if (!ran || hipMemcpy(h.data(), d_out, sizeof(double) * h.size(), hipMemcpyDeviceToHost) != hipSuccess)
-    return bfmmm_io_fail("bfmmm_post_psis: kernel launch or copy back failed");
+  float ms = 0.f;
+  for (int a0 = 0; a0 == 0 || a0 < n_aux; a0 += NAUX_MAX) {
+    const int na = std::min(NAUX_MAX, n_aux - a0);
+    const PsisKernel fn_k = psis_pick(na);
+    const PsisAux ax{na ? d_aux + (size_t)a0 * (size_t)aux_stride : nullptr, aux_stride, d_out + (6 + (size_t)a0) * (size_t)n, n};
+    (void)hipFuncSetAttribute((const void*)fn_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (!timed_launch([&] { hipLaunchKernelGGL(fn_k, dim3(n), dim3(NT), lds, 0, d_ll, ld, S, L, cap, o, ax); return true; }))
+      return bfmmm_io_fail(fn + ": kernel launch or copy back failed");
+    ms += (float)bfmmm_post_last_kernel_ms();
+  }
+  bfmmm_post_set_kernel_ms(ms);
+  std::vector<double> h((6 + (size_t)n_aux) * (size_t)n);
+  if (hipMemcpy(h.data(), d_out, sizeof(double) * h.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    return bfmmm_io_fail(fn + ": kernel launch or copy back failed");
   for (int q = 0; q < 6; ++q)
     if (out[q]) std::copy(h.begin() + (size_t)q * n, h.begin() + (size_t)(q + 1) * n, out[q]);
+  if (expect_host) std::copy(h.begin() + 6 * (size_t)n, h.end(), expect_host);
   return 0;
+}
+
+}  // namespace
+
+// the PSIS / WAIC pass over n rows of S values on the current device (row i at d_ll + i * ld); out: six host arrays of n
+// (lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic).  Shared by bfmmm_post_psis and the file-based entry points, which
+// keep the matrix on the device.
+int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]) {
+  return psis_run("bfmmm_post_psis", d_ll, ld, n, S, nullptr, 0, 0, out, nullptr);
+}
+
+// the same pass, and the expectations of n_aux auxiliary matrices (matrix a at d_aux + a * aux_stride, rows as d_ll's) under each
+// row's smoothed weights: expect_host[a * n + i].  The six arrays are post_psis_device's, bit for bit.
+int post_psis_expect_device(const double* d_ll, long long ld, int n, int S, const double* d_aux, int n_aux, long long aux_stride,
+                            double* const out[6], double* expect_host) {
+  if (n_aux < 1 || !d_aux || !expect_host) return bfmmm_io_fail("bfmmm_post_psis_expect: no auxiliary matrix");
+  return psis_run("bfmmm_post_psis_expect", d_ll, ld, n, S, d_aux, n_aux, aux_stride, out, expect_host);
 }
 
 extern "C" int bfmmm_post_psis(const double* ll, int32_t n, int32_t S, int32_t device, double* lppd, double* elpd_loo, double* p_loo,
@@ -300,4 +371,25 @@ extern "C" int bfmmm_post_psis(const double* ll, int32_t n, int32_t S, int32_t d
   if (hipMemcpy(d_ll, ll, sizeof(double) * count, hipMemcpyHostToDevice) != hipSuccess) return bfmmm_io_fail("bfmmm_post_psis: copy failed");
   double* const out[6] = {lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic};
   return post_psis_device(d_ll, S, n, S, out);
+}
+
+extern "C" int bfmmm_post_psis_expect(const double* ll, const double* h, int32_t n, int32_t S, int32_t n_aux, int32_t device, double* lppd,
+                                      double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, double* expect) {
+  const std::pair<const char*, const void*> ptrs[] = {{"ll", ll}, {"h", h}, {"lppd", lppd}, {"elpd_loo", elpd_loo}, {"p_loo", p_loo},
+                                                      {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic}, {"p_waic", p_waic}, {"expect", expect}};
+  for (const auto& e : ptrs)
+    if (!e.second) return bfmmm_io_fail(std::string("bfmmm_post_psis_expect: '") + e.first + "' is null");
+  if (n < 1 || S < 1 || n_aux < 1) return bfmmm_io_fail("bfmmm_post_psis_expect: bad dimensions");
+  if (S > S_MAX)
+    return bfmmm_io_fail("bfmmm_post_psis_expect: at most 4194304 (2^22) kept draws per curve in this build, got " + std::to_string(S));
+  if (select_device(device, "bfmmm_post_psis_expect")) return 1;
+  DevBufs b;
+  double *d_ll, *d_h;
+  const size_t count = (size_t)n * (size_t)S;
+  if (!b.put(&d_ll, nullptr, count) || !b.put(&d_h, nullptr, count * (size_t)n_aux)) { (void)hipGetLastError(); return bfmmm_io_fail("bfmmm_post_psis_expect: device allocation failed"); }
+  if (hipMemcpy(d_ll, ll, sizeof(double) * count, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_h, h, sizeof(double) * count * (size_t)n_aux, hipMemcpyHostToDevice) != hipSuccess)
+    return bfmmm_io_fail("bfmmm_post_psis_expect: copy failed");
+  double* const out[6] = {lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic};
+  return post_psis_expect_device(d_ll, S, n, S, d_h, n_aux, (long long)count, out, expect);
 }

@@ -1,0 +1,346 @@
+// Observation-level leave-one-out quantities of chain slots: for every chain q, slot t and observation j of
+// curve i, the law of y_ij given the REST of the curve and the draw, the scores chi_i integrated out.  With c and V_m as in
+// kernels_curve_ll.hip, b_j the j-th basis row of the curve (the unit vectors for the multivariate model):
+//     mu_j = b_j'c,  w_j = (b_j'V_1 .. b_j'V_M)',  r_j = y_ij - mu_j,
+//     A = sigma^2 I_M + V'G_i V = L L',  u = V'(s_i - G_i c),  beta = A^-1 u            (from the resident record, not from the rows)
+//     h_j = |L^-1 w_j|^2,  omega_j = 1 - h_j,  e_j = r_j - w_j'beta,
+//     l = -1/2 [ log 2 pi + log sigma^2 - log omega_j + e_j^2 / (sigma^2 omega_j) ],  z = e_j / (sigma sqrt omega_j),
+//     m = y_ij - e_j / omega_j,  v = sigma^2 / omega_j.
+// Four values per (observation, draw) go to four matrices of rows x (C S), draw fastest, then chain, then observation: l,
+// Phi(z) = erfc(-z / sqrt 2) / 2, m and m^2 + v: the log-likelihood matrix and the three auxiliary matrices of
+// post_psis_expect_device.
+//
+// Geometry.  A workgroup of 256 threads takes one row tile (up to 64 consecutive observations of one curve, from the host's tile
+// list), one chain and a run of slots.  The tile's dense basis rows, the curve's record and covariates are staged once; then
+// TB draws at a time:
+//   (1) every (draw, mt, p): c[p] (mt = 0) or V_mt[p] from the slot's nu, Phi (eta, xi), the k sum in order -> LDS, P x (M + 1) a draw
+//   (2) every (draw, mt, p): (G V_mt)[p] over the band window -> e = s - G c, G V_m
+//   (3) every (draw, m, l >= m): u_m = V_m'e and A_lm = V_m'(G V_l) (+ sigma^2 on the diagonal), p in order
+//   (4) lane g of the first wave: Cholesky of draw g's A in place, beta by the two triangular solves
+//   (5) wave w takes draws w, w + 4, ..: [mu | W] = B_tile [c | V] on v_mfma_f64_16x16x4_f64 (row tiles of 16, ceil((M + 1) / 16)
+//       column tiles, ceil(P / 4) k-steps; C/D: col = lane & 15, row = (lane >> 4) + 4 reg) into the wave's own LDS rows; then
+//       lane j owns observation j: w_j'beta, the forward solve L^-1 w_j in place in its row (L broadcast from LDS), the four
+//       values -> the staging table
+//   (6) the table -> the four matrices, one draw-contiguous segment per (matrix, observation)
+// L and beta of a (curve, draw) are recomputed by every tile of the curve, from the same record in the same order, so the tiles of
+// a curve agree bit for bit and there is neither a pre-pass nor a workspace.  fp64, vector stores only, no atomics; every sum has
+// a fixed order that depends on (observation, chain, slot) alone: the bits do not depend on the chunk, the grid or TB.
+#include "model.hpp"
+#include "launchers.hpp"
+
+#include <algorithm>
+#include <string>
+
+namespace bfmmm {
+
+namespace {
+
+constexpr int LP_NT = 256;
+constexpr int LP_TB_MAX = 8;
+constexpr size_t LP_LDS_SOFT = 64 * 1024;      // two workgroups per CU where the shape allows
+constexpr size_t LP_LDS_HARD = 160 * 1024;
+
+typedef double lp_v4 __attribute__((ext_vector_type(4)));
+
+struct LpArgs {
+  // chain 0's slot storage; chain q's is q * chain_bytes (covariate blocks: chain_bytes_cov) further
+  const double *c_Z, *c_nu, *c_Phi, *c_sigma, *c_eta, *c_xi;
+  const double *rec, *X, *y, *B;
+  const LpTile* tiles;
+  double* out;                                  // matrix v at out + v * out_stride
+  size_t out_stride, chain_bytes, chain_bytes_cov;
+  int n, K, P, M, D, BW, LG, LREC, cadj, mv;
+  int C, first_slot, S;
+  int TB, SCH;                                  // draws per staged batch, slots per workgroup (a multiple of TB)
+};
+
+// LDS doubles of k_loo_pointwise
+struct LpLds {
+  int BS, CVS, CVN, GVN, AS, MWS, TBS;
+  size_t b, rec, x, z, sig, cv, gv, a, mw, out, total;
+};
+__host__ __device__ inline LpLds lp_lds(int K, int P, int M, int LG, int TB) {
+  LpLds L;
+  L.BS = P | 1;                                 // a basis row
+  L.CVS = (M + 1) | 1;                          // row p of [c | V]
+  L.CVN = P * L.CVS;
+  L.GVN = (M + 1) * P;
+  L.AS = M * M + 2 * M;                         // A (lower triangle, row-major), u, beta
+  L.MWS = (M + 1) | 1;                          // row j of [mu | W]
+  L.TBS = TB | 1;
+  size_t o = 0;
+  L.b = o; o += (size_t)LP_ROWS * L.BS;
+  L.rec = o; o += (size_t)LG + P;
+  L.x = o; o += 8;
+  L.z = o; o += (size_t)TB * K;
+  L.sig = o; o += LP_TB_MAX;
+  L.cv = o; o += (size_t)TB * L.CVN;
+  L.gv = o; o += (size_t)TB * L.GVN;
+  L.a = o; o += (size_t)TB * L.AS;
+  L.mw = o; o += (size_t)(LP_NT / 64) * LP_ROWS * L.MWS;
+  L.out = o; o += (size_t)4 * LP_ROWS * L.TBS;
+  L.total = o;
+  return L;
+}
+
+__global__ __launch_bounds__(LP_NT) void k_loo_pointwise(LpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = a.K, P = a.P, M = a.M, D = a.D, M1 = M + 1, BW = a.BW, TB = a.TB, n = a.n;
+  const LpLds L = lp_lds(K, P, M, a.LG, TB);
+  const int BS = L.BS, CVS = L.CVS, CVN = L.CVN, GVN = L.GVN, AS = L.AS, MWS = L.MWS, TBS = L.TBS;
+  double* sB = sm + L.b;
+  double* sRec = sm + L.rec;
+  double* sX = sm + L.x;
+  double* sZ = sm + L.z;
+  double* sSig = sm + L.sig;
+  double* sCV = sm + L.cv;
+  double* sGV = sm + L.gv;
+  double* sA = sm + L.a;
+  double* sMW = sm + L.mw + (size_t)wave * LP_ROWS * MWS;
+  double* sOut = sm + L.out;
+
+  const LpTile tl = a.tiles[blockIdx.x];
+  const int i = tl.curve, nr = tl.rows;
+  const int q_chain = blockIdx.z;
+  const int s_lo = (int)blockIdx.y * a.SCH, s_hi = min(a.S, s_lo + a.SCH);     // slots relative to first_slot
+  const double* c_Z = ptr_shift(a.c_Z, (size_t)q_chain * a.chain_bytes);
+  const double* c_nu = ptr_shift(a.c_nu, (size_t)q_chain * a.chain_bytes);
+  const double* c_Phi = ptr_shift(a.c_Phi, (size_t)q_chain * a.chain_bytes);
+  const double* c_sigma = ptr_shift(a.c_sigma, (size_t)q_chain * a.chain_bytes);
+  const double* c_eta = D > 0 ? ptr_shift(a.c_eta, (size_t)q_chain * a.chain_bytes_cov) : nullptr;
+  const double* c_xi = D > 0 ? ptr_shift(a.c_xi, (size_t)q_chain * a.chain_bytes_cov) : nullptr;
+
+  // ---- once per workgroup: the tile's basis rows (zero rows beyond the tile), the curve's record and covariates ----
+  for (int e = tid; e < LP_ROWS * P; e += LP_NT) {
+    const int r = e / P, p = e - r * P;
+    double v = 0.0;
+    if (r < nr) v = a.mv ? (p == r ? 1.0 : 0.0) : a.B[(size_t)(tl.b0 + r) * P + p];
+    sB[r * BS + p] = v;
+  }
+  const double* rec = a.rec + (size_t)i * a.LREC;
+  for (int e = tid; e < a.LG + P; e += LP_NT) sRec[e] = rec[e];      // G(p, p + d) at [d P + p], then s
+  if (tid < D) sX[tid] = a.X[i + (size_t)n * tid];
+  double yv = 0.0;                                                    // lane j: y of observation j of the tile
+  if (lane < nr) yv = a.mv ? a.y[i + (size_t)n * lane] : a.y[tl.y0 + lane];
+  const double* sS = sRec + a.LG;
+
+  for (int sb = s_lo; sb < s_hi; sb += TB) {
+    const int gn = min(TB, s_hi - sb);
+    __syncthreads();                                                  // the previous batch's readers are done (and the set-up above)
+    for (int e = tid; e < gn * K; e += LP_NT) {
+      const int g = e / K, k = e - g * K;
+      sZ[g * K + k] = c_Z[(size_t)(a.first_slot + sb + g) * n * K + i + (size_t)n * k];
+    }
+    if (tid < gn) sSig[tid] = c_sigma[a.first_slot + sb + tid];
+    __syncthreads();
+    // (1) c and V_m at p
+    for (int e = tid; e < gn * GVN; e += LP_NT) {
+      const int g = e / GVN, r = e - g * GVN, mt = r / P, p = r - mt * P;
+      const size_t t = (size_t)(a.first_slot + sb + g);
+      const bool cov = D > 0 && (mt == 0 || a.cadj);
+      const double* z = sZ + g * K;
+      double v = 0.0;
+      for (int k = 0; k < K; ++k) {
+        double x = mt == 0 ? c_nu[t * K * P + (size_t)p * K + k] : c_Phi[t * K * P * M + k + (size_t)K * (p + P * (mt - 1))];
+        if (cov) {
+          const double* tx = mt == 0 ? c_eta + t * P * D * K + p + (size_t)P * D * k
+                                     : c_xi + t * K * P * D * M + p + (size_t)P * D * ((mt - 1) + M * k);
+          for (int d = 0; d < D; ++d) x += sX[d] * tx[(size_t)P * d];
+        }
+        v += z[k] * x;
+      }
+      sCV[g * CVN + p * CVS + mt] = v;
+    }
+    __syncthreads();
+    // (2) G times each of them at p, over the band window
+    for (int e = tid; e < gn * GVN; e += LP_NT) {
+      const int g = e / GVN, r = e - g * GVN, mt = r / P, p = r - mt * P;
+      const double* cv = sCV + g * CVN + mt;
+      double hv = 0.0;
+      for (int d = -BW; d <= BW; ++d) {
+        const int p2 = p + d;
+        if (p2 >= 0 && p2 < P) hv += sRec[(d < 0 ? -d : d) * P + min(p, p2)] * cv[p2 * CVS];
+      }
+      sGV[g * GVN + r] = mt == 0 ? sS[p] - hv : hv;
+    }
+    __syncthreads();
+    // (3) u_m = V_m'e, A_lm = V_m'(G V_l) for l >= m, sigma^2 on the diagonal
+    for (int e = tid; e < gn * M * M1; e += LP_NT) {
+      const int g = e / (M * M1), r = e - g * M * M1, m = r / M1, j = r - m * M1;      // j = 0: u_m, else l = j - 1
+      if (j > 0 && j - 1 < m) continue;
+      const double* vm = sCV + g * CVN + 1 + m;
+      const double* gv = sGV + g * GVN + j * P;
+      double s_ = 0.0;
+      for (int p = 0; p < P; ++p) s_ += vm[p * CVS] * gv[p];
+      double* A = sA + g * AS;
+      if (j == 0) A[M * M + m] = s_;
+      else A[(j - 1) * M + m] = (j - 1 == m) ? s_ + sSig[g] : s_;
+    }
+    __syncthreads();
+    // (4) lane g: A = L L' in place, beta = A^-1 u
+    if (tid < gn) {
+      double* A = sA + tid * AS;
+      const double* u = A + M * M;
+      double* beta = A + M * M + M;
+      for (int c = 0; c < M; ++c) {
+        double dg = A[c * M + c];
+        for (int k2 = 0; k2 < c; ++k2) { const double l2 = A[c * M + k2]; dg -= l2 * l2; }
+        const double l = sqrt(dg);
+        A[c * M + c] = l;
+        for (int r3 = c + 1; r3 < M; ++r3) {
+          double v = A[r3 * M + c];
+          for (int k2 = 0; k2 < c; ++k2) v -= A[r3 * M + k2] * A[c * M + k2];
+          A[r3 * M + c] = v / l;
+        }
+      }
+      for (int c = 0; c < M; ++c) {
+        double x = u[c];
+        for (int k2 = 0; k2 < c; ++k2) x -= A[c * M + k2] * beta[k2];
+        beta[c] = x / A[c * M + c];
+      }
+      for (int c = M - 1; c >= 0; --c) {
+        double x = beta[c];
+        for (int r3 = c + 1; r3 < M; ++r3) x -= A[r3 * M + c] * beta[r3];
+        beta[c] = x / A[c * M + c];
+      }
+    }
+    __syncthreads();
+    // (5) wave w: draws w, w + 4, ..
+    for (int g = wave; g < gn; g += LP_NT / 64) {
+      const double* cv = sCV + g * CVN;
+      const int lr = lane & 15, lk = lane >> 4;
+      for (int ti = 0; 16 * ti < nr; ++ti) {
+        const double* pa = sB + (16 * ti + lr) * BS;
+        for (int tj = 0; 16 * tj < M1; ++tj) {
+          const int col = 16 * tj + lr;
+          lp_v4 acc = {0.0, 0.0, 0.0, 0.0};
+          for (int kb = 0; 4 * kb < P; ++kb) {
+            const int p = 4 * kb + lk;
+            const bool in = p < P;
+            const double av = in ? pa[p] : 0.0;
+            const double bv = in && col < M1 ? cv[p * CVS + col] : 0.0;
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+          }
+          if (col < M1) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) sMW[(16 * ti + lk + 4 * reg) * MWS + col] = acc[reg];
+          }
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      if (lane < nr) {
+        double* w = sMW + lane * MWS;
+        const double* Lc = sA + g * AS;
+        const double* beta = Lc + M * M + M;
+        const double sig = sSig[g];
+        double dot = 0.0;
+        for (int m = 0; m < M; ++m) dot += w[1 + m] * beta[m];
+        const double ej = (yv - w[0]) - dot;
+        double hj = 0.0;
+        for (int c = 0; c < M; ++c) {
+          double x = w[1 + c];
+          for (int k2 = 0; k2 < c; ++k2) x -= Lc[c * M + k2] * w[1 + k2];
+          x /= Lc[c * M + c];
+          w[1 + c] = x;
+          hj += x * x;
+        }
+        const double om = 1.0 - hj;
+        const double zj = ej / sqrt(sig * om);
+        const double mj = yv - ej / om;
+        double* so = sOut + lane * TBS + g;
+        so[0] = -0.5 * (1.83787706640934548356 + log(sig) - log(om) + ej * ej / (sig * om));
+        so[LP_ROWS * TBS] = 0.5 * erfc(-zj * 0.70710678118654752440);
+        so[2 * LP_ROWS * TBS] = mj;
+        so[3 * LP_ROWS * TBS] = mj * mj + sig / om;
+      }
+      __builtin_amdgcn_wave_barrier();                               // the wave's rows are rewritten by its next draw
+    }
+    __syncthreads();
+    // (6) draw-contiguous segments
+    for (int e = tid; e < 4 * nr * gn; e += LP_NT) {
+      const int g = e % gn, r2 = e / gn, row = r2 % nr, v = r2 / nr;
+      a.out[(size_t)v * a.out_stride + (size_t)(tl.out_row + row) * a.C * a.S + (size_t)q_chain * a.S + (size_t)(sb + g)] =
+          sOut[(v * LP_ROWS + row) * TBS + g];
+    }
+  }
+}
+
+// x4 <- max(0, x4 - x3^2): the conditional variance from the fourth matrix and the third, for the host's var_trace
+__global__ __launch_bounds__(256) void k_loo_pointwise_var(const double* m, double* q, size_t count) {
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < count; e += (size_t)gridDim.x * 256) q[e] = fmax(0.0, q[e] - m[e] * m[e]);
+}
+
+int lp_pick_tb(const Dims& d, size_t* bytes_out) {
+  auto bytes = [&](int tb) { return lp_lds(d.K, d.P, d.M, d.LG, tb).total * sizeof(double); };
+  int TB = LP_TB_MAX;
+  while (TB > 4 && bytes(TB) > LP_LDS_SOFT) TB >>= 1;
+  while (TB > 1 && bytes(TB) > LP_LDS_HARD) TB >>= 1;
+  *bytes_out = bytes(TB);
+  return TB;
+}
+
+}  // namespace
+
+// "" or what k_loo_pointwise cannot take of the sampler's shape: asked before a call allocates anything
+std::string loo_pointwise_check(const Ctx& c) {
+  const Dims& d = c.d;
+  if (d.P < 1 || d.P > PMAX) return "k_loo_pointwise: P outside 1 .. 64";
+  if (d.M < 1 || d.M > 16) return "k_loo_pointwise: n_eigen outside 1 .. 16";
+  if (d.K < 1 || d.K > KMAX) return "k_loo_pointwise: K outside 1 .. 8";
+  if (d.D < 0 || d.D > 8) return "k_loo_pointwise: more than 8 covariates";
+  if (d.BW < 0 || d.BW > BWWIDE) return "k_loo_pointwise: band half-width above 31";
+  if (c.nch < 1 || c.nch > 65535) return "k_loo_pointwise: more than 65535 chains";
+  size_t bytes = 0;
+  (void)lp_pick_tb(d, &bytes);
+  if (bytes > LP_LDS_HARD)
+    return "k_loo_pointwise: the tile's basis rows, the record and one draw's [c | V] (P = " + std::to_string(d.P) + ", n_eigen = " +
+           std::to_string(d.M) + ", band " + std::to_string(d.BW) + ") need " + std::to_string(bytes) + " bytes of LDS, above the kernel's 163840";
+  return "";
+}
+
+// The four matrices of the n_tiles row tiles at `tiles` (device), every chain, slots [first_slot, first_slot + n_slots): matrix v
+// at out + v * out_stride, row tl.out_row + j of observation j of a tile, draw fastest, then chain.  B: the dense basis rows the
+// tiles index (null for the multivariate model), y: the sampler's observations.  Returns "" or what the kernel cannot take.
+std::string launch_loo_pointwise(const Ctx& c, const LpTile* tiles, long long n_tiles, const double* B, const double* y, int first_slot,
+                                 int n_slots, double* out, size_t out_stride, hipStream_t st) {
+  const Dims& d = c.d;
+  const std::string bad = loo_pointwise_check(c);
+  if (!bad.empty()) return bad;
+  if (n_tiles < 1 || n_tiles > 2147483647LL || !tiles || !y || !out || (!d.mv && !B)) return "k_loo_pointwise: bad arguments";
+  if (n_slots < 1 || first_slot < 0 || first_slot + n_slots > c.T) return "k_loo_pointwise: range outside the chain storage";
+  LpArgs a;
+  a.c_Z = c.c_Z; a.c_nu = c.c_nu; a.c_Phi = c.c_Phi; a.c_sigma = c.c_sigma;
+  a.c_eta = d.D > 0 ? c.c_eta : nullptr; a.c_xi = d.D > 0 ? c.c_xi : nullptr;
+  a.rec = c.rec; a.X = d.D > 0 ? c.X : nullptr; a.y = y; a.B = B; a.tiles = tiles; a.out = out; a.out_stride = out_stride;
+  a.chain_bytes = c.chain_bytes; a.chain_bytes_cov = c.chain_bytes_cov;
+  a.n = d.n; a.K = d.K; a.P = d.P; a.M = d.M; a.D = d.D; a.BW = d.BW; a.LG = d.LG; a.LREC = d.LREC;
+  a.cadj = (d.D > 0 && c.covariance_adj) ? 1 : 0;
+  a.mv = d.mv ? 1 : 0;
+  a.C = c.nch; a.first_slot = first_slot; a.S = n_slots;
+  size_t lds = 0;
+  a.TB = lp_pick_tb(d, &lds);
+  // slots per workgroup: eight batches, more where the grid's y extent would pass 65535
+  long long sch = (long long)a.TB * 8;
+  while (((long long)n_slots + sch - 1) / sch > 65535) sch *= 2;
+  a.SCH = (int)sch;
+  const dim3 grid((unsigned)n_tiles, (unsigned)((n_slots + a.SCH - 1) / a.SCH), (unsigned)c.nch);
+  if (hipFuncSetAttribute((const void*)k_loo_pointwise, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return "k_loo_pointwise: cannot set the LDS size";
+  }
+  hipLaunchKernelGGL(k_loo_pointwise, grid, dim3(LP_NT), lds, st, a);
+  if (hipGetLastError() != hipSuccess) return "k_loo_pointwise: launch failed";
+  return "";
+}
+
+// var[e] = max(0, second[e] - mean[e]^2) in place of second, `count` entries
+std::string launch_loo_pointwise_var(const double* mean, double* second, size_t count, hipStream_t st) {
+  if (!count) return "";
+  const unsigned blocks = (unsigned)std::min<size_t>((count + 255) / 256, 65535);
+  hipLaunchKernelGGL(k_loo_pointwise_var, dim3(blocks), dim3(256), 0, st, mean, second, count);
+  if (hipGetLastError() != hipSuccess) return "k_loo_pointwise_var: launch failed";
+  return "";
+}
+
+}  // namespace bfmmm

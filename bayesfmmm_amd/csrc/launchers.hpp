@@ -15,6 +15,8 @@ std::string diag_gather(const double* base, size_t chain_bytes, long long ss, lo
 
 // ---- kernels_loo.hip ----
 int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]);
+int post_psis_expect_device(const double* d_ll, long long ld, int n, int S, const double* d_aux, int n_aux, long long aux_stride,
+                            double* const out[6], double* expect_host);
 
 namespace bfmmm {
 
@@ -116,6 +118,17 @@ bool cov_block_fits(const Ctx& c);
 // per-curve marginal log-density of curves [i0, i0 + rows), every chain, slots [first_slot, first_slot + n_slots) into
 // out[(i - i0) C S + q S + (t - first_slot)] (device); "" or what the kernel cannot take
 std::string launch_chain_curve_ll(const Ctx& c, int first_slot, int n_slots, int i0, int rows, double* out, hipStream_t st);
+
+// ---- kernels_loo_pointwise.hip ----
+// A row tile of bfmmm_chain_loo_pointwise: `rows` <= LP_ROWS consecutive observations of `curve`, the first of them at
+// y[y0] and at basis row b0 of the launch's B (the multivariate model reads neither), their values in rows out_row .. of the chunk's
+// matrices.  The host lists the tiles of a chunk in the order of the result.
+constexpr int LP_ROWS = 64;
+struct LpTile { int32_t curve, rows; int64_t y0, b0, out_row; };
+std::string loo_pointwise_check(const Ctx& c);
+std::string launch_loo_pointwise(const Ctx& c, const LpTile* tiles, long long n_tiles, const double* B, const double* y, int first_slot,
+                                 int n_slots, double* out, size_t out_stride, hipStream_t st);
+std::string launch_loo_pointwise_var(const double* mean, double* second, size_t count, hipStream_t st);
 
 // ---- kernels_curve_fit.hip ----
 // One call of bfmmm_chain_curve_fit / _bands: which (0 mean, 1 fit), the G x P evaluation basis E, the curve of every result

@@ -12,6 +12,8 @@ int bfmmm_io_fail(const std::string& m);      // entry_points.cpp: sets bfmmm_en
 void bfmmm_post_set_kernel_ms(float ms);      // kernels_post.hip: what bfmmm_post_last_kernel_ms returns
 // kernels_loo.hip: the PSIS / WAIC pass over n rows of S values on the current device (also in launchers.hpp, for capi_chain.hip)
 int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]);
+int post_psis_expect_device(const double* d_ll, long long ld, int n, int S, const double* d_aux, int n_aux, long long aux_stride,
+                            double* const out[6], double* expect_host);
 
 namespace {      // internal to each including file: the library exports nothing from here
 

@@ -354,6 +354,44 @@ class Sampler:
             out["n_modes"] = n_modes
         return out
 
+    def loo_pointwise(self, curves=None, first_slot=0, n_slots=None, trace=False, max_workspace_bytes=0):
+        """Observation-level PSIS-LOO and LOO-PIT from the chain slots of every chain, pooled (bfmmm_chain_loo_pointwise):
+        every observation y_ij of the selected curves (None: all) is left out in turn with the rest of its curve kept and the scores
+        chi_i integrated out -- "does the model interpolate a curve between its own observations".  Returns the dict of `loo` over the
+        N_obs observations (curve by curve in the order of `curves`, then observation by observation; the multivariate model: the P
+        coordinates of a curve) and "pit": E_loo[Phi(z_ij)], uniform under a calibrated model, "mean" and "sd": the LOO predictive
+        mean and sd of every observation, all (N_obs,); "offsets": (n_curves + 1,), curve j of the selection owns entries
+        offsets[j]:offsets[j + 1]; "curve_elpd_loo": the sums of "pointwise_elpd_loo" per curve.  trace adds "loglik_trace",
+        "pit_trace", "mean_trace" and "var_trace": (N_obs, C, S), refused above REFINE_TRACE_BYTES on the host."""
+        from . import api
+        S = self._slots(first_slot, n_slots)
+        idx, pc, m = self._curve_list(curves)
+        sel = np.arange(self.n) if idx is None else idx
+        if sel.size and (sel.min() < 0 or sel.max() >= self.n):
+            raise ValueError(f"loo_pointwise: 'curves' must lie in 0 .. {self.n - 1}")
+        ni = np.full(self.n, self.P, dtype=np.int64) if self.offsets is None else np.diff(self.offsets)
+        offsets = np.zeros(m + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(ni[sel])
+        N = int(offsets[-1])
+        Cn, Sn = self.n_chains, max(S, 0)
+        tr = {}
+        if trace:
+            if 4 * 8 * N * Cn * Sn > self.REFINE_TRACE_BYTES:
+                raise ValueError(f"loo_pointwise: the four traces of {N} observations x {Cn} chains x {Sn} slots take "
+                                 f"{4 * 8 * N * Cn * Sn} bytes on the host, above REFINE_TRACE_BYTES = {self.REFINE_TRACE_BYTES}: "
+                                 f"select fewer curves or slots")
+            tr = {k: np.zeros((N, Cn, Sn)) for k in ("loglik_trace", "pit_trace", "mean_trace", "var_trace")}
+        outs = [np.zeros(N) for _ in range(9)]
+        opt = lambda k: _dp(tr[k]) if k in tr else None
+        _lib.check(self.lib.bfmmm_chain_loo_pointwise(self.h, pc, m, int(first_slot), S, int(max_workspace_bytes), *[_dp(o) for o in outs],
+                                                      opt("loglik_trace"), opt("pit_trace"), opt("mean_trace"), opt("var_trace"), N))
+        pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs[:6]))
+        out = api.loo_totals(pw, Cn * S)
+        out.update(pit=outs[6], mean=outs[7], sd=outs[8], offsets=offsets,
+                   curve_elpd_loo=np.array([outs[1][offsets[j]:offsets[j + 1]].sum() for j in range(m)]))
+        out.update(tr)
+        return out
+
     def _fit_args(self, E, which, curves, first_slot, n_slots):
         w = {"mean": 0, "fit": 1}.get(which, which)
         if isinstance(w, str):

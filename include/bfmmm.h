@@ -547,6 +547,23 @@ int bfmmm_chain_loo_marginal_laplace(bfmmm_handle* h, int first_slot, int n_slot
                                      double* lpd_trace, double* ess_trace, int32_t* n_modes, double* components,
                                      double* eta_samples, int64_t capacity);
 
+/* Observation-level PSIS-LOO and LOO-PIT from the chain slots: every single observation y_ij of the selected curves
+ * (curves null: all n; otherwise n_curves indices, repeats allowed) is left out in turn, the rest of its curve kept and the scores
+ * chi_i integrated out.  Under draw t the law of y_ij given y_i,-j is N(m_ij(t), v_ij(t)) by a leverage formula on the M x M system of
+ * bfmmm_chain_curve_loglik; PSIS (relative efficiency 1, the chains pooled: n_chains x n_slots draws a row) on
+ * l_ij(t) = log p(y_ij | y_i,-j, draw t) gives the six arrays of bfmmm_chain_loo per observation, and from the same smoothed weights
+ * pit = E_loo[Phi(z_ij)] (uniform under a calibrated model), mean = E_loo[m_ij] and sd = sqrt(E_loo[m_ij^2 + v_ij] - mean^2), the LOO
+ * predictive mean and sd of the observation.  All nine arrays hold one entry per observation, in the order of the selected curves and
+ * then of the observations of a curve (the multivariate model: the P coordinates); `capacity` entries each, at least the number of
+ * such observations.  The traces (null: not wanted) hold n_chains x n_slots values an observation, draw fastest, then chain:
+ * l_ij(t), Phi(z_ij(t)), m_ij(t) and v_ij(t).  The work is done in chunks of row tiles (up to 64 consecutive observations of a curve)
+ * whose four device matrices, with the dense basis rows, fit max_workspace_bytes (0: 256 MiB); the results do not depend on it, bit
+ * for bit.  One device; at most 2^22 draws a row. */
+int bfmmm_chain_loo_pointwise(bfmmm_handle* h, const int32_t* curves, int n_curves, int first_slot, int n_slots,
+                              int64_t max_workspace_bytes, double* lppd, double* elpd_loo, double* p_loo, double* pareto_k,
+                              double* elpd_waic, double* p_waic, double* pit, double* mean, double* sd, double* loglik_trace,
+                              double* pit_trace, double* mean_trace, double* var_trace, int64_t capacity);
+
 /* The fitted function of held-out, partly observed curves from the chain slots: bfmmm_chain_predict with the same
  * arguments -- the same samples, and lpd, z_mean, z_sd, ess_mean, ess_min and their traces bit for bit -- and, on the G rows of an
  * evaluation basis E (G x P row-major, rows in the sampler's basis as in bfmmm_chain_curve_bands; the identity for the
@@ -662,7 +679,10 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * "loo_marginal_psis", those of the PSIS pass (one per chunk).
  * Of the last bfmmm_chain_predict_laplace: "predict_stats" as above; "predict_laplace", k_predict_lap and the pooling kernel (two
  * per chunk).  Of the last bfmmm_chain_loo_marginal_laplace: "loo_marginal_laplace", k_predict_lap and the counting kernel (two per
- * chunk); "loo_marginal_psis" as above. */
+ * chunk); "loo_marginal_psis" as above.
+ * Of the last bfmmm_chain_loo_pointwise (always measured): "loo_pointwise", the device time and launches of the dense basis rows (one
+ * launch a call, spline handles only), k_loo_pointwise (one per chunk) and, where var_trace is asked for, the variance kernel (one per
+ * chunk); "loo_pointwise_psis", those of the PSIS pass with its three expectations (one per chunk). */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 

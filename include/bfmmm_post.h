@@ -65,6 +65,11 @@ int bfmmm_post_curve_loglik(const bfmmm_post_input* in, int32_t first_kept, doub
  * 2^22 draws per row in this build. */
 int bfmmm_post_psis(const double* ll, int32_t n, int32_t S, int32_t device, double* lppd, double* elpd_loo, double* p_loo,
                     double* pareto_k, double* elpd_waic, double* p_waic);
+/* The same pass, and the expectations of n_aux auxiliary host matrices under each row's Pareto-smoothed weights: h
+ * holds n_aux matrices of the shape and layout of ll, one after the other; expect[a n + i] = sum_t w_it h_a[i, t] / sum_t w_it with
+ * the weights of row i's elpd_loo, the terms in the order of that sum.  The six arrays are bfmmm_post_psis's bit for bit. */
+int bfmmm_post_psis_expect(const double* ll, const double* h, int32_t n, int32_t S, int32_t n_aux, int32_t device, double* lppd,
+                           double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, double* expect);
 /* Convergence diagnostics of every row of a host draws array: x[s + n_draws (c + n_chains p)] (draw fastest, then chain,
  * then parameter: R's draws_array order), p < n_param.  Split R-hat (rank-normalised, the max of bulk and folded), bulk and
  * tail ESS, ESS and MCSE of the mean, mean and sd over all draws (Vehtari et al. 2021): seven arrays of
