@@ -2,7 +2,8 @@
 // diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
 // per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it, the cluster
-// covariance surfaces with their bands and their eigenvalues and eigenfunctions, the prediction of held-out curves with
+// covariance surfaces with their bands and their eigenvalues and eigenfunctions, the reference's rescale step per draw with the
+// summaries, mean functions and covariance surfaces under it, the prediction of held-out curves with
 // their fitted functions, the marginal PSIS-LOO over the training curves with the memberships integrated out, and the
 // observation-level PSIS-LOO with its LOO-PIT.
 // An entry point is its argument checks (SlotCheck: slots, curve selection, the grid pair, x, alpha, probs and `units`, the one
@@ -923,13 +924,17 @@ extern "C" int bfmmm_chain_cluster_mean_bands(bfmmm_handle* h, const int32_t* pe
 // simultaneous band per pair: k_ccov_project once per call, then per chunk of consecutive result rows k_ccov_values into rows of
 // C S values and launch_bands_moments and launch_bands_quantiles on them as they are.  The band's deviations need every chunk's
 // mean and sd: with one chunk its values are reused, with several a second sweep forms them again for k_ccov_maxdev.
-extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* perm, const double* E1, int G1, const double* E2, int G2,
-                                             int diagonal, const int32_t* pairs, int n_pairs, const double* x, int first_slot, int n_slots,
-                                             const double* probs, int nq, double alpha, int64_t max_workspace_bytes, double* mean, double* sd,
-                                             double* quant, double* crit, double* lower, double* upper, double* trace, int64_t capacity) {
-  const SlotCheck ck{"bfmmm_chain_cluster_cov_bands", h, first_slot, n_slots};
+// The body of bfmmm_chain_cluster_cov_bands and bfmmm_chain_cluster_cov_bands_rescaled: the labels of a draw are its row of perm, or
+// (mix set) its K x K transform mix[(cs K + k) K + c], under which the tables are filled raw and mixed in a second pass.
+static int ccov_call(const char* name, bfmmm_handle* h, const int32_t* perm, const double* mix, const double* E1, int G1, const double* E2,
+                     int G2, int diagonal, const int32_t* pairs, int n_pairs, const double* x, int first_slot, int n_slots,
+                     const double* probs, int nq, double alpha, int64_t max_workspace_bytes, double* mean, double* sd, double* quant,
+                     double* crit, double* lower, double* upper, double* trace, int64_t capacity, bool rescaled) {
+  const SlotCheck ck{name, h, first_slot, n_slots};
   const std::string& fn = ck.fn;
-  if (ck.ptrs({{"h", h}, {"perm", perm}, {"E1", E1}, {"mean", mean}, {"sd", sd}}) || ck.grid_pair(G1, E2, G2, diagonal)) return 1;
+  if (ck.ptrs({{"h", h}, {rescaled ? "mix" : "perm", rescaled ? (const void*)mix : (const void*)perm}, {"E1", E1}, {"mean", mean}, {"sd", sd}}) ||
+      ck.grid_pair(G1, E2, G2, diagonal))
+    return 1;
   if (n_pairs < 0) return fail(fn + ": 'n_pairs' must not be negative");
   const Ctx& c = h->c;
   const int K = c.d.K, P = c.d.P, D = c.d.D;
@@ -953,7 +958,7 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
     return 1;
   const bool band = crit || lower || upper;
   if (band && !(crit && lower && upper)) return fail(fn + ": 'crit', 'lower' and 'upper' must be all null or all set");
-  if ((band && ck.alpha_inside(alpha)) || perm_check(ck, perm)) return 1;
+  if ((band && ck.alpha_inside(alpha)) || (!rescaled && perm_check(ck, perm))) return 1;
   CcovCall f;
   f.G1 = G1; f.G2 = G2; f.diagonal = diagonal ? 1 : 0; f.first_slot = first_slot; f.n_slots = n_slots; f.n_pairs = m;
   const std::string bad = ccov_check(c, f);
@@ -968,13 +973,13 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
   const size_t tab1 = ccov_table_doubles(c, f, 0), tab2 = E2 ? ccov_table_doubles(c, f, 1) : 0;
   const size_t shared = sizeof(double) * (tab1 + tab2 + (size_t)G1 * P + (E2 ? (size_t)G2 * P : 0) + (x ? (size_t)D : 0) + 17 +
                                           (band ? (size_t)m * N + (size_t)m : 0)) +
-                        sizeof(int32_t) * (((N * K + 1) & ~(size_t)1) + 2 * (size_t)m);
+                        (rescaled ? sizeof(double) * N * K * K : sizeof(int32_t) * ((N * K + 1) & ~(size_t)1)) + sizeof(int32_t) * 2 * (size_t)m;
   int64_t chunk = 0;
   if (ck.units(budget_of(max_workspace_bytes), shared, r.row_bytes(), len, 1 << 30, "row", &chunk)) return 1;
   const int64_t nchunks = (len + chunk - 1) / chunk;
   HIPCHK(hipSetDevice(h->device));
   CallBufs b;
-  double *d_E1 = nullptr, *d_E2 = nullptr, *d_x = nullptr, *d_probs = nullptr, *d_dev = nullptr, *d_crit = nullptr;
+  double *d_E1 = nullptr, *d_E2 = nullptr, *d_x = nullptr, *d_probs = nullptr, *d_dev = nullptr, *d_crit = nullptr, *d_mix = nullptr;
   int32_t *d_perm = nullptr, *d_pairs = nullptr;
   Timer values, maxdev;
   HIPCHK(b.timers({&values, &maxdev}));
@@ -986,7 +991,8 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
     HIPCHK(b.get(&f.tab2, tab2));
   }
   if (x) HIPCHK(b.put(h, &d_x, x, (size_t)D));
-  HIPCHK(b.put(h, &d_perm, perm, N * K));
+  if (rescaled) HIPCHK(b.put(h, &d_mix, mix, N * K * K));
+  else HIPCHK(b.put(h, &d_perm, perm, N * K));
   HIPCHK(b.put(h, &d_pairs, (const int32_t*)pr.data(), pr.size()));
   HIPCHK(probs_put(b, h, probs, nq, &d_probs, 1));      // [16]: 1 - alpha
   r.probs = d_probs;
@@ -997,7 +1003,7 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
     HIPCHK(b.get(&d_crit, (size_t)m));
     HIPCHK(hipMemsetAsync(d_dev, 0, sizeof(double) * (size_t)m * N, h->st));      // the maximum starts from 0.0
   }
-  f.E1 = d_E1; f.E2 = d_E2; f.x = d_x; f.perm = d_perm; f.pairs = d_pairs;
+  f.E1 = d_E1; f.E2 = d_E2; f.x = d_x; f.perm = d_perm; f.mix = d_mix; f.pairs = d_pairs;
   if (once(ck, b, PT_CCOV_PROJECT, E2 ? 2 : 1, [&] { return launch_ccov_project(c, f, h->st); })) return 1;
   double* const outs[2] = {mean, sd};
   auto dev_launch = [&](int64_t r0, int rows) {
@@ -1052,6 +1058,157 @@ extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* per
     }
   }
   return 0;
+}
+
+extern "C" int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* perm, const double* E1, int G1, const double* E2, int G2,
+                                             int diagonal, const int32_t* pairs, int n_pairs, const double* x, int first_slot, int n_slots,
+                                             const double* probs, int nq, double alpha, int64_t max_workspace_bytes, double* mean, double* sd,
+                                             double* quant, double* crit, double* lower, double* upper, double* trace, int64_t capacity) {
+  return ccov_call("bfmmm_chain_cluster_cov_bands", h, perm, nullptr, E1, G1, E2, G2, diagonal, pairs, n_pairs, x, first_slot, n_slots, probs, nq,
+                   alpha, max_workspace_bytes, mean, sd, quant, crit, lower, upper, trace, capacity, false);
+}
+
+// bfmmm_chain_cluster_cov_bands with the transform of every draw in place of its permutation: W~_k = sum_c A[k][c] W_c (k_ccov_mix)
+extern "C" int bfmmm_chain_cluster_cov_bands_rescaled(bfmmm_handle* h, const double* mix, const double* E1, int G1, const double* E2, int G2,
+                                                      int diagonal, const int32_t* pairs, int n_pairs, const double* x, int first_slot,
+                                                      int n_slots, const double* probs, int nq, double alpha, int64_t max_workspace_bytes,
+                                                      double* mean, double* sd, double* quant, double* crit, double* lower, double* upper,
+                                                      double* trace, int64_t capacity) {
+  return ccov_call("bfmmm_chain_cluster_cov_bands_rescaled", h, nullptr, mix, E1, G1, E2, G2, diagonal, pairs, n_pairs, x, first_slot, n_slots,
+                   probs, nq, alpha, max_workspace_bytes, mean, sd, quant, crit, lower, upper, trace, capacity, true);
+}
+
+// ---- the reference's rescale step per draw (kernels_rescale.hip) ----------------------------------------------------
+// A, A^-1, the pure curves, rcond and z_min of every draw: one launch of k_rescale_transform, one workgroup per draw.  transform
+// null: the rule under perm (null: the identity); else A is the caller's and perm is not read.
+extern "C" int bfmmm_chain_rescale(bfmmm_handle* h, const int32_t* perm, const double* transform, int first_slot, int n_slots, double* mix,
+                                   double* mix_inv, int32_t* curve, double* rcond, double* z_min, int64_t* n_singular, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_rescale", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"mix", mix}, {"mix_inv", mix_inv}, {"curve", curve}, {"rcond", rcond}, {"z_min", z_min}}) || ck.range() ||
+      ck.row_limit())
+    return 1;
+  const int K = h->c.d.K;
+  const size_t N = (size_t)ck.CS(), KK = (size_t)K * K;
+  if (ck.capacity(capacity, (int64_t)(N * KK)) || (!transform && perm && perm_check(ck, perm))) return 1;
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_RESCALE_TRANSFORM, PT_RESCALE_TRANSFORM);
+  CallBufs b;
+  double *d_given = nullptr, *d_mix = nullptr, *d_inv = nullptr, *d_rc = nullptr, *d_zm = nullptr;
+  int32_t *d_perm = nullptr, *d_curve = nullptr, *d_flag = nullptr;
+  std::vector<int32_t> flag(N);
+  Timer tr;
+  HIPCHK(b.timers({&tr}));
+  if (transform) HIPCHK(b.put(h, &d_given, transform, N * KK));
+  else if (perm) HIPCHK(b.put(h, &d_perm, perm, N * K));
+  HIPCHK(b.get(&d_mix, N * KK));
+  HIPCHK(b.get(&d_inv, N * KK));
+  HIPCHK(b.get(&d_curve, N * K));
+  HIPCHK(b.get(&d_rc, N));
+  HIPCHK(b.get(&d_zm, N));
+  HIPCHK(b.get(&d_flag, N));
+  const int rc = for_chunks(ck, 1, 1, [&](int64_t, int) {
+    std::string err = timed(tr, h->st, [&] {
+      return launch_rescale_transform(h->c, d_perm, d_given, first_slot, n_slots, d_mix, d_inv, d_curve, d_rc, d_zm, d_flag, h->st);
+    });
+    if (err.empty()) err = Back{h, 0, 1}(mix, d_mix, N * KK)(mix_inv, d_inv, N * KK)(curve, d_curve, N * K)(rcond, d_rc, N)(z_min, d_zm, N)(flag.data(), d_flag, N).done();
+    if (err.empty()) collect(h, tr, PT_RESCALE_TRANSFORM);
+    return err;
+  });
+  if (rc) return rc;
+  int64_t cnt = 0;
+  for (size_t o = 0; o < N; ++o) cnt += flag[o] ? 1 : 0;      // the kernel's own flag: rcond of a finite inverse can underflow to 0
+  if (n_singular) *n_singular = cnt;
+  return 0;
+}
+
+// bfmmm_chain_aligned_summary under the transform of every draw: k_rescale_gather, then the unchanged RowReducer.  The reference
+// rescales nu, Phi, eta and xi by A and Z by A^-1, and nothing else.
+extern "C" int bfmmm_chain_rescaled_summary(bfmmm_handle* h, const char* name, const double* mix, const double* mix_inv, int first_slot,
+                                            int n_slots, const double* probs, int nq, int64_t max_workspace_bytes, double* rhat,
+                                            double* ess_bulk, double* ess_tail, double* ess_mean, double* mcse_mean, double* mean, double* sd,
+                                            double* quant, int64_t capacity) {
+  SlotCheck ck{"bfmmm_chain_rescaled_summary", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"name", name}, {"mix", mix}, {"mix_inv", mix_inv}, {"rhat", rhat}, {"ess_bulk", ess_bulk}, {"ess_tail", ess_tail},
+               {"ess_mean", ess_mean}, {"mcse_mean", mcse_mean}, {"mean", mean}, {"sd", sd}}) ||
+      ck.range() || ck.budget_sign(max_workspace_bytes))
+    return 1;
+  const Ctx& c = h->c;
+  const std::string nm = name;
+  const bool by_inverse = nm == "Z";
+  if (!by_inverse && nm != "nu" && nm != "Phi" && nm != "eta" && nm != "xi")
+    return fail(ck.fn + ": the reference defines no rescale for '" + nm + "' (only for nu, Phi, eta, xi and Z)");
+  const ChainArr a = chain_array(c, h->T, nm);
+  int64_t inner = 0;
+  if (!a.p || !align_axis(c.d, nm, &inner) || inner < 1) return fail(ck.fn + ": no array '" + nm + "' (covariate arrays exist once covariates were set)");
+  ck.tag = "(" + nm + ")";
+  if (ck.capacity(capacity, a.len) || ck.row_limit() || ck.probs_list(probs, nq, 0, quant)) return 1;
+  const int C = h->nch, S = n_slots, K = c.d.K;
+  RowReducer r(ck, nq, true);
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), 0, r.row_bytes(), a.len, kNoCap, nullptr, &chunk)) return 1;
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_RESCALE_GATHER, PT_RESCALE_GATHER);
+  CallBufs b;
+  double *d_probs = nullptr, *d_w = nullptr;
+  Timer gather;
+  HIPCHK(b.timers({&gather}));
+  HIPCHK(r.alloc(b, chunk));
+  HIPCHK(b.put(h, &d_w, by_inverse ? mix_inv : mix, r.N * K * K));
+  HIPCHK(probs_put(b, h, probs, nq, &d_probs));
+  r.probs = d_probs;
+  double* const outs[7] = {rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
+  return for_chunks(ck, a.len, chunk, [&](int64_t p0, int rows) {
+    std::string err = timed(gather, h->st, [&] {
+      return launch_rescale_gather(a.p, a.cov ? c.chain_bytes_cov : c.chain_bytes, a.ss, a.ps, first_slot, S, C, (int)p0, rows, d_w,
+                                   by_inverse ? 1 : K, by_inverse ? K : 1, K, inner, r.x, h->st);
+    });
+    if (err.empty()) err = r.reduce(rows);
+    if (err.empty()) err = r.to_host(p0, rows, outs, quant, nullptr);
+    if (err.empty()) collect(h, gather, PT_RESCALE_GATHER);
+    return err;
+  });
+}
+
+// bfmmm_chain_cluster_mean_bands under the transform of every draw, at the covariate setting x (D entries; null: nu alone):
+// k_rescale_project into rows of C S values, then the unchanged RowReducer.
+extern "C" int bfmmm_chain_cluster_mean_bands_rescaled(bfmmm_handle* h, const double* mix, const double* E, int G, const double* x,
+                                                       int first_slot, int n_slots, const double* probs, int nq, int64_t max_workspace_bytes,
+                                                       double* mean, double* sd, double* quant, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_cluster_mean_bands_rescaled", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"mix", mix}, {"E", E}, {"mean", mean}, {"sd", sd}})) return 1;
+  if (G < 1) return fail(ck.fn + ": 'G' must be at least 1");
+  if (ck.range() || ck.budget_sign(max_workspace_bytes)) return 1;
+  const Ctx& c = h->c;
+  const int K = c.d.K, P = c.d.P, D = c.d.D;
+  if (x && !(D > 0 && c.c_eta)) return fail(ck.fn + ": 'x' is given but the sampler has no covariates");
+  if (x && D > 8) return fail(ck.fn + ": more than 8 covariates");
+  for (int d = 0; x && d < D; ++d)
+    if (!std::isfinite(x[d])) return fail(ck.fn + ": 'x'[" + std::to_string(d) + "] is not finite");
+  const int64_t len = (int64_t)K * G;
+  if (ck.capacity(capacity, len, "rows") || ck.row_limit() || ck.probs_list(probs, nq, 0, quant)) return 1;
+  RowReducer r(ck, nq, false);
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), 0, r.row_bytes(), len, 65535, nullptr, &chunk)) return 1;
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_RESCALE_PROJECT, PT_RESCALE_PROJECT);
+  CallBufs b;
+  double *d_E = nullptr, *d_probs = nullptr, *d_mix = nullptr, *d_x = nullptr;
+  Timer project;
+  HIPCHK(b.timers({&project}));
+  HIPCHK(r.alloc(b, chunk));
+  HIPCHK(b.put(h, &d_E, E, (size_t)G * P));
+  HIPCHK(b.put(h, &d_mix, mix, r.N * K * K));
+  if (x) HIPCHK(b.put(h, &d_x, x, (size_t)D));
+  HIPCHK(probs_put(b, h, probs, nq, &d_probs));
+  r.probs = d_probs;
+  double* const outs[2] = {mean, sd};
+  return for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
+    std::string err = timed(project, h->st, [&] { return launch_rescale_project(c, d_E, G, d_mix, d_x, first_slot, n_slots, (int)r0, rows, r.x, h->st); });
+    if (err.empty()) err = r.reduce(rows);
+    if (err.empty()) err = r.to_host(r0, rows, outs, quant, nullptr);
+    if (err.empty()) collect(h, project, PT_RESCALE_PROJECT);
+    return err;
+  });
 }
 
 // ---- cluster eigenvalues and eigenfunctions under aligned labels (kernels_cluster_eig.hip) --------------------

@@ -40,7 +40,7 @@ enum { PT_CURVE_LL = 0, PT_FIT_PROJECT, PT_FIT_ROWS, PT_FIT_VALUES, PT_FIT_REDUC
        PT_COV_PROJECT, PT_COV, PT_SIM_LOSS, PT_SIM_LOSS_REDUCE, PT_ALIGN_GRAM, PT_ALIGN_GATHER, PT_ALIGN_PROJECT,
        PT_CCOV_PROJECT, PT_CCOV, PT_CCOV_MAXDEV, PT_CEIG_GRAM, PT_CEIG, PT_CEIG_VALUES, PT_PREDICT_STATS, PT_PREDICT, PT_PREDICT_FIT,
        PT_LOO_MARGINAL, PT_LOO_MARGINAL_PSIS, PT_PREDICT_LAPLACE, PT_LOO_MARGINAL_LAPLACE, PT_LOO_POINTWISE, PT_LOO_POINTWISE_PSIS,
-       PT_COUNT };
+       PT_RESCALE_TRANSFORM, PT_RESCALE_GATHER, PT_RESCALE_PROJECT, PT_COUNT };
 inline constexpr const char* kPostNames[PT_COUNT] = {"curve_ll_ms", "curve_fit_project", "curve_fit_rows", "curve_fit_values",
                                                      "curve_fit_reduce", "curve_sim", "curve_sim_reduce", "similarity",
                                                      "curve_cov_project", "curve_cov", "similarity_loss", "similarity_loss_reduce",
@@ -49,7 +49,8 @@ inline constexpr const char* kPostNames[PT_COUNT] = {"curve_ll_ms", "curve_fit_p
                                                      "cluster_eig_gram", "cluster_eig", "cluster_eig_values",
                                                      "predict_stats", "predict", "predict_fit",
                                                      "loo_marginal", "loo_marginal_psis", "predict_laplace",
-                                                     "loo_marginal_laplace", "loo_pointwise", "loo_pointwise_psis"};
+                                                     "loo_marginal_laplace", "loo_pointwise", "loo_pointwise_psis",
+                                                     "rescale_transform", "rescale_gather", "rescale_project"};
 
 struct bfmmm_handle {
   bfmmm_config cfg;

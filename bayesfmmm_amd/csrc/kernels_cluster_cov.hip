@@ -15,6 +15,8 @@
 //                   operand reads of one MFMA below (16 rows x 4 values of m, 32 bytes a row) cover whole 64-byte segments, every
 //                   byte fetched is used, and with MB = 1 they are one run of 512 bytes.  Filled once per call for E1 and once
 //                   more for E2 where given.
+//   k_ccov_mix      Only where the call takes a transform A per draw in place of perm: k_ccov_project fills the
+//                   tables of the raw components and this pass mixes them in place, W~_k = sum_c A[k][c] W_c.
 //   k_ccov_values   A workgroup of four waves owns one 16 x 16 tile (g-tile, h-tile) of one pair and a block of 16 consecutive
 //                   draws, four per wave.  For a draw lane l reads its operands straight from the two tables, A[row l & 15][m =
 //                   4 mb + (l >> 4)] of W1_k and B[m][col l & 15] of W2_l (all eight loads of a wave's four draws are issued before
@@ -66,7 +68,8 @@ struct CcovArgs {
   // chain 0's slot storage; chain q's is q * chain_bytes (covariate blocks: chain_bytes_cov) further
   const double *c_Phi, *c_xi;
   size_t chain_bytes, chain_bytes_cov;
-  const int32_t* perm;            // [cs K + k]
+  const int32_t* perm;            // [cs K + k]; null: the identity (the tables of the raw components, for k_ccov_mix)
+  const double* mix;              // [(cs K + k) K + c]: the transform of every draw in place of perm, or null
   const int32_t* pairs;           // [2 r], [2 r + 1]
   const double* x;                // the covariate setting, or null
   const double *tab1, *tab2;      // the projection tables of E1 and E2 (tab2 == tab1: E2 = E1)
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(CC_NT) void k_ccov_project(CcovArgs a, const double
   const double* c_Phi = ptr_shift(a.c_Phi, (size_t)q * a.chain_bytes) + t * K * P * M;
   const double* c_xi = DX > 0 ? ptr_shift(a.c_xi, (size_t)q * a.chain_bytes_cov) + t * K * P * D * M : nullptr;
   if (tid < CC_DMAX) sx[tid] = tid < DX ? a.x[tid] : 0.0;
-  if (tid < KMAX) sp[tid] = tid < K ? a.perm[(size_t)cs * K + tid] : 0;
+  if (tid < KMAX) sp[tid] = tid < K ? (a.perm ? a.perm[(size_t)cs * K + tid] : tid) : 0;
   __syncthreads();
   const int perk = GP * MP, total = K * perk;
   double* out = tab + (size_t)cs * total;
@@ -107,6 +110,33 @@ __global__ __launch_bounds__(CC_NT) void k_ccov_project(CcovArgs a, const double
       }
     }
     out[e] = s;
+  }
+}
+
+// The second pass of a call that takes a transform per draw: the table holds W_c of the raw components c, and
+// every entry (g, m) becomes W~_k = sum_c A[k][c] W_c, c in order from 0.0, for all k at once, in place: a thread reads the K values
+// of its entry before it writes them, and no other thread touches them.  A permutation matrix leaves 1 W + 0 W' + .., the entries
+// k_ccov_project writes under that permutation (the padding stays zero).
+__global__ __launch_bounds__(CC_NT) void k_ccov_mix(CcovArgs a, int GP, double* tab) {
+  __shared__ double sA[KMAX * KMAX];
+  const int cs = (int)blockIdx.x, tid = threadIdx.x, K = a.K;
+  if (tid < K * K) sA[tid] = a.mix[(size_t)cs * K * K + tid];
+  __syncthreads();
+  const int perk = GP * a.MP;
+  double* t = tab + (size_t)cs * K * perk;
+  for (int e = tid; e < perk; e += CC_NT) {
+    double w[KMAX];
+#pragma unroll
+    for (int c = 0; c < KMAX; ++c) w[c] = c < K ? t[(size_t)c * perk + e] : 0.0;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < K) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < KMAX; ++c)
+          if (c < K) s += sA[k * K + c] * w[c];
+        t[(size_t)k * perk + e] = s;
+      }
   }
 }
 
@@ -239,7 +269,7 @@ CcovArgs ccov_args(const Ctx& c, const CcovCall& f, const CcovGeom& g) {
   CcovArgs a;
   a.c_Phi = c.c_Phi; a.c_xi = g.DX > 0 ? c.c_xi : nullptr;
   a.chain_bytes = c.chain_bytes; a.chain_bytes_cov = c.chain_bytes_cov;
-  a.perm = f.perm; a.pairs = f.pairs; a.x = g.DX > 0 ? f.x : nullptr;
+  a.perm = f.mix ? nullptr : f.perm; a.mix = f.mix; a.pairs = f.pairs; a.x = g.DX > 0 ? f.x : nullptr;
   a.MP = 4 * g.MB;
   a.tab1 = f.tab1; a.tab2 = f.tab2 ? f.tab2 : f.tab1;
   a.GP1 = g.GP1; a.GP2 = f.tab2 ? g.GP2 : g.GP1;
@@ -278,11 +308,15 @@ std::string launch_ccov_project(const Ctx& c, const CcovCall& f, hipStream_t st)
   CcovGeom g;
   const std::string err = ccov_geom(c, f, g);
   if (!err.empty()) return "k_ccov_project: " + err;
-  if (!f.E1 || !f.tab1 || !f.perm || (f.E2 && !f.tab2) || (f.x && (!c.covariance_adj || c.d.D < 1))) return "k_ccov_project: bad arguments";
+  if (!f.E1 || !f.tab1 || (!f.perm && !f.mix) || (f.E2 && !f.tab2) || (f.x && (!c.covariance_adj || c.d.D < 1))) return "k_ccov_project: bad arguments";
   const CcovArgs a = ccov_args(c, f, g);
   const dim3 grid((unsigned)a.N);
   hipLaunchKernelGGL(k_ccov_project, grid, dim3(CC_NT), 0, st, a, f.E1, f.G1, g.GP1, f.tab1);
   if (f.E2) hipLaunchKernelGGL(k_ccov_project, grid, dim3(CC_NT), 0, st, a, f.E2, f.G2, g.GP2, f.tab2);
+  if (f.mix) {
+    hipLaunchKernelGGL(k_ccov_mix, grid, dim3(CC_NT), 0, st, a, g.GP1, f.tab1);
+    if (f.E2) hipLaunchKernelGGL(k_ccov_mix, grid, dim3(CC_NT), 0, st, a, g.GP2, f.tab2);
+  }
   if (hipGetLastError() != hipSuccess) return "k_ccov_project: launch failed";
   return "";
 }

@@ -190,6 +190,20 @@ std::string launch_align_gather(const double* base, size_t chain_bytes, long lon
 std::string launch_align_project(const Ctx& c, const double* E, int G, const int32_t* perm, int first_slot, int n_slots, int r0, int rows,
                                  double* V, hipStream_t st);
 
+// ---- kernels_rescale.hip ----
+// The reference's rescale step per draw.  launch_rescale_transform: of every draw cs = q S + s of every chain and
+// slots [first_slot, first_slot + n_slots), mix[(cs K + k) K + c] = A, mix_inv[(cs K + c) K + k] = A^-1, curve[cs K + k], rcond[cs]
+// z_min[cs] and singular_flag[cs] (1: singular; all device).  given null: the rule, A[k][.] = the Z row of the first curve that attains max_i Z[i, perm[k]] (perm
+// null: the identity); else A = given (N K K) and curve = -1.  A singular draw: A^-1 and z_min NaN, rcond 0.
+// launch_rescale_gather: launch_align_gather with element e = a + inner (k + K b) = sum_c W[cs K K + k sk + c sc] src[a + inner (c +
+// K b)], inner >= 1.  launch_rescale_project: launch_align_project of sum_c A[k][c] (nu_c + sum_d x_d eta_c,d), x of D entries or null.
+std::string launch_rescale_transform(const Ctx& c, const int32_t* perm, const double* given, int first_slot, int n_slots, double* mix,
+                                     double* mix_inv, int32_t* curve, double* rcond, double* z_min, int32_t* singular_flag, hipStream_t st);
+std::string launch_rescale_gather(const double* base, size_t chain_bytes, long long ss, long long ps, int first, int S, int C, int p0, int P,
+                                  const double* W, int sk, int sc, int K, long long inner, double* ws, hipStream_t st);
+std::string launch_rescale_project(const Ctx& c, const double* E, int G, const double* mix, const double* x, int first_slot, int n_slots,
+                                   int r0, int rows, double* V, hipStream_t st);
+
 // ---- kernels_curve_cov.hip ----
 // One call of bfmmm_chain_curve_cov: the evaluation bases E1 (G1 x P) and E2 (G2 x P; null: E2 = E1, G2 = G1), whether only the
 // diagonal g = h is wanted (E2 null), the curve of every result row of the call (null: curve r), the slot range and the call's
@@ -217,6 +231,7 @@ struct CcovCall {
   long long n_pairs = 0;
   const double *E1 = nullptr, *E2 = nullptr, *x = nullptr;
   const int32_t *perm = nullptr, *pairs = nullptr;
+  const double* mix = nullptr;      // bfmmm_chain_cluster_cov_bands_rescaled: A[(cs K + k) K + c] of every draw, in place of perm
   double *tab1 = nullptr, *tab2 = nullptr;
 };
 std::string ccov_check(const Ctx& c, const CcovCall& f);

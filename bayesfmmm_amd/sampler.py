@@ -65,6 +65,31 @@ def _proposal_option(laplace, refused):
     return deco
 
 
+def _rescale_option(rescaled, with_x=False):
+    """Gives a method that takes `perm` the keyword-only option rescale=None.  None, the default, calls the method as it
+    is, with its own parameters and defaults, which are what inspect.signature shows.  With the dict `Sampler.rescale` returned for the
+    same slots it calls the method named `rescaled` with the same arguments; perm may then be left out or None, and where it is given it
+    must be the dict's.  with_x: the method also gains the keyword-only x=None, one covariate setting, honoured only with rescale and
+    refused without it."""
+    def deco(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def call(self, *args, rescale=None, **kw):
+            if with_x and rescale is None and kw.get("x") is not None:
+                raise ValueError(f"{fn.__name__}: 'x' is honoured only with rescale=: without it this is the mean function at x = 0")
+            extra = {"x": kw.pop("x", None)} if with_x else {}
+            if rescale is None:
+                return fn(self, *args, **kw)
+            b = sig.bind_partial(self, *args, **kw)
+            b.apply_defaults()
+            given = {k: v for k, v in b.arguments.items() if k != "self"}
+            given.setdefault("perm", None)
+            return getattr(self, rescaled)(rescale=rescale, **given, **extra)
+        return call
+    return deco
+
+
 def _probs_arg(probs):
     return np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
 
@@ -535,11 +560,17 @@ class Sampler:
             raise ValueError(f"perm must have shape ({self.n_chains}, {S}, {self.K}): align()['perm'] of the same slots")
         return p
 
+    @_rescale_option("_rescaled_summary")
     def aligned_summary(self, name, perm, probs=(0.025, 0.5, 0.975), first_slot=0, n_slots=None, max_workspace_bytes=0):
         """`diagnostics(name)` with every draw's components relabelled by its row of perm (`align`'s "perm" of the same slots),
         and pooled quantiles of the same values, on the device (bfmmm_chain_aligned_summary): memberships with
         credible intervals for "Z", and an R-hat of nu or Z that measures mixing rather than labelling.  Names without a component
-        axis are summarised as they are.  Returns the seven STAT_NAMES shaped like a draw, plus "quantiles": shape + (nq,) by
+        axis are summarised as they are.  Keyword-only rescale=None: the dict of `rescale` for the same slots, and the summary is the
+        one after the reference's rescale step (bfmmm_chain_rescaled_summary): "nu", "Phi", "eta" and "xi" mixed over
+        their component axis by every draw's A, "Z" by its A^-1 -- memberships that reach 0 and 1, the reference's ZCI; other names
+        are refused, the reference defines no rescale for them.  perm may then be left out or None (the dict has it); where it is
+        given it must be the dict's own: a dict made with perm=None takes no perm here, not even the identity.
+        Returns the seven STAT_NAMES shaped like a draw, plus "quantiles": shape + (nq,) by
         arma::quantile's rule, and "probs"."""
         S = self._slots(first_slot, n_slots)
         p = self._perm_arg(perm, S)
@@ -556,11 +587,15 @@ class Sampler:
         out["probs"] = pr
         return out
 
+    @_rescale_option("_cluster_mean_bands_rescaled", with_x=True)
     def cluster_mean_bands(self, E, perm, probs=(0.025, 0.5, 0.975), first_slot=0, n_slots=None, max_workspace_bytes=0):
         """Pointwise posterior mean, sd and quantiles of the K cluster mean functions E nu_k (E: G x P rows in the sampler's basis,
         as in `curve_fit`) with the labels aligned by perm (`align`'s "perm" of the same slots) and the chains pooled, on the
         device (bfmmm_chain_cluster_mean_bands); the reference's FMeanCI without rescale / trans_mats.  With
-        covariates set: the mean function at x = 0.  Returns {"mean": (K, G), "sd": (K, G), "quantiles": (K, G, nq), "probs"}."""
+        covariates set: the mean function at x = 0.  Keyword-only rescale=None: the dict of `rescale` for the same slots (perm as
+        in `aligned_summary`), and the bands are those of E sum_c A[k][c] (nu_c + sum_d x_d eta_c,d), the reference's FMeanCI with
+        rescale / trans_mats (bfmmm_chain_cluster_mean_bands_rescaled).  Keyword-only x=None: one covariate setting
+        of D entries (covariates must be set), honoured only with rescale and refused without it.  Returns {"mean": (K, G), "sd": (K, G), "quantiles": (K, G, nq), "probs"}."""
         Em = self._basis_arg(E, "E")
         S = self._slots(first_slot, n_slots)
         p = self._perm_arg(perm, S)
@@ -573,24 +608,32 @@ class Sampler:
         return {"mean": mean.reshape((K, G), order="F"), "sd": sd.reshape((K, G), order="F"),
                 "quantiles": qs.reshape((K, G, pr.size), order="F"), "probs": pr}
 
+    @_rescale_option("_cluster_cov_bands_rescaled")
     def cluster_cov_bands(self, E, perm, E2=None, pairs=None, x=None, diagonal=False, probs=(0.025, 0.5, 0.975),
                           simultaneous=None, trace=False, first_slot=0, n_slots=None, max_workspace_bytes=0):
         """The covariance surfaces between clusters, C^(k,l)(g, h) = sum_m (E_g . theta_km)(E2_h . theta_lm), theta_km = phi_km +
         sum_d x_d xi_kmd, with the labels aligned by perm (`align`'s "perm" of the same slots) and the chains pooled: pointwise
         mean, sd and quantiles and, with simultaneous=alpha, the simultaneous (1 - alpha) band of every pair by
         `curve_bands_simultaneous`' rule, on the device (bfmmm_chain_cluster_cov_bands); the reference's FCovCI
-        without rescale / trans_mats.  The sum over m does not see the signs of the eigenfunctions, so labels are all that has
-        to be aligned.  E (G1 x P) and E2 (G2 x P; default: E) are rows in the sampler's basis.  pairs: (k, l) pairs of aligned
+        without rescale / trans_mats.  Keyword-only rescale=None: the dict of `rescale` for the same slots (perm as in
+        `aligned_summary`), and theta~_km = sum_c A[k][c] theta_cm takes the place of theta_{perm[k], m}, the reference's FCovCI with
+        rescale / trans_mats (bfmmm_chain_cluster_cov_bands_rescaled).  The sum over m does not see the signs of the
+        eigenfunctions, so labels are all that has to be aligned.  E (G1 x P) and E2 (G2 x P; default: E) are rows in the sampler's basis.  pairs: (k, l) pairs of aligned
         components in any order (default: all k <= l, (0, 0), (0, 1), ..).  x: one covariate setting of D entries (covariance-
         adjusted samplers; default: phi alone).  diagonal: only g = h (E2 must be None), the variance function where k = l.
         trace: also the values of every draw, chain-major.
         Returns {"mean", "sd": (m, G1, G2), "quantiles": (m, G1, G2, nq), "probs", "pairs": (m, 2)}, with simultaneous also
         {"crit": (m,), "lower", "upper": (m, G1, G2), "alpha"}, with trace also {"trace": (m, G1, G2, N)}; with diagonal the G2
         axis is dropped."""
-        E1m = self._basis_arg(E, "E")
-        E2m = None if E2 is None else self._basis_arg(E2, "E2")
         S = self._slots(first_slot, n_slots)
         p = self._perm_arg(perm, S)
+        return self._cluster_cov(self.lib.bfmmm_chain_cluster_cov_bands, _ip(p), E, E2, pairs, x, diagonal, probs, simultaneous, trace,
+                                 first_slot, S, max_workspace_bytes)
+
+    def _cluster_cov(self, call, labels, E, E2, pairs, x, diagonal, probs, simultaneous, trace, first_slot, S, max_workspace_bytes):
+        """the body of `cluster_cov_bands` without and with rescale=: `labels` is the pointer to perm or to the transform"""
+        E1m = self._basis_arg(E, "E")
+        E2m = None if E2 is None else self._basis_arg(E2, "E2")
         pr = _probs_arg(probs)
         if pairs is None:
             pl = np.array([(k, l) for k in range(self.K) for l in range(k, self.K)], dtype=np.int32).reshape(-1, 2)
@@ -608,13 +651,106 @@ class Sampler:
         if trace:
             out["trace"] = np.zeros((m,) + cell + (N,))
         band = [_dp(out[k]) if simultaneous is not None else None for k in ("crit", "lower", "upper")]
-        _lib.check(self.lib.bfmmm_chain_cluster_cov_bands(
-            self.h, _ip(p), _dp(E1m), G1, None if E2m is None else _dp(E2m), G2, int(bool(diagonal)),
+        _lib.check(call(
+            self.h, labels, _dp(E1m), G1, None if E2m is None else _dp(E2m), G2, int(bool(diagonal)),
             None if pairs is None else _ip(pl), m if pairs is not None else 0, None if xv is None else _dp(xv),
             int(first_slot), S, _dp(pr) if pr.size else None, pr.size, float(simultaneous) if simultaneous is not None else 0.0,
             int(max_workspace_bytes), _dp(out["mean"]), _dp(out["sd"]), _dp(out["quantiles"]) if pr.size else None, *band,
             _dp(out["trace"]) if trace else None, out["mean"].size))
         return out
+
+    def rescale(self, perm=None, transform=None, first_slot=0, n_slots=None):
+        """The reference's `rescale` step for every draw of chain slots [first_slot, first_slot + n_slots) of every chain of the
+        batch, on the device (bfmmm_chain_rescale).  A mixed-membership model is identified only up to an invertible
+        K x K map of the simplex; the reference (ZCI, FMeanCI, FCovCI, MVMeanCI, MVCovCI, rescale on by default) reports Z A^-1,
+        A nu, A Phi, A eta and A xi with A the map that makes the purest curve of every component a vertex: row k of A is the Z row
+        of the first curve that attains max_i Z[i, perm[k]].  perm: `align`'s "perm" of the same slots (None: the identity).
+        transform: (C, S, K, K) matrices used as A instead of the rule, the reference's trans_mats, already in the aligned
+        labelling; perm is then only carried along.  The reference refuses the rule for K > 2, where Z A^-1 may leave the simplex;
+        here it is allowed and "z_min" reports by how much.  A singular draw (two components share their pure curve, or A is not
+        finite) gets a NaN inverse, rcond 0 and z_min NaN, is counted in "n_singular" and passes its NaN on to the pooled rows.
+        Returns {"transform", "inverse": (C, S, K, K), "curve": (C, S, K) int32 or None with `transform`, "rcond", "z_min": (C, S),
+        "n_singular", "perm", "first_slot", "n_slots"}: the keyword `rescale` of `aligned_summary`, `cluster_mean_bands` and
+        `cluster_cov_bands` for the same slots."""
+        S = self._slots(first_slot, n_slots)
+        Cn, K = self.n_chains, self.K
+        p = None if perm is None else self._perm_arg(perm, S)
+        tm = None
+        if transform is not None:
+            tm = np.ascontiguousarray(transform, dtype=np.float64)
+            if tm.shape != (Cn, S, K, K):
+                raise ValueError(f"transform must have shape ({Cn}, {S}, {K}, {K}): one K x K matrix per chain and slot")
+        Sn = max(S, 0)
+        out = {"transform": np.zeros((Cn, Sn, K, K)), "inverse": np.zeros((Cn, Sn, K, K)), "curve": np.zeros((Cn, Sn, K), dtype=np.int32),
+               "rcond": np.zeros((Cn, Sn)), "z_min": np.zeros((Cn, Sn))}
+        ns = C.c_int64(0)
+        _lib.check(self.lib.bfmmm_chain_rescale(self.h, None if p is None or tm is not None else _ip(p), None if tm is None else _dp(tm),
+                                                int(first_slot), S, _dp(out["transform"]), _dp(out["inverse"]), _ip(out["curve"]),
+                                                _dp(out["rcond"]), _dp(out["z_min"]), C.byref(ns), out["transform"].size))
+        if tm is not None:
+            out["curve"] = None
+        out.update(n_singular=int(ns.value), perm=p, first_slot=int(first_slot), n_slots=S)
+        return out
+
+    def _rescale_arg(self, rescale, perm, first_slot, S):
+        """the dict of `rescale` for these slots, checked against them and against perm where that is given too"""
+        need = ("transform", "inverse", "perm", "first_slot", "n_slots")
+        if not isinstance(rescale, dict) or any(k not in rescale for k in need):
+            raise ValueError("rescale must be the dict Sampler.rescale returns")
+        shp = (self.n_chains, S, self.K, self.K)
+        if (rescale["first_slot"], rescale["n_slots"]) != (int(first_slot), S):
+            raise ValueError(f"rescale is of slots [{rescale['first_slot']}, {rescale['first_slot'] + rescale['n_slots']}), not of "
+                             f"[{int(first_slot)}, {int(first_slot) + S}): call Sampler.rescale for the same slots")
+        for k in ("transform", "inverse"):
+            if np.shape(rescale[k]) != shp:
+                raise ValueError(f"rescale['{k}'] has shape {np.shape(rescale[k])}, not {shp}: it is of another sampler")
+        if perm is not None:
+            p = self._perm_arg(perm, S)
+            if rescale["perm"] is None or not np.array_equal(p, rescale["perm"]):
+                raise ValueError("perm differs from the perm the rescale dict was computed with")
+        return (np.ascontiguousarray(rescale["transform"], dtype=np.float64), np.ascontiguousarray(rescale["inverse"], dtype=np.float64))
+
+    def _rescaled_summary(self, name, rescale, perm=None, probs=(0.025, 0.5, 0.975), first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """`aligned_summary` with rescale= (bfmmm_chain_rescaled_summary)"""
+        S = self._slots(first_slot, n_slots)
+        A, Ai = self._rescale_arg(rescale, perm, first_slot, S)
+        pr = _probs_arg(probs)
+        shp = self._draw_shape(name) if name in DRAW_DIMS else (1,)
+        cnt = int(np.prod(shp, dtype=np.int64))
+        outs = [np.zeros(cnt) for _ in range(7)]
+        qs = np.zeros((cnt, pr.size))
+        _lib.check(self.lib.bfmmm_chain_rescaled_summary(self.h, name.encode(), _dp(A), _dp(Ai), int(first_slot), S,
+                                                         _dp(pr) if pr.size else None, pr.size, int(max_workspace_bytes),
+                                                         *[_dp(o) for o in outs], _dp(qs) if pr.size else None, cnt))
+        out = {k: o.reshape(shp, order="F") for k, o in zip(STAT_NAMES, outs)}
+        out["quantiles"] = qs.reshape(shp + (pr.size,), order="F") if shp else qs.reshape((pr.size,))
+        out["probs"] = pr
+        return out
+
+    def _cluster_mean_bands_rescaled(self, E, rescale, perm=None, x=None, probs=(0.025, 0.5, 0.975), first_slot=0, n_slots=None,
+                                     max_workspace_bytes=0):
+        """`cluster_mean_bands` with rescale= (bfmmm_chain_cluster_mean_bands_rescaled)"""
+        Em = self._basis_arg(E, "E")
+        S = self._slots(first_slot, n_slots)
+        A, _ = self._rescale_arg(rescale, perm, first_slot, S)
+        pr = _probs_arg(probs)
+        xv = self._x_arg(x)
+        G, K = Em.shape[0], self.K
+        mean, sd, qs = np.zeros(K * G), np.zeros(K * G), np.zeros((K * G, pr.size))
+        _lib.check(self.lib.bfmmm_chain_cluster_mean_bands_rescaled(self.h, _dp(A), _dp(Em), G, None if xv is None else _dp(xv),
+                                                                    int(first_slot), S, _dp(pr) if pr.size else None, pr.size,
+                                                                    int(max_workspace_bytes), _dp(mean), _dp(sd),
+                                                                    _dp(qs) if pr.size else None, K * G))
+        return {"mean": mean.reshape((K, G), order="F"), "sd": sd.reshape((K, G), order="F"),
+                "quantiles": qs.reshape((K, G, pr.size), order="F"), "probs": pr}
+
+    def _cluster_cov_bands_rescaled(self, E, rescale, perm=None, E2=None, pairs=None, x=None, diagonal=False, probs=(0.025, 0.5, 0.975),
+                                    simultaneous=None, trace=False, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """`cluster_cov_bands` with rescale= (bfmmm_chain_cluster_cov_bands_rescaled)"""
+        S = self._slots(first_slot, n_slots)
+        A, _ = self._rescale_arg(rescale, perm, first_slot, S)
+        return self._cluster_cov(self.lib.bfmmm_chain_cluster_cov_bands_rescaled, _dp(A), E, E2, pairs, x, diagonal, probs, simultaneous,
+                                 trace, first_slot, S, max_workspace_bytes)
 
     def cluster_eigen(self, E, perm, weights=None, n_functions=None, x=None, ref="mean", probs=(0.025, 0.5, 0.975), trace=False,
                       first_slot=0, n_slots=None, max_workspace_bytes=0):
@@ -622,7 +758,8 @@ class Sampler:
         eigenvalues lambda_k1 >= .. >= lambda_kM >= 0 and the J = n_functions leading eigenfunctions psi_kj on the grid of the
         operator C^(k,k) discretised with the quadrature weights w, the total variance sum_g w_g C^(k,k)(g, g) and the share
         lambda_kj / total each component explains, with the labels aligned by perm (`align`'s "perm" of the same slots) and the
-        chains pooled, on the device (bfmmm_chain_cluster_eigen).  These do not see the signs or the joint rotation of
+        chains pooled, on the device (bfmmm_chain_cluster_eigen).  Without the reference's rescale / trans_mats: the
+        per-draw transform of `rescale` is out of scope here.  These do not see the signs or the joint rotation of
         the sampler's own eigenfunction blocks, which are not identified.  E (G x P): rows in the sampler's basis (the identity for
         the multivariate model, where this is PCA of Phi_k Phi_k').  weights: G non-negative quadrature weights (default: 1).
         n_functions: default M.  x: one covariate setting of D entries (covariance-adjusted samplers; default: phi alone).

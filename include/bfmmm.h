@@ -391,6 +391,55 @@ int bfmmm_chain_cluster_cov_bands(bfmmm_handle* h, const int32_t* perm, const do
                                   double* mean, double* sd, double* quant, double* crit, double* lower, double* upper,
                                   double* trace, int64_t capacity);
 
+/* The reference's `rescale` step per draw (its ZCI, FMeanCI, FCovCI, MVMeanCI and MVCovCI rescale by default): a
+ * mixed-membership model is identified only up to an invertible K x K map of the simplex, and the reference reports Z A^-1, A nu,
+ * A Phi_m, A eta and A xi, with A the map under which the purest curve of every component is a vertex.  For draw cs = q n_slots + s
+ * of chain slots [first_slot, first_slot + n_slots) of EVERY chain of the batch:
+ *   rule mode (transform NULL): for the aligned component k, curve[cs K + k] = the smallest i that attains max_i Z[i, perm[k]]
+ *     (arma::index_max: the first maximum; a NaN is never the maximum) and A[k][c] = Z[curve, c] over the raw components c, copied.
+ *     perm: the draw's row of bfmmm_chain_align (NULL: the identity).  The reference refuses the rule for K > 2, where Z A^-1 may
+ *     leave the simplex; here it is allowed for every K <= 8 and z_min reports by how much.
+ *   given mode: A = transform[(cs K + k) K + c] (N K K doubles; the reference's trans_mats, already in the aligned labelling);
+ *     perm is not read and curve is -1.
+ *   mix[(cs K + k) K + c] = A,  mix_inv[(cs K + c) K + k] = A^-1      capacity >= N K K entries each, N = C n_slots
+ *   rcond[cs] = 1 / (|A|_1 |A^-1|_1),  z_min[cs] = min_{i,k} sum_c Z[i, c] A^-1[c][k]      N entries each; curve: N K
+ *   *n_singular (may be NULL): the singular draws -- a pivot exactly zero, A not finite or, under the rule, two components that
+ *     share their pure curve.
+ *     Such a draw gets A^-1 = NaN, rcond = 0 and z_min = NaN; it is counted, never dropped and never an error, and the pooled rows
+ *     of the calls below then carry the NaN.  A NaN among the rescaled memberships of a draw that is not singular is kept in z_min.
+ * A^-1 by Gauss-Jordan elimination with partial pivoting in one fixed order without fused multiply-adds, so repeated calls give the
+ * same bits.  At most 2^22 draws.  Runs on the sampler's stream and leaves its state and slots untouched. */
+int bfmmm_chain_rescale(bfmmm_handle* h, const int32_t* perm, const double* transform, int first_slot, int n_slots, double* mix,
+                        double* mix_inv, int32_t* curve, double* rcond, double* z_min, int64_t* n_singular, int64_t capacity);
+
+/* bfmmm_chain_aligned_summary under the transform of every draw (mix, mix_inv of bfmmm_chain_rescale for the same slots) in place of
+ * its permutation: for nu, Phi, eta and xi the element with aligned component k is sum_c A[k][c] (the element of component c), for
+ * Z it is sum_c Z[i, c] A^-1[c][k], c = 0 .. K - 1 in order without fused multiply-adds; with permutation matrices these are
+ * bfmmm_chain_aligned_summary's results bit for bit.  Any other name is refused: the reference defines no rescale for it.  The
+ * other arguments, the budget rule and the limits are those of bfmmm_chain_aligned_summary; the call holds 8 C n_slots K K bytes of
+ * the transform on the device. */
+int bfmmm_chain_rescaled_summary(bfmmm_handle* h, const char* name, const double* mix, const double* mix_inv, int first_slot, int n_slots,
+                                 const double* probs, int nq, int64_t max_workspace_bytes, double* rhat, double* ess_bulk,
+                                 double* ess_tail, double* ess_mean, double* mcse_mean, double* mean, double* sd, double* quant,
+                                 int64_t capacity);
+
+/* bfmmm_chain_cluster_mean_bands under the transform of every draw, the reference's FMeanCI with rescale / trans_mats:
+ *   v_kg(q, s) = sum_p E_gp sum_c A[k][c] (nu_c,p + sum_d x_d eta_c,p,d)      (p, c and d in order from 0)
+ * x: one covariate setting of D finite entries, which the reference's FMeanCI with X rescales too; it requires covariates to be
+ * set.  NULL: nu alone.  The other arguments are those of bfmmm_chain_cluster_mean_bands. */
+int bfmmm_chain_cluster_mean_bands_rescaled(bfmmm_handle* h, const double* mix, const double* E, int G, const double* x, int first_slot,
+                                            int n_slots, const double* probs, int nq, int64_t max_workspace_bytes, double* mean,
+                                            double* sd, double* quant, int64_t capacity);
+
+/* bfmmm_chain_cluster_cov_bands under the transform of every draw, the reference's FCovCI with rescale / trans_mats: the tables
+ * are filled for the raw components and a second pass forms W~_k = sum_c A[k][c] W_c (c in order from 0); the values, the bands,
+ * the chunks and every other argument are those of bfmmm_chain_cluster_cov_bands, and with permutation matrices so are the bits. */
+int bfmmm_chain_cluster_cov_bands_rescaled(bfmmm_handle* h, const double* mix, const double* E1, int G1, const double* E2, int G2,
+                                           int diagonal, const int32_t* pairs, int n_pairs, const double* x, int first_slot,
+                                           int n_slots, const double* probs, int nq, double alpha, int64_t max_workspace_bytes,
+                                           double* mean, double* sd, double* quant, double* crit, double* lower, double* upper,
+                                           double* trace, int64_t capacity);
+
 /* The eigenvalues and eigenfunctions of the cluster covariance operators with the labels aligned and the chains pooled (DESIGN.md
  * 7l): the principal components of the surfaces of bfmmm_chain_cluster_cov_bands.  For draw cs = q n_slots + s of chain slots
  * [first_slot, first_slot + n_slots) of EVERY chain of the batch, its row perm[cs K + .], a grid basis E (G x P, row-major in the
@@ -682,7 +731,11 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * chunk); "loo_marginal_psis" as above.
  * Of the last bfmmm_chain_loo_pointwise (always measured): "loo_pointwise", the device time and launches of the dense basis rows (one
  * launch a call, spline handles only), k_loo_pointwise (one per chunk) and, where var_trace is asked for, the variance kernel (one per
- * chunk); "loo_pointwise_psis", those of the PSIS pass with its three expectations (one per chunk). */
+ * chunk); "loo_pointwise_psis", those of the PSIS pass with its three expectations (one per chunk).
+ * Of the last bfmmm_chain_rescale / bfmmm_chain_rescaled_summary / bfmmm_chain_cluster_mean_bands_rescaled (always measured):
+ * "rescale_transform" (one launch), "rescale_gather" and "rescale_project" (one launch per chunk), the device time and launches of
+ * their own kernels.  bfmmm_chain_cluster_cov_bands_rescaled: the timers of bfmmm_chain_cluster_cov_bands, "cluster_cov_project"
+ * with the mixing pass in it. */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
