@@ -4,8 +4,8 @@
 // per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it, the cluster
 // covariance surfaces with their bands and their eigenvalues and eigenfunctions, the reference's rescale step per draw with the
 // summaries, mean functions and covariance surfaces under it, the prediction of held-out curves with
-// their fitted functions, the marginal PSIS-LOO over the training curves with the memberships integrated out, and the
-// observation-level PSIS-LOO with its LOO-PIT.
+// their fitted functions, the marginal PSIS-LOO over the training curves with the memberships integrated out, the
+// observation-level PSIS-LOO with its LOO-PIT and the leave-block-out PSIS cross-validation within curves.
 // An entry point is its argument checks (SlotCheck: slots, curve selection, the grid pair, x, alpha, probs and `units`, the one
 // budget rule), its workspace and the event pairs that time its launches into the handle's PT_* timers (CallBufs owns both) and
 // one for_chunks.  What several of them do is written once: `once` for a launch that runs once per call (the projections), Back
@@ -1984,6 +1984,182 @@ extern "C" int bfmmm_chain_loo_pointwise(bfmmm_handle* h, const int32_t* curves,
       if (err.empty()) err = Back{h, base, rows}(var_trace, (const double*)(d_x + 3 * stride), N).done();
       if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
       if (err.empty()) collect(h, vark, PT_LOO_POINTWISE);
+    }
+    return err;
+  });
+}
+
+// ---- leave-block-out PSIS cross-validation within curves (kernels_loo_blocks.hip) ------------------------------------
+// The unit of a chunk is a row tile of gathered rows: consecutive blocks of the list that belong to the same curve share a tile while
+// they fit LP_ROWS rows, one row per listed observation, in the order of the lists.  Per chunk the tile and row tables go up,
+// k_loo_blocks fills the four matrices of the chunk's rows (every row of a block with the block's log-density), the traces go to the
+// host where asked for (loglik_trace from each block's first row), post_psis_expect_device takes PSIS on the first matrix with the
+// other three as auxiliaries, and the host keeps the six PSIS results of each block's first row and finishes pit, mean and sd of
+// every row.  The dense basis rows as in bfmmm_chain_loo_pointwise.
+extern "C" int bfmmm_chain_loo_blocks(bfmmm_handle* h, const int32_t* block_curve, const int64_t* block_offsets, const int32_t* block_obs,
+                                      int64_t n_blocks, int first_slot, int n_slots, int64_t max_workspace_bytes, double* lppd,
+                                      double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, double* pit,
+                                      double* mean, double* sd, double* loglik_trace, double* pit_trace, double* mean_trace,
+                                      double* var_trace, int64_t block_capacity, int64_t row_capacity) {
+  const SlotCheck ck{"bfmmm_chain_loo_blocks", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"h", h}, {"block_curve", block_curve}, {"block_offsets", block_offsets}, {"block_obs", block_obs}, {"lppd", lppd},
+               {"elpd_loo", elpd_loo}, {"p_loo", p_loo}, {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic}, {"p_waic", p_waic}, {"pit", pit},
+               {"mean", mean}, {"sd", sd}}))
+    return 1;
+  if (n_blocks < 1) return fail(fn + ": 'n_blocks' must be at least 1");
+  if (block_offsets[0] != 0) return fail(fn + ": 'block_offsets'[0] must be 0");
+  const Ctx& c = h->c;
+  const Dims& d = c.d;
+  const int n = d.n, P = d.P;
+  for (int64_t k = 0; k < n_blocks; ++k) {
+    const int64_t len = block_offsets[k + 1] - block_offsets[k];
+    if (len < 1) return fail(fn + ": 'block_offsets' must increase: block " + std::to_string(k) + " is empty");
+    if (len > LP_ROWS) return fail(fn + ": block " + std::to_string(k) + " has " + std::to_string(len) + " observations, above 64");
+    if (block_curve[k] < 0 || block_curve[k] >= n)
+      return fail(fn + ": 'block_curve'[" + std::to_string(k) + "] = " + std::to_string(block_curve[k]) + " outside 0 .. " + std::to_string(n - 1));
+  }
+  const int64_t total = block_offsets[n_blocks];
+  if (block_capacity < n_blocks) return fail(fn + ": 'block_capacity' below " + std::to_string(n_blocks) + " blocks");
+  if (row_capacity < total) return fail(fn + ": 'row_capacity' below " + std::to_string(total) + " rows");
+  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.row_limit()) return 1;
+  const std::string bad = loo_blocks_check(c);
+  if (!bad.empty()) return fail(fn + ": " + bad);
+  HIPCHK(hipSetDevice(h->device));
+  std::vector<int> hni((size_t)n);
+  HIPCHK(hipStreamSynchronize(h->st));
+  HIPCHK(copy_sync(h, hni.data(), c.ni, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+  std::vector<int64_t> off((size_t)n + 1, 0);
+  for (int i = 0; i < n; ++i) off[i + 1] = off[i] + hni[i];
+  // the indices of every block, then the tiles and the rows of the whole list
+  struct Tile { LbTile t; int64_t blk0, blk1; };
+  std::vector<Tile> tiles;
+  std::vector<LbRow> rows_all((size_t)total);
+  {
+    std::vector<int64_t> seen;                      // per observation of the block's curve: the last block that listed it, plus one
+    int seen_curve = -1;
+    for (int64_t k = 0; k < n_blocks; ++k) {
+      const int i = block_curve[k], ni = hni[i];
+      const int64_t j0 = block_offsets[k], len = block_offsets[k + 1] - j0;
+      if (seen_curve != i) { seen.assign((size_t)ni, 0); seen_curve = i; }
+      for (int64_t j = j0; j < j0 + len; ++j) {
+        const int o = block_obs[j];
+        if (o < 0 || o >= ni)
+          return fail(fn + ": 'block_obs'[" + std::to_string(j) + "] = " + std::to_string(o) + " outside 0 .. " + std::to_string(ni - 1) +
+                      " (block " + std::to_string(k) + " of curve " + std::to_string(i) + ")");
+        if (seen[(size_t)o] == k + 1) return fail(fn + ": 'block_obs'[" + std::to_string(j) + "] = " + std::to_string(o) + " is repeated in block " + std::to_string(k));
+        seen[(size_t)o] = k + 1;
+      }
+      if (tiles.empty() || tiles.back().t.curve != i || tiles.back().t.rows + len > LP_ROWS) tiles.push_back({{i, 0, off[i], j0}, k, k});
+      Tile& tl = tiles.back();
+      for (int64_t j = j0; j < j0 + len; ++j)
+        rows_all[(size_t)j] = {off[i] + block_obs[j], block_obs[j], (int16_t)tl.t.rows, (int16_t)len};
+      tl.t.rows += (int32_t)len;
+      tl.blk1 = k + 1;
+    }
+  }
+  const bool from_basis = !h->B_host.empty(), spline = !d.mv && !from_basis;
+  const size_t N = (size_t)ck.CS();
+  // shared: the dense basis rows of every observation with the scratch record of their launch; a tile: its rows of the four matrices,
+  // the nine results a row, its entry of the list, its rows of the table and, from a host basis, its basis rows
+  const size_t shared = spline ? sizeof(double) * ((size_t)h->n_obs * P + (size_t)n * d.LREC) + sizeof(int) * ((size_t)n + 1) : 0;
+  const size_t per_tile = sizeof(double) * (size_t)LP_ROWS * (4 * N + 9 + (from_basis ? (size_t)P : 0)) + sizeof(LbTile) + sizeof(LbRow) * (size_t)LP_ROWS;
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), shared, per_tile, (int64_t)tiles.size(), (int64_t)1 << 24, "tile", &chunk)) return 1;
+  reset_timers(h, PT_LOO_BLOCKS, PT_LOO_BLOCKS_PSIS);
+  CallBufs b;
+  double *d_x = nullptr, *d_B = nullptr;
+  LbTile* d_tiles = nullptr;
+  LbRow* d_rows = nullptr;
+  Timer kern, vark, psis;
+  HIPCHK(b.timers({&kern, &vark, &psis}));
+  const size_t stride = (size_t)chunk * LP_ROWS * N;
+  HIPCHK(b.get(&d_x, 4 * stride));
+  HIPCHK(b.get(&d_tiles, (size_t)chunk));
+  HIPCHK(b.get(&d_rows, (size_t)chunk * LP_ROWS));
+  if (spline) {
+    double* rec_tmp = nullptr;
+    int *ni_tmp = nullptr, *d_err = nullptr;
+    HIPCHK(b.get(&d_B, (size_t)h->n_obs * P));
+    HIPCHK(b.get(&rec_tmp, (size_t)n * d.LREC));
+    HIPCHK(b.get(&ni_tmp, (size_t)n));
+    HIPCHK(b.get(&d_err, 1));
+    HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int), h->st));
+    if (once(ck, b, PT_LOO_BLOCKS, 0, [&] {
+          return launch_stats_functional(h->cfg.basis_degree, n, P, d.LREC, h->d_off, h->d_t, h->d_y, h->d_knots, h->n_knots, rec_tmp, ni_tmp,
+                                         d_B, d_err, h->st)
+                     ? std::string("unsupported basis_degree")
+                     : std::string();
+        }))
+      return 1;
+  } else if (from_basis) {
+    HIPCHK(b.get(&d_B, (size_t)chunk * LP_ROWS * P));
+  }
+  std::vector<LbTile> ht((size_t)chunk);
+  std::vector<double> hB(from_basis ? (size_t)chunk * LP_ROWS * P : 0), hexp, hpw, hll;
+  return for_chunks(ck, (int64_t)tiles.size(), chunk, [&](int64_t p0, int cnt) {
+    const int64_t base = tiles[(size_t)p0].t.row0;
+    const int64_t blk0 = tiles[(size_t)p0].blk0, blk1 = tiles[(size_t)p0 + cnt - 1].blk1;
+    int64_t rows64 = 0;
+    for (int q = 0; q < cnt; ++q) {
+      LbTile t = tiles[(size_t)p0 + q].t;
+      t.row0 -= base;
+      ht[(size_t)q] = t;
+      rows64 = t.row0 + t.rows;
+    }
+    const int rows = (int)rows64;
+    if (from_basis)
+      for (int r = 0; r < rows; ++r) {
+        const int64_t src = rows_all[(size_t)(base + r)].b;      // the observation's row of the handle's host basis
+        std::copy(h->B_host.begin() + (size_t)src * P, h->B_host.begin() + (size_t)(src + 1) * P, hB.begin() + (size_t)r * P);
+      }
+    std::vector<LbRow> hr(rows_all.begin() + (size_t)base, rows_all.begin() + (size_t)(base + rows));
+    if (from_basis)
+      for (int r = 0; r < rows; ++r) hr[(size_t)r].b = r;
+    if (copy_sync(h, d_tiles, ht.data(), sizeof(LbTile) * (size_t)cnt, hipMemcpyHostToDevice) != hipSuccess ||
+        copy_sync(h, d_rows, hr.data(), sizeof(LbRow) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess ||
+        (from_basis && copy_sync(h, d_B, hB.data(), sizeof(double) * (size_t)rows * P, hipMemcpyHostToDevice) != hipSuccess))
+      return std::string(kBackFailed);
+    std::string err = timed(kern, h->st, [&] {
+      return launch_loo_blocks(c, d_tiles, cnt, d_rows, d_B, h->d_y, first_slot, n_slots, d_x, stride, h->st);
+    });
+    if (err.empty() && loglik_trace) {
+      hll.resize((size_t)rows * N);
+      err = Back{h, 0, rows}(hll.data(), (const double*)d_x, N).queued();
+    }
+    if (err.empty())
+      err = Back{h, base, rows}(pit_trace, (const double*)(d_x + stride), N)(mean_trace, (const double*)(d_x + 2 * stride), N).done();
+    if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
+    if (!err.empty()) return err;
+    collect(h, kern, PT_LOO_BLOCKS);
+    if (loglik_trace)
+      for (int64_t k = blk0; k < blk1; ++k)
+        std::copy(hll.begin() + (size_t)(block_offsets[k] - base) * N, hll.begin() + (size_t)(block_offsets[k] - base + 1) * N, loglik_trace + (size_t)k * N);
+    // post_psis_expect_device runs on the device's default stream: done() has drained the sampler's
+    hpw.resize(6 * (size_t)rows);
+    double* const outs[6] = {hpw.data(), hpw.data() + rows, hpw.data() + 2 * (size_t)rows, hpw.data() + 3 * (size_t)rows,
+                             hpw.data() + 4 * (size_t)rows, hpw.data() + 5 * (size_t)rows};
+    hexp.resize(3 * (size_t)rows);
+    (void)hipEventRecord(psis.from, nullptr);
+    const int prc = post_psis_expect_device(d_x, (long long)N, rows, (int)N, d_x + stride, 3, (long long)stride, outs, hexp.data());
+    (void)hipEventRecord(psis.to, nullptr);
+    if (prc) return std::string(bfmmm_entry_last_error());
+    if (hipEventSynchronize(psis.to) != hipSuccess) return std::string(kBackFailed);
+    collect(h, psis, PT_LOO_BLOCKS_PSIS);
+    double* const res[6] = {lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic};
+    for (int64_t k = blk0; k < blk1; ++k)
+      for (int v = 0; v < 6; ++v) res[v][k] = outs[v][block_offsets[k] - base];
+    for (int r = 0; r < rows; ++r) {
+      const double e1 = hexp[(size_t)rows + r];
+      pit[base + r] = hexp[(size_t)r];
+      mean[base + r] = e1;
+      sd[base + r] = std::sqrt(std::max(0.0, hexp[2 * (size_t)rows + r] - e1 * e1));
+    }
+    if (var_trace) {
+      err = timed(vark, h->st, [&] { return launch_loo_pointwise_var(d_x + 2 * stride, d_x + 3 * stride, (size_t)rows * N, h->st); });
+      if (err.empty()) err = Back{h, base, rows}(var_trace, (const double*)(d_x + 3 * stride), N).done();
+      if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
+      if (err.empty()) collect(h, vark, PT_LOO_BLOCKS);
     }
     return err;
   });

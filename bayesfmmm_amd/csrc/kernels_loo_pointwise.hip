@@ -22,11 +22,13 @@
 //       lane j owns observation j: w_j'beta, the forward solve L^-1 w_j in place in its row (L broadcast from LDS), the four
 //       values -> the staging table
 //   (6) the table -> the four matrices, one draw-contiguous segment per (matrix, observation)
+// Steps (1) to (4) and the MFMA loop of (5) are loo_core.hpp's, shared with k_loo_blocks (kernels_loo_blocks.hip).
 // L and beta of a (curve, draw) are recomputed by every tile of the curve, from the same record in the same order, so the tiles of
 // a curve agree bit for bit and there is neither a pre-pass nor a workspace.  fp64, vector stores only, no atomics; every sum has
 // a fixed order that depends on (observation, chain, slot) alone: the bits do not depend on the chunk, the grid or TB.
 #include "model.hpp"
 #include "launchers.hpp"
+#include "loo_core.hpp"
 
 #include <algorithm>
 #include <string>
@@ -35,12 +37,10 @@ namespace bfmmm {
 
 namespace {
 
-constexpr int LP_NT = 256;
+constexpr int LP_NT = LC_NT;
 constexpr int LP_TB_MAX = 8;
 constexpr size_t LP_LDS_SOFT = 64 * 1024;      // two workgroups per CU where the shape allows
 constexpr size_t LP_LDS_HARD = 160 * 1024;
-
-typedef double lp_v4 __attribute__((ext_vector_type(4)));
 
 struct LpArgs {
   // chain 0's slot storage; chain q's is q * chain_bytes (covariate blocks: chain_bytes_cov) further
@@ -86,7 +86,7 @@ __host__ __device__ inline LpLds lp_lds(int K, int P, int M, int LG, int TB) {
 __global__ __launch_bounds__(LP_NT) void k_loo_pointwise(LpArgs a) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = a.K, P = a.P, M = a.M, D = a.D, M1 = M + 1, BW = a.BW, TB = a.TB, n = a.n;
+  const int K = a.K, P = a.P, M = a.M, D = a.D, M1 = M + 1, TB = a.TB, n = a.n;
   const LpLds L = lp_lds(K, P, M, a.LG, TB);
   const int BS = L.BS, CVS = L.CVS, CVN = L.CVN, GVN = L.GVN, AS = L.AS, MWS = L.MWS, TBS = L.TBS;
   double* sB = sm + L.b;
@@ -134,100 +134,17 @@ __global__ __launch_bounds__(LP_NT) void k_loo_pointwise(LpArgs a) {
     }
     if (tid < gn) sSig[tid] = c_sigma[a.first_slot + sb + tid];
     __syncthreads();
-    // (1) c and V_m at p
-    for (int e = tid; e < gn * GVN; e += LP_NT) {
-      const int g = e / GVN, r = e - g * GVN, mt = r / P, p = r - mt * P;
-      const size_t t = (size_t)(a.first_slot + sb + g);
-      const bool cov = D > 0 && (mt == 0 || a.cadj);
-      const double* z = sZ + g * K;
-      double v = 0.0;
-      for (int k = 0; k < K; ++k) {
-        double x = mt == 0 ? c_nu[t * K * P + (size_t)p * K + k] : c_Phi[t * K * P * M + k + (size_t)K * (p + P * (mt - 1))];
-        if (cov) {
-          const double* tx = mt == 0 ? c_eta + t * P * D * K + p + (size_t)P * D * k
-                                     : c_xi + t * K * P * D * M + p + (size_t)P * D * ((mt - 1) + M * k);
-          for (int d = 0; d < D; ++d) x += sX[d] * tx[(size_t)P * d];
-        }
-        v += z[k] * x;
-      }
-      sCV[g * CVN + p * CVS + mt] = v;
-    }
+    lc_coefficients(a, c_nu, c_Phi, c_eta, c_xi, sZ, sX, sCV, sb, gn, CVS, CVN, GVN, tid);      // (1) c and V_m at p
     __syncthreads();
-    // (2) G times each of them at p, over the band window
-    for (int e = tid; e < gn * GVN; e += LP_NT) {
-      const int g = e / GVN, r = e - g * GVN, mt = r / P, p = r - mt * P;
-      const double* cv = sCV + g * CVN + mt;
-      double hv = 0.0;
-      for (int d = -BW; d <= BW; ++d) {
-        const int p2 = p + d;
-        if (p2 >= 0 && p2 < P) hv += sRec[(d < 0 ? -d : d) * P + min(p, p2)] * cv[p2 * CVS];
-      }
-      sGV[g * GVN + r] = mt == 0 ? sS[p] - hv : hv;
-    }
+    lc_gram_times(a, sRec, sS, sCV, sGV, gn, CVS, CVN, GVN, tid);      // (2) G times each of them at p, over the band window
     __syncthreads();
-    // (3) u_m = V_m'e, A_lm = V_m'(G V_l) for l >= m, sigma^2 on the diagonal
-    for (int e = tid; e < gn * M * M1; e += LP_NT) {
-      const int g = e / (M * M1), r = e - g * M * M1, m = r / M1, j = r - m * M1;      // j = 0: u_m, else l = j - 1
-      if (j > 0 && j - 1 < m) continue;
-      const double* vm = sCV + g * CVN + 1 + m;
-      const double* gv = sGV + g * GVN + j * P;
-      double s_ = 0.0;
-      for (int p = 0; p < P; ++p) s_ += vm[p * CVS] * gv[p];
-      double* A = sA + g * AS;
-      if (j == 0) A[M * M + m] = s_;
-      else A[(j - 1) * M + m] = (j - 1 == m) ? s_ + sSig[g] : s_;
-    }
+    lc_u_and_a(a, sCV, sGV, sSig, sA, gn, CVS, CVN, GVN, AS, tid);      // (3) u_m = V_m'e, A_lm = V_m'(G V_l) for l >= m, sigma^2 on the diagonal
     __syncthreads();
-    // (4) lane g: A = L L' in place, beta = A^-1 u
-    if (tid < gn) {
-      double* A = sA + tid * AS;
-      const double* u = A + M * M;
-      double* beta = A + M * M + M;
-      for (int c = 0; c < M; ++c) {
-        double dg = A[c * M + c];
-        for (int k2 = 0; k2 < c; ++k2) { const double l2 = A[c * M + k2]; dg -= l2 * l2; }
-        const double l = sqrt(dg);
-        A[c * M + c] = l;
-        for (int r3 = c + 1; r3 < M; ++r3) {
-          double v = A[r3 * M + c];
-          for (int k2 = 0; k2 < c; ++k2) v -= A[r3 * M + k2] * A[c * M + k2];
-          A[r3 * M + c] = v / l;
-        }
-      }
-      for (int c = 0; c < M; ++c) {
-        double x = u[c];
-        for (int k2 = 0; k2 < c; ++k2) x -= A[c * M + k2] * beta[k2];
-        beta[c] = x / A[c * M + c];
-      }
-      for (int c = M - 1; c >= 0; --c) {
-        double x = beta[c];
-        for (int r3 = c + 1; r3 < M; ++r3) x -= A[r3 * M + c] * beta[r3];
-        beta[c] = x / A[c * M + c];
-      }
-    }
+    if (tid < gn) lc_factor_beta(sA + tid * AS, M);      // (4) lane g: A = L L' in place, beta = A^-1 u
     __syncthreads();
     // (5) wave w: draws w, w + 4, ..
     for (int g = wave; g < gn; g += LP_NT / 64) {
-      const double* cv = sCV + g * CVN;
-      const int lr = lane & 15, lk = lane >> 4;
-      for (int ti = 0; 16 * ti < nr; ++ti) {
-        const double* pa = sB + (16 * ti + lr) * BS;
-        for (int tj = 0; 16 * tj < M1; ++tj) {
-          const int col = 16 * tj + lr;
-          lp_v4 acc = {0.0, 0.0, 0.0, 0.0};
-          for (int kb = 0; 4 * kb < P; ++kb) {
-            const int p = 4 * kb + lk;
-            const bool in = p < P;
-            const double av = in ? pa[p] : 0.0;
-            const double bv = in && col < M1 ? cv[p * CVS + col] : 0.0;
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-          }
-          if (col < M1) {
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) sMW[(16 * ti + lk + 4 * reg) * MWS + col] = acc[reg];
-          }
-        }
-      }
+      lc_mfma_rows(sB, sCV + g * CVN, sMW, nr, P, M1, BS, CVS, MWS, lane);
       __builtin_amdgcn_wave_barrier();
       if (lane < nr) {
         double* w = sMW + lane * MWS;

@@ -130,6 +130,17 @@ std::string launch_loo_pointwise(const Ctx& c, const LpTile* tiles, long long n_
                                  int n_slots, double* out, size_t out_stride, hipStream_t st);
 std::string launch_loo_pointwise_var(const double* mean, double* second, size_t count, hipStream_t st);
 
+// ---- kernels_loo_blocks.hip ----
+// bfmmm_chain_loo_blocks.  A row of a tile is one listed observation: `obs` its index within the curve, b its basis row
+// in the launch's B (the multivariate model reads none), bpos the tile row at which its block begins and blen the block's length.
+// A tile: `rows` <= LP_ROWS such rows of `curve`, whole blocks only, at rows row0 .. of the chunk's row table and of its matrices;
+// y0: the curve's first observation in y.  The host lists tiles and rows in the order of the result.
+struct LbRow { int64_t b; int32_t obs; int16_t bpos, blen; };
+struct LbTile { int32_t curve, rows; int64_t y0, row0; };
+std::string loo_blocks_check(const Ctx& c);
+std::string launch_loo_blocks(const Ctx& c, const LbTile* tiles, long long n_tiles, const LbRow* rows, const double* B, const double* y,
+                              int first_slot, int n_slots, double* out, size_t out_stride, hipStream_t st);
+
 // ---- kernels_curve_fit.hip ----
 // One call of bfmmm_chain_curve_fit / _bands: which (0 mean, 1 fit), the G x P evaluation basis E, the curve of every result
 // row (null: curve r), the slot range and the call's projection table of G fit_directions() C n_slots doubles (all device).

@@ -94,6 +94,76 @@ def _probs_arg(probs):
     return np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
 
 
+BLOCK_MAX = 64      # the most observations of a block of loo_blocks: a row tile of k_loo_blocks
+
+
+def block_plan(ni, blocks=None, block_size=None, horizon=None, curves=None):
+    """The flat block lists of Sampler.loo_blocks (bfmmm_chain_loo_blocks) from one of its three spellings, ni the observation
+    counts of the curves: blocks, a sequence of (curve, indices within the curve) pairs; block_size=s, every selected curve cut
+    into consecutive blocks of s observations (the last one shorter); horizon=h, one block a selected curve, its last h
+    observations, which needs n_i > h.  curves (None: all, in order; repeats allowed) selects for the latter two.  Returns
+    (block_curve int32 (n_blocks,), block_offsets int64 (n_blocks + 1,), block_obs int32 (N_rows,)) in the order of the result.
+    ValueError: not exactly one spelling, curves with blocks, a curve or an index out of range, an empty block or one above
+    BLOCK_MAX observations, an index repeated within a block, a curve too short for the horizon."""
+    ni = np.asarray(ni, dtype=np.int64)
+    n = len(ni)
+    if sum(v is not None for v in (blocks, block_size, horizon)) != 1:
+        raise ValueError("loo_blocks: exactly one of 'blocks', 'block_size' and 'horizon' must be given")
+    pairs = []
+    if blocks is not None:
+        if curves is not None:
+            raise ValueError("loo_blocks: 'curves' goes with 'block_size' or 'horizon', not with 'blocks'")
+        for k, (i, idx) in enumerate(blocks):
+            pairs.append((int(i), np.array(list(idx), dtype=np.int64).reshape(-1)))
+            if not 0 <= pairs[-1][0] < n:
+                raise ValueError(f"loo_blocks: block {k}: curve {pairs[-1][0]} outside 0 .. {n - 1}")
+    else:
+        sel = np.arange(n) if curves is None else np.asarray(curves, dtype=np.int64).reshape(-1)
+        if sel.size and (sel.min() < 0 or sel.max() >= n):
+            raise ValueError(f"loo_blocks: 'curves' must lie in 0 .. {n - 1}")
+        # generated blocks are valid by construction: the lists are built curve by curve, not block by block
+        cur, sizes, obs = [], [], []
+        if block_size is not None:
+            s = int(block_size)
+            if not 1 <= s <= BLOCK_MAX:
+                raise ValueError(f"loo_blocks: 'block_size' must lie in 1 .. {BLOCK_MAX}, got {s}")
+            for i in sel:
+                m = int(ni[i])
+                nb = -(-m // s)
+                if nb:
+                    sz = np.full(nb, s, dtype=np.int64)
+                    sz[-1] = m - s * (nb - 1)
+                    cur.append(np.full(nb, i, dtype=np.int32)); sizes.append(sz); obs.append(np.arange(m, dtype=np.int32))
+        else:
+            hz = int(horizon)
+            if not 1 <= hz <= BLOCK_MAX:
+                raise ValueError(f"loo_blocks: 'horizon' must lie in 1 .. {BLOCK_MAX}, got {hz}")
+            for i in sel:
+                m = int(ni[i])
+                if m <= hz:
+                    raise ValueError(f"loo_blocks: curve {int(i)} has {m} observations, not more than the horizon {hz}")
+                cur.append(np.full(1, i, dtype=np.int32)); sizes.append(np.full(1, hz, dtype=np.int64)); obs.append(np.arange(m - hz, m, dtype=np.int32))
+        if not cur:
+            raise ValueError("loo_blocks: no blocks")
+        block_offsets = np.zeros(sum(len(c) for c in cur) + 1, dtype=np.int64)
+        block_offsets[1:] = np.cumsum(np.concatenate(sizes))
+        return np.concatenate(cur), block_offsets, np.concatenate(obs)
+    if not pairs:
+        raise ValueError("loo_blocks: no blocks")
+    for k, (i, idx) in enumerate(pairs):
+        if idx.size < 1 or idx.size > BLOCK_MAX:
+            raise ValueError(f"loo_blocks: block {k} has {idx.size} observations, outside 1 .. {BLOCK_MAX}")
+        if idx.min() < 0 or idx.max() >= ni[i]:
+            raise ValueError(f"loo_blocks: block {k}: an index outside 0 .. {int(ni[i]) - 1} of curve {i}")
+        if len(np.unique(idx)) != idx.size:
+            raise ValueError(f"loo_blocks: block {k} repeats an index")
+    block_curve = np.array([i for i, _ in pairs], dtype=np.int32)
+    block_offsets = np.zeros(len(pairs) + 1, dtype=np.int64)
+    block_offsets[1:] = np.cumsum([idx.size for _, idx in pairs])
+    block_obs = np.concatenate([idx for _, idx in pairs]).astype(np.int32)
+    return block_curve, block_offsets, block_obs
+
+
 def default_config(**kw):
     cfg = _lib.BfmmmConfig()
     _lib.load().bfmmm_config_defaults(C.byref(cfg))
@@ -414,6 +484,53 @@ class Sampler:
         out = api.loo_totals(pw, Cn * S)
         out.update(pit=outs[6], mean=outs[7], sd=outs[8], offsets=offsets,
                    curve_elpd_loo=np.array([outs[1][offsets[j]:offsets[j + 1]].sum() for j in range(m)]))
+        out.update(tr)
+        return out
+
+    def loo_blocks(self, blocks=None, block_size=None, horizon=None, curves=None, first_slot=0, n_slots=None, trace=False,
+                   max_workspace_bytes=0):
+        """Leave-block-out PSIS cross-validation within curves from the chain slots of every chain, pooled (bfmmm_chain_loo_blocks;
+        DESIGN.md 7s): every listed block of observations of a training curve is left out in turn with the rest of its curve kept, Z_i at
+        the draw's value and the scores chi_i integrated out -- "given part of a curve, how well does the model predict a stretch of
+        it".  Exactly one of blocks (a sequence of (curve, indices) pairs, in the order of the result), block_size (every selected
+        curve cut into consecutive blocks, the last one shorter) and horizon (one block a curve, its last `horizon` observations:
+        leave-future-out) is given; `curves` goes with the latter two (see block_plan).  A block has 1 to 64 distinct observations;
+        blocks may overlap.  The multivariate model: the P coordinates of a row are its observations.
+        Returns the dict of `loo` over the BLOCKS (PSIS on the block's joint log-density; "pareto_k" says when a block is too large
+        for the correction) and, per listed observation, "pit": E[Phi(z_j)], "mean" and "sd": the marginals of the leave-block-out
+        predictive law, (N_rows,); "offsets": (n_blocks + 1,), block k owns rows offsets[k]:offsets[k + 1]; "block_curve",
+        "block_size": (n_blocks,); "obs": (N_rows,), the index of each listed observation within its curve; "curve_elpd_loo" and
+        "curve_index": the sums of the block elpds per distinct curve, in order of first appearance.  trace adds "loglik_trace":
+        (n_blocks, C, S) and "pit_trace", "mean_trace", "var_trace": (N_rows, C, S), refused above REFINE_TRACE_BYTES on the host."""
+        from . import api
+        S = self._slots(first_slot, n_slots)
+        ni = np.full(self.n, self.P, dtype=np.int64) if self.offsets is None else np.diff(self.offsets)
+        bc, bo, bx = block_plan(ni, blocks=blocks, block_size=block_size, horizon=horizon, curves=curves)
+        nb, N = len(bc), int(bo[-1])
+        Cn, Sn = self.n_chains, max(S, 0)
+        tr = {}
+        if trace:
+            need = 8 * (3 * N + nb) * Cn * Sn
+            if need > self.REFINE_TRACE_BYTES:
+                raise ValueError(f"loo_blocks: the four traces of {nb} blocks and {N} observations x {Cn} chains x {Sn} slots take "
+                                 f"{need} bytes on the host, above REFINE_TRACE_BYTES = {self.REFINE_TRACE_BYTES}: "
+                                 f"list fewer blocks or slots")
+            tr = {"loglik_trace": np.zeros((nb, Cn, Sn))}
+            tr.update({k: np.zeros((N, Cn, Sn)) for k in ("pit_trace", "mean_trace", "var_trace")})
+        outs = [np.zeros(nb) for _ in range(6)] + [np.zeros(N) for _ in range(3)]
+        opt = lambda k: _dp(tr[k]) if k in tr else None
+        _lib.check(self.lib.bfmmm_chain_loo_blocks(self.h, _ip(bc), bo.ctypes.data_as(_lib.c_int64_p), _ip(bx), nb, int(first_slot), S,
+                                                   int(max_workspace_bytes), *[_dp(o) for o in outs], opt("loglik_trace"),
+                                                   opt("pit_trace"), opt("mean_trace"), opt("var_trace"), nb, N))
+        pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs[:6]))
+        out = api.loo_totals(pw, Cn * S)
+        # per distinct curve, in order of first appearance: the curve's blocks in the order of the list, summed
+        uniq, first = np.unique(bc, return_index=True)
+        order = np.argsort(bc, kind="stable")
+        sums = np.array([seg.sum() for seg in np.split(outs[1][order], np.cumsum(np.bincount(bc)[uniq])[:-1])])
+        by_first = np.argsort(first, kind="stable")
+        out.update(pit=outs[6], mean=outs[7], sd=outs[8], offsets=bo, block_curve=bc, block_size=np.diff(bo), obs=bx,
+                   curve_index=uniq[by_first], curve_elpd_loo=sums[by_first])
         out.update(tr)
         return out
 

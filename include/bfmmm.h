@@ -613,6 +613,31 @@ int bfmmm_chain_loo_pointwise(bfmmm_handle* h, const int32_t* curves, int n_curv
                               double* elpd_waic, double* p_waic, double* pit, double* mean, double* sd, double* loglik_trace,
                               double* pit_trace, double* mean_trace, double* var_trace, int64_t capacity);
 
+/* Leave-block-out PSIS cross-validation within curves from the chain slots: every listed block of observations of a
+ * training curve is left out in turn, the rest of its curve kept, Z_i at the draw's value and the scores chi_i integrated out.  Block k
+ * is the observations block_obs[block_offsets[k] .. block_offsets[k + 1]) of curve block_curve[k], given as indices within the curve
+ * (the multivariate model: coordinates), 1 to 64 distinct ones in any order; blocks may overlap and a curve may appear at several
+ * places of the list.  Under draw t the joint law of y_b given the rest of the curve is Gaussian in closed form on the M x M system of
+ * bfmmm_chain_loo_pointwise, A_-b = A - W_b'W_b; PSIS (relative efficiency 1, the chains pooled) on l_b(t) = log p(y_b | y_i,-b, draw t)
+ * gives the six arrays of bfmmm_chain_loo per BLOCK (block_capacity entries each, at least n_blocks), and from the block's smoothed
+ * weights, per listed OBSERVATION in the order of block_obs (row_capacity entries each, at least block_offsets[n_blocks]):
+ * pit = E[Phi(z_j)], mean = E[m_j] and sd = sqrt(max(0, E[m_j^2 + v_j] - mean^2)), m_j, v_j, z_j the marginals of the joint law.
+ * The traces (null: not wanted) hold n_chains x n_slots values, draw fastest, then chain: loglik_trace l_b(t) per block; pit_trace
+ * Phi(z_j(t)), mean_trace m_j(t) and var_trace v_j(t) per listed observation.  With one observation a block this is
+ * bfmmm_chain_loo_pointwise's law; with the whole curve as the block l_b is bfmmm_chain_curve_loglik's value.
+ * The work is done in chunks of row tiles: consecutive blocks of the list that belong to the same curve share a tile while they fit 64
+ * rows, a block never straddles tiles; a chunk's four device matrices (one row per listed observation), tables and basis rows fit
+ * max_workspace_bytes (0: 256 MiB).  A block's results depend on (block, chain, slot) alone, bit for bit: not on the budget, the
+ * other blocks or its place in the list.  PSIS runs on every row of a block (with the same bits), which the block's first row reports.
+ * Refused by name before anything is allocated: a null required pointer, n_blocks < 1, offsets that do not start at 0 or do not
+ * increase (an empty block), a block above 64, a curve outside 0 .. n - 1, an index outside 0 .. n_i - 1, a repeated index within a
+ * block, the two capacities, and the slot range, budget sign and row limit as elsewhere.  One device; at most 2^22 draws a row. */
+int bfmmm_chain_loo_blocks(bfmmm_handle* h, const int32_t* block_curve, const int64_t* block_offsets, const int32_t* block_obs,
+                           int64_t n_blocks, int first_slot, int n_slots, int64_t max_workspace_bytes,
+                           double* lppd, double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic,
+                           double* pit, double* mean, double* sd, double* loglik_trace,
+                           double* pit_trace, double* mean_trace, double* var_trace, int64_t block_capacity, int64_t row_capacity);
+
 /* The fitted function of held-out, partly observed curves from the chain slots: bfmmm_chain_predict with the same
  * arguments -- the same samples, and lpd, z_mean, z_sd, ess_mean, ess_min and their traces bit for bit -- and, on the G rows of an
  * evaluation basis E (G x P row-major, rows in the sampler's basis as in bfmmm_chain_curve_bands; the identity for the
@@ -732,6 +757,9 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * Of the last bfmmm_chain_loo_pointwise (always measured): "loo_pointwise", the device time and launches of the dense basis rows (one
  * launch a call, spline handles only), k_loo_pointwise (one per chunk) and, where var_trace is asked for, the variance kernel (one per
  * chunk); "loo_pointwise_psis", those of the PSIS pass with its three expectations (one per chunk).
+ * Of the last bfmmm_chain_loo_blocks (always measured): "loo_blocks", the device time and launches of the dense basis rows (one launch
+ * a call, spline handles only), k_loo_blocks (one per chunk) and, where var_trace is asked for, the variance kernel (one per chunk);
+ * "loo_blocks_psis", those of the PSIS pass with its three expectations (one per chunk).
  * Of the last bfmmm_chain_rescale / bfmmm_chain_rescaled_summary / bfmmm_chain_cluster_mean_bands_rescaled (always measured):
  * "rescale_transform" (one launch), "rescale_gather" and "rescale_project" (one launch per chunk), the device time and launches of
  * their own kernels.  bfmmm_chain_cluster_cov_bands_rescaled: the timers of bfmmm_chain_cluster_cov_bands, "cluster_cov_project"
