@@ -1,27 +1,15 @@
 // C ABI of the sampler (include/bfmmm.h), what is read off the chain slots after a run: the chain arrays, their convergence
-// diagnostics, the per-curve log-density with its diagnostics and PSIS-LOO, the pooled per-curve fitted functions and bands,
+// diagnostics, the per-curve log-density with its diagnostics, the pooled per-curve fitted functions and bands,
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
 // per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it, the cluster
 // covariance surfaces with their bands and their eigenvalues and eigenfunctions, the reference's rescale step per draw with the
-// summaries, mean functions and covariance surfaces under it, the prediction of held-out curves with
-// their fitted functions, the marginal PSIS-LOO over the training curves with the memberships integrated out, the
-// observation-level PSIS-LOO with its LOO-PIT and the leave-block-out PSIS cross-validation within curves.
-// An entry point is its argument checks (SlotCheck: slots, curve selection, the grid pair, x, alpha, probs and `units`, the one
-// budget rule), its workspace and the event pairs that time its launches into the handle's PT_* timers (CallBufs owns both) and
-// one for_chunks.  What several of them do is written once: `once` for a launch that runs once per call (the projections), Back
-// for a chunk's copies to the host, SortWs for the rule that long rows sort in a workspace, and RowReducer for a chunk of rows of
-// C S pooled values: its layout in one allocation, its reduction (moments or the seven statistics, then the quantiles) and its
-// copies back.
-#include "handle.hpp"
-#include "launchers.hpp"
-#include "../../include/bfmmm_entry.h"
-
-#include <algorithm>
-#include <cmath>
-#include <initializer_list>
-#include <utility>
-
-using namespace bfmmm;
+// summaries, mean functions and covariance surfaces under it and the prediction of held-out curves with
+// their fitted functions.  The PSIS-LOO family over the chain slots is capi_loo.hip's.
+// What an entry point is made of is capi_chain.hpp's (SlotCheck, CallBufs, for_chunks, `once`, Back), shared with that file.  What
+// several of the entry points here do is written once as well: SortWs for the rule that long rows sort in a workspace, and
+// RowReducer for a chunk of rows of C S pooled values: its layout in one allocation, its reduction (moments or the seven
+// statistics, then the quantiles) and its copies back.
+#include "capi_chain.hpp"
 
 namespace {
 
@@ -47,192 +35,6 @@ ChainArr chain_array(const Ctx& c, int T, const std::string& name) {
     }
   return {};
 }
-
-// ---- argument checks ----------------------------------------------------------------------------------------------------
-// The checks of a call over slots [first_slot, first_slot + n_slots) of every chain, each answering 0 or fail() with the entry
-// point's name in front; an entry point chains them with || in the order of its messages.  ptrs() first: the others read h.
-struct SlotCheck {
-  std::string fn;
-  bfmmm_handle* h;
-  int first_slot, n_slots;
-  std::string tag = "";      // bfmmm_chain_diagnostics: "(name)", shown by capacity() and the chunk loop's failure
-
-  long long CS() const { return (long long)h->nch * n_slots; }      // draws per row
-  int ptrs(std::initializer_list<std::pair<const char*, const void*>> l) const {
-    for (const auto& e : l)
-      if (!e.second) return fail(fn + ": '" + e.first + "' is null");
-    return 0;
-  }
-  int range() const {
-    if (first_slot < 0 || first_slot >= h->T) return fail(fn + ": 'first_slot' out of range");
-    if (n_slots < 1 || n_slots > h->T - first_slot) return fail(fn + ": 'n_slots' out of range (first_slot + n_slots > T)");
-    return 0;
-  }
-  int row_limit() const {
-    if (CS() <= diag_row_max()) return 0;
-    return fail(fn + ": at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " + std::to_string(CS()));
-  }
-  int budget_sign(int64_t bytes) const { return bytes < 0 ? fail(fn + ": 'max_workspace_bytes' must not be negative") : 0; }
-  // The budget rule: a workspace of `shared` bytes for the whole call and `per_unit` for every unit (noun: "curve", "block", "row")
-  // of a chunk; *chunk units fit the budget, at most `count` and `cap`.  No noun: rows with nothing shared.  per_unit 0: nothing
-  // to chunk, the shared part alone has to fit.
-  int units(size_t budget, size_t shared, size_t per_unit, int64_t count, int64_t cap, const char* noun, int64_t* chunk) const {
-    if (budget < shared + per_unit) {
-      const std::string need = fn + ": 'max_workspace_bytes' below the " + std::to_string(shared + per_unit) + " bytes ";
-      return fail(noun ? need + "one " + noun + " needs " + plan_text(shared, per_unit, noun) : need + "of one row");
-    }
-    *chunk = per_unit ? std::min<int64_t>(std::min<int64_t>(count, (int64_t)((budget - shared) / per_unit)), cap) : 1;
-    return 0;
-  }
-  static std::string plan_text(size_t shared, size_t per_unit, const std::string& noun) {
-    return "(" + std::to_string(shared) + " shared by all " + noun + "s + " + std::to_string(per_unit) + " per " + noun + ")";
-  }
-  int capacity(int64_t have, int64_t want, const char* unit = "entries") const { return have < want ? fail(fn + tag + ": 'capacity' below " + std::to_string(want) + " " + unit) : 0; }
-  // a selection of curves (null: all n): every index is one; *m: the curves of the result.  The caller checks n_curves by its own rule.
-  int curve_list(const int32_t* curves, int n_curves, int64_t* m) const {
-    const int n = h->c.d.n;
-    for (int j = 0; curves && j < n_curves; ++j)
-      if (curves[j] < 0 || curves[j] >= n)
-        return fail(fn + ": 'curves'[" + std::to_string(j) + "] = " + std::to_string(curves[j]) + " outside 0 .. " + std::to_string(n - 1));
-    *m = curves ? n_curves : n;
-    return 0;
-  }
-  // the grid pair of a covariance surface: E1 of G1 rows, E2 of G2 rows where given, `diagonal` only without E2
-  int grid_pair(int G1, const double* E2, int G2, int diagonal) const {
-    if (G1 < 1) return fail(fn + ": 'G1' must be at least 1");
-    if (E2 && G2 < 1) return fail(fn + ": 'G2' must be at least 1 where 'E2' is given");
-    if (diagonal && E2) return fail(fn + ": 'diagonal' requires 'E2' to be null");
-    return 0;
-  }
-  // a covariate setting x (null: none) of D finite entries, for covariance-adjusted samplers only
-  int covariate_setting(const double* x) const {
-    const int D = h->c.d.D;
-    if (x && !(h->c.covariance_adj && D > 0)) return fail(fn + ": 'x' is given but the sampler is not covariance-adjusted");
-    for (int d = 0; x && d < D; ++d)
-      if (!std::isfinite(x[d])) return fail(fn + ": 'x'[" + std::to_string(d) + "] is not finite");
-    return 0;
-  }
-  int alpha_inside(double alpha) const { return alpha > 0.0 && alpha < 1.0 ? 0 : fail(fn + ": 'alpha' must be inside (0, 1)"); }
-  // nq in nq_min .. 16, with probs inside [0, 1] and somewhere to put the quantiles where nq > 0
-  int probs_list(const double* probs, int nq, int nq_min, const double* quant) const {
-    if (nq < nq_min || nq > 16) return fail(fn + ": 'nq' outside " + std::to_string(nq_min) + " .. 16");
-    if (nq > 0 && ptrs({{"probs", probs}, {"quant", quant}})) return 1;
-    for (int q = 0; q < nq; ++q)
-      if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return fail(fn + ": 'probs'[" + std::to_string(q) + "] outside [0, 1]");
-    return 0;
-  }
-};
-constexpr int64_t kNoCap = INT64_MAX;      // SlotCheck::units without a cap of the call's own
-// the cap of a call whose kernels index 2^30 result entries of `cells` a curve
-int64_t cells_cap(int64_t cells) { return std::max<int64_t>(1, (1LL << 30) / cells); }
-size_t budget_of(int64_t max_workspace_bytes) { return max_workspace_bytes ? (size_t)max_workspace_bytes : (size_t)256 << 20; }
-
-// ---- what a call owns, its chunk loop and its timing ----------------------------------------------------------------------
-// A pair of events around a launch, or a sequence of launches, of a call.
-struct Timer { hipEvent_t from = nullptr, to = nullptr; };
-
-// The device buffers and events of one call: released when the call returns, whichever way.
-struct CallBufs {
-  std::vector<void*> p;
-  std::vector<hipEvent_t> ev;
-  ~CallBufs() {
-    for (void* q : p) (void)hipFree(q);
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
-  template <typename T>
-  hipError_t get(T** out, size_t count) {
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
-    return e;
-  }
-  // a device copy of the `count` elements at src
-  template <typename T>
-  hipError_t put(bfmmm_handle* h, T** out, const T* src, size_t count) {
-    const hipError_t e = get(out, count);
-    return e != hipSuccess ? e : copy_sync(h, *out, src, sizeof(T) * count, hipMemcpyHostToDevice);
-  }
-  hipError_t timers(std::initializer_list<Timer*> l) {
-    for (Timer* t : l)
-      for (hipEvent_t* e : {&t->from, &t->to}) {
-        const hipError_t err = hipEventCreate(e);
-        if (err != hipSuccess) return err;
-        ev.push_back(*e);
-      }
-    return hipSuccess;
-  }
-};
-
-// Rows [0, len) in chunks of `chunk`: body(p0, rows) launches, copies back and collects the times of one chunk and answers
-// "" or what failed, which ends the loop.  Then the stream is drained and a failure reported under the call's name.
-template <typename Body>
-int for_chunks(const SlotCheck& ck, int64_t len, int64_t chunk, Body body) {
-  std::string err;
-  for (int64_t p0 = 0; p0 < len && err.empty(); p0 += chunk) err = body(p0, (int)std::min<int64_t>(chunk, len - p0));
-  (void)hipStreamSynchronize(ck.h->st);
-  if (!err.empty()) { (void)hipGetLastError(); return fail(ck.fn + ck.tag + ": " + err); }
-  return 0;
-}
-
-// launch(), which answers "" or what failed, between the events of t on the stream; once the stream has been synchronised,
-// collect adds the device time between them to timer pt of the handle (handle.hpp) and counts it
-template <typename Launch>
-std::string timed(const Timer& t, hipStream_t st, Launch launch) {
-  (void)hipEventRecord(t.from, st);
-  const std::string err = launch();
-  (void)hipEventRecord(t.to, st);
-  return err;
-}
-void collect(bfmmm_handle* h, const Timer& t, int pt) {
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, t.from, t.to) != hipSuccess) { (void)hipGetLastError(); return; }
-  h->post_ms[pt] += ms;
-  h->post_launches[pt] += 1;
-}
-void reset_timers(bfmmm_handle* h, int first, int last) {
-  for (int pt = first; pt <= last; ++pt) { h->post_ms[pt] = 0; h->post_launches[pt] = 0; }
-}
-
-// one launch of k_chain_curve_ll between the handle's two events; curve_ll_collect adds its device time after a synchronise
-std::string curve_ll_timed(const SlotCheck& ck, int i0, int rows, double* d_x) {
-  bfmmm_handle* h = ck.h;
-  return timed({h->ev0, h->ev1}, h->st, [&] { return launch_chain_curve_ll(h->c, ck.first_slot, ck.n_slots, i0, rows, d_x, h->st); });
-}
-void curve_ll_collect(bfmmm_handle* h) { collect(h, {h->ev0, h->ev1}, PT_CURVE_LL); }
-
-// A launch that runs once per call (the projection tables), between an event pair of its own: launch, synchronise, a failure
-// under the call's name, the device time into timer pt.  count > 0: the timer reports that (the tables filled), not the launch.
-template <typename Launch>
-int once(const SlotCheck& ck, CallBufs& b, int pt, int count, Launch launch) {
-  bfmmm_handle* h = ck.h;
-  Timer t;
-  HIPCHK(b.timers({&t}));
-  const std::string err = timed(t, h->st, launch);
-  if (!err.empty()) { (void)hipStreamSynchronize(h->st); return fail(ck.fn + ": " + err); }
-  HIPCHK(hipStreamSynchronize(h->st));
-  collect(h, t, pt);
-  if (count) h->post_launches[pt] = count;
-  return 0;
-}
-
-// The copies of a chunk to the host: back(dst, src, per_row) queues rows [r0, r0 + rows) of per_row entries each from the chunk's
-// device buffer src to dst + r0 per_row (dst null: not asked for, skipped); done() synchronises the stream and answers "" or what
-// a body of for_chunks reports.
-constexpr const char* kBackFailed = "kernel or copy back failed";
-struct Back {
-  bfmmm_handle* h;
-  int64_t r0;
-  int rows;
-  bool ok = true;
-  template <typename T>
-  Back& operator()(T* dst, const T* src, size_t per_row) {
-    if (ok && dst)
-      ok = hipMemcpyAsync(dst + (size_t)r0 * per_row, src, sizeof(T) * (size_t)rows * per_row, hipMemcpyDeviceToHost, h->st) == hipSuccess;
-    return *this;
-  }
-  std::string done() const { return ok && hipStreamSynchronize(h->st) == hipSuccess ? "" : kBackFailed; }
-  std::string queued() const { return ok ? "" : kBackFailed; }      // more copies of the chunk follow: their done() synchronises
-};
 
 // 16 doubles on the device (owned by b) with the call's nq probabilities in front, and `extra` more behind them
 hipError_t probs_put(CallBufs& b, bfmmm_handle* h, const double* probs, int nq, double** d_probs, int extra = 0) {
@@ -434,36 +236,6 @@ extern "C" int bfmmm_chain_curve_diagnostics(bfmmm_handle* h, int first_slot, in
     return 1;
   double* const outs[7] = {rhat, ess_bulk, ess_tail, ess_mean, mcse_mean, mean, sd};
   return seven_stats(ck, h->c.d.n, max_workspace_bytes, outs, true, [&](int p0, int rows, double* d_x) { return curve_ll_timed(ck, p0, rows, d_x); });
-}
-
-// PSIS-LOO and WAIC over curves with the chains pooled: a row is the C n_slots draws of a curve, chain-major, relative
-// efficiency 1.  Chunks of consecutive curves go through the same post_psis_device on the device.
-extern "C" int bfmmm_chain_loo(bfmmm_handle* h, int first_slot, int n_slots, int64_t max_workspace_bytes, double* lppd,
-                               double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, int64_t capacity) {
-  const SlotCheck ck{"bfmmm_chain_loo", h, first_slot, n_slots};
-  if (ck.ptrs({{"h", h}, {"lppd", lppd}, {"elpd_loo", elpd_loo}, {"p_loo", p_loo}, {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic},
-               {"p_waic", p_waic}}) ||
-      ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, h->c.d.n) || ck.row_limit())
-    return 1;
-  const int64_t len = h->c.d.n;
-  const long long CS = ck.CS();
-  int64_t chunk = 0;
-  if (ck.units(budget_of(max_workspace_bytes), 0, sizeof(double) * (size_t)CS, len, kNoCap, nullptr, &chunk)) return 1;
-  HIPCHK(hipSetDevice(h->device));
-  reset_timers(h, PT_CURVE_LL, PT_CURVE_LL);
-  CallBufs b;
-  double* d_x = nullptr;
-  HIPCHK(b.get(&d_x, (size_t)CS * (size_t)chunk));
-  return for_chunks(ck, len, chunk, [&](int64_t p0, int rows) {
-    std::string err = curve_ll_timed(ck, (int)p0, rows, d_x);
-    // post_psis_device runs on the device's default stream: the matrix must be complete before it starts
-    if (err.empty() && (hipStreamSynchronize(h->st) != hipSuccess || hipGetLastError() != hipSuccess)) err = "kernel failed";
-    if (!err.empty()) return err;
-    curve_ll_collect(h);
-    double* const outs[6] = {lppd + p0, elpd_loo + p0, p_loo + p0, pareto_k + p0, elpd_waic + p0, p_waic + p0};
-    if (post_psis_device(d_x, CS, rows, (int)CS, outs)) err = bfmmm_entry_last_error();
-    return err;
-  });
 }
 
 // ---- pooled per-curve fitted functions of the chain slots and their bands (kernels_curve_fit.hip) ----------
@@ -1629,538 +1401,3 @@ extern "C" int bfmmm_chain_predict_laplace(bfmmm_handle* h, const double* y, con
                       nullptr, max_workspace_bytes, lpd, z_mean, z_sd, ess_mean, ess_min, lpd_trace, z_trace, ess_trace, nullptr, nullptr, capacity);
 }
 
-// ---- marginal PSIS-LOO over curves, the memberships integrated out (kernels_loo_marginal.hip) ------------------------
-// Per chunk of consecutive curves: k_predict on the resident records (the call of 7m with f.rec = c.rec, r = the curve's index, no
-// stats launch and no copy) into lpd_t, ess_t and a_last; with `refine` the count of the selected pairs, their list at the
-// prefix of the counts formed here, and k_lz_refine over the list; then k_lz_count once more for what is reported and
-// post_psis_device on the chunk's lpd_t, as bfmmm_chain_loo calls it.
-extern "C" int bfmmm_chain_loo_marginal(bfmmm_handle* h, int first_slot, int n_slots, int n_samples, int n_stages, uint64_t seed, int refine,
-                                        double ess_floor, int refine_samples, int refine_stages, int64_t max_workspace_bytes,
-                                        double* lppd, double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic,
-                                        double* ess_mean, double* ess_min, int32_t* n_refined, int32_t* n_below,
-                                        double* lpd_trace, double* ess_trace, double* ess_trace_first,
-                                        int32_t* refined_index, double* refine_prop, double* refine_samples_out, int64_t* n_ref,
-                                        int64_t capacity, int64_t ref_capacity) {
-  const SlotCheck ck{"bfmmm_chain_loo_marginal", h, first_slot, n_slots};
-  const std::string& fn = ck.fn;
-  if (ck.ptrs({{"h", h}, {"lppd", lppd}, {"elpd_loo", elpd_loo}, {"p_loo", p_loo}, {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic},
-               {"p_waic", p_waic}, {"ess_mean", ess_mean}, {"ess_min", ess_min}, {"n_refined", n_refined}, {"n_below", n_below}}))
-    return 1;
-  const bool ref_out = refined_index || refine_prop || refine_samples_out;
-  if (ref_out && ck.ptrs({{"n_ref", n_ref}})) return 1;
-  const int J = n_samples, R = n_stages, J2 = refine_samples, R2 = refine_stages;
-  if (J < 1) return fail(fn + ": 'n_samples' must be at least 1, got " + std::to_string(J));
-  if (R < 1) return fail(fn + ": 'n_stages' must be at least 1, got " + std::to_string(R));
-  if (J2 < 1) return fail(fn + ": 'refine_samples' must be at least 1, got " + std::to_string(J2));
-  if (R2 < 1) return fail(fn + ": 'refine_stages' must be at least 1, got " + std::to_string(R2));
-  if (!(std::isfinite(ess_floor) && ess_floor >= 0.0)) return fail(fn + ": 'ess_floor' must be finite and not negative, got " + std::to_string(ess_floor));
-  const Ctx& c = h->c;
-  const Dims& d = c.d;
-  const int n = d.n, K = d.K;
-  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, n, "rows") || ck.row_limit()) return 1;
-  if (ref_out && ref_capacity < 0) return fail(fn + ": 'ref_capacity' must not be negative");
-  // the RNG indices ((i R + st) J + j) K + k and ((i R2 + st) J2 + j) K + k are 32-bit counter words
-  if ((long double)n * (long double)R * (long double)J * (long double)K > 4294967296.0L)
-    return fail(fn + ": n x n_stages x n_samples x K = " + std::to_string(n) + " x " + std::to_string(R) + " x " + std::to_string(J) + " x " +
-                std::to_string(K) + " exceeds the 4294967296 (2^32) indices of the random number counter");
-  if (refine && (long double)n * (long double)R2 * (long double)J2 * (long double)K > 4294967296.0L)
-    return fail(fn + ": n x refine_stages x refine_samples x K = " + std::to_string(n) + " x " + std::to_string(R2) + " x " + std::to_string(J2) +
-                " x " + std::to_string(K) + " exceeds the 4294967296 (2^32) indices of the random number counter");
-  PredictCall f;
-  f.n_new = n; f.J = J; f.R = R; f.first_slot = first_slot; f.n_slots = n_slots; f.seed = seed;
-  f.rec = c.rec; f.ni = c.ni; f.X = c.X;
-  PredictCall f2 = f;
-  f2.J = J2; f2.R = R2;
-  std::string bad = predict_check(c, f, nullptr);
-  if (bad.empty() && refine) bad = lz_check(c, J2, R2, nullptr);
-  if (!bad.empty()) return fail(fn + ": " + bad);
-  const size_t N = (size_t)ck.CS(), NK = N * (size_t)K;
-  double* const want_prop = refine ? refine_prop : nullptr;
-  double* const want_smp = refine ? refine_samples_out : nullptr;
-  // a curve: lpd_t, ess_t and a_last (N (2 + K)), ess_mean and ess_min, the two counts and the offset; with `refine` the list (three
-  // ints a pair) and, where asked for, the proposals and the samples of the refinement, as if every pair were refined
-  const size_t per_curve = sizeof(double) * (N * (2 + (size_t)K) + 2 + (want_prop ? NK * R2 : 0) + (want_smp ? NK * R2 * (size_t)J2 : 0)) +
-                           sizeof(int32_t) * (2 + (refine ? 3 * N + 1 : 0)) + sizeof(int64_t);
-  const size_t budget = budget_of(max_workspace_bytes);
-  if (want_smp && budget < per_curve)
-    return fail(fn + ": 'refine_samples_out' of one curve (n_chains x n_slots x refine_stages x refine_samples x K doubles) with the rest need " +
-                std::to_string(per_curve) + " bytes, above 'max_workspace_bytes' = " + std::to_string(budget) + " " +
-                SlotCheck::plan_text(0, per_curve, "curve"));
-  int64_t chunk = 0;
-  const int64_t cells = (int64_t)std::max<size_t>(1, per_curve / sizeof(double) / std::max<size_t>(N, 1));
-  if (ck.units(budget, 0, per_curve, n, cells_cap(cells), "curve", &chunk)) return 1;
-  HIPCHK(hipSetDevice(h->device));
-  reset_timers(h, PT_LOO_MARGINAL, PT_LOO_MARGINAL_PSIS);
-  CallBufs b;
-  double *d_tr = nullptr, *d_out = nullptr, *d_prop = nullptr, *d_smp = nullptr;
-  int32_t *d_cnt = nullptr, *d_list = nullptr;
-  int64_t* d_off = nullptr;
-  Timer first, count, list, refk, pool, psis;
-  HIPCHK(b.timers({&first, &count, &list, &refk, &pool, &psis}));
-  HIPCHK(b.get(&d_tr, (size_t)chunk * (2 * N + NK)));
-  HIPCHK(b.get(&d_out, 2 * (size_t)chunk));
-  HIPCHK(b.get(&d_cnt, 2 * (size_t)chunk));
-  if (refine) {
-    HIPCHK(b.get(&d_off, (size_t)chunk));
-    HIPCHK(b.get(&d_list, 3 * (size_t)chunk * N));
-  }
-  if (want_prop) HIPCHK(b.get(&d_prop, (size_t)chunk * NK * R2));
-  if (want_smp) HIPCHK(b.get(&d_smp, (size_t)chunk * NK * R2 * J2));
-  double* d_lpd_t = d_tr;
-  double* d_ess_t = d_lpd_t + (size_t)chunk * N;
-  double* d_alast = d_ess_t + (size_t)chunk * N;
-  double* d_emean = d_out;
-  double* d_emin = d_emean + chunk;
-  int32_t* d_below = d_cnt + chunk;
-  std::vector<int32_t> hcnt((size_t)chunk);
-  std::vector<int64_t> hoff((size_t)chunk);
-  int64_t total_ref = 0;
-  const int rc = for_chunks(ck, n, chunk, [&](int64_t r0, int rows) {
-    std::string err = timed(first, h->st, [&] {
-      return launch_predict(c, f, (int)r0, rows, d_lpd_t, d_ess_t, nullptr, nullptr, nullptr, nullptr, h->st, refine ? d_alast : nullptr);
-    });
-    if (err.empty()) err = Back{h, r0, rows}(ess_trace_first, d_ess_t, N).queued();
-    int64_t n_list = 0;
-    std::fill(n_refined + r0, n_refined + r0 + rows, 0);
-    if (err.empty() && refine) {
-      err = timed(count, h->st, [&] { return launch_lz_count((long long)N, rows, d_lpd_t, d_ess_t, ess_floor, d_cnt, nullptr, nullptr, h->st); });
-      if (err.empty() && copy_sync(h, hcnt.data(), d_cnt, sizeof(int32_t) * (size_t)rows, hipMemcpyDeviceToHost) != hipSuccess) err = kBackFailed;
-      if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
-      if (!err.empty()) return err;
-      for (int r = 0; r < rows; ++r) {
-        if (hcnt[r] < 0 || (size_t)hcnt[r] > N) return std::string("k_lz_count: a count outside 0 .. n_chains x n_slots");
-        hoff[r] = n_list;
-        n_list += hcnt[r];
-        n_refined[r0 + r] = hcnt[r];
-      }
-      if (n_list > 0) {
-        if (ref_out && total_ref + n_list > ref_capacity)
-          return "'ref_capacity' below the " + std::to_string(total_ref + n_list) + " pairs refined up to curve " + std::to_string(r0 + rows - 1);
-        if (copy_sync(h, d_off, hoff.data(), sizeof(int64_t) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess) return std::string(kBackFailed);
-        err = timed(list, h->st, [&] {
-          return launch_lz_list((long long)N, n_slots, (int)r0, rows, d_lpd_t, d_ess_t, ess_floor, d_off, (long long)n_list, d_list, h->st);
-        });
-        if (err.empty())
-          err = timed(refk, h->st, [&] {
-            return launch_lz_refine(c, f2, (int)r0, rows, d_list, (long long)n_list, d_lpd_t, d_ess_t, d_alast, d_prop, d_smp, h->st);
-          });
-        if (err.empty())
-          err = Back{h, total_ref, (int)n_list}(refined_index, d_list, 3)(want_prop, d_prop, (size_t)K * R2)(want_smp, d_smp, (size_t)K * R2 * J2).queued();
-      }
-    }
-    if (err.empty())
-      err = timed(pool, h->st, [&] { return launch_lz_count((long long)N, rows, d_lpd_t, d_ess_t, ess_floor, d_below, d_emean, d_emin, h->st); });
-    if (err.empty())
-      err = Back{h, r0, rows}(lpd_trace, d_lpd_t, N)(ess_trace, d_ess_t, N)(ess_mean, d_emean, 1)(ess_min, d_emin, 1)(n_below, d_below, 1).done();
-    if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
-    if (!err.empty()) return err;
-    collect(h, first, PT_LOO_MARGINAL);
-    if (refine) collect(h, count, PT_LOO_MARGINAL);
-    if (n_list > 0) { collect(h, list, PT_LOO_MARGINAL); collect(h, refk, PT_LOO_MARGINAL); }
-    collect(h, pool, PT_LOO_MARGINAL);
-    total_ref += n_list;
-    // post_psis_device runs on the device's default stream: done() has drained the sampler's
-    double* const outs[6] = {lppd + r0, elpd_loo + r0, p_loo + r0, pareto_k + r0, elpd_waic + r0, p_waic + r0};
-    (void)hipEventRecord(psis.from, nullptr);
-    const int prc = post_psis_device(d_lpd_t, (long long)N, rows, (int)N, outs);
-    (void)hipEventRecord(psis.to, nullptr);
-    if (prc) return std::string(bfmmm_entry_last_error());
-    if (hipEventSynchronize(psis.to) != hipSuccess) return std::string(kBackFailed);
-    collect(h, psis, PT_LOO_MARGINAL_PSIS);
-    return err;
-  });
-  if (n_ref) *n_ref = total_ref;
-  return rc;
-}
-
-// ---- the marginal PSIS-LOO under the Laplace mixture proposal (kernels_predict_laplace.hip) --------------------------
-// Per chunk of consecutive curves: k_predict_lap on the resident records as the first and only pass (as bfmmm_chain_loo_marginal
-// runs k_predict on them), k_lz_count for what is reported and post_psis_device on the chunk's lpd_t.  There is no refinement.
-extern "C" int bfmmm_chain_loo_marginal_laplace(bfmmm_handle* h, int first_slot, int n_slots, int n_samples, uint64_t seed, double ess_floor,
-                                                int64_t max_workspace_bytes,
-                                                double* lppd, double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic,
-                                                double* p_waic, double* ess_mean, double* ess_min, int32_t* n_below,
-                                                double* lpd_trace, double* ess_trace, int32_t* n_modes, double* components,
-                                                double* eta_samples, int64_t capacity) {
-  const SlotCheck ck{"bfmmm_chain_loo_marginal_laplace", h, first_slot, n_slots};
-  const std::string& fn = ck.fn;
-  if (ck.ptrs({{"h", h}, {"lppd", lppd}, {"elpd_loo", elpd_loo}, {"p_loo", p_loo}, {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic},
-               {"p_waic", p_waic}, {"ess_mean", ess_mean}, {"ess_min", ess_min}, {"n_below", n_below}}))
-    return 1;
-  const int J = n_samples;
-  if (J < 1) return fail(fn + ": 'n_samples' must be at least 1, got " + std::to_string(J));
-  if (!(std::isfinite(ess_floor) && ess_floor >= 0.0)) return fail(fn + ": 'ess_floor' must be finite and not negative, got " + std::to_string(ess_floor));
-  const Ctx& c = h->c;
-  const Dims& d = c.d;
-  const int n = d.n, K = d.K;
-  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.capacity(capacity, n, "rows") || ck.row_limit()) return 1;
-  // the RNG index (i J + j)(K + 1) + . is a 32-bit counter word
-  if ((long double)n * (long double)J * (long double)(K + 1) > 4294967296.0L)
-    return fail(fn + ": n x n_samples x (K + 1) = " + std::to_string(n) + " x " + std::to_string(J) + " x " + std::to_string(K + 1) +
-                " exceeds the 4294967296 (2^32) indices of the random number counter");
-  PredictCall f;
-  f.n_new = n; f.J = J; f.R = 1; f.first_slot = first_slot; f.n_slots = n_slots; f.seed = seed;
-  f.rec = c.rec; f.ni = c.ni; f.X = c.X;
-  const std::string bad = predict_lap_check(c, f, nullptr);
-  if (!bad.empty()) return fail(fn + ": " + bad);
-  const size_t N = (size_t)ck.CS(), CD = (size_t)predict_lap_comp_doubles(K);
-  // a curve: lpd_t and ess_t (2 N), n_modes (an int a draw, counted as a double), ess_mean and ess_min, the count; the components
-  // and the samples where asked for
-  const size_t per_curve = sizeof(double) * (N * (3 + (components ? (size_t)(K + 2) * CD : 0) + (eta_samples ? (size_t)J * (K - 1) : 0)) + 2) +
-                           sizeof(int32_t) * 2;
-  const size_t budget = budget_of(max_workspace_bytes);
-  int64_t chunk = 0;
-  const int64_t cells = (int64_t)std::max<size_t>(1, per_curve / sizeof(double) / std::max<size_t>(N, 1));
-  if (ck.units(budget, 0, per_curve, n, cells_cap(cells), "curve", &chunk)) return 1;
-  HIPCHK(hipSetDevice(h->device));
-  reset_timers(h, PT_LOO_MARGINAL_PSIS, PT_LOO_MARGINAL_PSIS);
-  reset_timers(h, PT_LOO_MARGINAL_LAPLACE, PT_LOO_MARGINAL_LAPLACE);
-  CallBufs b;
-  double *d_tr = nullptr, *d_out = nullptr, *d_comp = nullptr, *d_eta = nullptr;
-  int32_t *d_below = nullptr, *d_nm = nullptr;
-  Timer first, pool, psis;
-  HIPCHK(b.timers({&first, &pool, &psis}));
-  HIPCHK(b.get(&d_tr, (size_t)chunk * 2 * N));
-  HIPCHK(b.get(&d_out, 2 * (size_t)chunk));
-  HIPCHK(b.get(&d_below, (size_t)chunk));
-  HIPCHK(b.get(&d_nm, (size_t)chunk * N));
-  if (components) HIPCHK(b.get(&d_comp, (size_t)chunk * N * (K + 2) * CD));
-  if (eta_samples) HIPCHK(b.get(&d_eta, (size_t)chunk * N * J * (K - 1)));
-  double* d_lpd_t = d_tr;
-  double* d_ess_t = d_lpd_t + (size_t)chunk * N;
-  double* d_emean = d_out;
-  double* d_emin = d_emean + chunk;
-  return for_chunks(ck, n, chunk, [&](int64_t r0, int rows) {
-    std::string err = timed(first, h->st, [&] {
-      return launch_predict_lap(c, f, (int)r0, rows, d_lpd_t, d_ess_t, nullptr, nullptr, d_nm, d_comp, d_eta, h->st);
-    });
-    if (err.empty())
-      err = timed(pool, h->st, [&] { return launch_lz_count((long long)N, rows, d_lpd_t, d_ess_t, ess_floor, d_below, d_emean, d_emin, h->st); });
-    if (err.empty())
-      err = Back{h, r0, rows}(n_modes, (const int32_t*)d_nm, N)(components, (const double*)d_comp, N * (K + 2) * CD)(
-                eta_samples, (const double*)d_eta, N * (size_t)J * (K - 1)).queued();
-    if (err.empty())
-      err = Back{h, r0, rows}(lpd_trace, (const double*)d_lpd_t, N)(ess_trace, (const double*)d_ess_t, N)(ess_mean, (const double*)d_emean, 1)(
-                ess_min, (const double*)d_emin, 1)(n_below, (const int32_t*)d_below, 1).done();
-    if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
-    if (!err.empty()) return err;
-    collect(h, first, PT_LOO_MARGINAL_LAPLACE);
-    collect(h, pool, PT_LOO_MARGINAL_LAPLACE);
-    // post_psis_device runs on the device's default stream: done() has drained the sampler's
-    double* const outs[6] = {lppd + r0, elpd_loo + r0, p_loo + r0, pareto_k + r0, elpd_waic + r0, p_waic + r0};
-    (void)hipEventRecord(psis.from, nullptr);
-    const int prc = post_psis_device(d_lpd_t, (long long)N, rows, (int)N, outs);
-    (void)hipEventRecord(psis.to, nullptr);
-    if (prc) return std::string(bfmmm_entry_last_error());
-    if (hipEventSynchronize(psis.to) != hipSuccess) return std::string(kBackFailed);
-    collect(h, psis, PT_LOO_MARGINAL_PSIS);
-    return err;
-  });
-}
-
-// ---- observation-level PSIS-LOO and LOO-PIT of the chain slots (kernels_loo_pointwise.hip) ---------------------------
-// The unit of a chunk is a row tile: up to LP_ROWS consecutive observations of one curve, listed on the host in the order of the
-// result (the curves as selected, then the observations).  Per chunk k_loo_pointwise fills the four matrices of the chunk's rows
-// (log-likelihood, PIT, conditional mean, second moment; draw fastest, then chain), post_psis_expect_device takes PSIS on the first
-// with the other three as auxiliaries, and the traces go to the host where asked for.  The dense basis rows: one
-// launch_stats_functional for the whole call where the handle has the spline inputs, the chunk's rows from the handle's host copy
-// where it was created from a basis, none for the multivariate model.
-extern "C" int bfmmm_chain_loo_pointwise(bfmmm_handle* h, const int32_t* curves, int n_curves, int first_slot, int n_slots,
-                                         int64_t max_workspace_bytes, double* lppd, double* elpd_loo, double* p_loo, double* pareto_k,
-                                         double* elpd_waic, double* p_waic, double* pit, double* mean, double* sd, double* loglik_trace,
-                                         double* pit_trace, double* mean_trace, double* var_trace, int64_t capacity) {
-  const SlotCheck ck{"bfmmm_chain_loo_pointwise", h, first_slot, n_slots};
-  const std::string& fn = ck.fn;
-  if (ck.ptrs({{"h", h}, {"lppd", lppd}, {"elpd_loo", elpd_loo}, {"p_loo", p_loo}, {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic},
-               {"p_waic", p_waic}, {"pit", pit}, {"mean", mean}, {"sd", sd}}))
-    return 1;
-  if (curves && n_curves < 1) return fail(fn + ": 'n_curves' must be at least 1 where 'curves' is given");
-  int64_t m = 0;
-  if (ck.curve_list(curves, n_curves, &m) || ck.range() || ck.budget_sign(max_workspace_bytes) || ck.row_limit()) return 1;
-  const Ctx& c = h->c;
-  const Dims& d = c.d;
-  const int n = d.n, P = d.P;
-  const std::string bad = loo_pointwise_check(c);
-  if (!bad.empty()) return fail(fn + ": " + bad);
-  HIPCHK(hipSetDevice(h->device));
-  // the tile list, from the curves' observation counts
-  std::vector<int> hni((size_t)n);
-  HIPCHK(hipStreamSynchronize(h->st));
-  HIPCHK(copy_sync(h, hni.data(), c.ni, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-  std::vector<int64_t> off((size_t)n + 1, 0);
-  for (int i = 0; i < n; ++i) off[i + 1] = off[i] + hni[i];
-  std::vector<LpTile> tiles;
-  int64_t total = 0;
-  for (int64_t j = 0; j < m; ++j) {
-    const int i = curves ? curves[j] : (int)j;
-    for (int r0 = 0; r0 < hni[i]; r0 += LP_ROWS) {
-      const int rows = std::min(LP_ROWS, hni[i] - r0);
-      tiles.push_back({i, rows, off[i] + r0, off[i] + r0, total});
-      total += rows;
-    }
-  }
-  if (ck.capacity(capacity, total, "rows")) return 1;
-  if (tiles.empty()) return 0;
-  const bool from_basis = !h->B_host.empty(), spline = !d.mv && !from_basis;
-  const size_t N = (size_t)ck.CS();
-  // shared: the dense basis rows of every observation with the scratch record of their launch; a tile: its rows of the four matrices,
-  // the nine results a row, its entry of the list and, from a host basis, its basis rows
-  const size_t shared = spline ? sizeof(double) * ((size_t)h->n_obs * P + (size_t)n * d.LREC) + sizeof(int) * ((size_t)n + 1) : 0;
-  const size_t per_tile = sizeof(double) * (size_t)LP_ROWS * (4 * N + 9 + (from_basis ? (size_t)P : 0)) + sizeof(LpTile);
-  int64_t chunk = 0;
-  if (ck.units(budget_of(max_workspace_bytes), shared, per_tile, (int64_t)tiles.size(), (int64_t)1 << 24, "tile", &chunk)) return 1;
-  reset_timers(h, PT_LOO_POINTWISE, PT_LOO_POINTWISE_PSIS);
-  CallBufs b;
-  double *d_x = nullptr, *d_B = nullptr;
-  LpTile* d_tiles = nullptr;
-  Timer kern, vark, psis;
-  HIPCHK(b.timers({&kern, &vark, &psis}));
-  const size_t stride = (size_t)chunk * LP_ROWS * N;
-  HIPCHK(b.get(&d_x, 4 * stride));
-  HIPCHK(b.get(&d_tiles, (size_t)chunk));
-  if (spline) {
-    double* rec_tmp = nullptr;
-    int *ni_tmp = nullptr, *d_err = nullptr;
-    HIPCHK(b.get(&d_B, (size_t)h->n_obs * P));
-    HIPCHK(b.get(&rec_tmp, (size_t)n * d.LREC));
-    HIPCHK(b.get(&ni_tmp, (size_t)n));
-    HIPCHK(b.get(&d_err, 1));
-    HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int), h->st));
-    if (once(ck, b, PT_LOO_POINTWISE, 0, [&] {
-          return launch_stats_functional(h->cfg.basis_degree, n, P, d.LREC, h->d_off, h->d_t, h->d_y, h->d_knots, h->n_knots, rec_tmp, ni_tmp,
-                                         d_B, d_err, h->st)
-                     ? std::string("unsupported basis_degree")
-                     : std::string();
-        }))
-      return 1;
-  } else if (from_basis) {
-    HIPCHK(b.get(&d_B, (size_t)chunk * LP_ROWS * P));
-  }
-  std::vector<LpTile> ht((size_t)chunk);
-  std::vector<double> hB(from_basis ? (size_t)chunk * LP_ROWS * P : 0), hexp;
-  return for_chunks(ck, (int64_t)tiles.size(), chunk, [&](int64_t p0, int cnt) {
-    const int64_t base = tiles[(size_t)p0].out_row;
-    int64_t rows64 = 0;
-    for (int q = 0; q < cnt; ++q) {
-      LpTile t = tiles[(size_t)p0 + q];
-      t.out_row -= base;
-      if (from_basis) {
-        std::copy(h->B_host.begin() + (size_t)t.b0 * P, h->B_host.begin() + (size_t)(t.b0 + t.rows) * P, hB.begin() + (size_t)t.out_row * P);
-        t.b0 = t.out_row;
-      }
-      ht[(size_t)q] = t;
-      rows64 = t.out_row + t.rows;
-    }
-    const int rows = (int)rows64;
-    if (copy_sync(h, d_tiles, ht.data(), sizeof(LpTile) * (size_t)cnt, hipMemcpyHostToDevice) != hipSuccess ||
-        (from_basis && copy_sync(h, d_B, hB.data(), sizeof(double) * (size_t)rows * P, hipMemcpyHostToDevice) != hipSuccess))
-      return std::string(kBackFailed);
-    std::string err = timed(kern, h->st, [&] {
-      return launch_loo_pointwise(c, d_tiles, cnt, d_B, h->d_y, first_slot, n_slots, d_x, stride, h->st);
-    });
-    if (err.empty())
-      err = Back{h, base, rows}(loglik_trace, (const double*)d_x, N)(pit_trace, (const double*)(d_x + stride), N)(
-                mean_trace, (const double*)(d_x + 2 * stride), N).done();
-    if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
-    if (!err.empty()) return err;
-    collect(h, kern, PT_LOO_POINTWISE);
-    // post_psis_expect_device runs on the device's default stream: done() has drained the sampler's
-    double* const outs[6] = {lppd + base, elpd_loo + base, p_loo + base, pareto_k + base, elpd_waic + base, p_waic + base};
-    hexp.resize(3 * (size_t)rows);
-    (void)hipEventRecord(psis.from, nullptr);
-    const int prc = post_psis_expect_device(d_x, (long long)N, rows, (int)N, d_x + stride, 3, (long long)stride, outs, hexp.data());
-    (void)hipEventRecord(psis.to, nullptr);
-    if (prc) return std::string(bfmmm_entry_last_error());
-    if (hipEventSynchronize(psis.to) != hipSuccess) return std::string(kBackFailed);
-    collect(h, psis, PT_LOO_POINTWISE_PSIS);
-    for (int r = 0; r < rows; ++r) {
-      const double e1 = hexp[(size_t)rows + r];
-      pit[base + r] = hexp[(size_t)r];
-      mean[base + r] = e1;
-      sd[base + r] = std::sqrt(std::max(0.0, hexp[2 * (size_t)rows + r] - e1 * e1));
-    }
-    if (var_trace) {
-      err = timed(vark, h->st, [&] { return launch_loo_pointwise_var(d_x + 2 * stride, d_x + 3 * stride, (size_t)rows * N, h->st); });
-      if (err.empty()) err = Back{h, base, rows}(var_trace, (const double*)(d_x + 3 * stride), N).done();
-      if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
-      if (err.empty()) collect(h, vark, PT_LOO_POINTWISE);
-    }
-    return err;
-  });
-}
-
-// ---- leave-block-out PSIS cross-validation within curves (kernels_loo_blocks.hip) ------------------------------------
-// The unit of a chunk is a row tile of gathered rows: consecutive blocks of the list that belong to the same curve share a tile while
-// they fit LP_ROWS rows, one row per listed observation, in the order of the lists.  Per chunk the tile and row tables go up,
-// k_loo_blocks fills the four matrices of the chunk's rows (every row of a block with the block's log-density), the traces go to the
-// host where asked for (loglik_trace from each block's first row), post_psis_expect_device takes PSIS on the first matrix with the
-// other three as auxiliaries, and the host keeps the six PSIS results of each block's first row and finishes pit, mean and sd of
-// every row.  The dense basis rows as in bfmmm_chain_loo_pointwise.
-extern "C" int bfmmm_chain_loo_blocks(bfmmm_handle* h, const int32_t* block_curve, const int64_t* block_offsets, const int32_t* block_obs,
-                                      int64_t n_blocks, int first_slot, int n_slots, int64_t max_workspace_bytes, double* lppd,
-                                      double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, double* pit,
-                                      double* mean, double* sd, double* loglik_trace, double* pit_trace, double* mean_trace,
-                                      double* var_trace, int64_t block_capacity, int64_t row_capacity) {
-  const SlotCheck ck{"bfmmm_chain_loo_blocks", h, first_slot, n_slots};
-  const std::string& fn = ck.fn;
-  if (ck.ptrs({{"h", h}, {"block_curve", block_curve}, {"block_offsets", block_offsets}, {"block_obs", block_obs}, {"lppd", lppd},
-               {"elpd_loo", elpd_loo}, {"p_loo", p_loo}, {"pareto_k", pareto_k}, {"elpd_waic", elpd_waic}, {"p_waic", p_waic}, {"pit", pit},
-               {"mean", mean}, {"sd", sd}}))
-    return 1;
-  if (n_blocks < 1) return fail(fn + ": 'n_blocks' must be at least 1");
-  if (block_offsets[0] != 0) return fail(fn + ": 'block_offsets'[0] must be 0");
-  const Ctx& c = h->c;
-  const Dims& d = c.d;
-  const int n = d.n, P = d.P;
-  for (int64_t k = 0; k < n_blocks; ++k) {
-    const int64_t len = block_offsets[k + 1] - block_offsets[k];
-    if (len < 1) return fail(fn + ": 'block_offsets' must increase: block " + std::to_string(k) + " is empty");
-    if (len > LP_ROWS) return fail(fn + ": block " + std::to_string(k) + " has " + std::to_string(len) + " observations, above 64");
-    if (block_curve[k] < 0 || block_curve[k] >= n)
-      return fail(fn + ": 'block_curve'[" + std::to_string(k) + "] = " + std::to_string(block_curve[k]) + " outside 0 .. " + std::to_string(n - 1));
-  }
-  const int64_t total = block_offsets[n_blocks];
-  if (block_capacity < n_blocks) return fail(fn + ": 'block_capacity' below " + std::to_string(n_blocks) + " blocks");
-  if (row_capacity < total) return fail(fn + ": 'row_capacity' below " + std::to_string(total) + " rows");
-  if (ck.range() || ck.budget_sign(max_workspace_bytes) || ck.row_limit()) return 1;
-  const std::string bad = loo_blocks_check(c);
-  if (!bad.empty()) return fail(fn + ": " + bad);
-  HIPCHK(hipSetDevice(h->device));
-  std::vector<int> hni((size_t)n);
-  HIPCHK(hipStreamSynchronize(h->st));
-  HIPCHK(copy_sync(h, hni.data(), c.ni, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-  std::vector<int64_t> off((size_t)n + 1, 0);
-  for (int i = 0; i < n; ++i) off[i + 1] = off[i] + hni[i];
-  // the indices of every block, then the tiles and the rows of the whole list
-  struct Tile { LbTile t; int64_t blk0, blk1; };
-  std::vector<Tile> tiles;
-  std::vector<LbRow> rows_all((size_t)total);
-  {
-    std::vector<int64_t> seen;                      // per observation of the block's curve: the last block that listed it, plus one
-    int seen_curve = -1;
-    for (int64_t k = 0; k < n_blocks; ++k) {
-      const int i = block_curve[k], ni = hni[i];
-      const int64_t j0 = block_offsets[k], len = block_offsets[k + 1] - j0;
-      if (seen_curve != i) { seen.assign((size_t)ni, 0); seen_curve = i; }
-      for (int64_t j = j0; j < j0 + len; ++j) {
-        const int o = block_obs[j];
-        if (o < 0 || o >= ni)
-          return fail(fn + ": 'block_obs'[" + std::to_string(j) + "] = " + std::to_string(o) + " outside 0 .. " + std::to_string(ni - 1) +
-                      " (block " + std::to_string(k) + " of curve " + std::to_string(i) + ")");
-        if (seen[(size_t)o] == k + 1) return fail(fn + ": 'block_obs'[" + std::to_string(j) + "] = " + std::to_string(o) + " is repeated in block " + std::to_string(k));
-        seen[(size_t)o] = k + 1;
-      }
-      if (tiles.empty() || tiles.back().t.curve != i || tiles.back().t.rows + len > LP_ROWS) tiles.push_back({{i, 0, off[i], j0}, k, k});
-      Tile& tl = tiles.back();
-      for (int64_t j = j0; j < j0 + len; ++j)
-        rows_all[(size_t)j] = {off[i] + block_obs[j], block_obs[j], (int16_t)tl.t.rows, (int16_t)len};
-      tl.t.rows += (int32_t)len;
-      tl.blk1 = k + 1;
-    }
-  }
-  const bool from_basis = !h->B_host.empty(), spline = !d.mv && !from_basis;
-  const size_t N = (size_t)ck.CS();
-  // shared: the dense basis rows of every observation with the scratch record of their launch; a tile: its rows of the four matrices,
-  // the nine results a row, its entry of the list, its rows of the table and, from a host basis, its basis rows
-  const size_t shared = spline ? sizeof(double) * ((size_t)h->n_obs * P + (size_t)n * d.LREC) + sizeof(int) * ((size_t)n + 1) : 0;
-  const size_t per_tile = sizeof(double) * (size_t)LP_ROWS * (4 * N + 9 + (from_basis ? (size_t)P : 0)) + sizeof(LbTile) + sizeof(LbRow) * (size_t)LP_ROWS;
-  int64_t chunk = 0;
-  if (ck.units(budget_of(max_workspace_bytes), shared, per_tile, (int64_t)tiles.size(), (int64_t)1 << 24, "tile", &chunk)) return 1;
-  reset_timers(h, PT_LOO_BLOCKS, PT_LOO_BLOCKS_PSIS);
-  CallBufs b;
-  double *d_x = nullptr, *d_B = nullptr;
-  LbTile* d_tiles = nullptr;
-  LbRow* d_rows = nullptr;
-  Timer kern, vark, psis;
-  HIPCHK(b.timers({&kern, &vark, &psis}));
-  const size_t stride = (size_t)chunk * LP_ROWS * N;
-  HIPCHK(b.get(&d_x, 4 * stride));
-  HIPCHK(b.get(&d_tiles, (size_t)chunk));
-  HIPCHK(b.get(&d_rows, (size_t)chunk * LP_ROWS));
-  if (spline) {
-    double* rec_tmp = nullptr;
-    int *ni_tmp = nullptr, *d_err = nullptr;
-    HIPCHK(b.get(&d_B, (size_t)h->n_obs * P));
-    HIPCHK(b.get(&rec_tmp, (size_t)n * d.LREC));
-    HIPCHK(b.get(&ni_tmp, (size_t)n));
-    HIPCHK(b.get(&d_err, 1));
-    HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int), h->st));
-    if (once(ck, b, PT_LOO_BLOCKS, 0, [&] {
-          return launch_stats_functional(h->cfg.basis_degree, n, P, d.LREC, h->d_off, h->d_t, h->d_y, h->d_knots, h->n_knots, rec_tmp, ni_tmp,
-                                         d_B, d_err, h->st)
-                     ? std::string("unsupported basis_degree")
-                     : std::string();
-        }))
-      return 1;
-  } else if (from_basis) {
-    HIPCHK(b.get(&d_B, (size_t)chunk * LP_ROWS * P));
-  }
-  std::vector<LbTile> ht((size_t)chunk);
-  std::vector<double> hB(from_basis ? (size_t)chunk * LP_ROWS * P : 0), hexp, hpw, hll;
-  return for_chunks(ck, (int64_t)tiles.size(), chunk, [&](int64_t p0, int cnt) {
-    const int64_t base = tiles[(size_t)p0].t.row0;
-    const int64_t blk0 = tiles[(size_t)p0].blk0, blk1 = tiles[(size_t)p0 + cnt - 1].blk1;
-    int64_t rows64 = 0;
-    for (int q = 0; q < cnt; ++q) {
-      LbTile t = tiles[(size_t)p0 + q].t;
-      t.row0 -= base;
-      ht[(size_t)q] = t;
-      rows64 = t.row0 + t.rows;
-    }
-    const int rows = (int)rows64;
-    if (from_basis)
-      for (int r = 0; r < rows; ++r) {
-        const int64_t src = rows_all[(size_t)(base + r)].b;      // the observation's row of the handle's host basis
-        std::copy(h->B_host.begin() + (size_t)src * P, h->B_host.begin() + (size_t)(src + 1) * P, hB.begin() + (size_t)r * P);
-      }
-    std::vector<LbRow> hr(rows_all.begin() + (size_t)base, rows_all.begin() + (size_t)(base + rows));
-    if (from_basis)
-      for (int r = 0; r < rows; ++r) hr[(size_t)r].b = r;
-    if (copy_sync(h, d_tiles, ht.data(), sizeof(LbTile) * (size_t)cnt, hipMemcpyHostToDevice) != hipSuccess ||
-        copy_sync(h, d_rows, hr.data(), sizeof(LbRow) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess ||
-        (from_basis && copy_sync(h, d_B, hB.data(), sizeof(double) * (size_t)rows * P, hipMemcpyHostToDevice) != hipSuccess))
-      return std::string(kBackFailed);
-    std::string err = timed(kern, h->st, [&] {
-      return launch_loo_blocks(c, d_tiles, cnt, d_rows, d_B, h->d_y, first_slot, n_slots, d_x, stride, h->st);
-    });
-    if (err.empty() && loglik_trace) {
-      hll.resize((size_t)rows * N);
-      err = Back{h, 0, rows}(hll.data(), (const double*)d_x, N).queued();
-    }
-    if (err.empty())
-      err = Back{h, base, rows}(pit_trace, (const double*)(d_x + stride), N)(mean_trace, (const double*)(d_x + 2 * stride), N).done();
-    if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
-    if (!err.empty()) return err;
-    collect(h, kern, PT_LOO_BLOCKS);
-    if (loglik_trace)
-      for (int64_t k = blk0; k < blk1; ++k)
-        std::copy(hll.begin() + (size_t)(block_offsets[k] - base) * N, hll.begin() + (size_t)(block_offsets[k] - base + 1) * N, loglik_trace + (size_t)k * N);
-    // post_psis_expect_device runs on the device's default stream: done() has drained the sampler's
-    hpw.resize(6 * (size_t)rows);
-    double* const outs[6] = {hpw.data(), hpw.data() + rows, hpw.data() + 2 * (size_t)rows, hpw.data() + 3 * (size_t)rows,
-                             hpw.data() + 4 * (size_t)rows, hpw.data() + 5 * (size_t)rows};
-    hexp.resize(3 * (size_t)rows);
-    (void)hipEventRecord(psis.from, nullptr);
-    const int prc = post_psis_expect_device(d_x, (long long)N, rows, (int)N, d_x + stride, 3, (long long)stride, outs, hexp.data());
-    (void)hipEventRecord(psis.to, nullptr);
-    if (prc) return std::string(bfmmm_entry_last_error());
-    if (hipEventSynchronize(psis.to) != hipSuccess) return std::string(kBackFailed);
-    collect(h, psis, PT_LOO_BLOCKS_PSIS);
-    double* const res[6] = {lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic};
-    for (int64_t k = blk0; k < blk1; ++k)
-      for (int v = 0; v < 6; ++v) res[v][k] = outs[v][block_offsets[k] - base];
-    for (int r = 0; r < rows; ++r) {
-      const double e1 = hexp[(size_t)rows + r];
-      pit[base + r] = hexp[(size_t)r];
-      mean[base + r] = e1;
-      sd[base + r] = std::sqrt(std::max(0.0, hexp[2 * (size_t)rows + r] - e1 * e1));
-    }
-    if (var_trace) {
-      err = timed(vark, h->st, [&] { return launch_loo_pointwise_var(d_x + 2 * stride, d_x + 3 * stride, (size_t)rows * N, h->st); });
-      if (err.empty()) err = Back{h, base, rows}(var_trace, (const double*)(d_x + 3 * stride), N).done();
-      if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
-      if (err.empty()) collect(h, vark, PT_LOO_BLOCKS);
-    }
-    return err;
-  });
-}

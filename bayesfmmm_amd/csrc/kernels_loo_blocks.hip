@@ -36,24 +36,14 @@ namespace bfmmm {
 namespace {
 
 constexpr int LB_NT = LC_NT;
-constexpr int LB_TB_MAX = 8;
+constexpr int LB_TB_MAX = LC_TB_MAX;
 constexpr int LB_GL = 16;                      // lanes of a block's group
 constexpr int LB_NG = 64 / LB_GL;              // blocks in flight in a wave
-constexpr size_t LB_LDS_SOFT = 64 * 1024;      // as k_loo_pointwise
-constexpr size_t LB_LDS_HARD = 160 * 1024;
 
-struct LbArgs {
-  // chain 0's slot storage; chain q's is q * chain_bytes (covariate blocks: chain_bytes_cov) further
-  const double *c_Z, *c_nu, *c_Phi, *c_sigma, *c_eta, *c_xi;
-  const double *rec, *X, *y, *B;
-  const LbTile* tiles;
-  const LbRow* rows;
-  double* out;                                  // matrix v at out + v * out_stride
-  size_t out_stride, chain_bytes, chain_bytes_cov;
-  int n, K, P, M, D, BW, LG, LREC, cadj, mv;
-  int C, first_slot, S;
-  int TB, SCH;                                  // draws per staged batch, slots per workgroup (a multiple of TB)
-};
+// loo_core.hpp's record with the row table behind the tile list, where it always was: with `rows` at the end of the record the
+// compiler schedules k_loo_blocks differently and its device time grows by 1% (measured at blocks of 50)
+struct LbRows { const LbRow* rows; };
+struct LbArgs : LcArgsHead<LbTile>, LbRows, LcArgsTail {};
 
 // LDS doubles of k_loo_blocks
 struct LbLds {
@@ -298,33 +288,13 @@ __global__ __launch_bounds__(LB_NT) void k_loo_blocks(LbArgs a) {
   }
 }
 
-int lb_pick_tb(const Dims& d, size_t* bytes_out) {
-  auto bytes = [&](int tb) { return lb_lds(d.K, d.P, d.M, d.LG, tb).total * sizeof(double); };
-  int TB = LB_TB_MAX;
-  while (TB > 4 && bytes(TB) > LB_LDS_SOFT) TB >>= 1;
-  while (TB > 1 && bytes(TB) > LB_LDS_HARD) TB >>= 1;
-  *bytes_out = bytes(TB);
-  return TB;
-}
-
 }  // namespace
 
 // "" or what k_loo_blocks cannot take of the sampler's shape: asked before a call allocates anything
 std::string loo_blocks_check(const Ctx& c) {
-  const Dims& d = c.d;
-  if (d.P < 1 || d.P > PMAX) return "k_loo_blocks: P outside 1 .. 64";
-  if (d.M < 1 || d.M > 16) return "k_loo_blocks: n_eigen outside 1 .. 16";
-  if (d.K < 1 || d.K > KMAX) return "k_loo_blocks: K outside 1 .. 8";
-  if (d.D < 0 || d.D > 8) return "k_loo_blocks: more than 8 covariates";
-  if (d.BW < 0 || d.BW > BWWIDE) return "k_loo_blocks: band half-width above 31";
-  if (c.nch < 1 || c.nch > 65535) return "k_loo_blocks: more than 65535 chains";
   size_t bytes = 0;
-  (void)lb_pick_tb(d, &bytes);
-  if (bytes > LB_LDS_HARD)
-    return "k_loo_blocks: the tile's basis rows, the record, one draw's [c | V] and the blocks' records (P = " + std::to_string(d.P) +
-           ", n_eigen = " + std::to_string(d.M) + ", band " + std::to_string(d.BW) + ") need " + std::to_string(bytes) +
-           " bytes of LDS, above the kernel's 163840";
-  return "";
+  (void)lc_pick_tb(c.d, lb_lds, &bytes);
+  return lc_shape_check(c, "k_loo_blocks", "the tile's basis rows, the record, one draw's [c | V] and the blocks' records", bytes);
 }
 
 // The four matrices of the n_tiles row tiles at `tiles` with their rows at `rows` (device), every chain, slots [first_slot,
@@ -333,34 +303,11 @@ std::string loo_blocks_check(const Ctx& c) {
 // host's: every row's block lies within its tile.  Returns "" or what the kernel cannot take.
 std::string launch_loo_blocks(const Ctx& c, const LbTile* tiles, long long n_tiles, const LbRow* rows, const double* B, const double* y,
                               int first_slot, int n_slots, double* out, size_t out_stride, hipStream_t st) {
-  const Dims& d = c.d;
-  const std::string bad = loo_blocks_check(c);
-  if (!bad.empty()) return bad;
-  if (n_tiles < 1 || n_tiles > 2147483647LL || !tiles || !rows || !y || !out || (!d.mv && !B)) return "k_loo_blocks: bad arguments";
-  if (n_slots < 1 || first_slot < 0 || first_slot + n_slots > c.T) return "k_loo_blocks: range outside the chain storage";
   LbArgs a;
-  a.c_Z = c.c_Z; a.c_nu = c.c_nu; a.c_Phi = c.c_Phi; a.c_sigma = c.c_sigma;
-  a.c_eta = d.D > 0 ? c.c_eta : nullptr; a.c_xi = d.D > 0 ? c.c_xi : nullptr;
-  a.rec = c.rec; a.X = d.D > 0 ? c.X : nullptr; a.y = y; a.B = B; a.tiles = tiles; a.rows = rows; a.out = out; a.out_stride = out_stride;
-  a.chain_bytes = c.chain_bytes; a.chain_bytes_cov = c.chain_bytes_cov;
-  a.n = d.n; a.K = d.K; a.P = d.P; a.M = d.M; a.D = d.D; a.BW = d.BW; a.LG = d.LG; a.LREC = d.LREC;
-  a.cadj = (d.D > 0 && c.covariance_adj) ? 1 : 0;
-  a.mv = d.mv ? 1 : 0;
-  a.C = c.nch; a.first_slot = first_slot; a.S = n_slots;
-  size_t lds = 0;
-  a.TB = lb_pick_tb(d, &lds);
-  // slots per workgroup: eight batches, more where the grid's y extent would pass 65535
-  long long sch = (long long)a.TB * 8;
-  while (((long long)n_slots + sch - 1) / sch > 65535) sch *= 2;
-  a.SCH = (int)sch;
-  const dim3 grid((unsigned)n_tiles, (unsigned)((n_slots + a.SCH - 1) / a.SCH), (unsigned)c.nch);
-  if (hipFuncSetAttribute((const void*)k_loo_blocks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return "k_loo_blocks: cannot set the LDS size";
-  }
-  hipLaunchKernelGGL(k_loo_blocks, grid, dim3(LB_NT), lds, st, a);
-  if (hipGetLastError() != hipSuccess) return "k_loo_blocks: launch failed";
-  return "";
+  const std::string bad = lc_fill(a, loo_blocks_check(c), "k_loo_blocks", c, tiles && rows, tiles, n_tiles, B, y, first_slot, n_slots, out, out_stride);
+  if (!bad.empty()) return bad;
+  a.rows = rows;
+  return lc_launch(k_loo_blocks, "k_loo_blocks", a, c.d, lb_lds, n_tiles, st);
 }
 
 }  // namespace bfmmm

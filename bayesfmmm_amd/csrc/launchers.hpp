@@ -1,5 +1,5 @@
-// Host interface of the kernel files to the two host files (bfmmm_capi.hip, the driver, and capi_chain.hip): every launcher,
-// geometry and prepare_* function they call.  Included by both and by every file that defines one of them, so that a
+// Host interface of the kernel files to the host files (bfmmm_capi.hip, the driver, capi_chain.hip and capi_loo.hip): every launcher,
+// geometry and prepare_* function they call.  Included by them and by every file that defines one of them, so that a
 // declaration and its definition cannot drift apart.
 #pragma once
 #include "model.hpp"

@@ -5,8 +5,12 @@
 // first_slot.  The LDS strides are the caller's: row p of a draw's [c | V] has CVS doubles and a draw CVN, [e | G V] of a draw GVN,
 // a draw's A / u / beta record AS (A: lower triangle, row-major, M x M; u at M M; beta at M M + M).
 // fp64; every sum has a fixed order.
+// Behind the device steps, the host half of the two kernels, written once as well: the argument record, the choice of TB, the
+// shape check, the filling of the record and the launch.
 #pragma once
 #include "model.hpp"
+
+#include <string>
 
 namespace bfmmm {
 
@@ -124,6 +128,94 @@ __device__ __forceinline__ void lc_mfma_rows(const double* sB, const double* cv,
       }
     }
   }
+}
+
+// ---- the host half of the two kernels ----------------------------------------------------------------------------------------------
+constexpr int LC_TB_MAX = 8;
+constexpr size_t LC_LDS_SOFT = 64 * 1024;      // two workgroups per CU where the shape allows
+constexpr size_t LC_LDS_HARD = 160 * 1024;
+
+// What both kernels take, in two parts that keep the order of the kernels' argument records: k_loo_blocks has its row table between
+// them (kernels_loo_blocks.hip).
+template <class Tile>
+struct LcArgsHead {
+  // chain 0's slot storage; chain q's is q * chain_bytes (covariate blocks: chain_bytes_cov) further
+  const double *c_Z, *c_nu, *c_Phi, *c_sigma, *c_eta, *c_xi;
+  const double *rec, *X, *y, *B;
+  const Tile* tiles;
+};
+struct LcArgsTail {
+  double* out;                                  // matrix v at out + v * out_stride
+  size_t out_stride, chain_bytes, chain_bytes_cov;
+  int n, K, P, M, D, BW, LG, LREC, cadj, mv;
+  int C, first_slot, S;
+  int TB, SCH;                                  // draws per staged batch, slots per workgroup (a multiple of TB)
+};
+template <class Tile>
+struct LcArgs : LcArgsHead<Tile>, LcArgsTail {};
+
+// draws per staged batch and the LDS bytes of the layout lds(K, P, M, LG, TB) with them: what fits LC_LDS_SOFT down to 4, then LC_LDS_HARD
+template <class Layout>
+int lc_pick_tb(const Dims& d, Layout lds, size_t* bytes_out) {
+  auto bytes = [&](int tb) { return lds(d.K, d.P, d.M, d.LG, tb).total * sizeof(double); };
+  int TB = LC_TB_MAX;
+  while (TB > 4 && bytes(TB) > LC_LDS_SOFT) TB >>= 1;
+  while (TB > 1 && bytes(TB) > LC_LDS_HARD) TB >>= 1;
+  *bytes_out = bytes(TB);
+  return TB;
+}
+
+// "" or what kernel `k` cannot take of the sampler's shape; `holds`: what its LDS holds, for a shape whose layout needs `bytes`
+inline std::string lc_shape_check(const Ctx& c, const std::string& k, const char* holds, size_t bytes) {
+  const Dims& d = c.d;
+  if (d.P < 1 || d.P > PMAX) return k + ": P outside 1 .. 64";
+  if (d.M < 1 || d.M > 16) return k + ": n_eigen outside 1 .. 16";
+  if (d.K < 1 || d.K > KMAX) return k + ": K outside 1 .. 8";
+  if (d.D < 0 || d.D > 8) return k + ": more than 8 covariates";
+  if (d.BW < 0 || d.BW > BWWIDE) return k + ": band half-width above 31";
+  if (c.nch < 1 || c.nch > 65535) return k + ": more than 65535 chains";
+  if (bytes > LC_LDS_HARD)
+    return k + ": " + holds + " (P = " + std::to_string(d.P) + ", n_eigen = " + std::to_string(d.M) + ", band " + std::to_string(d.BW) +
+           ") need " + std::to_string(bytes) + " bytes of LDS, above the kernel's 163840";
+  return "";
+}
+
+// all of LcArgs but TB and SCH; "" or what kernel `k` cannot take: `bad` of its shape check, or the arguments (`tables`: all given)
+template <class Args, class Tile>
+std::string lc_fill(Args& a, const std::string& bad, const std::string& k, const Ctx& c, bool tables, const Tile* tiles, long long n_tiles,
+                    const double* B, const double* y, int first_slot, int n_slots, double* out, size_t out_stride) {
+  const Dims& d = c.d;
+  if (!bad.empty()) return bad;
+  if (n_tiles < 1 || n_tiles > 2147483647LL || !tables || !y || !out || (!d.mv && !B)) return k + ": bad arguments";
+  if (n_slots < 1 || first_slot < 0 || first_slot + n_slots > c.T) return k + ": range outside the chain storage";
+  a.c_Z = c.c_Z; a.c_nu = c.c_nu; a.c_Phi = c.c_Phi; a.c_sigma = c.c_sigma;
+  a.c_eta = d.D > 0 ? c.c_eta : nullptr; a.c_xi = d.D > 0 ? c.c_xi : nullptr;
+  a.rec = c.rec; a.X = d.D > 0 ? c.X : nullptr; a.y = y; a.B = B; a.tiles = tiles; a.out = out; a.out_stride = out_stride;
+  a.chain_bytes = c.chain_bytes; a.chain_bytes_cov = c.chain_bytes_cov;
+  a.n = d.n; a.K = d.K; a.P = d.P; a.M = d.M; a.D = d.D; a.BW = d.BW; a.LG = d.LG; a.LREC = d.LREC;
+  a.cadj = (d.D > 0 && c.covariance_adj) ? 1 : 0;
+  a.mv = d.mv ? 1 : 0;
+  a.C = c.nch; a.first_slot = first_slot; a.S = n_slots;
+  return "";
+}
+
+// kernel `k` (named `name`, LDS layout `layout`) over n_tiles tiles, runs of a.SCH slots and the chains
+template <class Args, class Layout>
+std::string lc_launch(void (*k)(Args), const std::string& name, Args& a, const Dims& d, Layout layout, long long n_tiles, hipStream_t st) {
+  size_t lds = 0;
+  a.TB = lc_pick_tb(d, layout, &lds);
+  // slots per workgroup: eight batches, more where the grid's y extent would pass 65535
+  long long sch = (long long)a.TB * 8;
+  while (((long long)a.S + sch - 1) / sch > 65535) sch *= 2;
+  a.SCH = (int)sch;
+  const dim3 grid((unsigned)n_tiles, (unsigned)((a.S + a.SCH - 1) / a.SCH), (unsigned)a.C);
+  if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return name + ": cannot set the LDS size";
+  }
+  hipLaunchKernelGGL(k, grid, dim3(LC_NT), lds, st, a);
+  if (hipGetLastError() != hipSuccess) return name + ": launch failed";
+  return "";
 }
 
 }  // namespace bfmmm

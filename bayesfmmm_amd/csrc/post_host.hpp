@@ -1,6 +1,6 @@
 // Host side shared by the bfmmm_post_* entry points (kernels_post.hip, kernels_bands.hip, kernels_loo.hip, kernels_diag.hip):
 // the functions they call in each other's files, device selection, an owning list of device buffers and the event pair that
-// times a call's kernels.  capi_chain.hip has its own CallBufs, which reports hipError_t and owns events as well.
+// times a call's kernels.  capi_chain.hpp has its own CallBufs, which reports hipError_t and owns events as well.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,7 +10,7 @@
 
 int bfmmm_io_fail(const std::string& m);      // entry_points.cpp: sets bfmmm_entry_last_error, returns 1
 void bfmmm_post_set_kernel_ms(float ms);      // kernels_post.hip: what bfmmm_post_last_kernel_ms returns
-// kernels_loo.hip: the PSIS / WAIC pass over n rows of S values on the current device (also in launchers.hpp, for capi_chain.hip)
+// kernels_loo.hip: the PSIS / WAIC pass over n rows of S values on the current device (also in launchers.hpp, for capi_loo.hip)
 int post_psis_device(const double* d_ll, long long ld, int n, int S, double* const out[6]);
 int post_psis_expect_device(const double* d_ll, long long ld, int n, int S, const double* d_aux, int n_aux, long long aux_stride,
                             double* const out[6], double* expect_host);

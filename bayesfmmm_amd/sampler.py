@@ -29,6 +29,8 @@ DRAW_DIMS = {"nu": "KP", "Phi": "KPM", "chi": "nM", "Z": "nK", "pi": "K", "alpha
 # what get_state also answers: diagnostic vectors of fixed length
 STATE_ONLY = {"status": (1,), "stamps": (64,), "wgtrace": (3072,), "ztrace": (3 * 8192,), "zphase": (8 * 8192,), "fct": (8,)}
 STAT_NAMES = ("rhat", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean", "mean", "sd")
+# the six arrays every PSIS call fills first, by their names in the dict of api.psis_loo
+_PW_NAMES = ("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic")
 
 
 def _dp(a):
@@ -37,6 +39,17 @@ def _dp(a):
 
 def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _loo_dict(outs, draws):
+    """the dict of api.psis_loo from the six pointwise arrays in front of outs, `draws` draws a row"""
+    from . import api
+    return api.loo_totals(dict(zip(_PW_NAMES, outs[:6])), draws)
+
+
+def _opt(tr):
+    """k -> the array tr[k] as a pointer, None where it was not asked for"""
+    return lambda k: None if tr.get(k) is None else _dp(tr[k])
 
 
 def _proposal_option(laplace, refused):
@@ -277,6 +290,10 @@ class Sampler:
             raise ValueError(f"x must have {self.D} entries, one per covariate")
         return xv
 
+    def _obs_counts(self):
+        """(n,): the observations of every curve (the multivariate model: the P coordinates of a row)"""
+        return np.full(self.n, self.P, dtype=np.int64) if self.offsets is None else np.diff(self.offsets)
+
     def _curve_list(self, curves):
         """(the index array, which must outlive the call; its pointer; the curves of the result), all n where curves is None"""
         if curves is None:
@@ -359,12 +376,10 @@ class Sampler:
     def loo(self, first_slot=0, n_slots=None, max_workspace_bytes=0):
         """PSIS-LOO and WAIC over curves from the chain slots of every chain, pooled (bfmmm_chain_loo): the dict api.psis_loo
         returns for the (n, C * S) matrix `curve_loglik` holds, without that matrix leaving the device."""
-        from . import api
         S = self._slots(first_slot, n_slots)
         outs = [np.zeros(self.n) for _ in range(6)]
         _lib.check(self.lib.bfmmm_chain_loo(self.h, int(first_slot), S, int(max_workspace_bytes), *[_dp(o) for o in outs], self.n))
-        pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs))
-        return api.loo_totals(pw, self.n_chains * S)
+        return _loo_dict(outs, self.n_chains * S)
 
     REFINE_TRACE_BYTES = 512 << 20      # loo_marginal(trace=True): the most "refine_prop" and "refine_samples" may take on the host
 
@@ -392,7 +407,6 @@ class Sampler:
         no stages and no refinement -- n_stages other than its default and refine=True, refine_samples or refine_stages given
         explicitly are refused.  The result then holds "n_modes_mean": (n,) in place of "n_refined" and the refinement's parameters,
         and trace adds "n_modes", "components" and "eta_samples" as `predict` does."""
-        from . import api
         S = self._slots(first_slot, n_slots)
         n, Cn, K, Sn = self.n, self.n_chains, self.K, max(S, 0)
         J, R, R2 = int(n_samples), int(n_stages), int(refine_stages)
@@ -407,13 +421,12 @@ class Sampler:
             if refine and 8 * cap * max(R2, 0) * (1 + max(J2, 0)) * K <= self.REFINE_TRACE_BYTES:
                 prop, smp = np.zeros((cap, max(R2, 0), K)), np.zeros((cap, max(R2, 0), max(J2, 0), K))
         n_ref = C.c_int64(0)
-        opt = lambda a: None if a is None else _dp(a)
+        opt = _opt(dict(tr, prop=prop, smp=smp))
         _lib.check(self.lib.bfmmm_chain_loo_marginal(
             self.h, int(first_slot), S, J, R, int(seed), int(bool(refine)), float(ess_floor), J2, R2, int(max_workspace_bytes),
-            *[_dp(o) for o in outs], _ip(n_refined), _ip(n_below), opt(tr.get("lpd_trace")), opt(tr.get("ess_trace")),
-            opt(tr.get("ess_trace_first")), None if idx is None else _ip(idx), opt(prop), opt(smp), C.byref(n_ref), n, cap))
-        pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs[:6]))
-        out = api.loo_totals(pw, Cn * S)
+            *[_dp(o) for o in outs], _ip(n_refined), _ip(n_below), opt("lpd_trace"), opt("ess_trace"),
+            opt("ess_trace_first"), None if idx is None else _ip(idx), opt("prop"), opt("smp"), C.byref(n_ref), n, cap))
+        out = _loo_dict(outs, Cn * S)
         out.update(ess_mean=outs[6], ess_min=outs[7], n_refined=n_refined, n_below=n_below, n_samples=J, n_stages=R, refine=bool(refine),
                    ess_floor=float(ess_floor), refine_samples=J2, refine_stages=R2)
         out.update(tr)
@@ -426,7 +439,6 @@ class Sampler:
 
     def _loo_marginal_laplace(self, first_slot, n_slots, n_samples, seed, ess_floor, trace, max_workspace_bytes):
         """loo_marginal(proposal="laplace")"""
-        from . import api
         S = self._slots(first_slot, n_slots)
         n, Cn, K, Sn, J = self.n, self.n_chains, self.K, max(S, 0), int(n_samples)
         d = K - 1
@@ -436,12 +448,11 @@ class Sampler:
         if trace:
             tr = {"lpd_trace": np.zeros((n, Cn, Sn)), "ess_trace": np.zeros((n, Cn, Sn)),
                   "components": np.zeros((n, Cn, Sn, K + 2, d + d * (d + 1) // 2 + 2)), "eta_samples": np.zeros((n, Cn, Sn, max(J, 0), d))}
-        opt = lambda k: _dp(tr[k]) if k in tr else None
+        opt = _opt(tr)
         _lib.check(self.lib.bfmmm_chain_loo_marginal_laplace(
             self.h, int(first_slot), S, J, int(seed), float(ess_floor), int(max_workspace_bytes), *[_dp(o) for o in outs], _ip(n_below),
             opt("lpd_trace"), opt("ess_trace"), _ip(n_modes), opt("components"), opt("eta_samples"), n))
-        pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs[:6]))
-        out = api.loo_totals(pw, Cn * S)
+        out = _loo_dict(outs, Cn * S)
         out.update(ess_mean=outs[6], ess_min=outs[7], n_below=n_below, n_modes_mean=n_modes.mean(axis=(1, 2)), n_samples=J,
                    ess_floor=float(ess_floor), proposal="laplace")
         out.update(tr)
@@ -458,15 +469,13 @@ class Sampler:
         mean and sd of every observation, all (N_obs,); "offsets": (n_curves + 1,), curve j of the selection owns entries
         offsets[j]:offsets[j + 1]; "curve_elpd_loo": the sums of "pointwise_elpd_loo" per curve.  trace adds "loglik_trace",
         "pit_trace", "mean_trace" and "var_trace": (N_obs, C, S), refused above REFINE_TRACE_BYTES on the host."""
-        from . import api
         S = self._slots(first_slot, n_slots)
         idx, pc, m = self._curve_list(curves)
         sel = np.arange(self.n) if idx is None else idx
         if sel.size and (sel.min() < 0 or sel.max() >= self.n):
             raise ValueError(f"loo_pointwise: 'curves' must lie in 0 .. {self.n - 1}")
-        ni = np.full(self.n, self.P, dtype=np.int64) if self.offsets is None else np.diff(self.offsets)
         offsets = np.zeros(m + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum(ni[sel])
+        offsets[1:] = np.cumsum(self._obs_counts()[sel])
         N = int(offsets[-1])
         Cn, Sn = self.n_chains, max(S, 0)
         tr = {}
@@ -477,11 +486,10 @@ class Sampler:
                                  f"select fewer curves or slots")
             tr = {k: np.zeros((N, Cn, Sn)) for k in ("loglik_trace", "pit_trace", "mean_trace", "var_trace")}
         outs = [np.zeros(N) for _ in range(9)]
-        opt = lambda k: _dp(tr[k]) if k in tr else None
+        opt = _opt(tr)
         _lib.check(self.lib.bfmmm_chain_loo_pointwise(self.h, pc, m, int(first_slot), S, int(max_workspace_bytes), *[_dp(o) for o in outs],
                                                       opt("loglik_trace"), opt("pit_trace"), opt("mean_trace"), opt("var_trace"), N))
-        pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs[:6]))
-        out = api.loo_totals(pw, Cn * S)
+        out = _loo_dict(outs, Cn * S)
         out.update(pit=outs[6], mean=outs[7], sd=outs[8], offsets=offsets,
                    curve_elpd_loo=np.array([outs[1][offsets[j]:offsets[j + 1]].sum() for j in range(m)]))
         out.update(tr)
@@ -502,10 +510,8 @@ class Sampler:
         "block_size": (n_blocks,); "obs": (N_rows,), the index of each listed observation within its curve; "curve_elpd_loo" and
         "curve_index": the sums of the block elpds per distinct curve, in order of first appearance.  trace adds "loglik_trace":
         (n_blocks, C, S) and "pit_trace", "mean_trace", "var_trace": (N_rows, C, S), refused above REFINE_TRACE_BYTES on the host."""
-        from . import api
         S = self._slots(first_slot, n_slots)
-        ni = np.full(self.n, self.P, dtype=np.int64) if self.offsets is None else np.diff(self.offsets)
-        bc, bo, bx = block_plan(ni, blocks=blocks, block_size=block_size, horizon=horizon, curves=curves)
+        bc, bo, bx = block_plan(self._obs_counts(), blocks=blocks, block_size=block_size, horizon=horizon, curves=curves)
         nb, N = len(bc), int(bo[-1])
         Cn, Sn = self.n_chains, max(S, 0)
         tr = {}
@@ -518,12 +524,11 @@ class Sampler:
             tr = {"loglik_trace": np.zeros((nb, Cn, Sn))}
             tr.update({k: np.zeros((N, Cn, Sn)) for k in ("pit_trace", "mean_trace", "var_trace")})
         outs = [np.zeros(nb) for _ in range(6)] + [np.zeros(N) for _ in range(3)]
-        opt = lambda k: _dp(tr[k]) if k in tr else None
+        opt = _opt(tr)
         _lib.check(self.lib.bfmmm_chain_loo_blocks(self.h, _ip(bc), bo.ctypes.data_as(_lib.c_int64_p), _ip(bx), nb, int(first_slot), S,
                                                    int(max_workspace_bytes), *[_dp(o) for o in outs], opt("loglik_trace"),
                                                    opt("pit_trace"), opt("mean_trace"), opt("var_trace"), nb, N))
-        pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs[:6]))
-        out = api.loo_totals(pw, Cn * S)
+        out = _loo_dict(outs, Cn * S)
         # per distinct curve, in order of first appearance: the curve's blocks in the order of the list, summed
         uniq, first = np.unique(bc, return_index=True)
         order = np.argsort(bc, kind="stable")

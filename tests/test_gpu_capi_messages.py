@@ -1,6 +1,6 @@
-"""The full text of what the chain-slot entry points (capi_chain.hip) answer to bad calls: one message per check, the first
+"""The full text of what the chain-slot entry points (capi_chain.hip, capi_loo.hip) answer to bad calls: one message per check, the first
 message of calls that are wrong twice (the order of the checks), and the byte counts of the workspace refusals, worked out here
-by the formulas of capi_chain.hip for the shared tiny sampler (n = 6, K = 2, M = 2, P = 5, 2 chains, T = 4)."""
+by the formulas of those files for the shared tiny sampler (n = 6, K = 2, M = 2, P = 5, 2 chains, T = 4)."""
 import ctypes as C
 
 import numpy as np
