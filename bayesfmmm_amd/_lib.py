@@ -94,6 +94,11 @@ SYMBOLS = {
     "bfmmm_chain_cluster_cov_bands_rescaled": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int,
                                                          C.POINTER(C.c_int32), C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, C.c_int,
                                                          C.c_double, C.c_int64] + [c_double_p] * 7 + [C.c_int64]),
+    "bfmmm_chain_cluster_contrast_bands": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, C.c_int,
+                                                     c_double_p, C.c_int, C.c_int, c_double_p, C.c_int, C.c_double, C.c_int64,
+                                                     c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p,
+                                                     c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p, c_double_p,
+                                                     C.c_int64]),
     "bfmmm_chain_cluster_eigen": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), c_double_p, C.c_int, c_double_p, c_double_p, C.c_int,
                                             c_double_p, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int64] + [c_double_p] * 13 +
                                   [C.POINTER(C.c_int32), C.c_int64]),

@@ -3,7 +3,8 @@
 // their simultaneous bands, the pooled co-membership matrix of the curves and the least-squares draw against it, the pooled
 // per-curve covariance surfaces, the label alignment against a pivot, the pooled cluster summaries under it, the cluster
 // covariance surfaces with their bands and their eigenvalues and eigenfunctions, the reference's rescale step per draw with the
-// summaries, mean functions and covariance surfaces under it and the prediction of held-out curves with
+// summaries, mean functions and covariance surfaces under it, the contrasts of cluster mean functions and covariate effects
+// under either labelling and the prediction of held-out curves with
 // their fitted functions.  The PSIS-LOO family over the chain slots is capi_loo.hip's.
 // What an entry point is made of is capi_chain.hpp's (SlotCheck, CallBufs, for_chunks, `once`, Back), shared with that file.  What
 // several of the entry points here do is written once as well: SortWs for the rule that long rows sort in a workspace, and
@@ -980,6 +981,165 @@ extern "C" int bfmmm_chain_cluster_mean_bands_rescaled(bfmmm_handle* h, const do
     if (err.empty()) err = r.to_host(r0, rows, outs, quant, nullptr);
     if (err.empty()) collect(h, project, PT_RESCALE_PROJECT);
     return err;
+  });
+}
+
+// ---- contrasts of cluster mean functions and covariate effects (kernels_cluster_contrast.hip) ---------------------
+// k_contrast_coef once per call, then per chunk of consecutive result rows e = r G + g: k_contrast_values into rows of C S values,
+// the unchanged RowReducer, k_rows_count for prob_positive and k_contrast_norm into the R norm rows, which the second RowReducer (the
+// seven statistics and the quantiles) reduces once the last chunk is done.  The band is bfmmm_chain_cluster_cov_bands' with `diagonal`:
+// launch_ccov_maxdev, the second sweep where a call takes several chunks, launch_ccov_crit or the long-row sort; then k_rows_count on
+// dev against t_r for p_sim.
+extern "C" int bfmmm_chain_cluster_contrast_bands(bfmmm_handle* h, const double* mix, const double* E, int G, const double* w_nu,
+                                                  const double* w_eta, int R, const double* weights, int first_slot, int n_slots,
+                                                  const double* probs, int nq, double alpha, int64_t max_workspace_bytes, double* mean,
+                                                  double* sd, double* quant, int32_t* n_positive, double* crit, double* lower, double* upper,
+                                                  int32_t* n_exceed, double* norm_stats, double* norm_quant, double* trace, double* norm_trace,
+                                                  int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_cluster_contrast_bands", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  if (ck.ptrs({{"h", h}, {"mix", mix}, {"E", E}, {"w_nu", w_nu}, {"mean", mean}, {"sd", sd}, {"n_positive", n_positive}, {"norm_stats", norm_stats}}))
+    return 1;
+  if (G < 1) return fail(fn + ": 'G' must be at least 1");
+  if (R < 1 || R > 64) return fail(fn + ": 'R' = " + std::to_string(R) + " outside 1 .. 64");
+  const Ctx& c = h->c;
+  const int K = c.d.K, P = c.d.P, D = c.d.D;
+  if (w_eta && !(D > 0 && c.c_eta)) return fail(fn + ": 'w_eta' is given but the sampler has no covariates");
+  if (w_eta && D > 8) return fail(fn + ": more than 8 covariates");
+  const int KD = w_eta ? K * D : 0;
+  for (int r = 0; r < R; ++r) {
+    bool any = false;
+    for (int k = 0; k < K; ++k) {
+      if (!std::isfinite(w_nu[r * K + k])) return fail(fn + ": 'w_nu'[" + std::to_string(r) + ", " + std::to_string(k) + "] is not finite");
+      any = any || w_nu[r * K + k] != 0.0;
+    }
+    for (int e = 0; e < KD; ++e) {
+      if (!std::isfinite(w_eta[(size_t)r * KD + e]))
+        return fail(fn + ": 'w_eta'[" + std::to_string(r) + ", " + std::to_string(e / D) + ", " + std::to_string(e % D) + "] is not finite");
+      any = any || w_eta[(size_t)r * KD + e] != 0.0;
+    }
+    if (!any) return fail(fn + ": contrast " + std::to_string(r) + " has no weight other than zero");
+  }
+  for (int g = 0; weights && g < G; ++g)
+    if (!(weights[g] >= 0.0) || !std::isfinite(weights[g])) return fail(fn + ": 'weights'[" + std::to_string(g) + "] is negative or not finite");
+  const bool band = crit || lower || upper || n_exceed;
+  if (band && !(crit && lower && upper && n_exceed)) return fail(fn + ": 'crit', 'lower', 'upper' and 'n_exceed' must be all null or all set");
+  const int64_t len = (int64_t)R * G;
+  if ((band && ck.alpha_inside(alpha)) || ck.capacity(capacity, len, "rows") || ck.range() || ck.budget_sign(max_workspace_bytes) || ck.row_limit() ||
+      ck.probs_list(probs, nq, 0, quant) || (nq > 0 && ck.ptrs({{"norm_quant", norm_quant}})))
+    return 1;
+  ContrastCall f;
+  f.G = G; f.R = R; f.first_slot = first_slot; f.n_slots = n_slots;
+  const size_t N = (size_t)ck.CS();
+  const bool long_dev = band && (long long)N > ccov_sort_rows();               // dev's rows are sorted in the workspace too
+  RowReducer r(ck, nq, false, long_dev), nr(ck, nq, true);
+  // shared by all rows: the coefficient table, E, the label maps, the weights, probs, the R norm rows with their statistics, the
+  // counts of p_sim and, for the band, dev, crit and t; a row: its values, its sort workspace, its mean, sd, quantiles and count
+  const size_t shared = sizeof(double) * ((size_t)R * P * N + (size_t)G * P + N * K * K + (size_t)R * (K + KD) + (size_t)G + 17 +
+                                          (band ? (size_t)R * N + 2 * (size_t)R : 0)) +
+                        nr.row_bytes() * (size_t)R + sizeof(int32_t) * (((size_t)R + 1) & ~(size_t)1);
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), shared, r.row_bytes() + sizeof(double), len, 65535, "row", &chunk)) return 1;
+  const int64_t nchunks = (len + chunk - 1) / chunk;
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_CONTRAST_COEF, PT_CONTRAST_NORM);
+  CallBufs b;
+  double *d_E = nullptr, *d_mix = nullptr, *d_wn = nullptr, *d_we = nullptr, *d_w = nullptr, *d_probs = nullptr, *d_dev = nullptr,
+         *d_crit = nullptr, *d_thr = nullptr;
+  int32_t *d_cnt = nullptr, *d_cntR = nullptr;
+  Timer values, norm;
+  HIPCHK(b.timers({&values, &norm}));
+  HIPCHK(r.alloc(b, chunk));
+  HIPCHK(nr.alloc(b, R));
+  HIPCHK(b.get(&d_cnt, (size_t)chunk * 2));
+  HIPCHK(b.get(&d_cntR, ((size_t)R + 1) & ~(size_t)1));
+  HIPCHK(b.put(h, &d_E, E, (size_t)G * P));
+  HIPCHK(b.put(h, &d_mix, mix, N * K * K));
+  HIPCHK(b.put(h, &d_wn, w_nu, (size_t)R * K));
+  if (w_eta) HIPCHK(b.put(h, &d_we, w_eta, (size_t)R * KD));
+  const std::vector<double> even(weights ? 0 : (size_t)G, 1.0 / G);      // the default quadrature: the mean square over the grid
+  HIPCHK(b.put(h, &d_w, weights ? weights : even.data(), (size_t)G));
+  HIPCHK(b.get(&f.tab, (size_t)R * P * N));
+  HIPCHK(probs_put(b, h, probs, nq, &d_probs, 1));      // [16]: 1 - alpha
+  r.probs = nr.probs = d_probs;
+  HIPCHK(hipMemsetAsync(nr.x, 0, sizeof(double) * (size_t)R * N, h->st));         // the sums start from 0.0
+  const double p_crit = 1.0 - alpha;
+  if (band) {
+    HIPCHK(copy_sync(h, d_probs + 16, &p_crit, sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(b.get(&d_dev, (size_t)R * N));
+    HIPCHK(b.get(&d_crit, (size_t)R));
+    HIPCHK(b.get(&d_thr, (size_t)R));
+    HIPCHK(hipMemsetAsync(d_dev, 0, sizeof(double) * (size_t)R * N, h->st));      // the maximum starts from 0.0
+  }
+  f.E = d_E; f.mix = d_mix; f.w_nu = d_wn; f.w_eta = d_we; f.w = d_w;
+  if (once(ck, b, PT_CONTRAST_COEF, 0, [&] { return launch_contrast_coef(c, f, h->st); })) return 1;
+  CcovCall mf;                                          // what launch_ccov_maxdev reads: R "pairs" of G diagonal entries
+  mf.G1 = G; mf.G2 = G; mf.diagonal = 1; mf.n_pairs = R;
+  double* const outs[2] = {mean, sd};
+  auto dev_launch = [&](int64_t r0, int rows) { return launch_ccov_maxdev(mf, (long long)N, r0, rows, r.x, r.mean, r.sd, d_dev, h->st); };
+  int rc = for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
+    std::string err = timed(values, h->st, [&] { return launch_contrast_values(c, f, r0, rows, r.x, h->st); });
+    if (err.empty()) err = r.reduce(rows);
+    if (err.empty()) err = launch_rows_count(r.x, (long long)N, rows, nullptr, 0, d_cnt, h->st);
+    if (err.empty()) err = timed(norm, h->st, [&] { return launch_contrast_norm(c, f, r0, rows, r.x, nr.x, h->st); });
+    if (err.empty() && band && nchunks == 1) err = dev_launch(r0, rows);
+    if (err.empty()) err = Back{h, r0, rows}(n_positive, (const int32_t*)d_cnt, 1).queued();
+    if (err.empty()) err = r.to_host(r0, rows, outs, quant, trace);
+    if (!err.empty()) return err;
+    collect(h, values, PT_CONTRAST_VALUES);
+    collect(h, norm, PT_CONTRAST_NORM);
+    return err;
+  });
+  if (rc) return rc;
+  // the size of every contrast per draw: the seven statistics and the pooled quantiles of the R rows
+  rc = for_chunks(ck, 1, 1, [&](int64_t, int) {
+    std::string err = nr.reduce(R);
+    double* outs7[7];
+    for (int s = 0; s < 7; ++s) outs7[s] = norm_stats + (size_t)s * R;
+    if (err.empty()) err = nr.to_host(0, R, outs7, norm_quant, norm_trace);
+    return err;
+  });
+  if (rc || !band) return rc;
+  if (nchunks > 1) {
+    // the second sweep: the same kernel on the same table gives the same values, now against every chunk's mean and sd
+    rc = for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
+      std::string err = timed(values, h->st, [&] { return launch_contrast_values(c, f, r0, rows, r.x, h->st); });
+      if (err.empty() && (copy_sync(h, r.mean, mean + r0, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess ||
+                          copy_sync(h, r.sd, sd + r0, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice) != hipSuccess))
+        err = "copy of the chunk's mean and sd failed";
+      if (err.empty()) err = dev_launch(r0, rows);
+      if (err.empty() && (hipStreamSynchronize(h->st) != hipSuccess || hipGetLastError() != hipSuccess)) err = "kernel failed";
+      if (err.empty()) collect(h, values, PT_CONTRAST_VALUES);
+      return err;
+    });
+    if (rc) return rc;
+  }
+  // crit[r] as bfmmm_chain_cluster_cov_bands reads it off dev
+  rc = for_chunks(ck, R, long_dev ? std::min<int64_t>(R, chunk) : R, [&](int64_t p0, int cnt) {
+    std::string err;
+    if (!long_dev) err = launch_ccov_crit(d_dev + (size_t)p0 * N, (long long)N, cnt, p_crit, d_crit + p0, h->st);
+    else {
+      err = launch_bands_quantiles(d_dev + (size_t)p0 * N, (int)N, cnt, r.w, d_probs + 16, 1, d_crit + p0, h->st);
+      if (err.empty()) err = launch_fit_quantiles(r.w, (int)r.ws.NP, (int)N, cnt, d_probs + 16, 1, d_crit + p0, h->st);
+    }
+    return err.empty() ? Back{h, p0, cnt}(crit, (const double*)(d_crit + p0), 1).done() : err;
+  });
+  if (rc) return rc;
+  std::vector<double> thr((size_t)R, 0.0);
+  {
+#pragma clang fp contract(off)
+    for (int64_t e = 0; e < len; ++e) {
+      const double w = crit[e / G] * sd[e];
+      lower[e] = mean[e] - w;
+      upper[e] = mean[e] + w;
+      // t_r: the largest |mean| / sd over the grid points with sd > 0; the band at level p excludes zero somewhere where crit_p < t_r
+      if (sd[e] > 0.0) thr[(size_t)(e / G)] = std::max(thr[(size_t)(e / G)], std::fabs(mean[e]) / sd[e]);
+    }
+  }
+  HIPCHK(copy_sync(h, d_thr, thr.data(), sizeof(double) * (size_t)R, hipMemcpyHostToDevice));
+  return for_chunks(ck, 1, 1, [&](int64_t, int) {
+    const std::string err = launch_rows_count(d_dev, (long long)N, R, d_thr, 1, d_cntR, h->st);
+    return err.empty() ? Back{h, 0, R}(n_exceed, (const int32_t*)d_cntR, 1).done() : err;
   });
 }
 

@@ -258,6 +258,26 @@ std::string launch_ccov_maxdev(const CcovCall& f, long long N, long long r0, lon
 int ccov_sort_rows();
 std::string launch_ccov_crit(const double* dev, long long N, long long m, double p, double* crit, hipStream_t st);
 
+// ---- kernels_cluster_contrast.hip ----
+// One call of bfmmm_chain_cluster_contrast_bands: the evaluation basis E (G x P), the label map of every draw
+// mix[(cs K + k) K + c], the R contrasts w_nu[r K + k] and w_eta[(r K + k) D + d] (null: nu alone), the quadrature weights w (G), the
+// slot range and the call's coefficient table tab[(r P + p) N + cs], N = C n_slots.  All device.
+struct ContrastCall {
+  int G = 0, R = 0, first_slot = 0, n_slots = 0;
+  const double *E = nullptr, *mix = nullptr, *w_nu = nullptr, *w_eta = nullptr, *w = nullptr;
+  double* tab = nullptr;
+};
+std::string contrast_check(const Ctx& c, const ContrastCall& f);
+// tab: b_r[p] of every draw
+std::string launch_contrast_coef(const Ctx& c, const ContrastCall& f, hipStream_t st);
+// the values V[cs + N (e - r0)] of result rows e = r G + g in [r0, r0 + rows), rows <= 65535
+std::string launch_contrast_values(const Ctx& c, const ContrastCall& f, long long r0, long long rows, double* V, hipStream_t st);
+// acc[r N + cs] += w_g v^2 over the chunk's rows of contrast r, g ascending; where the chunk holds the contrast's last row the
+// square root takes the sum's place.  The chunks of a call must come in ascending order, acc starts from 0.0
+std::string launch_contrast_norm(const Ctx& c, const ContrastCall& f, long long r0, long long rows, const double* V, double* acc, hipStream_t st);
+// count[row] = #{cs < N : V[row N + cs] > thr[row]} (ge: >=) for row < rows; thr null: 0.0 for every row
+std::string launch_rows_count(const double* V, long long N, long long rows, const double* thr, int ge, int32_t* count, hipStream_t st);
+
 // ---- kernels_cluster_eig.hip ----
 // One call of bfmmm_chain_cluster_eigen: the grid basis E (G x P), the weights w (G; null: 1), the covariate
 // setting x (D entries; null: phi alone), the reference functions ref (K J G; null: the largest-entry rule), the permutation

@@ -177,6 +177,72 @@ def block_plan(ni, blocks=None, block_size=None, horizon=None, curves=None):
     return block_curve, block_offsets, block_obs
 
 
+def contrast_plan(K, D, contrasts="pairwise"):
+    """The weight arrays of Sampler.cluster_contrast_bands (bfmmm_chain_cluster_contrast_bands) from one of its
+    spellings, for K clusters and D covariates: "pairwise", nu_k - nu_l for all k < l in the order (0, 1), (0, 2), .., (1, 2), ..;
+    "effects", eta_kd for every k and d (r = k D + d; it requires covariates); a list of contrasts, each a list of terms (weight, k)
+    or (weight, k, x), where a term with a D-vector x also adds weight x_d to the eta weight of (k, d), so that [(1, k, x), (-1, k, x')]
+    is f_k(x) - f_k(x'); or a dict {"nu": (R, K), "eta": (R, K, D)} taken as is (either may be left out: zeros).  Returns (w_nu
+    (R, K), w_eta (R, K, D) or None where D = 0).  ValueError: an unknown spelling, "effects" or an x without covariates, no contrast,
+    a term of another length, a cluster outside 0 .. K - 1, an x of another length, arrays of another shape.  Contrasts whose weights
+    are all zero or not finite, and more than 64 of them, are refused by the call itself."""
+    K, D = int(K), int(D)
+    name = "cluster_contrast_bands"
+    if isinstance(contrasts, str):
+        if contrasts == "pairwise":
+            pairs = [(k, l) for k in range(K) for l in range(k + 1, K)]
+            w_nu = np.zeros((len(pairs), K))
+            for r, (k, l) in enumerate(pairs):
+                w_nu[r, k], w_nu[r, l] = 1.0, -1.0
+            w_eta = np.zeros((len(pairs), K, D))
+        elif contrasts == "effects":
+            if D < 1:
+                raise ValueError(f"{name}: contrasts='effects' requires covariates")
+            w_nu = np.zeros((K * D, K))
+            w_eta = np.zeros((K * D, K, D))
+            for k in range(K):
+                for d in range(D):
+                    w_eta[k * D + d, k, d] = 1.0
+        else:
+            raise ValueError(f"{name}: contrasts must be 'pairwise', 'effects', a list of contrasts or a dict, got {contrasts!r}")
+    elif isinstance(contrasts, dict):
+        if not contrasts or any(k not in ("nu", "eta") for k in contrasts):
+            raise ValueError(f"{name}: a contrasts dict has the keys 'nu' and 'eta'")
+        arrs = {k: np.array(v, dtype=np.float64) for k, v in contrasts.items()}
+        R = next(iter(arrs.values())).shape[0] if next(iter(arrs.values())).ndim else -1
+        w_nu = arrs.get("nu", np.zeros((max(R, 0), K)))
+        if w_nu.shape != (R, K):
+            raise ValueError(f"{name}: contrasts['nu'] must have shape (R, {K}), got {w_nu.shape}")
+        if "eta" in arrs and D < 1:
+            raise ValueError(f"{name}: contrasts['eta'] is given but the sampler has no covariates")
+        w_eta = arrs.get("eta", np.zeros((R, K, D)))
+        if w_eta.shape != (R, K, D):
+            raise ValueError(f"{name}: contrasts['eta'] must have shape ({R}, {K}, {D}), got {w_eta.shape}")
+    else:
+        rows = [list(c) for c in contrasts]
+        w_nu = np.zeros((len(rows), K))
+        w_eta = np.zeros((len(rows), K, D))
+        for r, terms in enumerate(rows):
+            for term in terms:
+                term = tuple(term)
+                if len(term) not in (2, 3):
+                    raise ValueError(f"{name}: contrast {r}: a term is (weight, k) or (weight, k, x), got {len(term)} entries")
+                wgt, k = float(term[0]), int(term[1])
+                if not 0 <= k < K:
+                    raise ValueError(f"{name}: contrast {r}: cluster {k} outside 0 .. {K - 1}")
+                w_nu[r, k] += wgt
+                if len(term) == 3:
+                    if D < 1:
+                        raise ValueError(f"{name}: contrast {r}: a term has an x but the sampler has no covariates")
+                    x = np.asarray(term[2], dtype=np.float64).reshape(-1)
+                    if x.size != D:
+                        raise ValueError(f"{name}: contrast {r}: x must have {D} entries, one per covariate, got {x.size}")
+                    w_eta[r, k] += wgt * x
+    if w_nu.shape[0] < 1:
+        raise ValueError(f"{name}: no contrasts")
+    return np.ascontiguousarray(w_nu), (np.ascontiguousarray(w_eta) if D > 0 else None)
+
+
 def default_config(**kw):
     cfg = _lib.BfmmmConfig()
     _lib.load().bfmmm_config_defaults(C.byref(cfg))
@@ -873,6 +939,65 @@ class Sampler:
         A, _ = self._rescale_arg(rescale, perm, first_slot, S)
         return self._cluster_cov(self.lib.bfmmm_chain_cluster_cov_bands_rescaled, _dp(A), E, E2, pairs, x, diagonal, probs, simultaneous,
                                  trace, first_slot, S, max_workspace_bytes)
+
+    def cluster_contrast_bands(self, E, contrasts="pairwise", perm=None, rescale=None, weights=None, probs=(0.025, 0.5, 0.975),
+                               simultaneous=None, trace=False, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """Contrasts of the cluster mean functions and covariate effects on the rows of E (G x P in the sampler's basis; the identity
+        for the multivariate model) with the chains pooled, on the device (bfmmm_chain_cluster_contrast_bands): where
+        clusters k and l differ (nu_k - nu_l), what covariate d does to cluster k's mean function (eta_kd), f_k(x) - f_k(x'), and
+        differences of differences, each with the joint posterior of its terms, which two marginal bands cannot give.  Exactly one of
+        perm (`align`'s "perm" of the same slots) and rescale (the dict of `rescale` for the same slots) says how every draw is
+        labelled.  contrasts: "pairwise", "effects", a list of contrasts of terms (weight, k) or (weight, k, x), or a dict {"nu": (R,
+        K), "eta": (R, K, D)}: the spellings of `contrast_plan`; at most 64.  weights: G quadrature weights, finite and >= 0, of the
+        size of a contrast per draw, norm = sqrt(sum_g w_g v(g)^2) (default 1 / G each: the root mean square over the grid).
+        Returns {"mean", "sd", "prob_positive": (R, G), "quantiles": (R, G, nq), "probs", "w_nu": (R, K), "w_eta": (R, K, D) or None,
+        "norm": the seven STAT_NAMES (R,) and "quantiles" (R, nq) of the size per draw -- its split R-hat says whether the chains
+        agree on how far apart two clusters are, whatever their labels}; prob_positive is the share of draws with v > 0, strictly.
+        With simultaneous=alpha also {"crit": (R,), "lower", "upper": (R, G), "excludes_zero": (R, G), "p_sim": (R,), "alpha"}: the
+        simultaneous (1 - alpha) band of every contrast by `cluster_cov_bands`' rule, where it excludes zero, and the smallest level
+        at which it would exclude the zero function somewhere (1.0 where the contrast does not vary).  With trace also {"trace":
+        (R, G, N), "norm_trace": (R, C, S)}."""
+        if (perm is None) == (rescale is None):
+            raise ValueError("cluster_contrast_bands: exactly one of 'perm' and 'rescale' must be given")
+        Em = self._basis_arg(E, "E")
+        S = self._slots(first_slot, n_slots)
+        K, Cn = self.K, self.n_chains
+        if rescale is not None:
+            A, _ = self._rescale_arg(rescale, None, first_slot, S)
+        else:
+            p = self._perm_arg(perm, S)
+            if not np.array_equal(np.sort(p, axis=-1), np.broadcast_to(np.arange(K, dtype=np.int32), p.shape)):
+                raise ValueError(f"cluster_contrast_bands: every row of perm must be a permutation of 0 .. {K - 1}")
+            A = np.ascontiguousarray((p[..., None] == np.arange(K)).astype(np.float64))      # [q, s, k, c] = 1 where c = perm[k]
+        w_nu, w_eta = contrast_plan(K, self.D, contrasts)
+        wv = None
+        if weights is not None:
+            wv = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if wv.size != Em.shape[0]:
+                raise ValueError(f"weights must have {Em.shape[0]} entries, one per row of E")
+        pr = _probs_arg(probs)
+        R, G, Sn = w_nu.shape[0], Em.shape[0], max(S, 0)
+        N = Cn * Sn
+        out = {"mean": np.zeros((R, G)), "sd": np.zeros((R, G)), "quantiles": np.zeros((R, G, pr.size)), "probs": pr}
+        npos, nexc = np.zeros((R, G), dtype=np.int32), np.zeros(R, dtype=np.int32)
+        stats, nq_out = np.zeros((7, R)), np.zeros((R, pr.size))
+        band = simultaneous is not None
+        if band:
+            out.update(crit=np.zeros(R), lower=np.zeros((R, G)), upper=np.zeros((R, G)))
+        tr = {"trace": np.zeros((R, G, N)), "norm_trace": np.zeros((R, Cn, Sn))} if trace else {}
+        _lib.check(self.lib.bfmmm_chain_cluster_contrast_bands(
+            self.h, _dp(A), _dp(Em), G, _dp(w_nu), None if w_eta is None else _dp(w_eta), R, None if wv is None else _dp(wv),
+            int(first_slot), S, _dp(pr) if pr.size else None, pr.size, float(simultaneous) if band else 0.0, int(max_workspace_bytes),
+            _dp(out["mean"]), _dp(out["sd"]), _dp(out["quantiles"]) if pr.size else None, _ip(npos),
+            *[_dp(out[k]) if band else None for k in ("crit", "lower", "upper")], _ip(nexc) if band else None, _dp(stats),
+            _dp(nq_out) if pr.size else None, _opt(tr)("trace"), _opt(tr)("norm_trace"), R * G))
+        out["prob_positive"] = npos / float(max(N, 1))
+        out["norm"] = dict(zip(STAT_NAMES, stats), quantiles=nq_out)
+        out.update(w_nu=w_nu, w_eta=w_eta)
+        if band:
+            out.update(excludes_zero=(out["lower"] > 0) | (out["upper"] < 0), p_sim=nexc / float(max(N, 1)), alpha=simultaneous)
+        out.update(tr)
+        return out
 
     def cluster_eigen(self, E, perm, weights=None, n_functions=None, x=None, ref="mean", probs=(0.025, 0.5, 0.975), trace=False,
                       first_slot=0, n_slots=None, max_workspace_bytes=0):

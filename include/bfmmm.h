@@ -440,6 +440,48 @@ int bfmmm_chain_cluster_cov_bands_rescaled(bfmmm_handle* h, const double* mix, c
                                            double* mean, double* sd, double* quant, double* crit, double* lower, double* upper,
                                            double* trace, int64_t capacity);
 
+/* Contrasts of cluster mean functions and covariate effects with pointwise and simultaneous bands, the chains pooled:
+ * where clusters k and l differ, what covariate d does to cluster k's mean function, f_k(x) - f_k(x'), differences of differences.
+ * For draw cs = q n_slots + s of chain slots [first_slot, first_slot + n_slots) of EVERY chain of the batch, its K x K label map
+ * A = mix[(cs K + k) K + c] (N K K doubles: the transform of bfmmm_chain_rescale, or the permutation matrix of the draw's row of
+ * bfmmm_chain_align, A[k][c] = 1 where c = perm[k]), rows E_g of an evaluation basis (G x P, row-major in the sampler's basis; the
+ * identity for the multivariate model) and contrast r < R with weights w_nu[r K + k] and w_eta[(r K + k) D + d] (NULL: nu alone;
+ * it requires covariates to be set, at most 8)
+ *   a_c    = sum_k w_nu[r, k] A[k][c],   a'_cd = sum_k w_eta[r, k, d] A[k][c]                  (k in order from 0)
+ *   b_r[p] = sum_c ( a_c nu_c,p + sum_d a'_cd eta_c,p,d )                                      (c, then d, in order from 0)
+ *   v_r(g) = sum_p E_gp b_r[p]                                                                 (p in order from 0)
+ * without fused multiply-adds.  With e = r G + g and N = C n_slots draws:
+ *   mean[e], sd[e] (N - 1)                     required;
+ *   quant[q + nq e]                            the nq <= 16 quantiles probs by arma::quantile's rule; nq = 0: probs, quant and
+ *                                              norm_quant may be NULL;
+ *   n_positive[e]                              required: the draws with v_r(g) > 0, strictly;
+ *   crit[r], lower[e], upper[e], n_exceed[r]   all NULL or all set: the simultaneous (1 - alpha) band of contrast r by the rule of
+ *                                              bfmmm_chain_cluster_cov_bands over the G grid points (dev_r(cs) = max_g |v - mean| / sd,
+ *                                              sd = 0 skipped, a NaN kept), and n_exceed[r] = #{cs : dev_r(cs) >= t_r} with t_r the
+ *                                              largest |mean| / sd over the grid points with sd > 0 (0 where there is none):
+ *                                              n_exceed / N is the smallest level at which the band excludes the zero function somewhere.
+ *                                              alpha inside (0, 1), checked only where the band is asked for;
+ *   norm_stats[s R + r]                        required: the seven statistics of bfmmm_chain_diagnostics (s = rhat, ess_bulk,
+ *                                              ess_tail, ess_mean, mcse_mean, mean, sd) of norm_r(cs) = sqrt(sum_g weights[g] v_r(g)^2),
+ *                                              g in order from 0, each term weights[g] (v v); weights: G finite entries >= 0 (NULL:
+ *                                              1 / G each);  norm_quant[q + nq r]: its pooled quantiles;
+ *   trace[e N + cs], norm_trace[r N + cs]      the values and the norms themselves.  NULL: not copied.
+ * capacity >= R G rows; trace holds capacity N doubles.  R in 1 .. 64; a contrast whose weights are all zero and a weight that is
+ * not finite are refused.  A value's bits depend on (draw, contrast, g) alone and a norm is summed in the order of g across the
+ * chunks, so the results do not depend on the chunk, on repeated calls or on the other contrasts of the call.  With permutation
+ * matrices and w_nu = e_k the values are those of bfmmm_chain_cluster_mean_bands bit for bit (but for the sign of a zero).
+ * Chunks of consecutive result rows keep the values, the sort workspace of rows of more than 8192 draws and the chunk's results
+ * within max_workspace_bytes (0: 256 MiB); the coefficient table (8 R P N bytes), E, mix, the weights, the norm rows with their
+ * statistics and the band's per-draw maxima are shared by all rows and count against it; a budget below what is shared plus one
+ * row is refused with the bytes needed.  With the band and more than one chunk a second sweep over the chunks forms the values
+ * again.  At most 2^22 draws.  Runs on the sampler's stream and leaves its state and slots untouched. */
+int bfmmm_chain_cluster_contrast_bands(bfmmm_handle* h, const double* mix, const double* E, int G, const double* w_nu,
+                                       const double* w_eta, int R, const double* weights, int first_slot, int n_slots,
+                                       const double* probs, int nq, double alpha, int64_t max_workspace_bytes, double* mean,
+                                       double* sd, double* quant, int32_t* n_positive, double* crit, double* lower, double* upper,
+                                       int32_t* n_exceed, double* norm_stats, double* norm_quant, double* trace, double* norm_trace,
+                                       int64_t capacity);
+
 /* The eigenvalues and eigenfunctions of the cluster covariance operators with the labels aligned and the chains pooled (DESIGN.md
  * 7l): the principal components of the surfaces of bfmmm_chain_cluster_cov_bands.  For draw cs = q n_slots + s of chain slots
  * [first_slot, first_slot + n_slots) of EVERY chain of the batch, its row perm[cs K + .], a grid basis E (G x P, row-major in the
@@ -763,7 +805,11 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * Of the last bfmmm_chain_rescale / bfmmm_chain_rescaled_summary / bfmmm_chain_cluster_mean_bands_rescaled (always measured):
  * "rescale_transform" (one launch), "rescale_gather" and "rescale_project" (one launch per chunk), the device time and launches of
  * their own kernels.  bfmmm_chain_cluster_cov_bands_rescaled: the timers of bfmmm_chain_cluster_cov_bands, "cluster_cov_project"
- * with the mixing pass in it. */
+ * with the mixing pass in it.
+ * Of the last bfmmm_chain_cluster_contrast_bands (always measured): "contrast_coef" (k_contrast_coef, one launch a call),
+ * "contrast_values" (k_contrast_values, one launch per chunk, and one more per chunk where the band takes a second sweep) and
+ * "contrast_norm" (k_contrast_norm, one launch per chunk), next to "rescale_project"; the reductions, the counts and the band's
+ * launches are not timed. */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
