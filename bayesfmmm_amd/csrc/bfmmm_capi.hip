@@ -240,7 +240,7 @@ static int create_impl(const bfmmm_config* cfg, int device, const double* y, con
   //  element -- the second half is masked, but the read must stay inside the request, whatever the arena's rounding)
   areq(ar, &c.pg_part, h->pg_part_doubles); areq(ar, &c.H, (size_t)d.R * d.LG + 2); areq(ar, &c.H2, (size_t)d.R * P * (2 * d.BW + 2));
   areq(ar, &c.tvec, (size_t)d.A * P); areq(ar, &c.rvec, (size_t)d.A * P); areq(ar, &c.hq, (size_t)d.A * P);
-  areq(ar, &c.gstd, (size_t)K * P * M + (size_t)K * M + 13 * K + 8); areq(ar, &c.zprep, (size_t)(3 * K + 5) * n);
+  areq(ar, &c.gstd, gstd_doubles(K, P, M)); areq(ar, &c.zprep, (size_t)(3 * K + 5) * n);
   areq(ar, &c.chi_norm, (size_t)n * M); areq(ar, &c.zrec, zrec_stride(n, K)); areq(ar, &c.piprep, 9 * KMAX + 16); areq(ar, &c.Lz, (size_t)d.A * P);
   areq(ar, &c.Cmat, (size_t)d.A * P * P + 2);
   {
@@ -940,7 +940,17 @@ static int run_impl(bfmmm_handle* h, uint32_t mask, int first_iter, int n_iters,
   const bool defer = !h->profile && !fuse && plan.z && plan.z_update && plan.factor && (mask & U_Z) && c.d.D == 0 && c.d.K <= 4 &&
                      c.d.BW <= 5 && n_iters >= 2 && tt_step == 0;
   if (n_iters > 0) record_curve_route(h, c, plan, fuse, defer);
+  {
+    // where the scalar jobs ride, for bfmmm_debug_get("hyper_route"): from the decisions the launchers read (Ctx::defer_hyper;
+    // launch_iteration's trail_z, which the deferred bodies set and which replaces k_curve_chi where the sweep has no chi pass;
+    // PgRoute::packed -> Ctx::pi_in_factor; k_pair_gram's PG_SOLO_LL; k_factor's npi)
+    const bool lean_host = defer && !plan.chi;
+    const double v[3] = {c.defer_hyper ? 2.0 : (lean_host ? 1.0 : 0.0), subs[0].r.packed ? 2.0 : (pg_route_solo_ll(subs[0].r) ? 1.0 : 0.0),
+                         (plan.factor && (mask & (U_PI | U_ALPHA3))) ? 1.0 : 0.0};
+    memcpy(h->last_hyper, v, sizeof v);
+  }
   if (!prepare_only && n_iters > 0) h->zrec_form = (rec_on && plan.z && plan.z_update) ? (fuse ? 2 : 1) : 0;
+  if (!prepare_only && n_iters > 0) h->pi_flag_stored = rec_on && (mask & (U_PI | U_ALPHA3)) != 0;
   if (h->profile) {
     if (prepare_only) return 0;
     HIPCHK(hipEventRecord(h->ev0, h->st));
@@ -1146,6 +1156,21 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
     *count = cnt;
     return 0;
   }
+  if (s == "hyper_route") {   // host-side record of the last bfmmm_run (run_impl)
+    const int64_t cnt = sizeof h->last_hyper / sizeof h->last_hyper[0];
+    if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
+    memcpy(out, h->last_hyper, sizeof h->last_hyper);
+    *count = cnt;
+    return 0;
+  }
+  if (s == "pi_prepared") {   // the selected chain's flag of the last run's last pi / alpha_3 job (scalar_jobs.hpp: job_pi_alpha)
+    if (!bfmmm::g_curve_record) return fail("bfmmm_debug_get(" + s + "): recording is off (bfmmm_set_curve_record)");
+    if (!h->pi_flag_stored) return fail("bfmmm_debug_get(" + s + "): the last run stored no flag (neither U_PI nor U_ALPHA3 in its mask, or recording was off)");
+    if (capacity < 1) return fail("bfmmm_debug_get(" + s + "): buffer too small");
+    HIPCHK(copy_sync(h, out, c.zrec + zrec_stride(d.n, d.K) - 1, sizeof(double), hipMemcpyDeviceToHost));
+    *count = 1;
+    return 0;
+  }
   if (s == "z_record" || s == "z_prepared") {     // the selected chain's record of the last run's last Z update (z_proposal.hpp)
     if (!bfmmm::g_curve_record) return fail("bfmmm_debug_get(" + s + "): recording is off (bfmmm_set_curve_record)");
     if (!h->zrec_form) return fail("bfmmm_debug_get(" + s + "): the last run stored no record (no Z update in its mask, or recording was off)");
@@ -1178,6 +1203,8 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
                       {"theta", c.theta, (int64_t)d.K * (d.M + 1) * d.P},
                       // the per-curve kernels' (k_curve_z, k_curve_chi); the last four exist once covariates were set
                       {"chi_norm", c.chi_norm, (int64_t)d.n * d.M}, {"zprep", c.zprep, (int64_t)(3 * d.K + 5) * d.n},
+                      // the scalar jobs' (scalar_jobs.hpp): the variates job_hyper_draws left (as allocated), the prepared pi / alpha_3 tables
+                      {"gstd", c.gstd, (int64_t)gstd_doubles(d.K, d.P, d.M)}, {"piprep", c.piprep, (int64_t)9 * KMAX + 16},      // (as allocated; PI_TAB_DOUBLES)
                       {"rss_part", c.rss_part, (int64_t)c.nblk_curve}, {"logz_part", c.logz_part, (int64_t)c.nblk_curve * d.K},
                       {"stil", c.stil, (int64_t)d.n * d.P}, {"yyp_part", c.yyp_part, (int64_t)c.nblk_curve},
                       {"cfull", c.cfull, (int64_t)d.n * d.P}, {"gfull", c.gfull, (int64_t)d.n * d.P},

@@ -102,6 +102,12 @@ struct bfmmm_handle {
   // bfmmm_debug_get("cov_route"): what launch_cov_block launches in every iteration of the last run {BW, LPC, DX (0 general), the D
   // instance of k_cov_w2, PP of k_cov_factor, NB2, NBS, NPG, k_cov_group launches, do_eta, do_xi} (BW -1: no covariates)
   double last_cov[11] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // bfmmm_debug_get("hyper_route"): where the scalar jobs of the last run ride (scalar_jobs.hpp) {job_hyper: 0 k_curve_chi, 1 the lean
+  // k_curve_z of the bodies and k_curve_chi of the closing iteration, 2 deferred to the next k_pair_gram and k_loglik_flush;
+  // job_pi_alpha: 0 k_pair_gram, 1 k_pair_gram with the deferred log-likelihood in a workgroup of its own, 2 k_factor;
+  // job_pi_prepare workgroups launched} (-1: no run yet)
+  double last_hyper[3] = {-1, -1, 0};
+  bool pi_flag_stored = false;         // the last run's job_pi_alpha stored its prepared flag (bfmmm_debug_get "pi_prepared")
   int64_t tab_key = -1;                // (MD, mask) the step tables of k_sweep_chain were built for
   int launch_error = 0;                // set while a run's launches are queued: 1 the sweep does not fit, 2 no per-curve instance
   int zrec_form = 0;                   // the Z record of the last run (Ctx::zrec): 0 none stored (recording off, or no Z update in the mask),

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256, (BW <= 5) ? 3 : 1) void k_factor(Ctx c0) {
     // batches it would cost k_pair_gram_pack or its reduction their register budget -- it needs 177 VGPRs, they 88 and 46).  The
     // one spare job that reads pi / alpha_3 of THIS iteration (job_pi_prepare, one workgroup) waits for it (wait_pi below); the
     // pi job is dispatched before it (lower workgroup index), so the wait cannot deadlock, and it is bounded anyway.
-    job_pi_alpha(c);
+    job_pi_alpha(c, true, c0.zrec != nullptr);
     __syncthreads();
     if (tid == 0) {
       __threadfence();

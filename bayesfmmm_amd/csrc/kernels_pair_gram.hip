@@ -326,7 +326,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pair_gram(Ctx c0, int KS, int nk
   if (ct == d.CTG + 1) {            // extra workgroups: pi / alpha_3 of chain ks, hidden under the contraction
     if (ks < nch && threadIdx.x < 256) {      // the scalar jobs are written for 256 threads (waves 4-7 leave)
       const Ctx c = chain_ctx(c0, (unsigned)ks);
-      job_pi_alpha(c, BATCH || !(do_pg & PG_SOLO_LL));      // (PG_SOLO_LL: the deferred log-likelihood runs in workgroup 2 nch below)
+      job_pi_alpha(c, BATCH || !(do_pg & PG_SOLO_LL), c0.zrec != nullptr);      // (PG_SOLO_LL: the deferred log-likelihood runs in workgroup 2 nch below)
       TSTAMP(c, 46);
     } else if (ks >= nch && ks < 2 * nch && threadIdx.x < 256) {
       // the previous iteration's scalar job (delta, A, gamma, tau), left pending by k_curve_chi (Ctx::defer_hyper): its results are
@@ -1044,6 +1044,8 @@ PgRoute pg_route_decide(const Dims& d, int nch_handle, int nch, bool pg, bool de
   }
   return r;
 }
+
+bool pg_route_solo_ll(const PgRoute& r) { return !r.packed && r.body <= 1 && (r.do_pg & PG_SOLO_LL) != 0; }
 
 void launch_pair_gram(const Ctx& c, const PgRoute& r, hipStream_t st) {
   const Dims& d = c.d;

@@ -65,6 +65,7 @@ struct PgRoute {
 };
 void pg_geometry(const Dims& d, int& NKS, int& KS);
 PgRoute pg_route_decide(const Dims& d, int nch_handle, int nch, bool pg, bool defer_loglik, size_t pg_part_doubles, bool may_pack);
+bool pg_route_solo_ll(const PgRoute& r);      // the launch gives the deferred log-likelihood a workgroup of its own (job_pi_alpha runs without it)
 size_t pgp_pack_doubles(const PgPack& g);
 void launch_pair_gram(const Ctx& c, const PgRoute& r, hipStream_t st);
 void launch_pg_reduce(const Ctx& c, int NKS, hipStream_t st);

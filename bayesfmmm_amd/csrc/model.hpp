@@ -138,8 +138,16 @@ struct Dims {
 };
 
 constexpr int ZREC_SCALARS = 6;      // scalar fields per curve of Ctx::zrec, in front of Znew[0 .. K) (z_proposal.hpp)
-// doubles per chain of Ctx::zrec: the (6 + K) x n record, then one flag (1: the update took PREPARED proposals, 0: it evaluated them in place)
+// doubles per chain of Ctx::zrec: the (6 + K) x n record, then two flags: whether the Z update took PREPARED proposals (1) or evaluated
+// them in place (0), and the same of the pi / alpha_3 tables of job_pi_alpha (scalar_jobs.hpp)
 __host__ __device__ inline size_t zrec_stride(int n, int K) { return (size_t)(ZREC_SCALARS + K) * n + 2; }
+// doubles per chain of Ctx::gstd: what job_hyper_draws writes (K P M gammas, K M deltas, K taus, 2K A proposals, 2K A uniforms, the
+// sigma^2 variate, 8K A terms), then GSTD_SPARE doubles it never touches; while recording, job_pi_alpha keeps its GSTD_REC
+// acceptance values in the first of them
+constexpr int GSTD_SPARE = 7, GSTD_REC = 2;
+static_assert(GSTD_REC <= GSTD_SPARE, "the recorded acceptance values live in the spare doubles of gstd");
+__host__ __device__ inline size_t gstd_used(int K, int P, int M) { return (size_t)K * P * M + (size_t)K * M + 13 * (size_t)K + 1; }
+__host__ __device__ inline size_t gstd_doubles(int K, int P, int M) { return gstd_used(K, P, M) + GSTD_SPARE; }
 
 // Everything a kernel needs, passed by value (kernarg).
 struct Ctx {

@@ -140,7 +140,9 @@ __device__ inline void job_pi_prepare(const Ctx& c) {
 }
 
 // loglik = false: the caller runs the deferred log-likelihood elsewhere in the same launch (k_pair_gram, PG_SOLO_LL)
-__device__ inline void job_pi_alpha(const Ctx& c, bool loglik = true) {
+// rec: the launch records for the tests (bfmmm_set_curve_record; the caller tests the kernel argument's zrec, not the chain's shifted
+// copy): lane 0 stores whether the tables were the prepared ones in the second trailing double of the chain's Z record
+__device__ inline void job_pi_alpha(const Ctx& c, bool loglik = true, bool rec = false) {
   // scratch carved from k_pair_gram's dynamic LDS (the launcher guarantees PI_ALPHA_LDS_DOUBLES)
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double (*red)[256] = (double (*)[256])smem;       // KMAX x 256
@@ -162,6 +164,7 @@ __device__ inline void job_pi_alpha(const Ctx& c, bool loglik = true) {
   // the data-independent tables: prepared during the previous iteration's k_factor, or evaluated here
   const bool pre = dyn->piprep_valid && dyn->piprep_iter == dyn->iter && dyn->tt_step == 0 &&
                    dyn->zprep_chain == c.chain && dyn->zprep_seed == c.seed;
+  if (rec && tid == 0) c.zrec[zrec_stride(n, K) - 1] = pre ? 1.0 : 0.0;
   if (pre) {
     for (int e = tid; e < PI_TAB_DOUBLES; e += 256) t.g[e] = c.piprep[e];
   } else {
@@ -208,6 +211,8 @@ __device__ inline void job_pi_alpha(const Ctx& c, bool loglik = true) {
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) pi[k] = pi_old[k];
     int pi_is_new = 0;
+    // (rec: the two acceptance values go to the first spare doubles of gstd, behind what job_hyper_draws writes: model.hpp, GSTD_REC)
+    double* acc_rec = c.gstd + gstd_used(K, d.P, d.M);
     if (mask & U_PI) {
       double lpdf_new = 0.0, lpdf_old = 0.0, pn = 0.0, po = 0.0;
 #pragma unroll
@@ -224,6 +229,7 @@ __device__ inline void job_pi_alpha(const Ctx& c, bool loglik = true) {
       const double lpn = pn - lB(0);
       const double lpo = po - lB(1);
       const double acc = lpdf_new - lpdf_old + lpo - lpn;
+      if (rec) acc_rec[0] = acc;
       if (lu[0] < acc) {
         pi_is_new = 1;
 #pragma unroll
@@ -244,6 +250,7 @@ __device__ inline void job_pi_alpha(const Ctx& c, bool loglik = true) {
       l_new -= n * lB(4 + pi_is_new);
       l_old += dt[0];
       l_new += dt[1];
+      if (rec) acc_rec[1] = l_new - l_old;
       if (lu[1] < l_new - l_old) alpha3 = a3_ph;
       dyn->alpha3 = alpha3;
     }

@@ -1286,6 +1286,16 @@ class Sampler:
                    fuse=bool(v[13]))
         return dict(z=z, chi=chi)
 
+    def hyper_route(self):
+        """Where the scalar jobs of the last `run` rode (bfmmm_debug_get "hyper_route", recorded on the host): "hyper", the host of
+        the delta / A / gamma / tau job ("chi": k_curve_chi; "lean_z": the lean k_curve_z of the bodies, k_curve_chi in the closing
+        iteration; "deferred": the next iteration's k_pair_gram, k_loglik_flush for the last), "pi", the host of the pi / alpha_3 job
+        ("pair_gram", "pair_gram_solo_ll": the deferred log-likelihood in a workgroup of its own, "factor"), and "pi_prepare",
+        whether k_factor prepares the next iteration's pi / alpha_3 tables."""
+        v = self.debug("hyper_route", 8)
+        return dict(hyper=("chi", "lean_z", "deferred")[int(v[0])] if v[0] >= 0 else None,
+                    pi=("pair_gram", "pair_gram_solo_ll", "factor")[int(v[1])] if v[1] >= 0 else None, pi_prepare=bool(v[2]))
+
     def cov_route(self):
         """What the eta / Xi block of every iteration of the last `run` launches (bfmmm_debug_get "cov_route", recorded on the
         host; covariates set): BW, LPC and DX (0: the general instance) of k_cov_group, the D instance of k_cov_w2, PP of

@@ -760,7 +760,18 @@ int bfmmm_chain_predict_fit(bfmmm_handle* h, const double* y, const double* t, c
  *   (the closing residual pass included), do_eta, do_xi};
  * "z_record" ((6 + K) x n, field-major): acceptance, log_uu, pr_old, pr_new, lpo, lpn, Znew of the last Z update of the last run
  *   (bfmmm_set_curve_record; fails when that run stored none);
- * "z_prepared" (1): whether that update took the proposals prepared ahead by k_factor (1) or evaluated them in place (0).
+ * "z_prepared" (1): whether that update took the proposals prepared ahead by k_factor (1) or evaluated them in place (0);
+ * "gstd" (K P M + K M + 13 K + 8, as allocated): what job_hyper_draws left for the last iteration's scalar job -- the standard gamma
+ *   variates of gamma (index (k P + p) M + m), delta (k M + i) and tau (k), the A proposals and uniforms (2 j + i), the sigma^2
+ *   variate, four log(tgamma) / log terms per A cell -- and, while bfmmm_set_curve_record is on, the acceptance values of the last
+ *   pi and alpha_3 steps in the two doubles behind;
+ * "piprep" (9 KMAX + 16): the pi / alpha_3 tables k_factor prepared for the next iteration (scalar_jobs.hpp: pi_alpha_layout);
+ * "pi_prepared" (1): whether the last pi / alpha_3 job took prepared tables (bfmmm_set_curve_record; fails when the last run's mask
+ *   had neither U_PI nor U_ALPHA3, or recording was off);
+ * "hyper_route" (3): where the scalar jobs of the last bfmmm_run rode, recorded on the host from the decisions the launchers read:
+ *   {delta / A / gamma / tau: 0 k_curve_chi, 1 the lean k_curve_z (k_curve_chi in the closing iteration), 2 deferred to the next
+ *   k_pair_gram and k_loglik_flush; pi / alpha_3: 0 k_pair_gram, 1 k_pair_gram with the deferred log-likelihood in a workgroup of its
+ *   own, 2 k_factor; whether k_factor prepares the next iteration's pi / alpha_3 tables}.
  * Returns the number of doubles written through *count. */
 int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capacity, int64_t* count);
 
