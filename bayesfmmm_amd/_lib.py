@@ -73,6 +73,8 @@ SYMBOLS = {
     "bfmmm_chain_similarity_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, c_double_p, C.c_int64, C.POINTER(C.c_int32),
                                               C.POINTER(C.c_int32), c_double_p]),
     "bfmmm_get_slot": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, c_double_p, C.c_int64]),
+    "bfmmm_set_chain": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, c_double_p, C.c_int64]),
+    "bfmmm_chain_slot_loglik": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, c_double_p, c_double_p, C.c_int64]),
     "bfmmm_chain_curve_cov": (C.c_int, [C.c_void_p, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
                                         C.c_int, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int64]),
     "bfmmm_chain_align": (C.c_int, [C.c_void_p, c_double_p, C.c_int, C.c_int, C.POINTER(C.c_int32), c_double_p, C.c_int64]),

@@ -464,6 +464,143 @@ def write_arma_field(file, field):
         lib.bfmmm_result_free(res)
 
 
+# ---- the on-disk chain batches as chain slots of a Sampler ----------------------------------------------
+# file name -> (get_chain name, kind): "cube" / "vec" / "mat" (draws along the last axis), "rows" (a draw a row: Tau), "field" (a
+# field of one cube per draw), "fieldK" (a field of K cubes per draw: (draw, cluster)), "cube_head" / "field_head": containers of
+# r_stored_iters entries of which only the first per_file are draws (save_batch in entry_points.cpp)
+_BATCH_FILES = (("Nu", "nu", "cube", 0), ("Chi", "chi", "cube", 0), ("Z", "Z", "cube", 0), ("Sigma", "sigma_sq", "vec", 0),
+                ("Phi", "Phi", "field", 0), ("Pi", "pi", "mat", 0), ("alpha_3", "alpha_3", "vec", 0), ("A", "A", "cube", 0),
+                ("Delta", "delta", "cube", 0), ("Tau", "tau", "rows", 0), ("Gamma", "gamma", "field", 0),
+                ("Eta", "eta", "field", 1), ("Tau_Eta", "tau_eta", "cube_head", 1),
+                ("Xi", "xi", "fieldK", 2), ("Gamma_Xi", "gamma_xi", "fieldK", 2), ("Delta_Xi", "delta_xi", "field", 2),
+                ("A_Xi", "A_xi", "field", 2))
+_BATCH_REQUIRED = ("Nu", "Chi", "Z", "Sigma", "Phi")
+
+
+def read_batches(dir, n_files, X=False, cov_adj=False, drop_unassigned=False):
+    """The reference's on-disk chain batches `<dir><Name><q>.txt`, q < n_files (BFMMM_warm_start and its relatives with `dir=`), as
+    arrays in Sampler.get_chain's layouts, concatenated over the files along the draws: a dict with "nu" (K, P, T), "chi"
+    (n, M, T), "Z" (n, K, T), "sigma_sq" (T,), "Phi" (K, P, M, T) and, where the files exist, "pi", "alpha_3", "A", "delta", "tau"
+    ((T, K)) and "gamma"; with X also "eta" and "tau_eta"; with cov_adj also "xi", "gamma_xi", "delta_xi" and "A_xi"; and
+    "n_draws" = T.  What Sampler.load_chain takes.
+    The covariate containers of a file hold r_stored_iters entries of which only the first per_file (the draws of Nu<q>.txt) are
+    draws; the rest is dropped.  The first entry of alpha_3 in every file is the reference's unassigned 0.  The default keeps that
+    draw, so that slot indices and `burnin_prop` mean what they mean for every file-route function (FLLik, ZCI, ...); predict and
+    loo_marginal, which read alpha_3, must then start after it (first_slot >= 1, one file).  drop_unassigned=True leaves the first
+    draw of every file out of every array instead."""
+    import os
+    if n_files <= 0:
+        raise ValueError("'n_files' must be greater than 0")
+    level = 2 if (X and cov_adj) else 1 if X else 0
+    parts = {}
+    per_file = []
+    for q in range(int(n_files)):
+        per = None
+        for fname, key, kind, lvl in _BATCH_FILES:
+            if lvl > level:
+                continue
+            path = os.path.join(str(dir), f"{fname}{q}.txt")
+            if not os.path.exists(path):
+                if fname in _BATCH_REQUIRED or key in parts:
+                    raise FileNotFoundError(f"read_batches: '{path}' is missing")
+                continue
+            if q > 0 and key not in parts:
+                raise FileNotFoundError(f"read_batches: '{fname}<q>.txt' exists for q = {q} but not for q = 0")
+            if kind == "vec":
+                a = ReadVec(path)
+            elif kind in ("cube", "mat", "rows", "cube_head"):
+                a = ReadCube(path)
+            else:
+                f = ReadFieldCube(path)
+                if per is not None and f.shape[0] < per:
+                    raise ValueError(f"'{fname}<q>.txt' holds fewer draws than 'Nu<q>.txt'")
+                rows = range(f.shape[0] if per is None else per)
+                if kind == "fieldK":
+                    a = np.stack([np.stack([f[l, k] for k in range(f.shape[1])], axis=-1) for l in rows], axis=-1)
+                else:
+                    a = np.stack([f[l, 0] for l in rows], axis=-1)
+            if fname == "Nu":
+                per = a.shape[-1]
+                per_file.append(per)
+            if kind == "cube_head":
+                a = a[..., :per]
+            have = a.shape[0] if kind == "rows" else a.shape[-1]
+            if have != per:
+                raise ValueError(f"'{fname}{q}.txt' holds {have} draws, 'Nu{q}.txt' {per}")
+            if q > 0:
+                lead0 = parts[key][0].shape[1:] if kind == "rows" else parts[key][0].shape[:-1]
+                lead = a.shape[1:] if kind == "rows" else a.shape[:-1]
+                if lead != lead0:
+                    raise ValueError(f"files '{fname}<q>.txt' differ in size")
+            if drop_unassigned:
+                a = a[1:] if kind == "rows" else a[..., 1:]
+            parts.setdefault(key, []).append(a)
+    out = {}
+    for fname, key, kind, lvl in _BATCH_FILES:
+        if key in parts:
+            out[key] = np.asfortranarray(np.concatenate(parts[key], axis=0 if kind == "rows" else -1))
+    out["n_draws"] = int(sum(per_file)) - (len(per_file) if drop_unassigned else 0)
+    return out
+
+
+def open_batches(dirs, n_files, Y, time=None, basis_degree=None, boundary_knots=None, internal_knots=None, X=None, cov_adj=False,
+                 drop_unassigned=False, device=0, **cfg_kw):
+    """A Sampler whose chain slots hold saved chains: `dirs` is one directory of on-disk batches (read_batches) or a list of them,
+    one chain each.  K, n_eigen, P and the number of draws T are read off the files; the sampler is built over Y (and time with
+    the spline basis; the multivariate model where time is None) with tot_mcmc_iters = T and n_chains = len(dirs), X is set where
+    given, every chain is loaded into slots [0, T) and the "loglik" slots are filled by slot_loglik(store=True).  Every summary
+    that reads chain slots (diagnostics, align, cluster_mean_bands, curve_bands, similarity, loo, predict, ...) then works on the
+    saved draws.  cfg_kw: further fields of the configuration.  Files that disagree with each other, with Y or with the basis
+    are refused."""
+    from .sampler import MODEL_FUNCTIONAL, MODEL_MULTIVARIATE, Sampler, default_config
+    if isinstance(dirs, (str, bytes)) or hasattr(dirs, "__fspath__"):
+        dirs = [dirs]
+    dirs = list(dirs)
+    if not dirs:
+        raise ValueError("open_batches: 'dirs' is empty")
+    chains = [read_batches(d, n_files, X=X is not None, cov_adj=cov_adj, drop_unassigned=drop_unassigned) for d in dirs]
+    c0 = chains[0]
+    K, P, T = c0["nu"].shape
+    n, M = c0["chi"].shape[:2]
+    for d, c in zip(dirs[1:], chains[1:]):
+        for key in c0:
+            same = c[key] == c0[key] if key == "n_draws" else (key in c and c[key].shape == c0[key].shape)
+            if not same:
+                raise ValueError(f"open_batches: the files of '{d}' and of '{dirs[0]}' differ in '{key}'")
+    if c0["Z"].shape[:2] != (n, K) or c0["Phi"].shape[:3] != (K, P, M):
+        raise ValueError("open_batches: the files 'Nu', 'Chi', 'Z' and 'Phi' differ in size")
+    mv = time is None
+    n_y = np.shape(Y)[0] if mv else len(Y)
+    if n_y != n:
+        raise ValueError("The number of functions in 'Y' must be equal to the number of rows of the saved 'Z' draws")
+    if X is not None:
+        Xm = np.asarray(X, dtype=np.float64)
+        if Xm.ndim != 2 or Xm.shape[0] != n or Xm.shape[1] != c0["eta"].shape[1]:
+            raise ValueError("The number of columns in 'X' must be equal to the number of covariates in the model")
+    if mv:
+        if np.ndim(Y) != 2 or np.shape(Y)[1] != P:
+            raise ValueError("the saved draws do not match the number of columns of 'Y'")
+        cfg = default_config(model=MODEL_MULTIVARIATE, K=int(K), n_eigen=int(M), tot_mcmc_iters=int(T), **cfg_kw)
+        s = Sampler(cfg, Y, device=device, n_chains=len(dirs))
+    else:
+        if basis_degree is None or boundary_knots is None or internal_knots is None:
+            raise ValueError("open_batches: 'basis_degree', 'boundary_knots' and 'internal_knots' are needed with 'time'")
+        if P != len(internal_knots) + int(basis_degree) + 1:
+            raise ValueError("the saved draws do not match the basis ('basis_degree', 'internal_knots')")
+        cfg = default_config(model=MODEL_FUNCTIONAL, K=int(K), n_eigen=int(M), basis_degree=int(basis_degree), tot_mcmc_iters=int(T), **cfg_kw)
+        s = Sampler(cfg, Y, time, internal_knots, boundary_knots, device=device, n_chains=len(dirs))
+    try:
+        if X is not None:
+            s.set_covariates(X, covariance_adj=cov_adj)
+        for q, c in enumerate(chains):
+            s.load_chain({k: v for k, v in c.items() if k != "n_draws"}, chain=q)
+        s.slot_loglik(store=True)
+    except Exception:
+        s.close()
+        raise
+    return s
+
+
 # ---- set-up pieces of the high-dimensional functional model (BSplines.h:18-120) -----------------------------------
 def TensorBSpline(t, basis_degree, boundary_knots, internal_knots):
     """Tensor-product B-spline basis of the points t (n_pts x dim): n_pts x prod_l (len(internal_knots[l]) + degree[l] + 1)."""

@@ -5,7 +5,8 @@
 // covariance surfaces with their bands and their eigenvalues and eigenfunctions, the reference's rescale step per draw with the
 // summaries, mean functions and covariance surfaces under it, the contrasts of cluster mean functions and covariate effects
 // under either labelling and the prediction of held-out curves with
-// their fitted functions.  The PSIS-LOO family over the chain slots is capi_loo.hip's.
+// their fitted functions; and what is written into the slots from outside (bfmmm_set_chain) with the log-likelihood of such slots.
+// The PSIS-LOO family over the chain slots is capi_loo.hip's.
 // What an entry point is made of is capi_chain.hpp's (SlotCheck, CallBufs, for_chunks, `once`, Back), shared with that file.  What
 // several of the entry points here do is written once as well: SortWs for the rule that long rows sort in a workspace, and
 // RowReducer for a chunk of rows of C S pooled values: its layout in one allocation, its reduction (moments or the seven
@@ -489,6 +490,79 @@ extern "C" int bfmmm_get_slot(bfmmm_handle* h, const char* name, int slot, doubl
   HIPCHK(hipMemcpy2DAsync(out, sizeof(double), a.p + (size_t)a.ss * slot, sizeof(double) * (size_t)a.ps, sizeof(double), (size_t)a.len,
                           hipMemcpyDeviceToHost, h->st));
   HIPCHK(hipStreamSynchronize(h->st));
+  return 0;
+}
+
+// ---- chains from outside and their log-likelihood (kernels_slot_ll.hip) ----------------------------------------
+// The mirror of bfmmm_get_chain: n_slots draws of `name`, in the layout that call returns for n_slots slots, into slots
+// [first_slot, first_slot + n_slots) of the selected chain.  Nothing else is touched.
+extern "C" int bfmmm_set_chain(bfmmm_handle* h, const char* name, int first_slot, int n_slots, const double* values, int64_t count) {
+  const std::string fn = "bfmmm_set_chain";
+  if (!h) return fail(fn + ": 'h' is null");
+  if (!name) return fail(fn + ": 'name' is null");
+  if (!values) return fail(fn + ": 'values' is null");
+  const std::string s(name);
+  const ChainArr a = chain_array(selc(h), h->T, s);
+  if (!a.p) return fail(fn + ": unknown name '" + s + "'");
+  if (first_slot < 0 || first_slot >= h->T) return fail(fn + "(" + s + "): 'first_slot' out of range");
+  if (n_slots < 1 || n_slots > h->T - first_slot) return fail(fn + "(" + s + "): 'n_slots' out of range (first_slot + n_slots > T)");
+  if (count != a.len * n_slots)
+    return fail(fn + "(" + s + "): 'count' must be " + std::to_string(a.len * n_slots) + " (" + std::to_string(a.len) + " entries x " +
+                std::to_string(n_slots) + " slots), got " + std::to_string(count));
+  const bool by_slot = a.ps == 1;      // else slot fastest (tau): values[t + n_slots e]
+  const bool positive = s == "sigma_sq";
+  for (int64_t o = 0; o < count; ++o) {
+    const bool finite = std::isfinite(values[o]);
+    if (finite && !(positive && values[o] <= 0.0)) continue;
+    const int64_t t = by_slot ? o / a.len : o % n_slots, e = by_slot ? o % a.len : o / n_slots;
+    return fail(fn + "(" + s + "): value at slot " + std::to_string(first_slot + t) + ", entry " + std::to_string(e) +
+                (finite ? " is not positive" : " is not finite"));
+  }
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->st));
+  double* dst = const_cast<double*>(a.p);
+  if (by_slot) HIPCHK(copy_sync(h, dst + (size_t)a.ss * first_slot, values, sizeof(double) * (size_t)count, hipMemcpyHostToDevice));
+  else      // one run of n_slots slots per entry
+    for (int64_t e = 0; e < a.len; ++e)
+      HIPCHK(copy_sync(h, dst + (size_t)a.ps * e + (size_t)a.ss * first_slot, values + (size_t)n_slots * e, sizeof(double) * (size_t)n_slots,
+                       hipMemcpyHostToDevice));
+  HIPCHK(hipStreamSynchronize(h->st));
+  return 0;
+}
+
+// loglik(q, t) of every chain and slot of the range from the records and the slots, in chunks of consecutive curves: k_slot_rss fills
+// the chunk's rows, k_slot_ll_reduce adds them in curve order to the call's accumulator, and the last chunk's reduction applies
+// k_loglik's closed form (and stores where asked).  curve: the rows as l_i, chunk by chunk.
+extern "C" int bfmmm_chain_slot_loglik(bfmmm_handle* h, int first_slot, int n_slots, int store, int64_t max_workspace_bytes, double* loglik,
+                                       double* curve, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_slot_loglik", h, first_slot, n_slots};
+  if (ck.ptrs({{"h", h}, {"loglik", loglik}}) || ck.range() || ck.budget_sign(max_workspace_bytes)) return 1;
+  const int n = h->c.d.n;
+  const size_t N = (size_t)ck.CS();
+  if (ck.capacity(capacity, curve ? (int64_t)n * (int64_t)N : (int64_t)N)) return 1;
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), sizeof(double) * N, sizeof(double) * N, n, kNoCap, "curve", &chunk)) return 1;
+  HIPCHK(hipSetDevice(h->device));
+  reset_timers(h, PT_SLOT_LL, PT_SLOT_LL_REDUCE);
+  CallBufs b;
+  double *d_acc = nullptr, *d_part = nullptr;
+  Timer kernel, reduce;
+  HIPCHK(b.timers({&kernel, &reduce}));
+  HIPCHK(b.get(&d_acc, N));
+  HIPCHK(b.get(&d_part, (size_t)chunk * N));
+  const int rc = for_chunks(ck, n, chunk, [&](int64_t i0, int rows) {
+    std::string err = timed(kernel, h->st, [&] { return launch_slot_rss(h->c, first_slot, n_slots, (int)i0, rows, d_part, h->st); });
+    if (err.empty())
+      err = timed(reduce, h->st, [&] { return launch_slot_ll_reduce(h->c, first_slot, n_slots, (int)i0, rows, curve != nullptr, store != 0, d_part, d_acc, h->st); });
+    if (err.empty()) err = Back{h, i0, rows}(curve, (const double*)d_part, N).done();
+    if (err.empty() && hipGetLastError() != hipSuccess) err = "kernel failed";
+    if (!err.empty()) return err;
+    collect(h, kernel, PT_SLOT_LL);
+    collect(h, reduce, PT_SLOT_LL_REDUCE);
+    return err;
+  });
+  if (rc) return rc;
+  HIPCHK(copy_sync(h, loglik, d_acc, sizeof(double) * N, hipMemcpyDeviceToHost));
   return 0;
 }
 

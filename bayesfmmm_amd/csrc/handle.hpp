@@ -39,13 +39,13 @@ enum { FAM_TOTAL = 0, FAM_Z, FAM_PG, FAM_FACTOR, FAM_SWEEP, FAM_CHI, FAM_LOGLIK,
 // bfmmm_chain_loo_blocks launches on the sampler's stream (the dense basis rows once, k_loo_blocks and, where the variance trace is
 // asked for, k_loo_pointwise_var per chunk), PT_LOO_BLOCKS_PSIS: its PSIS pass, one per chunk; PT_CONTRAST_COEF: k_contrast_coef (one
 // launch a call), PT_CONTRAST_VALUES: k_contrast_values, one launch per chunk and sweep over the chunks, PT_CONTRAST_NORM:
-// k_contrast_norm, one launch per chunk.
+// k_contrast_norm, one launch per chunk; PT_SLOT_LL: k_slot_rss, PT_SLOT_LL_REDUCE: k_slot_ll_reduce, one launch each per chunk.
 enum { PT_CURVE_LL = 0, PT_FIT_PROJECT, PT_FIT_ROWS, PT_FIT_VALUES, PT_FIT_REDUCE, PT_SIM, PT_SIM_REDUCE, PT_SIMILARITY,
        PT_COV_PROJECT, PT_COV, PT_SIM_LOSS, PT_SIM_LOSS_REDUCE, PT_ALIGN_GRAM, PT_ALIGN_GATHER, PT_ALIGN_PROJECT,
        PT_CCOV_PROJECT, PT_CCOV, PT_CCOV_MAXDEV, PT_CEIG_GRAM, PT_CEIG, PT_CEIG_VALUES, PT_PREDICT_STATS, PT_PREDICT, PT_PREDICT_FIT,
        PT_LOO_MARGINAL, PT_LOO_MARGINAL_PSIS, PT_PREDICT_LAPLACE, PT_LOO_MARGINAL_LAPLACE, PT_LOO_POINTWISE, PT_LOO_POINTWISE_PSIS,
        PT_RESCALE_TRANSFORM, PT_RESCALE_GATHER, PT_RESCALE_PROJECT, PT_LOO_BLOCKS, PT_LOO_BLOCKS_PSIS, PT_CONTRAST_COEF,
-       PT_CONTRAST_VALUES, PT_CONTRAST_NORM, PT_COUNT };
+       PT_CONTRAST_VALUES, PT_CONTRAST_NORM, PT_SLOT_LL, PT_SLOT_LL_REDUCE, PT_COUNT };
 inline constexpr const char* kPostNames[PT_COUNT] = {"curve_ll_ms", "curve_fit_project", "curve_fit_rows", "curve_fit_values",
                                                      "curve_fit_reduce", "curve_sim", "curve_sim_reduce", "similarity",
                                                      "curve_cov_project", "curve_cov", "similarity_loss", "similarity_loss_reduce",
@@ -57,7 +57,8 @@ inline constexpr const char* kPostNames[PT_COUNT] = {"curve_ll_ms", "curve_fit_p
                                                      "loo_marginal_laplace", "loo_pointwise", "loo_pointwise_psis",
                                                      "rescale_transform", "rescale_gather", "rescale_project",
                                                      "loo_blocks", "loo_blocks_psis",
-                                                     "contrast_coef", "contrast_values", "contrast_norm"};
+                                                     "contrast_coef", "contrast_values", "contrast_norm",
+                                                     "slot_loglik", "slot_loglik_reduce"};
 
 struct bfmmm_handle {
   bfmmm_config cfg;

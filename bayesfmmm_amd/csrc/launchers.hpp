@@ -120,6 +120,16 @@ bool cov_block_fits(const Ctx& c);
 // out[(i - i0) C S + q S + (t - first_slot)] (device); "" or what the kernel cannot take
 std::string launch_chain_curve_ll(const Ctx& c, int first_slot, int n_slots, int i0, int rows, double* out, hipStream_t st);
 
+// ---- kernels_slot_ll.hip ----
+// Log-likelihood of the chain slots given the scores.  launch_slot_rss: rss_i of curves [i0, i0 + rows), every chain,
+// slots [first_slot, first_slot + n_slots) into part[(i - i0) C S + q S + (t - first_slot)] (device).  launch_slot_ll_reduce: those
+// rows added in curve order to acc[q S + t], which holds the sums of curves [0, i0); per_curve: the rows become l_i; the chunk that
+// ends at curve n leaves loglik(q, t) in acc and, with store, in the "loglik" slots of the range of every chain.  The chunks of a
+// call must come in ascending order.  "" or what the kernel cannot take.
+std::string launch_slot_rss(const Ctx& c, int first_slot, int n_slots, int i0, int rows, double* part, hipStream_t st);
+std::string launch_slot_ll_reduce(const Ctx& c, int first_slot, int n_slots, int i0, int rows, int per_curve, int store, double* part,
+                                  double* acc, hipStream_t st);
+
 // ---- kernels_loo_pointwise.hip ----
 // A row tile of bfmmm_chain_loo_pointwise: `rows` <= LP_ROWS consecutive observations of `curve`, the first of them at
 // y[y0] and at basis row b0 of the launch's B (the multivariate model reads neither), their values in rows out_row .. of the chunk's

@@ -703,6 +703,56 @@ class Sampler:
                 self.select_chain(prev)
         return out
 
+    def set_chain(self, name, values, first_slot=0, chain=None):
+        """Writes draws of `name` (a get_chain name) into chain slots [first_slot, first_slot + n_slots): the mirror of get_chain
+        (bfmmm_set_chain).  values: shaped as get_chain returns it, (..., n_slots) ("tau": (n_slots, K)).  chain: the
+        chain to write (default: the selected one); the selection is restored afterwards.  Nothing but those slots changes.
+        Returns the number of slots written."""
+        lead = self._draw_shape(name) if name in DRAW_DIMS else ()      # an unknown name: the library refuses it
+        a = np.asarray(values, dtype=np.float64)
+        if name == "tau":
+            if a.ndim != 2 or a.shape[1] != self.K:
+                raise ValueError(f"set_chain('tau'): values must be shaped (n_slots, {self.K}), got {a.shape}")
+            S = a.shape[0]
+        else:
+            if a.ndim != len(lead) + 1 or a.shape[:-1] != lead:
+                raise ValueError(f"set_chain('{name}'): values must be shaped {lead + ('n_slots',)}, got {a.shape}")
+            S = a.shape[-1]
+        a = np.asfortranarray(a)
+        prev = self.lib.bfmmm_selected_chain(self.h)
+        if chain is not None:
+            self.select_chain(chain)
+        try:
+            _lib.check(self.lib.bfmmm_set_chain(self.h, name.encode(), int(first_slot), int(S), _dp(a), a.size))
+        finally:
+            if chain is not None:
+                self.select_chain(prev)
+        return S
+
+    def load_chain(self, arrays, first_slot=0, chain=None):
+        """set_chain for every entry of the dict `arrays` (name -> array in get_chain's layout), which must agree on the number of
+        draws.  Returns the number of slots written."""
+        counts = {nm: (np.shape(v)[0] if nm == "tau" else np.shape(v)[-1]) for nm, v in arrays.items()}
+        if len(set(counts.values())) > 1:
+            raise ValueError(f"load_chain: the arrays disagree on the number of draws: {counts}")
+        S = 0
+        for nm, v in arrays.items():
+            S = self.set_chain(nm, v, first_slot=first_slot, chain=chain)
+        return S
+
+    def slot_loglik(self, first_slot=0, n_slots=None, store=False, per_curve=False, max_workspace_bytes=0):
+        """The log-likelihood given the scores of chain slots [first_slot, first_slot + n_slots) of every chain of the batch,
+        recomputed on the device from the resident per-curve statistics and the slots (bfmmm_chain_slot_loglik): what
+        a run stores in "loglik", for chains that were loaded with set_chain, and a check of the stored array otherwise.  store:
+        also write it into the "loglik" slots of the range.  Returns the (C, S) array, or with per_curve
+        {"loglik": (C, S), "curve": (n, C, S)}, curve the log-density of each curve given its scores."""
+        S = self._slots(first_slot, n_slots)
+        ll = np.zeros((self.n_chains, max(S, 0)))
+        cv = np.zeros((self.n, self.n_chains, max(S, 0))) if per_curve else None
+        _lib.check(self.lib.bfmmm_chain_slot_loglik(self.h, int(first_slot), S, int(bool(store)), int(max_workspace_bytes), _dp(ll),
+                                                    _dp(cv) if per_curve else None, cv.size if per_curve else ll.size))
+        return {"loglik": ll, "curve": cv} if per_curve else ll
+
     def representative_draw(self, names=("Z",), first_slot=0, n_slots=None, max_workspace_bytes=0):
         """The least-squares draw of the clustering (`similarity_loss` without its diagnostics) and the arrays `names` of that
         draw, all in the draw's own consistent labelling.  Returns {"chain", "slot", "loss"} plus one array per name."""

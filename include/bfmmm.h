@@ -292,6 +292,41 @@ int bfmmm_chain_similarity_loss(bfmmm_handle* h, int first_slot, int n_slots, in
  * others ("tau": its K entries); capacity >= the entries of one draw. */
 int bfmmm_get_slot(bfmmm_handle* h, const char* name, int slot, double* out, int64_t capacity);
 
+/* The mirror of bfmmm_get_chain: writes n_slots draws of `name` into chain slots [first_slot, first_slot + n_slots) of the selected
+ * chain (bfmmm_select_chain), so that draws that were made elsewhere -- an earlier run, the reference's on-disk batches, a chain on
+ * another device -- can be read by every chain-slot call.
+ *   values   n_slots draws in exactly the layout bfmmm_get_chain returns for n_slots slots: draw after draw, each as the reference
+ *            lays it out ("tau": n_slots x K column-major, slot fastest)
+ *   count    the entries of values: (entries of one draw) x n_slots, anything else is refused
+ * Every bfmmm_get_chain name is accepted, "loglik" included and, once bfmmm_set_covariates was called, the covariate blocks.
+ * Refused with a message: a null argument, an unknown name, a slot range outside [0, T), a wrong count, a value that is not finite
+ * (the message names its slot and entry) and a "sigma_sq" that is not positive.  There is no simplex check on "Z": rescaled
+ * memberships may leave it.  The call synchronises the sampler's stream before and after the copy and touches nothing else: the
+ * working state, the iteration counter, the slot base, the RNG keys and the other slots stay as they are, and a later bfmmm_run
+ * overwrites slots as it always did. */
+int bfmmm_set_chain(bfmmm_handle* h, const char* name, int first_slot, int n_slots, const double* values, int64_t count);
+
+/* The log-likelihood given the scores of chain slots [first_slot, first_slot + n_slots) of EVERY chain of the batch, from the
+ * resident per-curve records and the slots alone; nothing is uploaded.  With x_i the covariates (xi only where the
+ * sampler is covariance-adjusted)
+ *   theta_i = sum_k Z_ik (nu_k + eta_k x_i) + sum_m chi_im sum_k Z_ik (phi_km + xi_km x_i)
+ *   rss_i   = yy_i - 2 theta_i's_i + theta_i'G_i theta_i
+ *   l_i     = -n_i (0.5 log 2 pi + log sqrt(sigma^2)) - rss_i / (2 sigma^2)              (functional)
+ *   l_i     = -((P / 2) log(2 pi sigma^2)) - rss_i / (2 sigma^2), P / 2 an integer division (multivariate, as the reference has it)
+ * and loglik(q, t) = sum_i l_i, formed as the sweep forms what it stores in "loglik": from sum_i rss_i, added in curve order.
+ *   loglik[q n_slots + (t - first_slot)]                       capacity >= C n_slots entries (C chains)
+ *   curve (may be NULL)  l_i at [i C n_slots + q n_slots + (t - first_slot)], the layout of bfmmm_chain_curve_loglik;
+ *                        capacity >= n C n_slots entries where it is given
+ *   store != 0           the totals are also written into the "loglik" slots of the range of every chain, and nowhere else
+ * For a loaded chain (bfmmm_set_chain) it supplies the one array the reference's files do not carry; for a chain the sampler ran
+ * it is an independent check of the stored "loglik".  Chunks of consecutive curves keep what the call allocates within
+ * max_workspace_bytes (0: 256 MiB): 8 C n_slots bytes per curve and as much shared by all curves; a budget below one curve is
+ * refused with the bytes needed.  fp64, every sum in a fixed order, no atomics: the bits do not depend on the budget or on repeated
+ * calls.  Runs on the sampler's stream; without store it leaves state and slots untouched.  bfmmm_get_timing: "slot_loglik", the
+ * device time and launches (one per chunk) of k_slot_rss, and "slot_loglik_reduce", those of the kernel that adds a chunk's rows. */
+int bfmmm_chain_slot_loglik(bfmmm_handle* h, int first_slot, int n_slots, int store, int64_t max_workspace_bytes, double* loglik,
+                            double* curve, int64_t capacity);
+
 /* Pooled per-curve covariance surfaces under chain slots [first_slot, first_slot + n_slots) of EVERY chain of the batch, on the
  * rows of two evaluation bases E1 (G1 x P) and E2 (G2 x P), row-major in the sampler's basis.  With the scores
  * chi_im ~ N(0, 1), the covariance function of curve i under a draw is
@@ -820,7 +855,9 @@ int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capa
  * Of the last bfmmm_chain_cluster_contrast_bands (always measured): "contrast_coef" (k_contrast_coef, one launch a call),
  * "contrast_values" (k_contrast_values, one launch per chunk, and one more per chunk where the band takes a second sweep) and
  * "contrast_norm" (k_contrast_norm, one launch per chunk), next to "rescale_project"; the reductions, the counts and the band's
- * launches are not timed. */
+ * launches are not timed.
+ * Of the last bfmmm_chain_slot_loglik (always measured): "slot_loglik" (k_slot_rss) and "slot_loglik_reduce" (k_slot_ll_reduce), the
+ * device time and launches of each, one per chunk. */
 int bfmmm_set_profile(bfmmm_handle* h, int enable);
 int bfmmm_get_timing(bfmmm_handle* h, const char* name, double* ms, int64_t* launches);
 
