@@ -125,6 +125,8 @@ SYMBOLS = {
                                   [c_double_p] * 13 + [C.c_int64]),
     "bfmmm_chain_loo_blocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), c_int64_p, C.POINTER(C.c_int32), C.c_int64, C.c_int, C.c_int,
                                          C.c_int64] + [c_double_p] * 13 + [C.c_int64, C.c_int64]),
+    "bfmmm_chain_loo_by_chain": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int64] +
+                                 [c_double_p] * 6 + [C.c_int64]),
     "bfmmm_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, c_double_p, C.c_int64, c_int64_p]),
     "bfmmm_set_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "bfmmm_get_timing": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), c_int64_p]),

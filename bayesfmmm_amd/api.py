@@ -120,6 +120,9 @@ POST_SYMBOLS = {
     "bfmmm_post_psis": (C.c_int, [c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                   c_double_p, c_double_p]),
     "bfmmm_post_psis_expect": (C.c_int, [c_double_p, c_double_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [c_double_p] * 7),
+    "bfmmm_post_stacking": (C.c_int, [c_double_p, C.c_int64, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, C.c_double, c_double_p,
+                                      c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bfmmm_post_stacking_geometry": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "bfmmm_FLOO": (C.c_int, [C.POINTER(PostArgs), C.POINTER(C.c_void_p)]),
     "bfmmm_post_diagnostics": (C.c_int, [c_double_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p,
                                          c_double_p, c_double_p, c_double_p, c_double_p]),
@@ -1020,6 +1023,81 @@ def psis_expect(ll, h, device=0):
     pw = dict(zip(("lppd", "pointwise_elpd_loo", "pointwise_p_loo", "pareto_k", "pointwise_elpd_waic", "pointwise_p_waic"), outs))
     out = loo_totals(pw, S)
     out["expect"] = expect[0] if hm.ndim == 2 else expect
+    return out
+
+
+# ---- stacking of predictive distributions (include/bfmmm_post.h) ------------------------------------------
+def stacking_geometry():
+    """(threads, max_workgroups) of the stacking iteration: one grid-stride pass covers threads * max_workgroups units"""
+    t, g = C.c_int32(0), C.c_int32(0)
+    _lib_entry().bfmmm_post_stacking_geometry(C.byref(t), C.byref(g))
+    return t.value, g.value
+
+
+def stacking(lpd, init=None, max_iter=10000, check_every=16, tol=1e-8, device=0):
+    """Stacking weights (Yao et al. 2018) of the Q candidates -- models, or chains (Yao et al. 2022) -- whose leave-one-out log
+    predictive densities are the columns of the (n, Q) matrix `lpd`: the simplex weights that maximise the LOO log score of the
+    mixture, sum_i log sum_q w_q exp(lpd[i, q]), by the EM fixed point on the device (bfmmm_post_stacking).  -inf is
+    allowed; NaN, +inf and a unit that is -inf under every candidate are refused.  The loop stops at the first iterate, at a
+    multiple of check_every, whose certificate "gap" is at most tol: the stacked elpd is then within n * gap nats of the optimum.
+    tol=0 runs max_iter iterations.  `init`: Q positive weights that add to 1 (None: uniform).
+    Returns "weights": (Q,), "pointwise": (n,) the stacked log density of every unit, "elpd" and "se_elpd": its total and standard
+    error, "objective" (the total, as the device adds it), "gap", "n_iter" and "converged"."""
+    lib = _lib_entry()
+    m = np.asarray(lpd, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError("'lpd' must be an n x Q matrix, units by candidates")
+    n, Q = m.shape
+    cm = np.ascontiguousarray(m.T)                      # candidate-major
+    w0 = None
+    if init is not None:
+        w0 = np.ascontiguousarray(init, dtype=np.float64).reshape(-1)
+        if w0.size != Q:
+            raise ValueError(f"'init' must have {Q} entries, one per candidate")
+    weights, pointwise = np.zeros(Q), np.zeros(n)
+    obj, gap = C.c_double(0.0), C.c_double(0.0)
+    n_iter, conv = C.c_int(0), C.c_int(0)
+    _check(lib.bfmmm_post_stacking(cm.ctypes.data_as(c_double_p), n, Q, device, None if w0 is None else w0.ctypes.data_as(c_double_p),
+                                   int(max_iter), int(check_every), float(tol), weights.ctypes.data_as(c_double_p),
+                                   pointwise.ctypes.data_as(c_double_p), C.byref(obj), C.byref(gap), C.byref(n_iter), C.byref(conv)))
+    elpd, se = _total_se(pointwise)
+    return dict(weights=weights, pointwise=pointwise, elpd=elpd, se_elpd=se, objective=obj.value, gap=gap.value,
+                n_iter=n_iter.value, converged=bool(conv.value))
+
+
+def compare_table(L):
+    """the comparison of the Q columns of the (n, Q) pointwise elpd matrix L, host arithmetic in unit order: "elpd" and "se" (Q,),
+    "best" (the largest elpd, the first of equals), "elpd_diff" and "se_diff" against it from the paired differences over units,
+    sqrt(n var_{n-1}(L[:, q] - L[:, best])) (0 and 0 for the best), and "pseudo_bma", the softmax of the totals"""
+    n, Q = L.shape
+    tot = [_total_se(L[:, q]) for q in range(Q)]
+    elpd = np.array([t[0] for t in tot])
+    best = int(np.argmax(elpd))
+    diff = [(0.0, 0.0) if q == best else _total_se(L[:, q] - L[:, best]) for q in range(Q)]
+    e = np.exp(elpd - elpd[best])
+    return dict(elpd=elpd, se=np.array([t[1] for t in tot]), best=best, elpd_diff=np.array([d[0] for d in diff]),
+                se_diff=np.array([d[1] for d in diff]), pseudo_bma=e / e.sum())
+
+
+def stack_models(results, names=None, **kw):
+    """Compares and stacks Q fits of the same data.  `results`: one entry per fit, the dict of loo_pointwise, loo_blocks, loo,
+    loo_marginal or psis_loo (its "pointwise_elpd_loo" is read) or a plain (n,) array of log predictive densities, such as the "lpd"
+    of `predict` over the folds of a K-fold split; all of one length.  Returns the dict of `stacking` (keywords go to it) and the
+    compare table: "elpd", "se", "elpd_diff", "se_diff", "pseudo_bma": (Q,), "best" and "names" (default "model0", ...).  "elpd" is
+    the candidates' here; the stacked total is "objective", its standard error "se_elpd".  Prefer "weights" to "pseudo_bma" and to
+    picking "best" (Yao et al. 2018)."""
+    cols = [np.asarray(r["pointwise_elpd_loo"] if isinstance(r, dict) else r, dtype=np.float64).reshape(-1) for r in results]
+    if not cols:
+        raise ValueError("stack_models: 'results' is empty")
+    if any(c.size != cols[0].size for c in cols):
+        raise ValueError(f"stack_models: the entries of 'results' must cover the same units, got lengths {[c.size for c in cols]}")
+    names = [f"model{q}" for q in range(len(cols))] if names is None else list(names)
+    if len(names) != len(cols):
+        raise ValueError(f"stack_models: 'names' must have {len(cols)} entries")
+    L = np.stack(cols, axis=1)
+    out = stacking(L, **kw)
+    out.update(compare_table(L))
+    out["names"] = names
     return out
 
 

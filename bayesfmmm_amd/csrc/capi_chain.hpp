@@ -37,9 +37,10 @@ struct SlotCheck {
     if (n_slots < 1 || n_slots > h->T - first_slot) return fail(fn + ": 'n_slots' out of range (first_slot + n_slots > T)");
     return 0;
   }
-  int row_limit() const {
-    if (CS() <= diag_row_max()) return 0;
-    return fail(fn + ": at most 4194304 (2^22) draws per row (n_chains x n_slots) in this build, got " + std::to_string(CS()));
+  int row_limit() const { return row_limit(CS(), "n_chains x n_slots"); }
+  int row_limit(long long draws, const char* what) const {      // a call whose rows are not the pooled n_chains x n_slots draws
+    if (draws <= diag_row_max()) return 0;
+    return fail(fn + ": at most 4194304 (2^22) draws per row (" + what + ") in this build, got " + std::to_string(draws));
   }
   int budget_sign(int64_t bytes) const { return bytes < 0 ? fail(fn + ": 'max_workspace_bytes' must not be negative") : 0; }
   // The budget rule: a workspace of `shared` bytes for the whole call and `per_unit` for every unit (noun: "curve", "block", "row")

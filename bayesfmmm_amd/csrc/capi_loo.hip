@@ -1,10 +1,12 @@
 // C ABI of the sampler (include/bfmmm.h), the PSIS-LOO family over the chain slots: over curves (bfmmm_chain_loo),
 // over curves with the memberships integrated out (bfmmm_chain_loo_marginal, 7o) and the same under the Laplace mixture proposal
-// (bfmmm_chain_loo_marginal_laplace, 7p), over observations with the LOO-PIT (bfmmm_chain_loo_pointwise, 7q) and over blocks of
-// observations within curves (bfmmm_chain_loo_blocks, 7s).  The entry points are built as capi_chain.hip's, from capi_chain.hpp.
+// (bfmmm_chain_loo_marginal_laplace, 7p), over observations with the LOO-PIT (bfmmm_chain_loo_pointwise, 7q), over blocks of
+// observations within curves (bfmmm_chain_loo_blocks, 7s) and chain by chain over curves or observations
+// (bfmmm_chain_loo_by_chain, 7v).  The entry points are built as capi_chain.hip's, from capi_chain.hpp.
 // What several of them do is written once here: psis_step for the PSIS pass of a chunk with its handshake between the two streams,
-// kPsisNames for the six arrays it fills, DenseBasis for the dense basis rows of the two row calls and row_chunk_end for what they
-// finish on the host.  The two marginal calls share psis_step alone: their checks interleave and their chunk bodies are short.
+// kPsisNames for the six arrays it fills, DenseBasis for the dense basis rows of the two row calls, row_chunk_end for what they
+// finish on the host, pointwise_tiles and pointwise_chunk for the tile plan and the launch of the observation-level calls.  The two
+// marginal calls share psis_step alone: their checks interleave and their chunk bodies are short.
 #include "capi_chain.hpp"
 
 namespace {
@@ -107,6 +109,44 @@ std::string row_chunk_end(bfmmm_handle* h, const std::vector<double>& hexp, int6
   if (err.empty() && hipGetLastError() != hipSuccess) err = kBackFailed;
   if (err.empty()) collect(h, vark, pt);
   return err;
+}
+
+// The row tiles of bfmmm_chain_loo_pointwise for the m selected curves (curves null: curve j is j), in the order of the result:
+// up to LP_ROWS consecutive observations of a curve each.  Answers the rows of the result.
+int64_t pointwise_tiles(const DenseBasis& basis, const int32_t* curves, int64_t m, std::vector<LpTile>& tiles) {
+  int64_t total = 0;
+  for (int64_t j = 0; j < m; ++j) {
+    const int i = curves ? curves[j] : (int)j;
+    for (int r0 = 0; r0 < basis.ni[i]; r0 += LP_ROWS) {
+      const int rows = std::min(LP_ROWS, basis.ni[i] - r0);
+      tiles.push_back({i, rows, basis.off[i] + r0, basis.off[i] + r0, total});
+      total += rows;
+    }
+  }
+  return total;
+}
+
+// Tiles [p0, p0 + cnt) of that list as a chunk: their rows counted from the chunk's first, *base of the result, into ht and to the
+// device with their basis rows, then k_loo_pointwise on the chunk's *rows rows between the events of kern.  "" or what failed.
+std::string pointwise_chunk(const SlotCheck& ck, DenseBasis& basis, const std::vector<LpTile>& tiles, int64_t p0, int cnt, std::vector<LpTile>& ht,
+                            LpTile* d_tiles, const Timer& kern, double* d_x, size_t stride, int64_t* base, int* rows) {
+  bfmmm_handle* h = ck.h;
+  *base = tiles[(size_t)p0].out_row;
+  int64_t rows64 = 0;
+  for (int q = 0; q < cnt; ++q) {
+    LpTile t = tiles[(size_t)p0 + q];
+    t.out_row -= *base;
+    basis.stage(t.b0, t.rows, t.out_row);
+    if (basis.from_basis) t.b0 = t.out_row;
+    ht[(size_t)q] = t;
+    rows64 = t.out_row + t.rows;
+  }
+  *rows = (int)rows64;
+  if (copy_sync(h, d_tiles, ht.data(), sizeof(LpTile) * (size_t)cnt, hipMemcpyHostToDevice) != hipSuccess || !basis.upload(*rows))
+    return std::string(kBackFailed);
+  return timed(kern, h->st, [&] {
+    return launch_loo_pointwise(h->c, d_tiles, cnt, basis.d_B, h->d_y, ck.first_slot, ck.n_slots, d_x, stride, h->st);
+  });
 }
 
 }  // namespace
@@ -375,15 +415,7 @@ extern "C" int bfmmm_chain_loo_pointwise(bfmmm_handle* h, const int32_t* curves,
   DenseBasis basis(h);
   if (basis.counts()) return 1;
   std::vector<LpTile> tiles;
-  int64_t total = 0;
-  for (int64_t j = 0; j < m; ++j) {
-    const int i = curves ? curves[j] : (int)j;
-    for (int r0 = 0; r0 < basis.ni[i]; r0 += LP_ROWS) {
-      const int rows = std::min(LP_ROWS, basis.ni[i] - r0);
-      tiles.push_back({i, rows, basis.off[i] + r0, basis.off[i] + r0, total});
-      total += rows;
-    }
-  }
+  const int64_t total = pointwise_tiles(basis, curves, m, tiles);
   if (ck.capacity(capacity, total, "rows")) return 1;
   if (tiles.empty()) return 0;
   const size_t N = (size_t)ck.CS();
@@ -404,22 +436,9 @@ extern "C" int bfmmm_chain_loo_pointwise(bfmmm_handle* h, const int32_t* curves,
   std::vector<LpTile> ht((size_t)chunk);
   std::vector<double> hexp;
   return for_chunks(ck, (int64_t)tiles.size(), chunk, [&](int64_t p0, int cnt) {
-    const int64_t base = tiles[(size_t)p0].out_row;
-    int64_t rows64 = 0;
-    for (int q = 0; q < cnt; ++q) {
-      LpTile t = tiles[(size_t)p0 + q];
-      t.out_row -= base;
-      basis.stage(t.b0, t.rows, t.out_row);
-      if (basis.from_basis) t.b0 = t.out_row;
-      ht[(size_t)q] = t;
-      rows64 = t.out_row + t.rows;
-    }
-    const int rows = (int)rows64;
-    if (copy_sync(h, d_tiles, ht.data(), sizeof(LpTile) * (size_t)cnt, hipMemcpyHostToDevice) != hipSuccess || !basis.upload(rows))
-      return std::string(kBackFailed);
-    std::string err = timed(kern, h->st, [&] {
-      return launch_loo_pointwise(c, d_tiles, cnt, basis.d_B, h->d_y, first_slot, n_slots, d_x, stride, h->st);
-    });
+    int64_t base = 0;
+    int rows = 0;
+    std::string err = pointwise_chunk(ck, basis, tiles, p0, cnt, ht, d_tiles, kern, d_x, stride, &base, &rows);
     if (err.empty())
       err = Back{h, base, rows}(loglik_trace, (const double*)d_x, N)(pit_trace, (const double*)(d_x + stride), N)(
                 mean_trace, (const double*)(d_x + 2 * stride), N).done();
@@ -430,6 +449,82 @@ extern "C" int bfmmm_chain_loo_pointwise(bfmmm_handle* h, const int32_t* curves,
     err = psis_step(h, d_x, N, rows, res, base, &psis, PT_LOO_POINTWISE_PSIS, d_x + stride, 3, stride, hexp.data());
     if (!err.empty()) return err;
     return row_chunk_end(h, hexp, base, rows, pit, mean, sd, d_x, stride, N, var_trace, vark, PT_LOO_POINTWISE);
+  });
+}
+
+// ---- PSIS-LOO chain by chain ----------------------------------------------------------------------------------------
+// A row of bfmmm_chain_loo's and of bfmmm_chain_loo_pointwise's chunk matrix holds its C S draws chain-major: the matrix is also
+// rows x C rows of S = n_slots draws, and the same psis_step takes it as that.  unit 0 is bfmmm_chain_loo's chunk loop, unit 1
+// bfmmm_chain_loo_pointwise's (its tile plan, pointwise_chunk and so k_loo_pointwise as they are; of the four matrices it fills only
+// the log-density goes through PSIS, without auxiliaries).  Entry r C + c of the six arrays: chain c of row r.
+extern "C" int bfmmm_chain_loo_by_chain(bfmmm_handle* h, int unit, const int32_t* curves, int n_curves, int first_slot, int n_slots,
+                                        int64_t max_workspace_bytes, double* lppd, double* elpd_loo, double* p_loo, double* pareto_k,
+                                        double* elpd_waic, double* p_waic, int64_t capacity) {
+  const SlotCheck ck{"bfmmm_chain_loo_by_chain", h, first_slot, n_slots};
+  const std::string& fn = ck.fn;
+  double* const res[6] = {lppd, elpd_loo, p_loo, pareto_k, elpd_waic, p_waic};
+  if (ck.ptrs({{"h", h}}) || psis_ptrs(ck, res)) return 1;
+  if (unit != 0 && unit != 1) return fail(fn + ": 'unit' must be 0 (curve) or 1 (observation), got " + std::to_string(unit));
+  if (unit == 0 && curves) return fail(fn + ": 'curves' must be null with 'unit' 0: the curves are not selected there");
+  if (curves && n_curves < 1) return fail(fn + ": 'n_curves' must be at least 1 where 'curves' is given");
+  int64_t m = 0;
+  if (ck.curve_list(curves, n_curves, &m) || ck.range() || ck.budget_sign(max_workspace_bytes) || ck.row_limit(n_slots, "n_slots")) return 1;
+  const int64_t C = h->nch;
+  const size_t N = (size_t)ck.CS(), S = (size_t)n_slots;
+  const int64_t row_cap = (int64_t)2147483647 / C;      // rows x C is the PSIS pass's count of rows, an int
+  if (unit == 0) {
+    const int64_t len = h->c.d.n;
+    if (ck.capacity(capacity, len * C)) return 1;
+    int64_t chunk = 0;
+    if (ck.units(budget_of(max_workspace_bytes), 0, sizeof(double) * N, len, row_cap, nullptr, &chunk)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    reset_timers(h, PT_CURVE_LL, PT_CURVE_LL);
+    CallBufs b;
+    double* d_x = nullptr;
+    HIPCHK(b.get(&d_x, N * (size_t)chunk));
+    return for_chunks(ck, len, chunk, [&](int64_t p0, int rows) {
+      std::string err = curve_ll_timed(ck, (int)p0, rows, d_x);
+      if (err.empty() && (hipStreamSynchronize(h->st) != hipSuccess || hipGetLastError() != hipSuccess)) err = "kernel failed";
+      if (!err.empty()) return err;
+      curve_ll_collect(h);
+      return psis_step(h, d_x, S, rows * (int)C, res, p0 * C);
+    });
+  }
+  const std::string bad = loo_pointwise_check(h->c);
+  if (!bad.empty()) return fail(fn + ": " + bad);
+  HIPCHK(hipSetDevice(h->device));
+  DenseBasis basis(h);
+  if (basis.counts()) return 1;
+  std::vector<LpTile> tiles;
+  const int64_t total = pointwise_tiles(basis, curves, m, tiles);
+  if (ck.capacity(capacity, total * C)) return 1;
+  if (tiles.empty()) return 0;
+  // a tile: its rows of the four matrices, the six results a (row, chain), its entry of the list and what DenseBasis takes
+  const size_t per_tile = sizeof(double) * (size_t)LP_ROWS * (4 * N + 6 * (size_t)C) + basis.tile_bytes() + sizeof(LpTile);
+  int64_t chunk = 0;
+  if (ck.units(budget_of(max_workspace_bytes), basis.shared_bytes(), per_tile, (int64_t)tiles.size(),
+               std::min<int64_t>((int64_t)1 << 24, std::max<int64_t>(1, row_cap / LP_ROWS)), "tile", &chunk))
+    return 1;
+  reset_timers(h, PT_LOO_POINTWISE, PT_LOO_POINTWISE_PSIS);
+  CallBufs b;
+  double* d_x = nullptr;
+  LpTile* d_tiles = nullptr;
+  Timer kern, psis;
+  HIPCHK(b.timers({&kern, &psis}));
+  const size_t stride = (size_t)chunk * LP_ROWS * N;
+  HIPCHK(b.get(&d_x, 4 * stride));
+  HIPCHK(b.get(&d_tiles, (size_t)chunk));
+  if (basis.prepare(ck, b, chunk, PT_LOO_POINTWISE)) return 1;
+  std::vector<LpTile> ht((size_t)chunk);
+  return for_chunks(ck, (int64_t)tiles.size(), chunk, [&](int64_t p0, int cnt) {
+    int64_t base = 0;
+    int rows = 0;
+    std::string err = pointwise_chunk(ck, basis, tiles, p0, cnt, ht, d_tiles, kern, d_x, stride, &base, &rows);
+    // post_psis_device runs on the device's default stream: the matrix must be complete before it starts
+    if (err.empty() && (hipStreamSynchronize(h->st) != hipSuccess || hipGetLastError() != hipSuccess)) err = kBackFailed;
+    if (!err.empty()) return err;
+    collect(h, kern, PT_LOO_POINTWISE);
+    return psis_step(h, d_x, S, rows * (int)C, res, base * C, &psis, PT_LOO_POINTWISE_PSIS);
   });
 }
 

@@ -18,6 +18,14 @@ int post_psis_device(const double* d_ll, long long ld, int n, int S, double* con
 int post_psis_expect_device(const double* d_ll, long long ld, int n, int S, const double* d_aux, int n_aux, long long aux_stride,
                             double* const out[6], double* expect_host);
 
+// ---- kernels_stacking.hip ----
+// Stacking weights of the Q x n log densities at d_L (candidate-major; overwritten) on the current device: the
+// results of bfmmm_post_stacking to the host.  init: Q host weights on the simplex, or null.  The geometry: one grid-stride pass of
+// k_stack_em covers threads x max_workgroups units.
+int post_stacking_device(double* d_L, long long n, int Q, const double* init, int max_iter, int check_every, double tol, double* weights,
+                         double* pointwise, double* objective, double* gap, int* n_iter, int* converged);
+void post_stacking_geometry(int* threads, int* max_workgroups);
+
 namespace bfmmm {
 
 // ---- kernels_stats.hip ----

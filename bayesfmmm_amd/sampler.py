@@ -267,6 +267,7 @@ class Sampler:
         chain the state / chain accessors address."""
         self.lib = _lib.load()
         self.cfg = cfg
+        self.device = int(device)
         self.h = C.c_void_p()
         if basis is not None:
             self.offsets = np.zeros(len(Y) + 1, dtype=np.int64)
@@ -559,6 +560,53 @@ class Sampler:
         out.update(pit=outs[6], mean=outs[7], sd=outs[8], offsets=offsets,
                    curve_elpd_loo=np.array([outs[1][offsets[j]:offsets[j + 1]].sum() for j in range(m)]))
         out.update(tr)
+        return out
+
+    def loo_by_chain(self, unit="observation", curves=None, first_slot=0, n_slots=None, max_workspace_bytes=0):
+        """PSIS-LOO and WAIC of every chain of the batch by itself (bfmmm_chain_loo_by_chain): the six pointwise arrays
+        of `loo` (unit "curve"; `curves` must be None) or of `loo_pointwise` (unit "observation", with its "offsets"), each of shape
+        (rows, C), column c from PSIS on the n_slots draws of chain c alone -- api.psis_loo of that chain's log-density matrix, bit
+        for bit.  "elpd_loo" and "se_elpd_loo": (C,), per chain; "khat_threshold" for S = n_slots draws and "n_khat_above": (C,).  A
+        chain has 1 / C of the pooled draws, so its k-hat is worse than the pooled one: read "n_khat_above" first."""
+        from . import api
+        units = {"curve": 0, "observation": 1}
+        if unit not in units:
+            raise ValueError(f"loo_by_chain: 'unit' must be one of {sorted(units)}")
+        if unit == "curve" and curves is not None:
+            raise ValueError("loo_by_chain: 'curves' goes with unit \"observation\"")
+        S = self._slots(first_slot, n_slots)
+        idx, pc, m = self._curve_list(curves)
+        out = {}
+        rows = self.n
+        if unit == "observation":
+            sel = np.arange(self.n) if idx is None else idx
+            if sel.size and (sel.min() < 0 or sel.max() >= self.n):
+                raise ValueError(f"loo_by_chain: 'curves' must lie in 0 .. {self.n - 1}")
+            offsets = np.zeros(m + 1, dtype=np.int64)
+            offsets[1:] = np.cumsum(self._obs_counts()[sel])
+            rows = int(offsets[-1])
+            out["offsets"] = offsets
+        Cn = self.n_chains
+        outs = [np.zeros((rows, Cn)) for _ in range(6)]
+        _lib.check(self.lib.bfmmm_chain_loo_by_chain(self.h, units[unit], pc, m if curves is not None else 0, int(first_slot), S,
+                                                     int(max_workspace_bytes), *[_dp(o) for o in outs], rows * Cn))
+        out.update(zip(_PW_NAMES, outs))
+        tot = [api._total_se(outs[1][:, c]) for c in range(Cn)]
+        with np.errstate(divide="ignore"):
+            thr = float(min(1.0 - 1.0 / np.log10(float(S)), 0.7))
+        out.update(elpd_loo=np.array([t[0] for t in tot]), se_elpd_loo=np.array([t[1] for t in tot]), khat_threshold=thr,
+                   n_khat_above=np.sum(outs[3] > thr, axis=0).astype(np.int64))
+        return out
+
+    def chain_stacking(self, unit="observation", curves=None, first_slot=0, n_slots=None, max_workspace_bytes=0, **kw):
+        """Stacking weights of the chains of the batch (Yao et al. 2022): `loo_by_chain`, then api.stacking (keywords go
+        to it) on its "pointwise_elpd_loo" with the chains as candidates.  Returns the dict of api.stacking -- "weights": (C,); a
+        weight near zero says that the chain sits in a mode that predicts worse -- and "by_chain", the dict of `loo_by_chain`.  A
+        diagnostic: the pooled summaries of this class weight the chains equally."""
+        from . import api
+        by = self.loo_by_chain(unit=unit, curves=curves, first_slot=first_slot, n_slots=n_slots, max_workspace_bytes=max_workspace_bytes)
+        out = api.stacking(by["pointwise_elpd_loo"], device=self.device, **kw)
+        out["by_chain"] = by
         return out
 
     def loo_blocks(self, blocks=None, block_size=None, horizon=None, curves=None, first_slot=0, n_slots=None, trace=False,

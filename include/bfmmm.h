@@ -690,6 +690,19 @@ int bfmmm_chain_loo_pointwise(bfmmm_handle* h, const int32_t* curves, int n_curv
                               double* elpd_waic, double* p_waic, double* pit, double* mean, double* sd, double* loglik_trace,
                               double* pit_trace, double* mean_trace, double* var_trace, int64_t capacity);
 
+/* PSIS-LOO and WAIC separately for every chain of the batch: the six arrays of bfmmm_chain_loo with PSIS run on the
+ * n_slots draws of each chain by itself, relative efficiency 1.  unit 0: the rows are the curves, as bfmmm_chain_loo's (all n;
+ * `curves` must be null); unit 1: the observations of the selected curves, as bfmmm_chain_loo_pointwise's, in its order, without
+ * its pit, mean, sd and traces.  A row of those calls holds its n_chains x n_slots draws chain-major, so the same device matrix is
+ * n_chains rows of n_slots draws per unit and goes through the same PSIS pass: entry r n_chains + c of every array is what
+ * bfmmm_post_psis gives for chain c's draws of row r, bit for bit.  `capacity` entries each, at least rows x n_chains.  The chunks
+ * and max_workspace_bytes are those of the pooled call; the results do not depend on them.  The timers are the pooled calls':
+ * "curve_ll_ms" (unit 0), "loo_pointwise" and "loo_pointwise_psis" (unit 1).  Refused by name: a null pointer, a unit other than
+ * 0 or 1, `curves` with unit 0, the curve list, the slot range, the capacity, the budget sign, more than 2^22 draws a chain. */
+int bfmmm_chain_loo_by_chain(bfmmm_handle* h, int unit, const int32_t* curves, int n_curves, int first_slot, int n_slots,
+                             int64_t max_workspace_bytes, double* lppd, double* elpd_loo, double* p_loo, double* pareto_k,
+                             double* elpd_waic, double* p_waic, int64_t capacity);
+
 /* Leave-block-out PSIS cross-validation within curves from the chain slots: every listed block of observations of a
  * training curve is left out in turn, the rest of its curve kept, Z_i at the draw's value and the scores chi_i integrated out.  Block k
  * is the observations block_obs[block_offsets[k] .. block_offsets[k + 1]) of curve block_curve[k], given as indices within the curve

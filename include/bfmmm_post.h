@@ -70,6 +70,20 @@ int bfmmm_post_psis(const double* ll, int32_t n, int32_t S, int32_t device, doub
  * the weights of row i's elpd_loo, the terms in the order of that sum.  The six arrays are bfmmm_post_psis's bit for bit. */
 int bfmmm_post_psis_expect(const double* ll, const double* h, int32_t n, int32_t S, int32_t n_aux, int32_t device, double* lppd,
                            double* elpd_loo, double* p_loo, double* pareto_k, double* elpd_waic, double* p_waic, double* expect);
+/* Stacking of predictive distributions (Yao et al. 2018, 2022): the simplex weights that maximise
+ * f(w) = sum_i log sum_q w_q exp(lpd[q n + i]) for n units and 1 <= Q <= 64 candidates (models, or chains), lpd their leave-one-out
+ * log predictive densities on the host, candidate-major.  -inf is an entry like any other (density 0); a NaN, a +inf or a unit that
+ * is -inf for every candidate is refused with the first such (unit, candidate) and their number.  The EM fixed point
+ * w_q <- w_q g_q / n, g_q = sum_i P_iq / d_i, d_i = sum_q w_q P_iq, P_iq = exp(lpd_iq - max_q lpd_iq), from `init` (Q weights on
+ * the simplex, every one positive; NULL: uniform), one launch an iteration.  gap(w) = max_q g_q(w) / n - 1 bounds the distance
+ * to the optimum: f(w*) - f(w) <= n gap(w).  The call returns the first iterate w_t, t a multiple of check_every or t = max_iter,
+ * with gap(w_t) <= tol, or w_max_iter: weights (Q), pointwise[i] = log sum_q w_q exp(lpd_iq) (n), *objective = f(w_t), *gap,
+ * *n_iter = t and *converged = (gap <= tol).  check_every decides where the loop may stop, never the iterates; tol = 0 runs
+ * max_iter iterations.  Every sum has an order that depends on (n, Q) alone and there are no floating-point atomics: two calls
+ * give the same bits.  bfmmm_post_stacking_geometry: one grid-stride pass of the iteration covers threads x max_workgroups units. */
+int bfmmm_post_stacking(const double* lpd, int64_t n, int Q, int device, const double* init, int max_iter, int check_every, double tol,
+                        double* weights, double* pointwise, double* objective, double* gap, int* n_iter, int* converged);
+void bfmmm_post_stacking_geometry(int32_t* threads, int32_t* max_workgroups);
 /* Convergence diagnostics of every row of a host draws array: x[s + n_draws (c + n_chains p)] (draw fastest, then chain,
  * then parameter: R's draws_array order), p < n_param.  Split R-hat (rank-normalised, the max of bulk and folded), bulk and
  * tail ESS, ESS and MCSE of the mean, mean and sd over all draws (Vehtari et al. 2021): seven arrays of
