@@ -1,8 +1,11 @@
-// What the two files of chain-slot entry points share (capi_chain.hip, what is read off the chain slots after a run, and
-// capi_loo.hip, the PSIS-LOO family over them): an entry point is its argument checks (SlotCheck: slots, curve selection, the grid
-// pair, x, alpha, probs and `units`, the one budget rule), its workspace and the event pairs that time its launches into the
-// handle's PT_* timers (CallBufs owns both) and one for_chunks.  What several of them do is written once: `once` for a launch that
-// runs once per call (the projections), Back for a chunk's copies to the host.
+// What the three files of chain-slot entry points share (capi_chain.hip, what is read off the chain slots after a run,
+// capi_cluster.hip, the cluster-level calls under aligned or rescaled labels, and capi_loo.hip, the PSIS-LOO family): an entry
+// point is its argument checks (SlotCheck: slots, curve selection, the grid pair, x, perm, alpha, probs and `units`, the one budget
+// rule), its workspace and the event pairs that time its launches into the handle's PT_* timers (CallBufs owns both) and one
+// for_chunks.  What several of them do is written once: `once` for a launch that runs once per call (the projections), Back for a
+// chunk's copies to the host, chain_array for the layout of a chain array, SortWs for the rule that long rows sort in a workspace,
+// RowReducer for a chunk of rows of C S pooled values (its layout in one allocation, its reduction and its copies back) and
+// RowCall for a call that is such rows and nothing else.
 #pragma once
 #include "handle.hpp"
 #include "launchers.hpp"
@@ -76,10 +79,33 @@ struct SlotCheck {
   }
   // a covariate setting x (null: none) of D finite entries, for covariance-adjusted samplers only
   int covariate_setting(const double* x) const {
-    const int D = h->c.d.D;
-    if (x && !(h->c.covariance_adj && D > 0)) return fail(fn + ": 'x' is given but the sampler is not covariance-adjusted");
-    for (int d = 0; x && d < D; ++d)
+    if (x && !(h->c.covariance_adj && h->c.d.D > 0)) return fail(fn + ": 'x' is given but the sampler is not covariance-adjusted");
+    return x_finite(x);
+  }
+  int x_finite(const double* x) const {
+    for (int d = 0; x && d < h->c.d.D; ++d)
       if (!std::isfinite(x[d])) return fail(fn + ": 'x'[" + std::to_string(d) + "] is not finite");
+    return 0;
+  }
+  // an argument `what` (null: not given) that only a sampler with covariates takes, at most 8 of them
+  int covariates(const char* what, const void* given) const {
+    if (!given) return 0;
+    if (!(h->c.d.D > 0 && h->c.c_eta)) return fail(fn + ": '" + what + "' is given but the sampler has no covariates");
+    return h->c.d.D > 8 ? fail(fn + ": more than 8 covariates") : 0;
+  }
+  // every row perm[(q S + s) K + .] a permutation of 0 .. K - 1, or fail() naming the first draw that is not
+  int perm_check(const int32_t* perm) const {
+    const int K = h->c.d.K, S = n_slots;
+    for (long long o = 0; o < CS(); ++o) {
+      unsigned seen = 0;
+      for (int l = 0; l < K; ++l) {
+        const int32_t v = perm[o * K + l];
+        if (v < 0 || v >= K || (seen >> v & 1u))
+          return fail(fn + ": 'perm' of chain " + std::to_string(o / S) + ", slot " + std::to_string(first_slot + o % S) +
+                      " is not a permutation of 0 .. " + std::to_string(K - 1));
+        seen |= 1u << v;
+      }
+    }
     return 0;
   }
   int alpha_inside(double alpha) const { return alpha > 0.0 && alpha < 1.0 ? 0 : fail(fn + ": 'alpha' must be inside (0, 1)"); }
@@ -202,6 +228,136 @@ struct Back {
   }
   std::string done() const { return ok && hipStreamSynchronize(h->st) == hipSuccess ? "" : kBackFailed; }
   std::string queued() const { return ok ? "" : kBackFailed; }      // more copies of the chunk follow: their done() synchronises
+};
+
+// ---- the chain arrays ---------------------------------------------------------------------------------------------------
+// Element e of slot t of array `name` is p[t ss + e ps] in the chain of context c, and q * c.chain_bytes (cov: chain_bytes_cov)
+// bytes further in the q-th chain after it.  p null: no array of that name (covariate arrays exist once covariates were set).
+struct ChainArr { const char* nm; const double* p; int64_t len; bool cov; int64_t ss, ps; };
+ChainArr chain_array(const Ctx& c, int T, const std::string& name) {
+  const Dims& d = c.d;
+  const int64_t n = d.n, K = d.K, P = d.P, M = d.M, D = d.D;
+  const ChainArr arrs[] = {{"nu", c.c_nu, K * P}, {"chi", c.c_chi, n * M}, {"Z", c.c_Z, n * K}, {"pi", c.c_pi, K},
+                           {"alpha_3", c.c_alpha3, 1}, {"delta", c.c_delta, K * M}, {"A", c.c_A, K * 2},
+                           {"sigma_sq", c.c_sigma, 1}, {"gamma", c.c_gamma, K * P * M}, {"Phi", c.c_Phi, K * P * M},
+                           {"loglik", c.c_loglik, 1},
+                           {"eta", c.c_eta, P * D * K, true}, {"xi", c.c_xi, K * P * D * M, true}, {"tau_eta", c.c_tau_eta, K * D, true},
+                           {"gamma_xi", c.c_gamma_xi, K * P * D * M, true}, {"delta_xi", c.c_delta_xi, K * M * D, true},
+                           {"A_xi", c.c_A_xi, K * 2 * D, true},
+                           {"tau", c.c_tau, K, false, 1, T}};      // tau: T_alloc x K column-major (slot fastest)
+  for (ChainArr a : arrs)
+    if (name == a.nm && a.p) {
+      if (!a.ps) { a.ss = a.len; a.ps = 1; }      // the others: slot by slot
+      return a;
+    }
+  return {};
+}
+
+// 16 doubles on the device (owned by b) with the call's nq probabilities in front, and `extra` more behind them
+hipError_t probs_put(CallBufs& b, bfmmm_handle* h, const double* probs, int nq, double** d_probs, int extra = 0) {
+  const hipError_t e = b.get(d_probs, 16 + (size_t)extra);
+  return e != hipSuccess || !nq ? e : copy_sync(h, *d_probs, probs, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice);
+}
+
+// ---- rows of N = C S pooled values (kernels_bands.hip, kernels_diag.hip) ---------------------------------------------------------
+// Where quantiles are wanted, rows of up to fit_lds_rows() draws sort in LDS and longer ones in a workspace of NP doubles a row
+// (k_bands_quantiles_big); `also`: the caller sorts such rows by a threshold of its own.
+struct SortWs {
+  bool on;
+  size_t NP;
+  SortWs(long long N, bool wanted, bool also = false)
+      : on((wanted && N > fit_lds_rows()) || also), NP(on ? (size_t)bands_sort_pad((int)N) : 0) {}
+};
+
+// A chunk of rows of N values in one allocation, their reduction and the copies back.  Two flavours: mean and sd
+// (launch_bands_moments; a row takes N + 2 + nq + NP doubles) or the seven statistics (diag_launch; N + tier + 7 + nq + NP), then
+// the nq quantiles (launch_bands_quantiles) where nq > 0.  The sub-buffers hold `chunk` rows each, in the order of the members.
+struct RowReducer {
+  bfmmm_handle* h;
+  int C, S, nq;
+  bool seven;
+  size_t N, tier;
+  SortWs ws;
+  const double* probs = nullptr;      // the nq probabilities on the device
+  double *x = nullptr, *mean = nullptr, *sd = nullptr, *out7 = nullptr, *tws = nullptr, *q = nullptr, *w = nullptr;
+  std::vector<double> hb;             // the seven statistics of a chunk, statistic by statistic
+
+  RowReducer(const SlotCheck& ck, int nq, bool seven, bool also_sort = false)
+      : h(ck.h), C(ck.h->nch), S(ck.n_slots), nq(nq), seven(seven), N((size_t)ck.CS()), tier(seven ? diag_row_ws_doubles(C, S) : 0),
+        ws(ck.CS(), nq > 0, also_sort) {}
+  size_t res_doubles() const { return (seven ? tier + 7 : 2) + (size_t)nq + ws.NP; }      // of a row, without its values
+  size_t row_bytes() const { return sizeof(double) * (N + res_doubles()); }
+  // the sub-buffers of `chunk` rows: the values at vals, the rest from res on
+  void place(double* vals, double* res, int64_t chunk) {
+    const size_t n = (size_t)chunk;
+    x = vals;
+    if (seven) { out7 = res; tws = out7 + 7 * n; q = tws + tier * n; }
+    else { mean = res; sd = mean + n; q = sd + n; }
+    w = q + (size_t)nq * n;
+  }
+  hipError_t alloc(CallBufs& b, int64_t chunk) {
+    double* p = nullptr;
+    const hipError_t e = b.get(&p, row_bytes() / sizeof(double) * (size_t)chunk);
+    if (e == hipSuccess) place(p, p + (size_t)chunk * N, chunk);
+    return e;
+  }
+  std::string reduce(long long rows) const {
+    std::string err = seven ? diag_launch(x, rows, C, S, out7, rows, tws, rows, h->st) : launch_bands_moments(x, (int)N, rows, mean, sd, h->st);
+    if (err.empty() && nq) err = launch_bands_quantiles(x, (int)N, rows, w, probs, nq, q, h->st);
+    return err;
+  }
+  // rows [r0, r0 + rows) of the results to the host: quant and trace where asked for, then outs: mean and sd, or the seven statistics
+  std::string to_host(int64_t r0, int rows, double* const* outs, double* quant, double* trace) {
+    Back back{h, r0, rows};
+    back(nq ? quant : nullptr, q, (size_t)nq)(trace, x, N);
+    if (!seven) return back(outs[0], mean, 1)(outs[1], sd, 1).done();
+    hb.resize(7 * (size_t)rows);
+    const std::string err = Back{h, 0, 1, back.ok}(hb.data(), out7, 7 * (size_t)rows).done();
+    for (int s = 0; err.empty() && s < 7; ++s) std::copy(hb.begin() + (size_t)s * rows, hb.begin() + (size_t)(s + 1) * rows, outs[s] + r0);
+    return err;
+  }
+};
+
+// A call that is `len` rows and their reduction (split R-hat, ESS and MCSE of the chain arrays and of the per-curve log-density,
+// DESIGN.md 7c; the cluster summaries, mean functions and eigenfunctions of capi_cluster.hip), in two steps, since what a call puts
+// on the device comes after the refusal of its budget.  plan(): the budget rule (`shared` bytes for the whole call, a row of the
+// reducer for every row of a chunk, at most `cap` rows; SlotCheck::units), the device, the chunk's workspace and the probabilities.
+// run(): per chunk, fill(r0, rows, d_x) puts rows [r0, r0 + rows) into the workspace (row-major: draw fastest, then chain), the
+// reducer reduces them and outs (mean and sd, or the seven statistics), quant and trace go to the host (null: not asked for).
+// pt >= 0: timer pt of the handle starts from zero, fill runs between a pair of events and the timer collects their device time
+// chunk by chunk.
+struct RowCall {
+  const SlotCheck& ck;
+  int64_t len;
+  RowReducer r;
+  CallBufs b;      // owns the workspace; what the caller's kernels read goes here too
+  int64_t chunk = 0;
+  int pt;
+
+  RowCall(const SlotCheck& ck, int64_t len, int nq, bool seven, int pt) : ck(ck), len(len), r(ck, nq, seven), pt(pt) {}
+  int plan(int64_t max_workspace_bytes, size_t shared, int64_t cap, const char* noun, const double* probs) {
+    if (ck.units(budget_of(max_workspace_bytes), shared, len > 0 ? r.row_bytes() : 0, len, cap, noun, &chunk)) return 1;
+    HIPCHK(hipSetDevice(ck.h->device));
+    if (pt >= 0) reset_timers(ck.h, pt, pt);
+    if (len > 0) HIPCHK(r.alloc(b, chunk));
+    double* d_probs = nullptr;
+    if (r.nq) HIPCHK(probs_put(b, ck.h, probs, r.nq, &d_probs));
+    r.probs = d_probs;
+    return 0;
+  }
+  template <typename Fill>
+  int run(double* const* outs, double* quant, double* trace, Fill fill) {
+    bfmmm_handle* h = ck.h;
+    Timer t;
+    if (pt >= 0) HIPCHK(b.timers({&t}));
+    return for_chunks(ck, len, chunk, [&](int64_t r0, int rows) {
+      std::string err = pt >= 0 ? timed(t, h->st, [&] { return fill(r0, rows, r.x); }) : fill(r0, rows, r.x);
+      if (err.empty()) err = r.reduce(rows);
+      if (err.empty()) err = r.to_host(r0, rows, outs, quant, trace);
+      if (err.empty() && pt >= 0) collect(h, t, pt);
+      return err;
+    });
+  }
 };
 
 }  // namespace

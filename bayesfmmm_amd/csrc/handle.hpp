@@ -1,4 +1,4 @@
-// What the host files share (bfmmm_capi.hip, the driver, and capi_chain.hip with capi_loo.hip, the chain-slot post-processing): the handle,
+// What the host files share (bfmmm_capi.hip, the driver, and capi_chain.hip, capi_cluster.hip and capi_loo.hip, the chain-slot post-processing): the handle,
 // the kernel-family ids of its timing tables, the HIP error check and three helpers the driver defines.
 #pragma once
 #include "../../include/bfmmm.h"
@@ -22,7 +22,7 @@
 
 enum { FAM_TOTAL = 0, FAM_Z, FAM_PG, FAM_FACTOR, FAM_SWEEP, FAM_CHI, FAM_LOGLIK, FAM_REDUCE, FAM_COUNT };
 
-// The timers of the chain-slot calls (capi_chain.hip, capi_loo.hip), from HIP events around their launches, and their public names: PT_CURVE_LL
+// The timers of the chain-slot calls (capi_chain.hip, capi_cluster.hip, capi_loo.hip), from HIP events around their launches, and their public names: PT_CURVE_LL
 // is read by bfmmm_debug_get, the others by bfmmm_get_timing ("curve_fit": the sum of the four PT_FIT_*).  PT_SIM: k_fit_sim and
 // k_fit_sim_band, PT_SIM_REDUCE: the long-row sort; PT_COV_PROJECT counts the tables filled (1 or 2), not its launches;
 // PT_SIM_LOSS: k_similarity_loss, PT_SIM_LOSS_REDUCE: k_similarity_loss_reduce, one launch each per chunk; PT_ALIGN_GRAM:

@@ -1,12 +1,17 @@
-"""Rows above 8192 draws through the host code of the cluster summaries (capi_chain.hip): Sampler.cluster_cov_bands and
-Sampler.cluster_eigen on the 2 chains x 4100 slots of tests/test_gpu_align.py::test_rows_longer_than_8192_draws, N = 8200 draws
-per row, where the quantiles sort in a workspace (k_bands_quantiles_big), the band's deviations do too, and with several chunks
-the second sweep runs and crit is read off in pieces.  The reductions are held to the returned traces by the helpers of
-tests/test_gpu_cluster_cov.py and tests/test_gpu_cluster_eig.py with their bounds; chunked calls equal the one-chunk call byte for
-byte and launch as often as their chunks say."""
+"""Rows above 8192 draws through the host code of the cluster summaries (capi_cluster.hip): Sampler.cluster_cov_bands,
+Sampler.cluster_contrast_bands and Sampler.cluster_eigen on the 2 chains x 4100 slots of
+tests/test_gpu_align.py::test_rows_longer_than_8192_draws, N = 8200 draws per row, where the quantiles sort in a workspace
+(k_bands_quantiles_big), the band's deviations do too, and with several chunks the second sweep runs and crit is read off in pieces.
+The reductions are held to the returned traces by the helpers of tests/test_gpu_cluster_cov.py and tests/test_gpu_cluster_eig.py
+with their bounds, the band of the contrasts to tests/cluster_cov_ref.py's rule on the returned trace; chunked calls equal the
+one-chunk call byte for byte and launch as often as their chunks say."""
+import re
+
 import numpy as np
 import pytest
 
+import cluster_cov_ref as CCR
+import test_gpu_cluster_contrast as CT
 import test_gpu_cluster_cov as CC
 import test_gpu_cluster_eig as CE
 
@@ -45,6 +50,29 @@ def test_cluster_cov_bands(long_rows):
         got = smp.cluster_cov_bands(E, perm, max_workspace_bytes=shared + rows * per_row + 7, **kw)
         CC._same(got, one, CC.ALL)
         assert smp.timing("cluster_cov")[1] == 2 * nchunks and smp.timing("cluster_cov_maxdev")[1] == nchunks
+
+
+def test_cluster_contrast_bands(long_rows):
+    """the band of the contrasts on long rows: dev's rows sort in the workspace, and with several chunks the second sweep runs"""
+    smp, perm, E = long_rows["smp"], long_rows["perm"], long_rows["E"]
+    lists = [[(1, 0), (-1, 1)], [(1, 0)], [(1, 1)]]
+    kw = dict(perm=perm, probs=(0.05, 0.5, 0.95), simultaneous=0.1, trace=True)
+    one = smp.cluster_contrast_bands(E, lists, **kw)                  # 3 contrasts x 3 = 9 rows in one chunk
+    assert one["trace"].shape == (3, P, N) and one["norm_trace"].shape == (3, NCH, T)
+    assert smp.timing("contrast_values")[1] == 1 and smp.timing("contrast_norm")[1] == 1
+    s = CCR.sim_bands(one["trace"], 0.1, one["mean"], one["sd"])
+    for k in ("crit", "lower", "upper"):
+        assert one[k].tobytes() == np.ascontiguousarray(s[k]).tobytes(), k
+    with pytest.raises(Exception) as ei:
+        smp.cluster_contrast_bands(E, lists, max_workspace_bytes=1, **kw)
+    m = re.search(r"\((\d+) shared by all rows \+ (\d+) per row\)", str(ei.value))
+    assert m and "bfmmm_chain_cluster_contrast_bands: 'max_workspace_bytes' below the" in str(ei.value), str(ei.value)
+    shared, per_row = int(m.group(1)), int(m.group(2))
+    # 4 rows a chunk: crit's 3 rows in one piece; 2 rows a chunk: in two
+    for rows, nchunks in ((4, 3), (2, 5)):
+        got = smp.cluster_contrast_bands(E, lists, max_workspace_bytes=shared + rows * per_row + 7, **kw)
+        CT._same(got, one, CT.KEYS + CT.BAND + ("trace", "norm_trace"))
+        assert smp.timing("contrast_values")[1] == 2 * nchunks and smp.timing("contrast_norm")[1] == nchunks
 
 
 def test_cluster_eigen(long_rows):
