@@ -1189,6 +1189,14 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
     *count = 1;
     return 0;
   }
+  if (s == "ni") {            // the record builder's per-curve observation counts (an int array: widened on the host)
+    if (capacity < d.n) return fail("bfmmm_debug_get(" + s + "): buffer too small");
+    std::vector<int> hni((size_t)d.n);
+    HIPCHK(copy_sync(h, hni.data(), c.ni, sizeof(int) * hni.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < d.n; ++i) out[i] = (double)hni[i];
+    *count = d.n;
+    return 0;
+  }
   if (s == kPostNames[PT_CURVE_LL]) {
     if (capacity < 1) return fail("bfmmm_debug_get: buffer too small");
     out[0] = h->post_ms[PT_CURVE_LL];

@@ -39,9 +39,12 @@ __device__ inline int eval_basis(double xv, const double* __restrict__ knots, in
       const double right = knots[j + q + 1] - xv;
       const double left = xv - knots[j + 1 - d + q];
       const double denom = right + left;
-      const double temp = (denom != 0.0) ? N[q] / denom : 0.0;
-      N[q] = saved + right * temp;
-      saved = left * temp;
+      const double nq = N[q];
+      const double temp = (denom != 0.0) ? nq / denom : 0.0;
+      // where one difference is 0 the other's weight is denom / denom = 1: N[q] is handed on as it is (x (1 / x) can be
+      // 1 - 2^-53), so that B(b0)[0] = B(b1)[P - 1] = 1.0 bit for bit; 0 / 0 = 0 stays
+      N[q] = (left == 0.0 && right != 0.0) ? saved + nq : saved + right * temp;
+      saved = (right == 0.0 && left != 0.0) ? nq : left * temp;
     }
     N[d] = saved;
   }

@@ -813,6 +813,8 @@ int bfmmm_chain_predict_fit(bfmmm_handle* h, const double* y, const double* t, c
  *   variates of gamma (index (k P + p) M + m), delta (k M + i) and tau (k), the A proposals and uniforms (2 j + i), the sigma^2
  *   variate, four log(tgamma) / log terms per A cell -- and, while bfmmm_set_curve_record is on, the acceptance values of the last
  *   pi and alpha_3 steps in the two doubles behind;
+ * "ni" (n): the record builder's per-curve observation counts (an int array on the device, widened to double on the host;
+ *   multivariate model: P each);
  * "piprep" (9 KMAX + 16): the pi / alpha_3 tables k_factor prepared for the next iteration (scalar_jobs.hpp: pi_alpha_layout);
  * "pi_prepared" (1): whether the last pi / alpha_3 job took prepared tables (bfmmm_set_curve_record; fails when the last run's mask
  *   had neither U_PI nor U_ALPHA3, or recording was off);
