@@ -52,6 +52,7 @@ SYMBOLS = {
                                           c_double_p, C.c_int, C.POINTER(C.c_void_p)]),
     "bfmmm_tempered_transition": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint32,
                                             c_double_p, C.POINTER(C.c_int)]),
+    "bfmmm_debug_run_tt": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, C.c_double, C.c_uint32]),
     "bfmmm_get_chain": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, c_double_p, C.c_int64]),
     "bfmmm_chain_diagnostics": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int64, c_double_p, c_double_p, c_double_p,
                                           c_double_p, c_double_p, c_double_p, c_double_p, C.c_int64]),

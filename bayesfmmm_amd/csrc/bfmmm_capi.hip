@@ -1018,6 +1018,20 @@ extern "C" int bfmmm_prepare_run(bfmmm_handle* h, uint32_t mask, int first_iter,
   return run_impl(h, mask, first_iter, n_iters, seed, chain, phi_chi_zero, 1.0, 0, true);
 }
 
+// One sweep of a tempered-transition block: an ordinary iteration of the kernels in `mask` (and the log-likelihood) at temperature
+// beta with the RNG counter word tt_step, writing chain slot `iter`.  n_iters = 1 and tt_step != 0: the unfused route.
+static int run_tt_sweep(bfmmm_handle* h, uint32_t mask, int iter, uint64_t seed, uint32_t chain, double beta, uint32_t tt_step) {
+  return run_impl(h, mask | U_LOGLIK, iter, 1, seed, chain, 0, beta, tt_step);
+}
+
+// For the tests: the call the loop of bfmmm_tempered_transition makes for sweep l = tt_step, on its own.
+extern "C" int bfmmm_debug_run_tt(bfmmm_handle* h, uint32_t mask, int iter, uint64_t seed, uint32_t chain, double beta,
+                                  uint32_t tt_step) {
+  if (!h) return fail("bfmmm_debug_run_tt: null handle");
+  if (tt_step > 0xFFFFu) return fail("bfmmm_debug_run_tt: tt_step does not fit the counter word");
+  return run_tt_sweep(h, mask, iter, seed, chain, beta, tt_step);
+}
+
 // Tempered-transition block of BFMMM_MTT_warm_start (BFMMM.h:1556-1657) for chain iteration `iter`, whose regular
 // updates have already run (the sampler's working state is slot `iter`).  The 2 N_t tempered sweeps are ordinary
 // iterations of the same kernels with beta from the ladder and the RNG counter word tt_step = l; they write chain
@@ -1062,11 +1076,12 @@ extern "C" int bfmmm_tempered_transition(bfmmm_handle* h, uint32_t mask, int ite
   const double geom_mult = std::pow(beta_N_t, 1.0 / N_t);
   for (int i = 1; i < N_t; ++i) ladder[i] = ladder[i - 1] * geom_mult;
   const int L = 2 * N_t + 1;
-  std::vector<double> sig((size_t)L), rss((size_t)L);
+  std::vector<double> sig((size_t)L), rss((size_t)L), betas((size_t)(L - 1));
   sig[0] = dyn0.sigma2; rss[0] = dyn0.rss;
   int temp_ind = 0;
   for (int l = 1; l < L; ++l) {
-    if (run_impl(h, mask | U_LOGLIK, iter, 1, seed, chain, 0, ladder[temp_ind], (uint32_t)l)) return 1;
+    betas[l - 1] = ladder[temp_ind];
+    if (run_tt_sweep(h, mask, iter, seed, chain, ladder[temp_ind], (uint32_t)l)) return 1;
     Dyn dl;
     if (dyn_get(h, dl)) return 1;
     sig[l] = dl.sigma2; rss[l] = dl.rss;
@@ -1104,6 +1119,15 @@ extern "C" int bfmmm_tempered_transition(bfmmm_handle* h, uint32_t mask, int ite
   if (dyn_get(h, dn)) return 1;
   dn.iter = (uint32_t)(iter + 1); dn.slot = (uint32_t)(iter + 1 - h->slot_base); dn.tt_step = 0; dn.beta = 1.0;
   if (dyn_put(h, dn)) return 1;
+  {
+    std::vector<double>& tr = h->tt_trace;
+    tr.assign(1, (double)N_t);
+    tr.insert(tr.end(), ladder.begin(), ladder.end());
+    tr.insert(tr.end(), betas.begin(), betas.end());
+    tr.insert(tr.end(), sig.begin(), sig.end());
+    tr.insert(tr.end(), rss.begin(), rss.end());
+    tr.push_back(logu); tr.push_back(logA); tr.push_back((double)accepted);
+  }
   if (logA_out) *logA_out = logA;
   if (accepted_out) *accepted_out = accepted;
   return 0;
@@ -1156,6 +1180,14 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
     *count = cnt;
     return 0;
   }
+  if (s == "tt_trace") {      // host-side record of the last bfmmm_tempered_transition
+    const int64_t cnt = (int64_t)h->tt_trace.size();
+    if (cnt == 0) return fail("bfmmm_debug_get(" + s + "): no tempered-transition block has run on this handle");
+    if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
+    memcpy(out, h->tt_trace.data(), sizeof(double) * (size_t)cnt);
+    *count = cnt;
+    return 0;
+  }
   if (s == "hyper_route") {   // host-side record of the last bfmmm_run (run_impl)
     const int64_t cnt = sizeof h->last_hyper / sizeof h->last_hyper[0];
     if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
@@ -1187,6 +1219,18 @@ extern "C" int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, i
     if (dyn_get(h, dn)) return 1;
     out[0] = dn.rss;
     *count = 1;
+    return 0;
+  }
+  if (s == "dyn") {           // the scalars of Dyn a hand-over between runs depends on (include/bfmmm.h has the order)
+    Dyn dn;
+    if (dyn_get(h, dn)) return 1;
+    const double v[] = {(double)dn.iter, (double)dn.slot, (double)dn.tt_step, (double)dn.status, (double)dn.slot_base, dn.beta,
+                        (double)dn.zprep_valid, (double)dn.zprep_iter, (double)dn.zprep_tt, (double)dn.znorm_valid, (double)dn.znorm_iter,
+                        (double)dn.znorm_tt, (double)dn.piprep_valid, (double)dn.piprep_iter, dn.sigma2, dn.alpha3, dn.rss, dn.loglik};
+    const int64_t cnt = sizeof v / sizeof v[0];
+    if (capacity < cnt) return fail("bfmmm_debug_get: buffer too small");
+    memcpy(out, v, sizeof v);
+    *count = cnt;
     return 0;
   }
   if (s == "ni") {            // the record builder's per-curve observation counts (an int array: widened on the host)

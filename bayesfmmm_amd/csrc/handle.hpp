@@ -115,6 +115,9 @@ struct bfmmm_handle {
                                        // 1 stand-alone or lean update (its "prepared" flag holds), 2 fused update (always prepared)
   int slot_base = 0;                   // chain slot of iteration i is i - slot_base (bfmmm_set_slot_base)
   double* tt_save = nullptr;            // state saved across a tempered-transition block
+  // bfmmm_debug_get("tt_trace"): what the last bfmmm_tempered_transition computed on the host {N_t, ladder[0 .. N_t - 1], the beta of
+  // sweep l = 1 .. 2 N_t, sig[0 .. 2 N_t], rss[0 .. 2 N_t], log u, logA, accepted} (empty: no block yet)
+  std::vector<double> tt_trace;
   std::vector<double> B_host;           // bfmmm_create_from_basis: the caller's basis rows (bfmmm_get_basis)
   bool state_dirty = true;             // the state was changed from the host: proposals prepared on the device are stale
   int profile = 0;

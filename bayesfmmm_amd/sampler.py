@@ -402,6 +402,22 @@ class Sampler:
                                                       C.byref(la), C.byref(acc)))
         return la.value, bool(acc.value)
 
+    def run_tt(self, mask, iteration, beta, tt_step, seed=1, chain=0):
+        """For the tests: sweep `tt_step` of a tempered-transition block on its own (bfmmm_debug_run_tt), the call the block's loop
+        makes.  The debug reads and route words afterwards describe that sweep."""
+        _lib.check(self.lib.bfmmm_debug_run_tt(self.h, mask, int(iteration), seed, chain, float(beta), int(tt_step)))
+
+    def tt_trace(self):
+        """What the last `tempered_transition` computed on the host (bfmmm_debug_get "tt_trace"): {"N_t", "ladder": (N_t,), "betas":
+        (2 N_t,), the temperature of sweep l = 1 .. 2 N_t, "sig" and "rss": (2 N_t + 1,), sigma^2 and the RSS before the block and
+        after every sweep, "log_u", "logA", "accepted"}."""
+        v = self.debug("tt_trace", 1 << 16)
+        N = int(v[0])
+        assert v.size == 7 * N + 6, (N, v.size)
+        o = np.cumsum([1, N, 2 * N, 2 * N + 1, 2 * N + 1])
+        return dict(N_t=N, ladder=v[o[0]:o[1]], betas=v[o[1]:o[2]], sig=v[o[2]:o[3]], rss=v[o[3]:o[4]], log_u=float(v[o[4]]),
+                    logA=float(v[o[4] + 1]), accepted=bool(v[o[4] + 2]))
+
     def get_chain(self, name, n_slots=None):
         T = self.T if n_slots is None else n_slots
         shp = (T, self.K) if name == "tau" else self._draw_shape(name) + (T,)      # tau: slot fastest
@@ -1366,6 +1382,14 @@ class Sampler:
         d["YY"] = float(v[13])
         d["BWP"] = int(v[14])
         return d
+
+    DYN_NAMES = ("iter", "slot", "tt_step", "status", "slot_base", "beta", "zprep_valid", "zprep_iter", "zprep_tt", "znorm_valid",
+                 "znorm_iter", "znorm_tt", "piprep_valid", "piprep_iter", "sigma2", "alpha3", "rss", "loglik")
+
+    def dyn(self):
+        """The scalars of the selected chain's device state that a hand-over between runs depends on (bfmmm_debug_get "dyn")."""
+        v = self.debug("dyn", 32)
+        return {k: (float(x) if k in ("beta", "sigma2", "alpha3", "rss", "loglik") else int(x)) for k, x in zip(self.DYN_NAMES, v)}
 
     def sweep_route(self):
         """Which sweep kernel the last `run` launched (bfmmm_debug_get "sweep_route", recorded on the host)."""

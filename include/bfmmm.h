@@ -821,9 +821,20 @@ int bfmmm_chain_predict_fit(bfmmm_handle* h, const double* y, const double* t, c
  * "hyper_route" (3): where the scalar jobs of the last bfmmm_run rode, recorded on the host from the decisions the launchers read:
  *   {delta / A / gamma / tau: 0 k_curve_chi, 1 the lean k_curve_z (k_curve_chi in the closing iteration), 2 deferred to the next
  *   k_pair_gram and k_loglik_flush; pi / alpha_3: 0 k_pair_gram, 1 k_pair_gram with the deferred log-likelihood in a workgroup of its
- *   own, 2 k_factor; whether k_factor prepares the next iteration's pi / alpha_3 tables}.
+ *   own, 2 k_factor; whether k_factor prepares the next iteration's pi / alpha_3 tables};
+ * "tt_trace" (7 N_t + 6): what the last bfmmm_tempered_transition computed on the host, {N_t, ladder[0 .. N_t - 1], the beta of sweep
+ *   l = 1 .. 2 N_t, sigma^2 before the block and after every sweep (2 N_t + 1), RSS likewise (2 N_t + 1), log u, logA, accepted}
+ *   (fails before the first block);
+ * "dyn" (18): the scalars of the chain's device state a hand-over between runs depends on, {iter, slot, tt_step, status, slot_base,
+ *   beta, zprep_valid, zprep_iter, zprep_tt, znorm_valid, znorm_iter, znorm_tt, piprep_valid, piprep_iter, sigma^2, alpha_3, rss,
+ *   loglik} as doubles.
  * Returns the number of doubles written through *count. */
 int bfmmm_debug_get(bfmmm_handle* h, const char* name, double* out, int64_t capacity, int64_t* count);
+
+/* For the tests: sweep l = tt_step of a tempered-transition block on its own -- the call the loop of bfmmm_tempered_transition makes
+ * (one iteration of the updates in `mask` and the log-likelihood at temperature beta, RNG counter word tt_step, written to the chain
+ * slot of `iter`), through the same helper.  Every "last run" name of bfmmm_debug_get then describes that sweep. */
+int bfmmm_debug_run_tt(bfmmm_handle* h, uint32_t mask, int iter, uint64_t seed, uint32_t chain, double beta, uint32_t tt_step);
 
 /* Timing of the last bfmmm_run: milliseconds between HIP events recorded on the sampler's stream
  * around the whole run and, per kernel family, accumulated over iterations when `profile` was

@@ -233,6 +233,11 @@ double orc_CalculateTTAcceptance(const orc_data* d, int N_t, const double* beta,
 
 static double* dalloc0(size_t n) { return (double*)calloc(n ? n : 1, sizeof(double)); }
 
+/* Test hook (tests/tempered_ref.py): while a buffer of at least 2 L + 1 doubles is set, every tempered-transition block leaves
+ * {sigma^2 of its L = 2 N_t + 1 states, their residual sums of squares, log u} there (the last block's stay). */
+static struct { double* buf; int cap; } g_tt_trace;
+void orc_tt_trace_hook(double* buf, int cap) { g_tt_trace.buf = buf; g_tt_trace.cap = cap; }
+
 /* The tempered-transition block of iteration i, BFMMM.h:1556-1657.  On return slot i of `c` holds the accepted or
  * the original state and slot i+1 is re-initialised from it (every block but gamma, as in the reference).
  * Keyed RNG: (seed, chain, iteration i, tt_step l) for the tempered sweeps, (.., tt_step 0, UPD_TT_ACC) for the test. */
@@ -322,6 +327,10 @@ void orc_tt_block_cov(const orc_data* d, const orc_hyper* h, uint64_t seed, uint
   const double logA = orc_CalculateTTAcceptance(d, N_t, ladder, &tt);
   orc_rng r0 = {seed, chain, (uint32_t)i, 0};
   const double logu = log(orc_runif(&r0, UPD_TT_ACC, 0));
+  if (g_tt_trace.buf && g_tt_trace.cap >= 2 * L + 1) {
+    for (int l = 0; l < L; ++l) { g_tt_trace.buf[l] = tt.sigma[l]; g_tt_trace.buf[L + l] = orc_state_rss(d, l, &tt); }
+    g_tt_trace.buf[2 * L] = logu;
+  }
   int accepted = 0;
   if (logu < logA) {                         /* BFMMM.h:1641-1657 */
     const int f = L - 1;

@@ -71,6 +71,8 @@ double orc_rnorm_ms(const orc_rng* r, uint32_t upd, uint32_t idx, double mean, d
 void   orc_rnorm_hook(int arm, uint32_t upd, const double* inject, double* rec_mean_sd, int cap);
 void   orc_test_fill(uint64_t seed, uint32_t chain, uint32_t iter, uint32_t upd, int kind,
                      double p1, double p2, int count, double* out);
+void   orc_test_fill_tt(uint64_t seed, uint32_t chain, uint32_t iter, uint32_t tt_step, uint32_t upd, int kind,
+                        double p1, double p2, int count, double* out);
 
 /* ---- linalg.c ---- (column-major P x P) */
 int  orc_chol_lower(int P, const double* A, double* L);              /* 0 ok, 1 not SPD */
@@ -195,6 +197,8 @@ void orc_set_row_window(int on);
 void orc_beta_ladder(int N_t, double beta_N_t, double* ladder);
 double orc_calculatePZeta(const orc_data* d, double beta_i, int iter, const orc_chain* c);
 double orc_calculatePZetaCov(const orc_data* d, double beta_i, int iter, const orc_chain* c);   /* updates.c */
+double orc_state_rss(const orc_data* d, int iter, const orc_chain* c);                          /* updates.c, test hook */
+void   orc_tt_trace_hook(double* buf, int cap);                                                 /* test hook */
 double orc_CalculateTTAcceptance(const orc_data* d, int N_t, const double* beta, const orc_chain* tt);
 void orc_tt_block(const orc_data* d, const orc_hyper* h, uint64_t seed, uint32_t chain, int i, int N_t,
                   double beta_N_t, orc_chain* c, double* logA_out, int* accepted_out);

@@ -209,7 +209,13 @@ double orc_rtruncnorm(const orc_rng* r, uint32_t upd, uint32_t idx, double mu, d
  * kind 0 uniform, 1 normal, 2 gamma(p1=shape,p2=scale), 3 truncnorm(p1=mu,p2=sd, [0,inf)) */
 void orc_test_fill(uint64_t seed, uint32_t chain, uint32_t iter, uint32_t upd, int kind,
                    double p1, double p2, int count, double* out) {
-  orc_rng r = {seed, chain, iter, 0};
+  orc_test_fill_tt(seed, chain, iter, 0, upd, kind, p1, p2, count, out);
+}
+
+/* ... of sweep tt_step of a tempered-transition block (counter word 1: attempt | tt_step << 16; 0: a plain iteration) */
+void orc_test_fill_tt(uint64_t seed, uint32_t chain, uint32_t iter, uint32_t tt_step, uint32_t upd, int kind,
+                      double p1, double p2, int count, double* out) {
+  orc_rng r = {seed, chain, iter, tt_step};
   for (int i = 0; i < count; ++i) {
     switch (kind) {
       case 0: out[i] = orc_runif(&r, upd, (uint32_t)i); break;

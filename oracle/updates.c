@@ -727,6 +727,22 @@ double orc_calculatePZetaCov(const orc_data* d, double beta_i, int iter, const o
   return logAcceptance;
 }
 
+/* Test hook (tests/tempered_ref.py): the residual sum of squares of state `iter`, the only way but sigma^2 in which the tempered
+ * log-likelihood above depends on a state (every model: the same fitted value), summed in long double. */
+double orc_state_rss(const orc_data* d, int iter, const orc_chain* c) {
+  DIMS;
+  (void)K; (void)M; (void)D; (void)P;
+  long double ss = 0.0L;
+  for (int i = 0; i < n; ++i) {
+    const int ni = NI(i);
+    for (int l = 0; l < ni; ++l) {
+      const long double rr = (long double)YOBS(i, l) - (long double)fitted_skipzero(d, c, iter, i, BROW(i, l));
+      ss += rr * rr;
+    }
+  }
+  return (double)ss;
+}
+
 /* ========================= covariate-adjusted extras ======================================= */
 
 /* updateEta, UpdateEta.h:28-94 (d outer, j inner; pinv + symmetrise; Tempered :116-185) */

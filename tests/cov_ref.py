@@ -247,11 +247,11 @@ def wdir64(c, st, X, order=None):
     return W
 
 
-def normals(c, q=0, it=0):
+def normals(c, q=0, it=0, tt=0):
     """z_a (A2, P) of the oracle's keyed generator with k_cov_factor's index formulas"""
     import oracle_lib as O
-    ze = O.fill(1, c.K * c.D * c.P, seed=SEED, chain=q, it=it, upd=UPD_ETA).reshape(-1, c.P)
-    zx = O.fill(1, c.K * c.M * c.D * c.P, seed=SEED, chain=q, it=it, upd=UPD_XI).reshape(-1, c.P)
+    ze = O.fill(1, c.K * c.D * c.P, seed=SEED, chain=q, it=it, upd=UPD_ETA, tt=tt).reshape(-1, c.P)
+    zx = O.fill(1, c.K * c.M * c.D * c.P, seed=SEED, chain=q, it=it, upd=UPD_XI, tt=tt).reshape(-1, c.P)
     out = np.zeros((c.A2, c.P))
     for a in range(c.A2):
         j, mt, d = dir2_of(c, a)
@@ -340,11 +340,11 @@ def is_pinv(c, a):
     return c.empty is not None and j == c.empty and mt == 0 and c.kind != "mv"
 
 
-def check_factor(c, st, H2aa, C2, Lz2, f, mask, q=0, it=0, pcz=False):
+def check_factor(c, st, H2aa, C2, Lz2, f, mask, q=0, it=0, pcz=False, tt=0):
     """C_a and L_a z_a of every updated direction (module docstring): dict(worst_C, worst_L, kappa, rho, routes, fails)"""
     H = np.asarray(H2aa, dtype=np.float64).reshape(-1, c.LG)
     Cm, Lz = np.asarray(C2, dtype=np.float64).reshape(c.A2, c.P, c.P), np.asarray(Lz2, dtype=np.float64).reshape(c.A2, c.P)
-    z = normals(c, q, it)
+    z = normals(c, q, it, tt)
     out = dict(worst_C=0.0, worst_L=0.0, kappa=0.0, rho=np.inf, routes=set(), fails=[])
     for a in visited(c, mask, pcz):
         Prec = LD(f) * band_dense(H[pair_row(c, a, a)], c.P, LD) + prior_ld(c, st, a)
@@ -540,7 +540,7 @@ def gstd2_shapes(c, st_old, hyp):
     return sh
 
 
-def check_gstd2(c, st_old, gstd2, before, hyp, mask, q=0, it=0, pcz=False):
+def check_gstd2(c, st_old, gstd2, before, hyp, mask, q=0, it=0, pcz=False, tt=0):
     """ "gstd2" against the oracle's keyed standard gamma variates.  Both are Marsaglia-Tsang draws d (1 + c z)^3 of the same
     uniforms, d = shape - 1/3, c = 1 / sqrt(9 d): the AS241 allowance of the normal, (32 |z| + 4) u, passes through the cube as
     3 c (32 |z| + 4) u / (1 + c z) relative, with z and 1 + c z recovered from the oracle's variate; + 8 u for the products.  Parts
@@ -554,12 +554,12 @@ def check_gstd2(c, st_old, gstd2, before, hyp, mask, q=0, it=0, pcz=False):
     ref = np.zeros(len(sh))
     n_tau, n_del = K * D, K * M * D
     if on[17]:
-        ref[:n_tau] = O.fill(2, n_tau, seed=SEED, chain=q, it=it, upd=17, p1=sh[0][2], p2=1.0)
+        ref[:n_tau] = O.fill(2, n_tau, seed=SEED, chain=q, it=it, upd=17, p1=sh[0][2], p2=1.0, tt=tt)
     if on[19]:
         for e in range(n_tau, n_tau + n_del):
-            ref[e] = O.fill(2, sh[e][1] + 1, seed=SEED, chain=q, it=it, upd=19, p1=sh[e][2], p2=1.0)[-1]
+            ref[e] = O.fill(2, sh[e][1] + 1, seed=SEED, chain=q, it=it, upd=19, p1=sh[e][2], p2=1.0, tt=tt)[-1]
     if on[22]:
-        ref[n_tau + n_del:] = O.fill(2, len(sh) - n_tau - n_del, seed=SEED, chain=q, it=it, upd=22, p1=sh[-1][2], p2=1.0)
+        ref[n_tau + n_del:] = O.fill(2, len(sh) - n_tau - n_del, seed=SEED, chain=q, it=it, upd=22, p1=sh[-1][2], p2=1.0, tt=tt)
     fails = []
     for e, (upd, idx, shape) in enumerate(sh):
         if not on[upd]:
@@ -576,21 +576,21 @@ def check_gstd2(c, st_old, gstd2, before, hyp, mask, q=0, it=0, pcz=False):
     return fails
 
 
-def axi_reference(c, st_old, dx_cur, hyp, q=0, it=0):
+def axi_reference(c, st_old, dx_cur, hyp, q=0, it=0, tt=0):
     """the A_xi step (UpdateA.h:137-205) of every cell (j, i, d) from the oracle's keyed proposal (UPD_AXI_PROP, rtruncnorm at 0) and
     uniform (UPD_AXI_ACC), index (j 2 + i) D + d: list of dict(cell, cur, na, sd, logu, acc(na) -> (value, sum of absolute terms))"""
     import oracle_lib as O
     K, M, D = c.K, c.M, c.D
     L = O.lib()
     out = []
-    uu = O.fill(0, K * 2 * D, seed=SEED, chain=q, it=it, upd=21)
+    uu = O.fill(0, K * 2 * D, seed=SEED, chain=q, it=it, upd=21, tt=tt)
     for j in range(K):
         for i in range(2):
             for d in range(D):
                 idx = (j * 2 + i) * D + d
                 sd = hyp["var_epsilon1"] / hyp["beta1l"] if i == 0 else hyp["var_epsilon2"] / hyp["beta2l"]
                 cur = float(st_old["A_xi"][j, i, d])
-                na = float(O.fill(3, idx + 1, seed=SEED, chain=q, it=it, upd=20, p1=cur, p2=sd)[-1])
+                na = float(O.fill(3, idx + 1, seed=SEED, chain=q, it=it, upd=20, p1=cur, p2=sd, tt=tt)[-1])
                 lg = np.log(_ld(dx_cur)[j, :, d])
 
                 def acc(na, cur=cur, sd=sd, i=i, lg=lg):
@@ -609,7 +609,7 @@ def axi_reference(c, st_old, dx_cur, hyp, q=0, it=0):
     return out
 
 
-def check_axi(c, st_old, A_new, dx_cur, hyp, mask, q=0, it=0, pcz=False):
+def check_axi(c, st_old, A_new, dx_cur, hyp, mask, q=0, it=0, pcz=False, tt=0):
     """every cell of A_xi: bit-equal to its old value or (within the AS241 allowance sd (32 |x| + 4) u + 2 u |na|) the oracle's keyed
     proposal, and the decision agrees with the longdouble acceptance value wherever |log u - acc_ref| exceeds its bound
     16 u (sum of absolute terms + 1) + |acc(na +- tolerance) - acc(na)|: the device's log(tgamma), log, erfc and the proposal's own
@@ -618,7 +618,7 @@ def check_axi(c, st_old, A_new, dx_cur, hyp, mask, q=0, it=0, pcz=False):
     if not ((mask & U_A_XI) and c.cov_adj and not pcz):
         return [] if np.array_equal(A_new, np.asarray(st_old["A_xi"], dtype=np.float64)) else [f"{c.name}: k_cov_hyper: A_xi changed although its step is off"]
     fails = []
-    for r in axi_reference(c, st_old, dx_cur, hyp, q, it):
+    for r in axi_reference(c, st_old, dx_cur, hyp, q, it, tt):
         j, i, d = r["cell"]
         got, cur, na = float(A_new[j, i, d]), r["cur"], r["na"]
         tol = r["sd"] * (32 * abs((na - cur) / r["sd"]) + 4) * U + 2 * U * abs(na)
@@ -892,12 +892,12 @@ def emulate(c, rec, st, X, c0, g0, mask, beta, z, gstd2, hyp, variant="kernel", 
     return out
 
 
-def check_all(c, rec, st, X, c0, g0, mask, beta, dev, hyp, q=0, it=0, pcz=False, gstd2=None, e_c=None, e_g=None):
+def check_all(c, rec, st, X, c0, g0, mask, beta, dev, hyp, q=0, it=0, pcz=False, gstd2=None, e_c=None, e_g=None, tt=0):
     """every check on one run's arrays `dev` (the keys of emulate's result; sigma2: the block's): dict(check: result)"""
     f = beta / float(dev["sigma2"])
     res = dict(wdir=dict(worst=0.0, fails=check_wdir(c, st, X, dev["Wdir"]) if visited(c, mask, pcz) else []))
     res["h2aa"] = check_h2aa(c, rec, dev["Wdir"], dev["H2aa"], mask, pcz)
-    res["factor"] = check_factor(c, st, dev["H2aa"], dev["C2"], dev["Lz2"], f, mask, q, it, pcz)
+    res["factor"] = check_factor(c, st, dev["H2aa"], dev["C2"], dev["Lz2"], f, mask, q, it, pcz, tt)
     res["steps"] = check_steps(c, rec, dev["Wdir"], dev["H2aa"], dev["C2"], dev["Lz2"], theta_of(c, st), dev["th_new"], c0, g0, f, mask, pcz,
                                e_g=e_g)
     res["final"] = check_final(c, rec, res["steps"], c0, g0, dev["cfull"], dev["gfull"], e_c, e_g)

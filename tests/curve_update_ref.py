@@ -84,7 +84,9 @@ recorded Z_new; pr_old / pr_new and log_uu as above.  These tolerances cannot be
 different log / pow): they are MEASURED, the oracle's float64 arithmetic against the longdouble restatement over every case, in
 units of u -- Z_new 2.94 (relative), lpn 2.01, lpo 2.3 (of their sums of absolute terms) -- and the device's own libm gets 4 x
 that.  reference_z is the whole update from the oracle's variates; tests/test_curve_update_ref.py holds it to the oracle's
-updateZ_PM (1e-9).  Not restated: the tempered in-place branches, kernels_cov.hip, the scalar jobs.
+updateZ_PM (1e-9).  The functions that fetch keyed variates take tt (the sweep of a tempered-transition block, counter word
+tt_step; 0: a plain iteration): tests/test_gpu_tempered_steps.py runs them on the in-place branches of tempered sweeps.  Not restated
+here: kernels_cov.hip (tests/cov_ref.py), the scalar jobs (tests/scalar_jobs_ref.py).
 """
 import zlib
 
@@ -328,9 +330,11 @@ def chi_forms(c, G, s, th, tha, Z, chi):
     return dict(u=u, ua=ua, c0=c0, c0a=c0a, A=u @ Gu.T, Sa=ua @ Gua.T, b=u @ d, Sb=ua @ da, d=d, da=da)
 
 
-def check_chi(c, rec, st, chi_new, znorm, beta, X=None):
+def check_chi(c, rec, st, chi_new, znorm, beta, X=None, ztol=None):
     """every Gauss-Seidel step of every curve against longdouble, each judged alone (module docstring).  st: the state the update
-    started from (Z, chi, nu, Phi, sigma_sq, eta / xi); chi_new (n, M): the device's; znorm (n, M): its normals.
+    started from (Z, chi, nu, Phi, sigma_sq, eta / xi); chi_new (n, M): the device's; znorm (n, M): its normals.  ztol (n, M):
+    the absolute allowance of znorm where it is the oracle's keyed normal and not the device's own (an iteration judged from chain
+    slots alone; check_chi_norm has the figure): it enters the bound through sqrt(W).
     Returns dict(ok, worst, where (i, m), fails [messages], vacuous (largest bound / |dl|))."""
     M, n = c.M, c.n
     Gb, sv, _ = split_rec(c, rec)
@@ -353,6 +357,8 @@ def check_chi(c, rec, st, chi_new, znorm, beta, X=None):
             dA = cn["c_A"] * U * Sa[m, m]
             bound = G_CHI * (W * f * E_r + W * f * abs(chi0[i, m]) * dA + abs(f * (r + chi0[i, m] * A[m, m]) + zn[i, m] / (2 * sq)) * W * W * f * dA
                              + 8 * U * (W * f * (abs(r) + abs(chi0[i, m]) * A[m, m]) + abs(chi0[i, m]) + sq * abs(zn[i, m])) + U * abs(ref))
+            if ztol is not None:
+                bound = bound + sq * LD(float(np.asarray(ztol).reshape(n, M)[i, m]))
             err = abs(chi1[i, m] - ref)
             ratio = _ratio(err, bound)
             step = abs(ref - chi0[i, m])
@@ -476,7 +482,7 @@ def lgamma_ld(x):
     return (x - LD(0.5)) * np.log(x) - x + LOG_SQRT_2PI + ser - shift
 
 
-def oracle_gammas(c, Z_old, a_Z_PM, chain_id, it):
+def oracle_gammas(c, Z_old, a_Z_PM, chain_id, it, tt=0):
     """the K keyed gamma variates per curve of the Dirichlet proposal (UPD_Z_PROP, index i K + k, shape a_Z_PM Z_old,k, or 10 where
     that is <= 0: Distributions.h:24-28) from the oracle, without touching it: fill(.., idx + 1, ..)[-1] is the variate of index idx"""
     import oracle_lib as O
@@ -485,7 +491,7 @@ def oracle_gammas(c, Z_old, a_Z_PM, chain_id, it):
     for i in range(c.n):
         for k in range(c.K):
             a = a_Z_PM * Z0[i, k]
-            g[i, k] = O.fill(2, i * c.K + k + 1, seed=SEED, chain=chain_id, it=it, upd=UPD_Z_PROP, p1=float(10.0 if a <= 0 else a), p2=1.0)[-1]
+            g[i, k] = O.fill(2, i * c.K + k + 1, seed=SEED, chain=chain_id, it=it, upd=UPD_Z_PROP, p1=float(10.0 if a <= 0 else a), p2=1.0, tt=tt)[-1]
     return g
 
 
@@ -524,14 +530,14 @@ def measure_proposal(c, q=0, it=0, a_Z_PM=10000.0):
     return out
 
 
-def check_proposal(c, Z_old, zrec, a_Z_PM, chain_id, it):
+def check_proposal(c, Z_old, zrec, a_Z_PM, chain_id, it, tt=0):
     """the data-independent half of the recorded proposal against the restatement: Z_new against the oracle's keyed gamma
     variates, normalised in longdouble, under PROP_MARGIN MEASURED_PROP["Znew"] u Z_new; lpn and lpo against the longdouble
     densities AT the recorded Z_new under PROP_MARGIN MEASURED_PROP[.] u S (the sums of absolute terms).  A curve with a zero only
     has its Z_new checked (its densities are infinite and unused).  Returns dict(fails, worst: {field: error / tolerance})."""
     zr = split_zrec(c, zrec)
     Z0 = np.asarray(Z_old, dtype=np.float64).reshape(c.n, c.K)
-    gam = oracle_gammas(c, Z0, a_Z_PM, chain_id, it)
+    gam = oracle_gammas(c, Z0, a_Z_PM, chain_id, it, tt)
     fails, worst = [], dict(Znew=0.0, lpn=0.0, lpo=0.0)
     for i in range(c.n):
         g = gam[i].astype(LD)
@@ -553,7 +559,7 @@ def check_proposal(c, Z_old, zrec, a_Z_PM, chain_id, it):
     return dict(fails=fails, worst=worst)
 
 
-def reference_z(c, rec, st, beta, a_Z_PM, chain_id, it, X=None):
+def reference_z(c, rec, st, beta, a_Z_PM, chain_id, it, X=None, tt=0):
     """the whole Z update in longdouble from the oracle's keyed variates (gamma: UPD_Z_PROP, uniform: UPD_Z_ACC): Z_out (n, K) float64
     and the acceptance values"""
     import oracle_lib as O
@@ -561,8 +567,8 @@ def reference_z(c, rec, st, beta, a_Z_PM, chain_id, it, X=None):
     Gb, sv, yy = split_rec(c, rec)
     th, tha = theta_rows(c, st, X, M)
     chi, Z0 = _ld(st["chi"]), np.asarray(st["Z"], dtype=np.float64)
-    gam = oracle_gammas(c, Z0, a_Z_PM, chain_id, it)
-    luu = np.log(O.fill(0, n, seed=SEED, chain=chain_id, it=it, upd=UPD_Z_ACC).astype(LD))
+    gam = oracle_gammas(c, Z0, a_Z_PM, chain_id, it, tt)
+    luu = np.log(O.fill(0, n, seed=SEED, chain=chain_id, it=it, upd=UPD_Z_ACC, tt=tt).astype(LD))
     coef = LD(float(np.ravel(st["alpha_3"])[0])) * _ld(np.ravel(st["pi"])) - 1
     f2 = LD(beta) / (2 * LD(float(np.ravel(st["sigma_sq"])[0])))
     Z1, acc = Z0.copy(), np.zeros(n)
@@ -781,23 +787,23 @@ def check_prior_terms(c, Z_old, zrec, pi, alpha3):
     return fails
 
 
-def check_log_uu(c, zrec, chain_id, it):
+def check_log_uu(c, zrec, chain_id, it, tt=0):
     """the recorded log_uu against the log of the oracle's keyed uniform (UPD_Z_ACC, index i)"""
     import oracle_lib as O
-    uu = O.fill(0, c.n, seed=SEED, chain=chain_id, it=it, upd=UPD_Z_ACC)
+    uu = O.fill(0, c.n, seed=SEED, chain=chain_id, it=it, upd=UPD_Z_ACC, tt=tt)
     ref = np.log(uu.astype(LD))
     got = split_zrec(c, zrec)["log_uu"]
     bad = [i for i in range(c.n) if not abs(LD(got[i]) - ref[i]) <= 4 * U * abs(ref[i]) + 2 * U]
     return [f"{c.name}: log_uu of curves {bad} differs from log(runif(UPD_Z_ACC, i)) of iteration {it}: {got[bad]} against {np.asarray(ref[bad], dtype=np.float64)}"] if bad else []
 
 
-def check_chi_norm(c, znorm, chain_id, it):
+def check_chi_norm(c, znorm, chain_id, it, tt=0):
     """chi_norm against the oracle's keyed rnorm (UPD_CHI, index i M + m).  Both are AS241 (PPND16) of the same uniform: a ratio
     of two degree-7 polynomials, each Horner step one rounding (16 u relative at most on the ratio, usually 3), and in the tails
     r = sqrt(-log(min(p, 1 - p))) through two libm paths of <= 2 ulp each, which the polynomials (condition below 4 in r) carry
     to <= 16 u: 32 u |z| + 4 u (q = p - 1/2 near zero: absolute)."""
     import oracle_lib as O
-    ref = O.fill(1, c.n * c.M, seed=SEED, chain=chain_id, it=it, upd=UPD_CHI).reshape(c.n, c.M)
+    ref = O.fill(1, c.n * c.M, seed=SEED, chain=chain_id, it=it, upd=UPD_CHI, tt=tt).reshape(c.n, c.M)
     got = np.asarray(znorm, dtype=np.float64).reshape(c.M, c.n).T      # the device holds it curve-fastest
     bad = np.argwhere(~(np.abs(got - ref) <= 32 * U * np.abs(ref) + 4 * U))
     return [f"{c.name}: chi_norm differs from rnorm(UPD_CHI, i M + m) of iteration {it} at (i, m) {bad[:4].tolist()}: {got[tuple(bad[0])]!r} against {ref[tuple(bad[0])]!r}"] if len(bad) else []

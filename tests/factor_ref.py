@@ -226,13 +226,14 @@ def case_state(c, q=0):
     return st
 
 
-def normals(c, q=0):
+def normals(c, q=0, it=0, tt=0):
     """z_a of every direction from the oracle's keyed generator with k_factor's index layout: idx0 = j P (nu, UPD_NU),
-    (j M + mt - 1) P (Phi, UPD_PHI); iteration 0, chain id q.  Returns (A, P)."""
+    (j M + mt - 1) P (Phi, UPD_PHI); iteration `it` (tt: sweep of a tempered-transition block, 0 a plain iteration), chain id q.
+    Returns (A, P)."""
     import oracle_lib as O
     K, M, P, MD = c.K, c.M, c.P, c.MD
-    znu = O.fill(1, K * P, seed=SEED, chain=q, it=0, upd=UPD_NU)
-    zphi = O.fill(1, K * M * P, seed=SEED, chain=q, it=0, upd=UPD_PHI)
+    znu = O.fill(1, K * P, seed=SEED, chain=q, it=it, upd=UPD_NU, tt=tt)
+    zphi = O.fill(1, K * M * P, seed=SEED, chain=q, it=it, upd=UPD_PHI, tt=tt)
     z = np.zeros((c.A, P))
     for j in range(K):
         z[j * MD] = znu[j * P:(j + 1) * P]

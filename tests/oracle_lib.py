@@ -62,6 +62,10 @@ def lib():
         L.orc_fitted.restype = C.c_double
         L.orc_test_fill.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_double,
                                     C.c_double, C.c_int, c_double_p]
+        L.orc_test_fill_tt.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_double,
+                                       C.c_double, C.c_int, c_double_p]
+        L.orc_tt_trace_hook.restype = None
+        L.orc_tt_trace_hook.argtypes = [c_double_p, C.c_int]
         L.orc_run_sweeps.argtypes = [C.POINTER(OrcData), C.POINTER(OrcHyper), C.c_uint64, C.c_uint32, C.c_int,
                                      C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OrcChain)]
         L.orc_init_nu_z.argtypes = [C.POINTER(OrcData), C.POINTER(OrcHyper), C.c_uint64, C.c_uint32,
@@ -82,9 +86,11 @@ def philox(ctr, key):
     return list(out)
 
 
-def fill(kind, count, seed=1, chain=0, it=0, upd=1, p1=0.0, p2=0.0):
+def fill(kind, count, seed=1, chain=0, it=0, upd=1, p1=0.0, p2=0.0, tt=0):
+    """draws 0 .. count - 1 of update `upd` (kind 0 uniform, 1 normal, 2 gamma(p1, p2), 3 truncated normal) at iteration `it`; tt: the
+    sweep of a tempered-transition block (counter word tt_step; 0: a plain iteration)"""
     out = np.empty(count)
-    lib().orc_test_fill(seed, chain, it, upd, kind, p1, p2, count, dp(out))
+    lib().orc_test_fill_tt(seed, chain, it, tt, upd, kind, p1, p2, count, dp(out))
     return out
 
 

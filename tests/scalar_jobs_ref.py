@@ -238,15 +238,15 @@ def pnorm(x):
 # ---------------------------------------------------------------------------------------------------------------------
 # keyed variates
 # ---------------------------------------------------------------------------------------------------------------------
-def gamma_variate(upd, idx, shape, seed, q, it, count=1):
+def gamma_variate(upd, idx, shape, seed, q, it, count=1, tt=0):
     """the oracle's keyed standard gamma variates of indices idx .. idx + count - 1 at one shape and their allowances (module
     docstring): (values, absolute tolerances)"""
     import oracle_lib as O
     shape = float(shape)
-    ref = O.fill(2, idx + count, seed=seed, chain=q, it=it, upd=upd, p1=shape, p2=1.0)[idx:]
+    ref = O.fill(2, idx + count, seed=seed, chain=q, it=it, upd=upd, p1=shape, p2=1.0, tt=tt)[idx:]
     a, base, extra = shape, ref, 0.0
     if shape < 1.0:
-        base = O.fill(2, idx + count, seed=seed, chain=q, it=it, upd=upd, p1=shape + 1.0, p2=1.0)[idx:]
+        base = O.fill(2, idx + count, seed=seed, chain=q, it=it, upd=upd, p1=shape + 1.0, p2=1.0, tt=tt)[idx:]
         extra = (8 + 4 * np.abs(np.log(ref / base))) * U
         a = shape + 1.0
     d = a - 1.0 / 3.0
@@ -271,33 +271,34 @@ def a_sd(hyp, i):
     return hyp["var_epsilon1"] / hyp["beta1l"] if i == 0 else hyp["var_epsilon2"] / hyp["beta2l"]
 
 
-def variates(c, A_old, hyp, dims, q=0, it=0, seed=SEED, mut=None):
+def variates(c, A_old, hyp, dims, q=0, it=0, seed=SEED, mut=None, tt=0, sigma_shape=None):
     """what job_hyper_draws must leave in "gstd" for the iteration that starts with A_old (K, 2), from the oracle's keyed generator:
-    dict(g: the array up to the A terms, tol: its absolute allowances)"""
+    dict(g: the array up to the A terms, tol: its absolute allowances).  tt: the sweep of a tempered-transition block (counter word
+    tt_step), whose sigma^2 variate has the shape sigma_shape (tempered_ref.sigma_shape) in place of alpha_0 + half_sum"""
     import oracle_lib as O
     K, P, M = c.K, c.P, c.M
     lay = gstd_layout(c)
     g, tol = np.zeros(lay["aterm"][1]), np.zeros(lay["aterm"][1])
     A_old = np.asarray(A_old, dtype=np.float64).reshape(K, 2)
     if K * P * M:
-        g[slice(*lay["gamma"])], tol[slice(*lay["gamma"])] = gamma_variate(UPD_GAMMA, 0, (hyp["nu_1"] + 1) / 2, seed, q, it, K * P * M)
+        g[slice(*lay["gamma"])], tol[slice(*lay["gamma"])] = gamma_variate(UPD_GAMMA, 0, (hyp["nu_1"] + 1) / 2, seed, q, it, K * P * M, tt=tt)
     for k in range(K):
         for i in range(M):
             shape = A_old[k, 0] + (P * M) / 2.0 if i == 0 else A_old[k, 1] + (P * (M - i)) / 2.0
             e = lay["delta"][0] + k * M + i
-            g[e:e + 1], tol[e:e + 1] = gamma_variate(UPD_DELTA, k * M + i, shape, seed, q, it)
-    g[slice(*lay["tau"])], tol[slice(*lay["tau"])] = gamma_variate(UPD_TAU, 0, hyp["alpha_nu"] + (P / 2.0 if mut == "tau_shape_real_div" else P // 2), seed, q, it, K)
+            g[e:e + 1], tol[e:e + 1] = gamma_variate(UPD_DELTA, k * M + i, shape, seed, q, it, tt=tt)
+    g[slice(*lay["tau"])], tol[slice(*lay["tau"])] = gamma_variate(UPD_TAU, 0, hyp["alpha_nu"] + (P / 2.0 if mut == "tau_shape_real_div" else P // 2), seed, q, it, K, tt=tt)
     half = dims["n_obs_total"] // 2 if c.kind == "mv" else dims["half_sum"]
     if mut == "sigma_half_sum_real":
         half = dims["n_obs_total"] / 2.0
     e = lay["sigma"][0]
-    g[e:e + 1], tol[e:e + 1] = gamma_variate(UPD_SIGMA, 0, hyp["alpha_0"] + half, seed, q, it)
-    g[slice(*lay["aunif"])] = O.fill(0, 2 * K, seed=seed, chain=q, it=it, upd=UPD_A_ACC)
+    g[e:e + 1], tol[e:e + 1] = gamma_variate(UPD_SIGMA, 0, hyp["alpha_0"] + half if sigma_shape is None else sigma_shape, seed, q, it, tt=tt)
+    g[slice(*lay["aunif"])] = O.fill(0, 2 * K, seed=seed, chain=q, it=it, upd=UPD_A_ACC, tt=tt)
     tol[slice(*lay["aunif"])] = 2 * U
     for j in range(K):
         for i in range(2):
             cell, cur, sd = 2 * j + i, float(A_old[j, i]), a_sd(hyp, i)
-            na = float(O.fill(3, cell + 1, seed=seed, chain=q, it=it, upd=UPD_A_PROP, p1=cur, p2=sd)[-1])
+            na = float(O.fill(3, cell + 1, seed=seed, chain=q, it=it, upd=UPD_A_PROP, p1=cur, p2=sd, tt=tt)[-1])
             tn = sd * (32 * abs((na - cur) / sd) + 4) * U + 2 * U * abs(na)
             g[lay["aprop"][0] + cell], tol[lay["aprop"][0] + cell] = na, tn
             e = lay["aterm"][0] + 4 * cell
@@ -340,7 +341,7 @@ def lg_bound(x):
     return float(8 * U * ((x - LD(0.5)) * abs(np.log(x)) + x + 1 + abs(lp)) + LD(1.2e-14))
 
 
-def pi_draws(c, pi_old, alpha3, hyp, q, it, seed):
+def pi_draws(c, pi_old, alpha3, hyp, q, it, seed, tt=0):
     """the keyed variates of the pi / alpha_3 job of iteration `it`: the K gammas (allowances), the truncated-normal proposal of
     alpha_3 (allowance), log u of both tests"""
     import oracle_lib as O
@@ -349,11 +350,11 @@ def pi_draws(c, pi_old, alpha3, hyp, q, it, seed):
     g, gt = np.zeros(K), np.zeros(K)
     for k in range(K):
         a = hyp["a_pi_PM"] * pi_old[k]
-        g[k:k + 1], gt[k:k + 1] = gamma_variate(UPD_PI_PROP, k, 10.0 if a <= 0 else a, seed, q, it)
+        g[k:k + 1], gt[k:k + 1] = gamma_variate(UPD_PI_PROP, k, 10.0 if a <= 0 else a, seed, q, it, tt=tt)
     sd = hyp["var_alpha3"]
-    ph = float(O.fill(3, 1, seed=seed, chain=q, it=it, upd=UPD_A3_PROP, p1=float(alpha3), p2=sd)[0])
+    ph = float(O.fill(3, 1, seed=seed, chain=q, it=it, upd=UPD_A3_PROP, p1=float(alpha3), p2=sd, tt=tt)[0])
     pt = sd * (32 * abs((ph - float(alpha3)) / sd) + 4) * U + 2 * U * abs(ph)
-    lu = [np.log(LD(O.fill(0, 1, seed=seed, chain=q, it=it, upd=u)[0])) for u in (UPD_PI_ACC, UPD_A3_ACC)]
+    lu = [np.log(LD(O.fill(0, 1, seed=seed, chain=q, it=it, upd=u, tt=tt)[0])) for u in (UPD_PI_ACC, UPD_A3_ACC)]
     pn = _ld(g) / _ld(g).sum()
     rel = gt / g + (gt / g).max() + 4 * U
     return dict(g=g, gtol=gt, pi_new=pn, pi_rel=rel, ph=ph, ph_tol=pt, lu=lu)
@@ -411,13 +412,13 @@ def _judge(name, what, logu, a0, bound, took, acc_dev, out):
         out["fails"].append(f"{name}: {what}: the bound {float(bound):.3g} is not below {NONVACUOUS} of the margin {float(margin):.3g}")
 
 
-def check_pi_alpha(c, pi_old, a3_old, Z, pi_dev, a3_dev, hyp, mask, q=0, it=0, seed=SEED, acc_dev=None):
+def check_pi_alpha(c, pi_old, a3_old, Z, pi_dev, a3_dev, hyp, mask, q=0, it=0, seed=SEED, acc_dev=None, tt=0):
     """the pi and alpha_3 steps of iteration `it` (module docstring): dict(worst, vacuous, fails, outcome: {"pi", "alpha_3": bool})"""
     out = dict(worst=0.0, vacuous=0.0, fails=[], outcome={})
     pi_old, pi_dev = np.asarray(pi_old, dtype=np.float64).ravel(), np.asarray(pi_dev, dtype=np.float64).ravel()
     a3_old, a3_dev = float(np.ravel(a3_old)[0]), float(np.ravel(a3_dev)[0])
     S = np.log(_ld(Z).reshape(c.n, c.K)).sum(axis=0)
-    dr = pi_draws(c, pi_old, a3_old, hyp, q, it, seed)
+    dr = pi_draws(c, pi_old, a3_old, hyp, q, it, seed, tt)
     if mask & U_PI:
         took = not np.array_equal(pi_dev, pi_old)
         x = dr["pi_new"]
@@ -455,7 +456,7 @@ def check_pi_alpha(c, pi_old, a3_old, Z, pi_dev, a3_dev, hyp, mask, q=0, it=0, s
     return out
 
 
-def check_piprep(c, tab, pi, alpha3, hyp, q, it, seed=SEED):
+def check_piprep(c, tab, pi, alpha3, hyp, q, it, seed=SEED, tt=0):
     """ "piprep" as job_pi_prepare leaves it for iteration `it` from pi and alpha_3 (module docstring): dict(worst, fails)"""
     K = c.K
     t = np.asarray(tab, dtype=np.float64)
@@ -464,7 +465,7 @@ def check_piprep(c, tab, pi, alpha3, hyp, q, it, seed=SEED):
         out["fails"].append(f"{c.name}: \"piprep\" has {t.shape[0]} entries")
         return out
     g, lg, ph, lu, lp, dt = t[:K], t[KMAX:KMAX + 6 * K + 6], t[7 * KMAX + 8], t[7 * KMAX + 10:7 * KMAX + 12], t[7 * KMAX + 12:7 * KMAX + 12 + 2 * K], t[9 * KMAX + 12:9 * KMAX + 14]
-    dr = pi_draws(c, pi, alpha3, hyp, q, it, seed)
+    dr = pi_draws(c, pi, alpha3, hyp, q, it, seed, tt)
     po, a3, sd = _ld(pi).ravel(), float(np.ravel(alpha3)[0]), hyp["var_alpha3"]
 
     def hold(what, got, ref, bound):

@@ -15,8 +15,9 @@ directions outside the mask keep theta0.  Step s, a = a_s:
 and after the last step  RSS = YY - sum_a theta1_a'(t_a + r1_a),  r1_a = r0_a - sum_{all u} H_{a, a_u} delta_u.
 sigma^2 is then 1 / Gamma(a, 1 / b) with b = RSS / 2 + beta_0 in every plain run: bfmmm_run passes tt_step = 0 whatever beta
 is, and the kernels' `tempered` form (b = (beta / 2) RSS + beta_0, UpdateSigma.h:75-113) is taken for tt_step != 0 only; beta
-enters a plain run through f alone.  (sigma^2 itself needs the gamma variate, which the device does not expose: it stays on
-oracle parity.)
+enters a plain run through f alone; the tempered form is judged by tests/tempered_ref.py on runs of Sampler.run_tt, with check_steps
+and check_rss of this file at f = beta / sigma^2.  (sigma^2 itself needs the gamma variate: tests/test_gpu_sweep.py::check_sigma
+takes the oracle's, tests/scalar_jobs_ref.py the device's "gstd".)
 
 Step check (check_steps).  Step s is judged ALONE: r_a^(s) is formed in np.longdouble from the device's own theta1 of the
 earlier steps (delta_u = theta1_{a_u} - theta0_{a_u} is exact in longdouble), so an error of step 3 is not charged to step 7.

@@ -88,7 +88,7 @@ def push(smp, states):
 HYP_NAMES = ("alpha_eta", "beta_eta", "nu_1", "alpha1l", "alpha2l", "beta1l", "beta2l", "var_epsilon1", "var_epsilon2")
 
 
-def judge(smp, c, what, q, st_in, c0, g0, run, it, rec, g_before, e_c=None, e_g=None):
+def judge(smp, c, what, q, st_in, c0, g0, run, it, rec, g_before, e_c=None, e_g=None, tt=0):
     """every check of cov_ref on the selected chain's arrays after a run whose last iteration `it` started from st_in"""
     hyp = {nm: float(getattr(smp.cfg, nm)) for nm in HYP_NAMES}
     dev = dict(Wdir=smp.debug("Wdir"), H2aa=smp.debug("H2aa"), C2=smp.debug("C2"), Lz2=smp.debug("Lz2"), cfull=smp.debug("cfull"),
@@ -101,11 +101,11 @@ def judge(smp, c, what, q, st_in, c0, g0, run, it, rec, g_before, e_c=None, e_g=
         fails.append(f"{what}: \"thetaX\" differs from the eta / xi of the working state")
     rc = smp.debug("rec")
     res = V.check_all(c, rc, st_in, R.case_X(c), c0, g0, run.mask, run.beta, dev, hyp, q=q, it=it, pcz=run.pcz, gstd2=smp.debug("gstd2"), e_c=e_c,
-                      e_g=e_g)
+                      e_g=e_g, tt=tt)
     for k, r in res.items():
         fails += [f"{what}: {m}" for m in r["fails"]]
-    fails += [f"{what}: {m}" for m in V.check_gstd2(c, st_in, smp.debug("gstd2"), g_before, hyp, run.mask, q, it, run.pcz)]
-    fails += [f"{what}: {m}" for m in V.check_axi(c, st_in, now["A_xi"], now["delta_xi"], hyp, run.mask, q, it, run.pcz)]
+    fails += [f"{what}: {m}" for m in V.check_gstd2(c, st_in, smp.debug("gstd2"), g_before, hyp, run.mask, q, it, run.pcz, tt)]
+    fails += [f"{what}: {m}" for m in V.check_axi(c, st_in, now["A_xi"], now["delta_xi"], hyp, run.mask, q, it, run.pcz, tt)]
     fac = res["factor"]
     if c.regime == "stiff" and c.kind != "mv" and not fac["rho"] >= 1e-9:      # (from the device's own H2aa; the diagonal model has no pivots)
         fails.append(f"{what}: the smallest Cholesky pivot ratio {fac['rho']:.3g} is not a factor 1000 above the kernels' 1e-12 decision")

@@ -112,22 +112,23 @@ def chi_form_name(route):
     return f"chi<{x['BW']},{x['LPC']},{'cov' if x['COV'] else '-'},{inst}>"
 
 
-def check_z_run(smp, rec, what, c, q, X, st_in, route, it, beta=1.0, M=None, prepared=True):
+def check_z_run(smp, rec, what, c, q, X, st_in, route, it, beta=1.0, M=None, prepared=True, tt=0):
     """the Z update the record describes, from the state it started from; the chain slot and the working state must agree;
-    prepared: whether the update must have taken the proposals k_factor prepared ahead ("z_prepared")"""
+    prepared: whether the update must have taken the proposals k_factor prepared ahead ("z_prepared"); tt: the sweep of a
+    tempered-transition block whose keys the update drew with (0: a plain iteration)"""
     rc = smp.debug("rec")
     Z_out = smp.get_state("Z")
     pre = smp.debug("z_prepared")[0]
     if pre != (1.0 if prepared else 0.0):
         rec["fails"].append(f"{what}: the update {'evaluated its proposals in place' if prepared else 'took prepared proposals'} (z_prepared {pre})")
-    pr = R.check_proposal(c, st_in["Z"], smp.debug("z_record"), smp.cfg.a_Z_PM, q, it)
+    pr = R.check_proposal(c, st_in["Z"], smp.debug("z_record"), smp.cfg.a_Z_PM, q, it, tt)
     rec["fails"] += [f"{what} [{z_form_name(route)}]: {m}" for m in pr["fails"]]
     print(f"{what}: proposal error / tolerance: " + ", ".join(f"{k} {v:.3g}" for k, v in pr["worst"].items()))
     for k, v in pr["worst"].items():
         note(rec, z_form_name(route), "prop_" + k, dict(worst=v, fails=[]))
     res = R.check_z(c, rc, st_in, smp.debug("z_record"), Z_out, beta, X, M=M, logz_part=smp.debug("logz_part"))
     prior = R.check_prior_terms(c, st_in["Z"], smp.debug("z_record"), st_in["pi"], st_in["alpha_3"])
-    res["fails"] = [f"{what} [{z_form_name(route)}]: {m}" for m in res["fails"] + prior + R.check_log_uu(c, smp.debug("z_record"), q, it)]
+    res["fails"] = [f"{what} [{z_form_name(route)}]: {m}" for m in res["fails"] + prior + R.check_log_uu(c, smp.debug("z_record"), q, it, tt)]
     slot = smp.get_chain("Z", it + 1)[..., it]
     if not np.array_equal(slot, Z_out):
         res["fails"].append(f"{what}: chain slot {it} of Z differs from the working state")
@@ -154,13 +155,13 @@ def check_cfull_run(smp, rec, what, c, X, st_in, chi_new, route):
     note(rec, chi_form_name(route), "gfull", dict(worst=g["worst_g"], fails=[]))
 
 
-def check_chi_run(smp, rec, what, c, q, X, st_in, route, it, beta=1.0):
+def check_chi_run(smp, rec, what, c, q, X, st_in, route, it, beta=1.0, tt=0):
     """the chi update of iteration `it` from the state it started from, the residual sums and the log-likelihood"""
     rc = smp.debug("rec")
     chi_new = smp.get_state("chi")
     zn = smp.debug("chi_norm").reshape(c.M, c.n).T
     res = R.check_chi(c, rc, st_in, chi_new, zn, beta, X)
-    res["fails"] = [f"{what} [{chi_form_name(route)}]: {m}" for m in res["fails"] + R.check_chi_norm(c, smp.debug("chi_norm"), q, it)]
+    res["fails"] = [f"{what} [{chi_form_name(route)}]: {m}" for m in res["fails"] + R.check_chi_norm(c, smp.debug("chi_norm"), q, it, tt)]
     if not np.array_equal(smp.get_chain("chi", it + 1)[..., it], chi_new):
         res["fails"].append(f"{what}: chain slot {it} of chi differs from the working state")
     if not res["vacuous"] <= R.NONVACUOUS:

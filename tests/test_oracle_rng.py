@@ -45,6 +45,24 @@ def test_uniform_and_normal_distribution():
     np.testing.assert_array_equal(O.fill(1, 16, it=3, chain=2), O.fill(1, 16, it=3, chain=2))
 
 
+def test_tempered_fill_equals_the_plain_one_at_tt_0_and_differs_at_tt_1():
+    """orc_test_fill_tt (counter word 1 = attempt | tt_step << 16) against orc_test_fill: every kind, bit for bit at tt_step 0, another
+    stream at tt_step 1, and again another at tt_step 2; fill(..) goes through the new entry and defaults to tt_step 0"""
+    for kind, p1, p2 in ((0, 0.0, 0.0), (1, 0.0, 0.0), (2, 0.3, 2.0), (2, 60.0, 0.01), (3, 0.2, 1.0)):
+        kw = dict(seed=7, chain=3, it=11, upd=9, p1=p1, p2=p2)
+        old = np.empty(64)
+        O.lib().orc_test_fill(7, 3, 11, 9, kind, p1, p2, 64, O.dp(old))
+        plain = O.fill(kind, 64, **kw)
+        np.testing.assert_array_equal(plain, old)
+        np.testing.assert_array_equal(O.fill(kind, 64, tt=0, **kw), old)
+        one, two = O.fill(kind, 64, tt=1, **kw), O.fill(kind, 64, tt=2, **kw)
+        assert not (one == plain).any() and not (two == plain).any() and not (one == two).any(), kind
+    # the word holds the attempt in its low 16 bits: tt_step 1 is not attempt 65536 of tt_step 0, and it is what the Philox block says
+    blk = O.philox([5, 1 << 16, 11, (3 << 8) | 9], [7, 0])
+    u0 = ((blk[0] >> 6) * 67108864.0 + (blk[1] >> 6) + 0.5) / 4503599627370496.0
+    assert O.fill(0, 6, seed=7, chain=3, it=11, upd=9, tt=1)[5] == u0
+
+
 def test_gamma_distribution():
     for shape, scale in [(0.3, 2.0), (1.0, 1.0), (2.5, 0.5), (60.0, 0.01), (20481.0, 1e-4)]:
         g = O.fill(2, 100000, p1=shape, p2=scale, upd=11)
